@@ -25,6 +25,13 @@ evaluates the batch's constant-subject patterns on its shard (phase A), the resu
 prodFeature with ONE hash repartition per step (rdfgpu_exchange_repartition: counts first, then the rows, RCCL
 grouped send / recv), and the candidate join + FILTER pipeline (phase B) runs on the rank's object-sharded copy of
 the productFeature triples (sharding.shard_dataset_hybrid): both sides of the join shrink with N.
+
+A plain run sets up, executes the first batch three times (the cold start: the first execution builds the cached join
+tables; their times are reported under config.cold_start), warms up, times the steps and prints the headline.  `--full`
+adds everything else the benchmark measures or checks: the roofline of the dominant kernel and the per-kernel table, the no-table-cache / table-rebuild /
+fresh-plan steps, single-instance latency, the CPU baselines with their parity checks against the timed path, the scan +
+FILTER rooflines and, for N > 1, the other scaling mode and the sharded-result check.  `--dump-outputs DIR` writes the
+bindings of the last timed step (N = 1, batched) as float64 .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -147,6 +154,47 @@ def pmc_traffic(kernels, workload, profiles_dir=None):
     return None, None
 
 
+BATCH_SEED = 12345
+
+
+def draw_batch(rng, ds, Q, n_inst):
+    """The %Product% constants of one batch of n_inst instances: draws of Q distinct products each (a batch of more than Q
+    instances repeats products, as a BSBM driver's uniform draws would; instance tags stay distinct).  main() draws the
+    warm-up batches, then the timed ones, from one default_rng(BATCH_SEED)."""
+    parts = [ds.product_base + rng.choice(ds.n_products, size=min(Q, n_inst - k), replace=False) for k in range(0, n_inst, Q)]
+    return np.ascontiguousarray(np.concatenate(parts).astype(np.uint32))
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE_INSTANCES = 8192
+
+
+def dump_outputs(cols, n_inst, out_dir, seed=0):
+    """The bindings (inst, product, productLabel) of one step — 3 u32 columns, instance tags 1..n_inst, rows in no fixed
+    order — as float64 .npy files (ids < 2^53: exact) of at most DUMP_BYTES in all:
+      bindings_per_instance  rows of every instance tag 1..n_inst (covers the whole output)
+      inst, product, product_label  every binding of a fixed, seeded sample of DUMP_SAMPLE_INSTANCES instance tags, sorted
+    Sampling by instance and sorting make the files depend only on the multiset of bindings, not on the order the
+    kernels emitted them in: two builds that compute the same step write identical files."""
+    inst, prod, label = (np.asarray(c) for c in cols)
+    counts = np.bincount(inst, minlength=n_inst + 1)[1:n_inst + 1]
+    if len(counts) * 8 > DUMP_BYTES // 2:
+        raise ValueError(f"{n_inst} instances: their row counts alone exceed half of the {DUMP_BYTES >> 20} MB dump")
+    rng = np.random.default_rng(seed)
+    chosen = np.zeros(n_inst + 1, dtype=bool)
+    chosen[1 + rng.choice(n_inst, size=min(n_inst, DUMP_SAMPLE_INSTANCES), replace=False)] = True
+    keep = chosen[inst]
+    sample = np.stack([inst[keep], prod[keep], label[keep]])
+    sample = sample[:, np.lexsort(sample[::-1])]
+    max_rows = (DUMP_BYTES - 8 * len(counts)) // (8 * 3)
+    sample = sample[:, :max_rows]                      # a cap that the default workload (~1 M sampled rows) stays far below
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"bindings_per_instance": counts, "inst": sample[0], "product": sample[1], "product_label": sample[2]}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -169,7 +217,14 @@ def main():
     ap.add_argument("--no-cold", action="store_true", help="skip the cold-start / no-table-cache side measurements")
     ap.add_argument("--allow-host-transport", action="store_true",
                     help="N > 1: when the RCCL communicator cannot be created, measure over the host-staged transport instead of failing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (rooflines, kernel table, cold / no-cache steps, CPU baselines, scan rooflines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's bindings to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.per_instance):
+        ap.error("--dump-outputs: only the single-GPU batched step (--gpus 1, without --per-instance)")
 
     import threading
     import torch
@@ -211,23 +266,18 @@ def main():
     del g, s, p, o
     load_s = time.time() - t0
 
-    rng = np.random.default_rng(12345)
+    rng = np.random.default_rng(BATCH_SEED)
     n_batches = args.steps + args.warmup
     Q = args.queries
     if Q > ds.n_products:
         raise SystemExit(f"--queries {Q} exceeds the {ds.n_products} products of this scale (instances of one batch are distinct products)")
     # every step gets its own query mix: Q distinct products, drawn independently per batch (same seed on every rank)
-    all_products = np.array([ds.product(i) for i in range(ds.n_products)], dtype=np.uint32)
-    def draw(n_inst):
-        """one batch: draws of Q distinct products each (a batch of more than Q instances repeats products, as a BSBM driver's
-        uniform draws would; instance tags stay distinct)"""
-        parts = [all_products[rng.choice(ds.n_products, size=min(Q, n_inst - k), replace=False)] for k in range(0, n_inst, Q)]
-        return np.ascontiguousarray(np.concatenate(parts))
+    draw = lambda n_inst: draw_batch(rng, ds, Q, n_inst)
     Q_step = Q * world if args.scaling == "weak" else Q      # instances per step over all ranks
     batches = [draw(Q_step) for _ in range(n_batches)]
     # N > 1: a short run of the other scaling mode after the timed region (3 warm-up + 5 timed steps), reported beside the headline
     Q_other = Q if args.scaling == "weak" else Q * world
-    other_batches = [draw(Q_other) for _ in range(8)] if world > 1 and not args.per_instance else []
+    other_batches = [draw(Q_other) for _ in range(8)] if args.full and world > 1 and not args.per_instance else []
     products = np.concatenate(batches)                   # the instances the latency / CPU-baseline samples are taken from
 
     kstats = {}
@@ -426,9 +476,8 @@ def main():
                 nxt = start(i + 1) if i + 1 < len(bs) else None
                 t_b = time.perf_counter()
                 total += phase_b(box["tab"], timing)
-                if timing:
-                    phase_ms[0] += box["t"][0]; phase_ms[1] += box["t"][1]; phase_ms[2] += (time.perf_counter() - t_b) * 1e3
-                    phase_ms[3] += waited                                      # what phase A + exchange cost beyond the previous phase B
+                phase_ms[0] += box["t"][0]; phase_ms[1] += box["t"][1]; phase_ms[2] += (time.perf_counter() - t_b) * 1e3
+                phase_ms[3] += waited                                          # what phase A + exchange cost beyond the previous phase B
             return total
 
     if not args.per_instance:
@@ -453,13 +502,14 @@ def main():
     else:
         for b in batches[:args.warmup]:
             step(b, False)
-    # Per-kernel HIP events cost stream time (two events per launch, ~5 us each: a tenth of a 0.6 ms step).  The timed region
-    # therefore brackets ONLY the kernel that took longest when every launch was timed (one untimed step here) — the kernel the
-    # `roofline` object is about; the table of all kernels is measured right after the timed region, with every launch bracketed.
-    focus = 1 if args.per_instance else 2
-    if not args.per_instance:
+    # Per-kernel HIP events cost stream time (two events per launch, ~5 us each: a tenth of a 0.6 ms step).  With --full the timed
+    # region therefore brackets ONLY the kernel that took longest when every launch was timed (one untimed step here) — the kernel
+    # the `roofline` object is about; the table of all kernels is measured right after the timed region, with every launch
+    # bracketed.  A plain run brackets nothing.
+    focus = (1 if args.per_instance else 2) if args.full else False
+    if args.full and not args.per_instance:
         step(batches[0], 1)
-    kstats.clear(); lat_ms.clear()
+    kstats.clear(); lat_ms.clear(); phase_ms[:] = [0.0] * 4     # (host clock readings: taken in every mode, kept for the timed steps)
     barrier()
     t0 = time.perf_counter()
     local_rows = 0
@@ -470,9 +520,11 @@ def main():
             local_rows += step(b, focus)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:                      # the plan still holds the last timed step's bindings
+        dump_outputs(plan.fetch(), Q_step, args.dump_outputs)
     kstats_timed = dict(kstats)                # the dominant kernel(s), from the timed region
     kstats_steps = args.steps
-    if not args.per_instance:                  # every kernel, from three further steps (not part of `value`)
+    if args.full and not args.per_instance:    # every kernel, from three further steps (not part of `value`)
         saved_phase = list(phase_ms)
         kstats.clear()
         extra = batches[args.warmup:args.warmup + min(3, args.steps)]
@@ -511,7 +563,7 @@ def main():
 
     # ------------------------------------------------------------------ sharded run: are the shards' bindings the unsharded answer?
     shard_check = None
-    if dist is not None and not args.no_shard_check:
+    if args.full and dist is not None and not args.no_shard_check:
         def checksum(cols):      # order-independent (count, sum of per-row mixes mod 2^64) of a binding table
             a, b, c = (np.asarray(x, dtype=np.uint64) for x in cols)
             with np.errstate(over="ignore"):
@@ -591,7 +643,7 @@ def main():
     # step — rdfgpu_store_drop_tables, what any extend / remove does to the caches — so the step itself builds the CSR / direct /
     # decoded-value tables and the band join's entries again before it joins.
     fused_rebuild = None
-    if world == 1 and not args.per_instance and not args.no_cold and not args.no_table_cache and cold is not None:
+    if args.full and world == 1 and not args.per_instance and not args.no_cold and not args.no_table_cache and cold is not None:
         ms_fr, rows_fr, detail = [], 0, None
         for b in batches[-min(5, len(batches)):]:
             store.drop_tables()
@@ -615,7 +667,7 @@ def main():
     # RDFGPU_OPT_NO_TABLE_CACHE: nothing survives an execution — every HashJoinExec builds its table inside the step, like
     # the reference's HashJoinExec(CollectLeft) does per query (..Q5 (Execution Plan).snap:10-30).  Like for like with a
     # per-query engine; the headline above is the steady state with the slices' tables cached per store version.
-    if world == 1 and not args.per_instance and not args.no_cold and not args.no_table_cache and cold is not None:
+    if args.full and world == 1 and not args.per_instance and not args.no_cold and not args.no_table_cache and cold is not None:
         plan_nc = store.plan(bsbm.q5_batch_plan(ds)).set_option("NO_TABLE_CACHE", 1)
         def step_nc(batch):
             t, ptrs, n = params_on_device(batch)
@@ -685,7 +737,7 @@ def main():
     single = None
     single_drained = None
     timed_check = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         sample = [int(x) for x in products[:max(8, args.cpu_sample)]]
         lat, lat_drained = [], []
         for x in sample + [int(y) for y in products[len(sample):len(sample) + 24]]:   # the reference's per-query protocol, one stream:
@@ -700,7 +752,7 @@ def main():
             lat.append((t2 - t1) * 1e3); lat_drained.append((t3 - t1) * 1e3)
         single = round(float(np.median(lat)), 3)
         single_drained = round(float(np.median(lat_drained)), 3)
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
         from oracle import oracle as orc
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import kat_util as ku
@@ -849,7 +901,7 @@ def main():
                 out["config"]["speedup_per_query_vs_cpu_port_all_cores"] = round((1e3 / single) / cpu["all_cores"]["queries_per_s"], 1)
         if cpu and cpu.get("tuned_columnar"):
             out["config"]["speedup_batched_vs_batched_columnar_cpu"] = round((n_q / elapsed) / cpu["tuned_columnar"]["queries_per_s"], 1)
-        if world == 1 and not args.no_scan:
+        if args.full and world == 1 and not args.no_scan:
             # the BGP scan + FILTER kernel on a partition larger than the Infinity Cache (BASELINE config 2)
             mem("the Q5 part")
             out["scan_roofline"] = scan_roofline(rf, local_rank, args.scan_log2_rows)

@@ -55,9 +55,42 @@ def test_pmc_traffic_is_quoted_only_for_the_same_workload_and_the_same_kernel_so
             assert t is None or (os.path.basename(src) != f and json.load(open(os.path.join(ROOT, src))).get("_source_sha16") == now), (f, src)
 
 
+def test_dump_outputs_depend_only_on_the_multiset_of_bindings(tmp_path):
+    """--dump-outputs: float64 .npy files within the size cap, identical for the same bindings in another row order, different
+    when one binding differs"""
+    import numpy as np
+    b = load_bench()
+    rng = np.random.default_rng(3)
+    n_inst = 20000
+    inst = rng.integers(1, n_inst + 1, 300_000).astype(np.uint32)
+    prod = rng.integers(1, 1 << 30, len(inst)).astype(np.uint32)       # ids above 2^24: float32 would round them
+    label = rng.integers(1, 1 << 30, len(inst)).astype(np.uint32)
+    perm = rng.permutation(len(inst))
+    d1, d2, d3 = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    out = b.dump_outputs([inst, prod, label], n_inst, str(d1))
+    b.dump_outputs([inst[perm], prod[perm], label[perm]], n_inst, str(d2))
+    names = sorted(os.listdir(d1))
+    assert names == ["bindings_per_instance.npy", "inst.npy", "product.npy", "product_label.npy"]
+    assert sum(os.path.getsize(d1 / n) for n in names) <= b.DUMP_BYTES
+    for n in names:
+        a1, a2 = np.load(d1 / n), np.load(d2 / n)
+        assert a1.dtype == np.float64
+        np.testing.assert_array_equal(a1, a2)
+    counts = np.load(d1 / "bindings_per_instance.npy")
+    assert len(counts) == n_inst and counts.sum() == len(inst)
+    np.testing.assert_array_equal(counts, np.bincount(inst, minlength=n_inst + 1)[1:])
+    tags = np.load(d1 / "inst.npy")
+    assert len(np.unique(tags)) <= b.DUMP_SAMPLE_INSTANCES and len(tags) == counts[np.unique(tags).astype(int) - 1].sum()
+    np.testing.assert_array_equal(np.load(d1 / "product.npy"), out["product"].astype(np.float64))   # exact u32 round trip
+    k = int(np.flatnonzero(np.isin(inst, out["inst"]))[0])                  # one binding of a sampled instance changes
+    label2 = label.copy(); label2[k] ^= 1
+    b.dump_outputs([inst, prod, label2], n_inst, str(d3))
+    assert not np.array_equal(np.load(d1 / "product_label.npy"), np.load(d3 / "product_label.npy"))
+
+
 def test_bench_flags_follow_the_contract():
     src = open(os.path.join(ROOT, "bench.py")).read()
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert f'"{flag}"' in src
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"ms_per_step"', '"higher_is_better"', '"scaling"', '"vs_baseline"', '"dtype"', '"data"',
                 '"config"', '"roofline"', '"cpu_baseline"', '"workload"'):
