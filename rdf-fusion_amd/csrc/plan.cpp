@@ -28,6 +28,17 @@ namespace {
 bool is_cmp(u8 op) {
   return op == RDFGPU_EX_GT || op == RDFGPU_EX_LT || op == RDFGPU_EX_GEQ || op == RDFGPU_EX_LEQ || op == RDFGPU_EX_EQ || op == RDFGPU_EX_NEQ;
 }
+bool range_op(u8 op) { return op == RDFGPU_EX_GT || op == RDFGPU_EX_LT || op == RDFGPU_EX_GEQ || op == RDFGPU_EX_LEQ; }
+// whether column `c` of a join's [left cols, right cols] schema belongs to its build side
+bool on_build_side(const LdsJoinArgs& a, u32 c) { return (c < a.n_left_cols) == (a.build_is_left != 0); }
+
+// The literal, arithmetic and comparison of one half of the window shape (detect_join_filter_shape 3) that starts at node `o`.
+TvLiteral window_literal(const rdfgpu_expr_node* e, u32 o) {
+  TvLiteral l{};
+  l.lo = e[o + 4].lo; l.hi = e[o + 4].hi; l.aux = e[o + 4].u; l.tag = e[o + 4].tag; l.flags = e[o + 4].flags;
+  l.arith_sub = e[o + 5].op == RDFGPU_EX_SUB; l.cmp_op = e[o + 6].op;
+  return l;
+}
 
 // Type-checks a postfix program against `n_cols` input columns; returns the kind it leaves.
 u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 0) {
@@ -632,12 +643,10 @@ u64* Plan::new_counter() {
   if (counters_used >= 255) fail(RDFGPU_ERR_UNSUPPORTED, "plan needs more than 255 cardinality counters");   // slot 255: run-time error flags
   return counters + counters_used++;
 }
-u64 Plan::read_u64(const u64* dev) {
-  u64 v = 0;
-  RDFGPU_HIP(hipMemcpyAsync(&v, dev, sizeof v, hipMemcpyDeviceToHost, stream));
+void Plan::read_back(void* host, const void* dev, size_t bytes) {
+  RDFGPU_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
   RDFGPU_HIP(hipStreamSynchronize(stream));
   metrics.host_syncs++;
-  return v;
 }
 
 // First execution of a plan over big caller-supplied tables (a batch of query instances): nothing is known yet, so every
@@ -752,8 +761,7 @@ void Plan::execute() {
     LocateJob* jobs_dev = static_cast<LocateJob*>(ctx->jobs_dev);
     RDFGPU_HIP(hipMemcpyAsync(jobs_dev, jobs, sources.size() * sizeof(LocateJob), hipMemcpyHostToDevice, stream));
     timed(KC_LOCATE, 0, sources.size(), nullptr, 0, nullptr, 0, 0, [&] { launch_locate(jobs_dev, (u32)sources.size(), ctx->lohi_dev, stream); });
-    RDFGPU_HIP(hipMemcpyAsync(ctx->lohi_host, ctx->lohi_dev, sources.size() * kLocateWords * sizeof(u64), hipMemcpyDeviceToHost, stream));
-    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+    read_back(ctx->lohi_host, ctx->lohi_dev, sources.size() * kLocateWords * sizeof(u64));
     for (size_t i = 0; i < sources.size(); i++) {
       const u64* w = ctx->lohi_host + kLocateWords * i;
       SourceInfo& s = sources[i];
@@ -777,7 +785,6 @@ void Plan::execute() {
   }
   bool slow_missed = false;
   for (const BandBlockCounter& c : band_block_counters) {
-    if (!c.node) continue;
     c.node->band_blocks = ctx->counters_host[c.counter];
     c.node->band_slow_rows = ctx->counters_host[c.slow_counter] & 0xFFFFFFFFull;
     c.node->band_run_stats = ctx->counters_host[c.runs_counter];
@@ -830,11 +837,7 @@ DevTable Plan::exec_node(u32 idx) {
     case RDFGPU_NODE_TOPK: t = exec_topk(nd); break;
     case RDFGPU_NODE_CLOSURE: {
       const DevTable in = exec_node((u32)nd.d.left);
-      u64 n = in.cap;
-      if (in.n_dev && in.cap) {
-        RDFGPU_HIP(hipMemcpyAsync(&n, in.n_dev, sizeof(u64), hipMemcpyDeviceToHost, stream));
-        RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-      }
+      const u64 n = in.n_dev && in.cap ? read_back<u64>(in.n_dev) : in.cap;
       u32* out[3] = {nullptr, nullptr, nullptr};
       ClosureStats cs;
       const u64 rows = closure_exec(in.cols[0], in.cols[1], in.cols[2], n, nd.d.join_type == 1, stream, [&](u64 m) { return scratch<u32>(m); }, out, &cs);
@@ -922,9 +925,7 @@ DevTable Plan::exec_source(NodeInfo& nd) {
   for (int k = 0; k < 4; k++) n_pred_cols += job.pred[k].kind != RDFGPU_PRED_NONE && job.pred[k].kind != RDFGPU_PRED_FALSE;
   timed(KC_SCAN_COUNT, 0, n, nullptr, 4ull * n_pred_cols, nullptr, 0, 0, [&] { launch_scan_count(job, counts, stream); });
   timed(scan_class(n_blocks + 1), 0, n_blocks + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(counts, offs, n_blocks + 1, temp, tb, stream); });
-  u32 total = 0;
-  RDFGPU_HIP(hipMemcpyAsync(&total, offs + n_blocks, 4, hipMemcpyDeviceToHost, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+  const u32 total = read_back<u32>(offs + n_blocks);
   t.cap = total;
   if (total == 0) return t;
   for (u32 c = 0; c < s.n_out; c++) { job.out[c] = scratch<u32>(total); t.cols[c] = job.out[c]; }
@@ -1087,9 +1088,7 @@ DevTable Plan::exec_topk(NodeInfo& nd) {
   a.n_groups = 1;
   if (a.has_group) {
     timed(KC_TOPK_MAX, 0, in.cap, in.n_dev, 4, nullptr, 0, 0, [&] { launch_topk_max(a.in[a.group_col], in.n_dev, in.cap, flags, stream); });
-    u32 mx = 0;
-    RDFGPU_HIP(hipMemcpyAsync(&mx, flags, sizeof(u32), hipMemcpyDeviceToHost, stream));
-    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+    const u32 mx = read_back<u32>(flags);
     if (mx >= (1u << 24)) fail(RDFGPU_ERR_UNSUPPORTED, "TopK: group ids up to %u (dense ids below 2^24 expected)", mx);
     a.n_groups = mx + 1;
   }
@@ -1114,8 +1113,7 @@ DevTable Plan::exec_topk(NodeInfo& nd) {
   exclusive_scan_u32(a.out_counts, a.out_offsets, ng + 1, temp, tb, stream);
   timed(KC_TOPK_WRITE, 0, 0, nullptr, 0, n_out, 0, 8ull * nd.n_proj, [&] { launch_topk_write(a, stream); });
   const u32 i0 = (u32)(n_out - counters);
-  RDFGPU_HIP(hipMemcpyAsync(ctx->counters_host + i0, counters + i0, 2 * sizeof(u64), hipMemcpyDeviceToHost, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+  read_back(ctx->counters_host + i0, counters + i0, 2 * sizeof(u64));
   if ((ctx->counters_host[i0 + 1] >> 32) != 0) fail(RDFGPU_ERR_UNSUPPORTED, "TopK: SORT_BY_TERM over a column that is not all strings / IRIs / blank nodes");
   t.cap = std::min<u64>(out_cap, ctx->counters_host[i0]);
   t.n_dev = n_out;
@@ -1223,7 +1221,8 @@ bool Plan::plan_chain(NodeInfo& top, ChainRequest& req) {
 
 // Resolves the chain against the base join's inputs; false (nothing changed in `a` that matters) if some column cannot
 // be addressed the way the kernel needs.
-bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& L, const DevTable& R, bool build_left, LdsJoinArgs& a, u64& stage_bytes, BandArgs* band, bool* use_band) {
+bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& L, const DevTable& R, bool build_left, SliceTable* build_table, LdsJoinArgs& a,
+                       u64& stage_bytes, BandArgs* band, bool* use_band) {
   std::vector<ColRef> cur(base.n_proj);
   for (u32 k = 0; k < base.n_proj; k++) {
     const u32 c = base.proj[k];
@@ -1261,11 +1260,9 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
       st.is_eq = N.prog.nodes[2].op == RDFGPU_EX_ID_EQ;
     } else if (N.shape == 3) {
       const rdfgpu_expr_node* e = N.prog.nodes;
-      auto lit = [&](u32 o) { TvLiteral l{}; l.lo = e[o + 4].lo; l.hi = e[o + 4].hi; l.aux = e[o + 4].u; l.tag = e[o + 4].tag; l.flags = e[o + 4].flags;
-                              l.arith_sub = e[o + 5].op == RDFGPU_EX_SUB; l.cmp_op = e[o + 6].op; return l; };
       st.fs = 3; n_fcols = 4;
       st.f[0] = resolve(e[0].u); st.f[1] = resolve(e[2].u); st.f[2] = resolve(e[8].u); st.f[3] = resolve(e[10].u);
-      st.l0 = lit(0); st.l1 = lit(8);
+      st.l0 = window_literal(e, 0); st.l1 = window_literal(e, 8);
     } else return false;
     for (u32 q = 0; q < n_fcols; q++) if (st.f[q].src > 1 && st.f[q].src != 2u + (u32)t) return false;   // base columns or this stage's
     // integer window whose x operand is a column of this stage's slice and whose y operands are base columns: use the
@@ -1283,10 +1280,7 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
         u32* bad = reinterpret_cast<u32*>(new_counter());
         launch_fill_i64(val, INT64_MIN, tab->kn, stream);
         launch_direct_values(ln.slice.cols[key_local], st.f[0].ptr, ln.slice.cap, tab->kmin, tab->kn, typed_table(), val, bad, stream);
-        u32 is_bad = 0;
-        RDFGPU_HIP(hipMemcpyAsync(&is_bad, bad, sizeof(u32), hipMemcpyDeviceToHost, stream));
-        RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-        if (is_bad) { store->table_free(val); val = nullptr; }
+        if (read_back<u32>(bad)) { store->table_free(val); val = nullptr; }
         SliceTable::ValueColumn fresh{st.f[0].ptr, val, val != nullptr};
         if (val) {   // value range: the bias of the band join's 32-bit window intervals
           long long* mm = reinterpret_cast<long long*>(new_counter()); (void)new_counter();
@@ -1294,8 +1288,7 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
           RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, stream));
           launch_val_minmax(val, tab->kn, mm, stream);
           long long got[2];
-          RDFGPU_HIP(hipMemcpyAsync(got, mm, sizeof got, hipMemcpyDeviceToHost, stream));
-          RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+          read_back(got, mm, sizeof got);
           fresh.vmin = got[0]; fresh.vmax = got[1];
         }
         tab->values.push_back(fresh);
@@ -1314,19 +1307,17 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
   // stage filters are integer windows between a stage value and probe columns, the chain runs group by group — both
   // sides partitioned by the key, the pair tests in registers — instead of probe row by probe row.
   *use_band = false;
-  if (band && a.csr_off && cur_build_table && !opt.on(RDFGPU_OPT_NO_BAND_JOIN) && arg_slots_used < ExecContext::kArgSlots) {
+  if (band && a.csr_off && build_table && !opt.on(RDFGPU_OPT_NO_BAND_JOIN) && arg_slots_used < ExecContext::kArgSlots) {
     const DevTable& B = build_left ? L : R; const DevTable& Pp = build_left ? R : L;
-    auto from_build = [&](u32 c) { return (c < L.n_cols) == build_left; };
-    auto range_op = [](u8 op) { return op == RDFGPU_EX_GT || op == RDFGPU_EX_LT || op == RDFGPU_EX_GEQ || op == RDFGPU_EX_LEQ; };
     BandArgs b{};
     bool ok = a.n_keys == 1 && (a.has_filter == 0 || a.has_filter == 2) && a.has_probe_filter == 0 && a.visited == nullptr;
     if (ok && a.has_filter == 2) {
-      const bool ab = from_build(a.idp.a), bb = from_build(a.idp.b);
+      const bool ab = on_build_side(a, a.idp.a), bb = on_build_side(a, a.idp.b);
       ok = ab != bb;
       if (ok) { b.has_neq = 1; b.neq_is_eq = a.idp.is_eq; b.neq_build = a.cols[ab ? a.idp.a : a.idp.b]; b.neq_probe = a.cols[ab ? a.idp.b : a.idp.a]; }
     }
     if (ok && a.has_post) {
-      ok = from_build(a.post.col);
+      ok = on_build_side(a, a.post.col);
       b.has_post = 1; b.post_col = a.cols[a.post.col]; b.post_lit = a.post.lit; b.post_is_eq = a.post.is_eq;
     }
     b.n_stages = (u32)req.links.size();
@@ -1352,14 +1343,12 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
       else { ok = b.n_entry_cols < kBandMaxSideCols; if (ok) { b.out_from_row[k] = 0; b.out_sel[k] = (u8)(2 + b.n_entry_cols); b.entry_col[b.n_entry_cols++] = cur[k]; } }
     }
     if (ok) {   // group sizes: the largest decides (one wave joins a whole group), measured once per table
-      SliceTable* tab = cur_build_table;
+      SliceTable* tab = build_table;
       std::unique_lock<std::mutex> building(store->slice_build_mu);
       if (tab->csr_max_group == 0) {
         u32* mx = reinterpret_cast<u32*>(new_counter());
         launch_csr_max_group(a.csr_off, a.direct_n, mx, stream);
-        u32 got = 0;
-        RDFGPU_HIP(hipMemcpyAsync(&got, mx, sizeof got, hipMemcpyDeviceToHost, stream));
-        RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+        const u32 got = read_back<u32>(mx);
         tab->csr_max_group = got ? got : 1;
       }
       ok = tab->csr_max_group <= kBandMaxGroup && B.cap >= 4ull * a.direct_n && Pp.cap * 4 >= a.direct_n && Pp.cap < (1ull << 31);
@@ -1371,11 +1360,10 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
   // the group is kept sorted by that value (built once per store version, kept with the CSR table).
   if (!*use_band) {
     const ChainStage& s0 = stages[0];
-    auto range_op = [](u8 op) { return op == RDFGPU_EX_GT || op == RDFGPU_EX_LT || op == RDFGPU_EX_GEQ || op == RDFGPU_EX_LEQ; };
     const DevTable& B = build_left ? L : R;
-    if (a.csr_off && cur_build_table && s0.val && s0.fs == 3 && s0.key.src == 1 && s0.f[1].src == 0 && s0.f[3].src == 0 &&
+    if (a.csr_off && build_table && s0.val && s0.fs == 3 && s0.key.src == 1 && s0.f[1].src == 0 && s0.f[3].src == 0 &&
         range_op(s0.l0.cmp_op) && range_op(s0.l1.cmp_op) && !opt.on(RDFGPU_OPT_NO_RANGE_INDEX)) {
-      SliceTable* tab = cur_build_table;
+      SliceTable* tab = build_table;
       std::unique_lock<std::mutex> building(store->slice_build_mu);
       SliceTable::RangeIndex* ri = nullptr;
       for (auto& r : tab->ranges) if (r.val == s0.val && r.link_col == s0.key.ptr) ri = &r;
@@ -1387,8 +1375,7 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
         RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, stream));
         launch_range_minmax(s0.key.ptr, a.csr_rows, n, s0.val, s0.kmin, s0.kn, mm, stream);
         long long got[2];
-        RDFGPU_HIP(hipMemcpyAsync(got, mm, sizeof got, hipMemcpyDeviceToHost, stream));
-        RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+        read_back(got, mm, sizeof got);
         if (got[0] <= got[1] && (unsigned long long)(got[1] - got[0]) < 0xFFFFFFF0ull && n < (1ull << 32)) {
           u64* key_in = scratch<u64>(n); u64* key_out = scratch<u64>(n); u32* rows_in = scratch<u32>(n);
           fresh.rows = store->table_alloc<u32>(n);
@@ -1416,6 +1403,17 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
   for (size_t k = 0; k < cur.size(); k++) a.chain_out[k] = cur[k];
   a.n_out_cols = (u32)cur.size();
   return true;
+}
+
+// The held-back write pass of an ordered slice join runs before anything reads its table, except the band join that consumes
+// it: it may stay pending into a join only while the table is that join's probe side — an inner LDS join whose band join took
+// the records last time (the sides as exec_join chooses them below).  exec_lds_join then hands it on to the band join or runs
+// it just before the probe side is read.
+bool Plan::keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const {
+  if (!nd.band_takes_records || nd.d.kind != RDFGPU_NODE_HASH_JOIN || left_join || lf || rf || opt.on(RDFGPU_OPT_NO_LDS_JOIN)) return false;
+  const bool build_left = choose_build_left(nd, L, R, false, false, false);
+  const DevTable& B = build_left ? L : R; const DevTable& P = build_left ? R : L;
+  return (B.cap <= kLdsJoinMaxBuild || !opt.on(RDFGPU_OPT_NO_GLOBAL_TABLE_JOIN)) && P.cols[0] == pending_oj.first_col && B.cols[0] != pending_oj.first_col;
 }
 
 // The held-back write pass of an ordered slice join, run after all: its consumer turned out not to take the band join's records.
@@ -1458,7 +1456,7 @@ DevTable Plan::exec_join(NodeInfo& nd) {
   DevTable L = lf ? exec_node((u32)nodes[nd.d.left].d.left) : exec_node((u32)nd.d.left);
   DevTable R = rf ? exec_node((u32)nodes[nd.d.right].d.left) : exec_node((u32)nd.d.right);
   pending_chain = for_this_join;
-  if (pending_oj.active && !(nd.band_takes_records && nd.d.kind == RDFGPU_NODE_HASH_JOIN && !left_join && !lf && !rf)) flush_pending_oj();
+  if (pending_oj.active && !keeps_pending_oj(nd, L, R, left_join, lf, rf)) flush_pending_oj();
   const NodeInfo* post = nullptr;   // a build-side FilterExec kept as a conjunct of the join filter (see below)
   if (lf || rf) {
     // `col <=|!=> literal` over a store slice: if the join builds on that slice (index join through the slice's cached
@@ -1480,7 +1478,6 @@ DevTable Plan::exec_join(NodeInfo& nd) {
   t.n_cols = nd.n_proj;
 
   if (nd.d.kind == RDFGPU_NODE_CROSS_JOIN) {
-    flush_pending_oj();
     const u64 cap = L.cap * R.cap;
     if (cap == 0) { t.cap = 0; return t; }
     if (cap >= (1ull << 40)) fail(RDFGPU_ERR_UNSUPPORTED, "cross join of %llu x %llu rows", (unsigned long long)L.cap, (unsigned long long)R.cap);
@@ -1510,7 +1507,6 @@ DevTable Plan::exec_join(NodeInfo& nd) {
       return exec_lds_join(nd, L, R, build_left, pf, post);
     }
   }
-  flush_pending_oj();
   JoinArgs a{};
   for (u32 c = 0; c < L.n_cols; c++) a.left[c] = L.cols[c];
   for (u32 c = 0; c < R.n_cols; c++) a.right[c] = R.cols[c];
@@ -1553,10 +1549,7 @@ DevTable Plan::exec_join(NodeInfo& nd) {
     timed(hash ? KC_JOIN_COUNT : KC_NLJ_COUNT, 0, R.cap, R.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0,
           [&] { if (hash) launch_join_count(a, stream); else launch_nlj_count(a, stream); });
     timed(scan_class(R.cap), 0, R.cap, nullptr, 8, nullptr, 0, 0, [&] { inclusive_scan_u32(counts, offs, R.cap, temp, tb, stream); });
-    u32 tot32 = 0;
-    RDFGPU_HIP(hipMemcpyAsync(&tot32, offs + R.cap - 1, 4, hipMemcpyDeviceToHost, stream));
-    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-    total = tot32;
+    total = read_back<u32>(offs + R.cap - 1);
   }
   const u64 cap = total + (left_join ? L.cap : 0);
   if (cap == 0) { t.cap = 0; return t; }
@@ -1569,13 +1562,40 @@ DevTable Plan::exec_join(NodeInfo& nd) {
   }
   t.cap = cap;
   if (left_join) {
-    a.n_out_dev = new_counter();
-    RDFGPU_HIP(hipMemcpyAsync(a.n_out_dev, &total, sizeof(u64), hipMemcpyHostToDevice, stream));
+    u64* n_out = new_counter();
+    RDFGPU_HIP(hipMemcpyAsync(n_out, &total, sizeof(u64), hipMemcpyHostToDevice, stream));
     RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;   // `total` is a stack variable
-    timed(KC_LEFT_TAIL, 0, L.cap, L.n_dev, 1, nullptr, 0, 0, [&] { launch_join_left_unmatched(a, stream); });
-    t.n_dev = a.n_out_dev;
+    left_join_tail(nd, L, R, a.out, a.visited, n_out, 0);
+    t.n_dev = n_out;
   }
   return t;
+}
+
+// The two kernels both direct-address forms start with: min / max of the single key column (one read-back) and, when the id
+// range is at most `max_range` ids, one store per row into a table of one slot per id with a duplicate flag (a second
+// read-back).  The table is kept with the store's tables (`cached`) or is scratch of this execution; `direct` is set only when
+// the keys turned out unique.
+Plan::DirectTable Plan::build_direct(const u32* key, u64 n, u64 max_range, bool cached) {
+  DirectTable d;
+  u32* mm = reinterpret_cast<u32*>(new_counter());   // {min, max}
+  d.flags = reinterpret_cast<u32*>(new_counter());   // {duplicate seen, unsorted seen (build_dense_table)}
+  const u32 init[2] = {0xFFFFFFFFu, 0u};
+  RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, stream));
+  timed(KC_MINMAX, 4ull * n, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_minmax_u32(key, n, mm, stream); });
+  u32 got[2];
+  read_back(got, mm, sizeof got);
+  const u64 range = got[0] <= got[1] ? (u64)(got[1] - got[0]) + 1 : ~0ull;
+  if (range > max_range) return d;
+  d.dense = true; d.kmin = got[0]; d.kn = got[1] - got[0] + 1;
+  // more rows than ids in the range: some key repeats (pigeonhole: null keys only make it more so when they are few; with many nulls the
+  // attempt below would have succeeded — then the CSR form is merely the more general table for the same join) — no direct-address attempt
+  if (n > (u64)d.kn) return d;
+  u32* direct = cached ? store->table_alloc<u32>(d.kn) : scratch<u32>(d.kn);
+  RDFGPU_HIP(hipMemsetAsync(direct, 0xFF, (size_t)d.kn * sizeof(u32), stream));
+  timed(KC_GDIRECT_BUILD, 0, n, nullptr, 8, nullptr, 0, 0, [&] { launch_gdirect_build(key, n, direct, d.kmin, d.kn, d.flags, stream); });
+  if (!read_back<u32>(d.flags)) d.direct = direct;
+  else if (cached) store->table_free(direct);
+  return d;
 }
 
 // The dense join tables of a single-key store slice (decided once per slice and store version, with `slice_build_mu` held):
@@ -1583,45 +1603,22 @@ DevTable Plan::exec_join(NodeInfo& nd) {
 // key) if not; `dense_failed` when the id range is not worth a 4-byte-per-id table.  Costs a few small kernels and host
 // syncs at that time, nothing afterwards.
 void Plan::build_dense_table(SliceTable* st, const u32* key, u64 n) {
-  u32* mm = reinterpret_cast<u32*>(new_counter());     // {min, max}
-  u32* flags = reinterpret_cast<u32*>(new_counter());  // {duplicate seen, unsorted seen}
-  const u32 init[2] = {0xFFFFFFFFu, 0u};
-  RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, stream));
-  timed(KC_MINMAX, 4ull * n, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_minmax_u32(key, n, mm, stream); });
-  u32 got[2];
-  RDFGPU_HIP(hipMemcpyAsync(got, mm, sizeof(got), hipMemcpyDeviceToHost, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
   // "dense" = the id range is worth a 4-B-per-id table: up to 4 ids per row outright; up to 64 ids per row while
   // the table stays small (16 M ids = 64 MB) — a subject-hash shard of a slice keeps the slice's id range with
   // 1/G of its rows, and must not fall off the index-join path for that
-  const u64 range = got[0] <= got[1] ? (u64)(got[1] - got[0]) + 1 : ~0ull;
-  const bool dense = range <= 4 * n + 1024 || (range <= 64 * n + 1024 && range <= (16ull << 20));
-  if (!dense) { st->dense_failed = true; st->dense_tried = true; return; }
+  const DirectTable d = build_direct(key, n, std::max<u64>(4 * n + 1024, std::min<u64>(64 * n + 1024, 16ull << 20)), true);
+  if (!d.dense) { st->dense_failed = true; st->dense_tried = true; return; }
   metrics.tables_built++;
-  const u32 kmin = got[0], kn = got[1] - got[0] + 1;
+  const u32 kmin = d.kmin, kn = d.kn;
   st->kmin = kmin; st->kn = kn;
-  // more rows than ids in the range: some key repeats (pigeonhole: null keys only make it more so when they are few; with many nulls the
-  // attempt below would have succeeded — then the CSR form is merely the more general table for the same join) — no direct-address attempt
-  if (n <= (u64)kn) {
-    u32* direct = store->table_alloc<u32>(kn);
-    RDFGPU_HIP(hipMemsetAsync(direct, 0xFF, (size_t)kn * sizeof(u32), stream));
-    timed(KC_GDIRECT_BUILD, 0, n, nullptr, 8, nullptr, 0, 0, [&] { launch_gdirect_build(key, n, direct, kmin, kn, flags, stream); });
-    u32 is_dup = 0;
-    RDFGPU_HIP(hipMemcpyAsync(&is_dup, flags, sizeof(u32), hipMemcpyDeviceToHost, stream));
-    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-    if (!is_dup) { st->direct = direct; st->dense_tried = true; return; }
-    store->table_free(direct);
-  }
+  if (d.direct) { st->direct = d.direct; st->dense_tried = true; return; }
   // duplicates: CSR (offsets + row ids grouped by key) — by boundary searches when the slice is sorted by the key, by one radix sort otherwise
   u32* off = store->table_alloc<u32>((u64)kn + 2); u32* rows = nullptr;
   if (n >= (1ull << 32)) fail(RDFGPU_ERR_UNSUPPORTED, "CSR table of %llu rows", (unsigned long long)n);
   u32* rel = scratch<u32>(n);
-  timed(KC_CSR_HIST, 0, n, nullptr, 8, nullptr, 0, 0, [&] { launch_csr_rel_keys(key, n, kmin, kn, rel, flags + 1, stream); });
-  u32 unsorted = 0;
-  RDFGPU_HIP(hipMemcpyAsync(&unsorted, flags + 1, sizeof(u32), hipMemcpyDeviceToHost, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+  timed(KC_CSR_HIST, 0, n, nullptr, 8, nullptr, 0, 0, [&] { launch_csr_rel_keys(key, n, kmin, kn, rel, d.flags + 1, stream); });
   const u32* grouped = rel;
-  if (unsorted) {   // else the slice is sorted by the key: rows[] is the identity and is never materialised
+  if (read_back<u32>(d.flags + 1)) {   // unsorted; else the slice is sorted by the key: rows[] is the identity and is never materialised
     rows = store->table_alloc<u32>(n);
     u32 bits = 1;
     while ((1ull << bits) <= kn) bits++;             // keys 0 .. kn (kn = joins nothing: sorts to the end)
@@ -1638,249 +1635,22 @@ void Plan::build_dense_table(SliceTable* st, const u32* key, u64 n) {
   st->dense_tried = true;
 }
 
-// The direct-address form for a build side that is NOT cached (RDFGPU_OPT_NO_TABLE_CACHE, or an intermediate with a host-known row
-// count): built inside this execution, in scratch memory, when the single key turns out unique over a dense id range — the same two
-// kernels as the cached form (min / max, then one store per row with a duplicate flag) and two host round trips.  4 bytes per ID
-// instead of 8 bytes per SLOT at load <= 0.5: the 285 k-row property slices of BSBM-100M are 1.1 MB (resident in every XCD's L2)
-// instead of an 8 MB hash table that 0.54 G random probes fetch from the Infinity Cache line by line.  false: not unique / not dense.
-bool Plan::build_transient_direct(LdsJoinArgs& a, u64 n) {
-  const u32* key = a.build_key[0];
-  u32* mm = reinterpret_cast<u32*>(new_counter());     // {min, max}
-  u32* flags = reinterpret_cast<u32*>(new_counter());  // {duplicate seen, -}
-  const u32 init[2] = {0xFFFFFFFFu, 0u};
-  RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, stream));
-  timed(KC_MINMAX, 4ull * n, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_minmax_u32(key, n, mm, stream); });
-  u32 got[2];
-  RDFGPU_HIP(hipMemcpyAsync(got, mm, sizeof(got), hipMemcpyDeviceToHost, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-  const u64 range = got[0] <= got[1] ? (u64)(got[1] - got[0]) + 1 : ~0ull;
-  if (range > 4 * n + 1024 || n > range) return false;   // sparse ids, or more rows than ids (some key repeats)
-  const u32 kmin = got[0], kn = (u32)range;
-  u32* direct = scratch<u32>(kn);
-  RDFGPU_HIP(hipMemsetAsync(direct, 0xFF, (size_t)kn * sizeof(u32), stream));
-  timed(KC_GDIRECT_BUILD, 0, n, nullptr, 8, nullptr, 0, 0, [&] { launch_gdirect_build(key, n, direct, kmin, kn, flags, stream); });
-  u32 is_dup = 0;
-  RDFGPU_HIP(hipMemcpyAsync(&is_dup, flags, sizeof(u32), hipMemcpyDeviceToHost, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-  if (is_dup) return false;
-  metrics.tables_built++;
-  a.direct = direct; a.direct_min = kmin; a.direct_n = kn;
-  return true;
-}
-
-// HashJoinExec whose build side fits one workgroup's LDS: one fused kernel, optimistic output capacity.
+// HashJoinExec whose build side is one table — a copy per workgroup in LDS, a store slice's cached table, a table built in this
+// execution, or one per partition: one fused kernel, optimistic output capacity.
 DevTable Plan::exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R, bool build_left, const NodeInfo* probe_filter, const NodeInfo* post_filter) {
-  // a LEFT join built on its right input preserves its PROBE side (choose_build_left): for everything below it is an inner join whose
-  // kernel adds one null-extended row per unmatched probe row — no visited flags, no tail pass
-  const bool probe_outer = nd.d.join_type == RDFGPU_JOIN_LEFT && !build_left;
-  const bool left_join = nd.d.join_type == RDFGPU_JOIN_LEFT && build_left;
-  const DevTable& B = build_left ? L : R;
-  const DevTable& P = build_left ? R : L;
-  DevTable t;
-  t.n_cols = nd.n_proj;
-  LdsJoinArgs a{};
-  cur_build_table = nullptr;
-  for (u32 c = 0; c < L.n_cols; c++) a.cols[c] = L.cols[c];
-  for (u32 c = 0; c < R.n_cols; c++) a.cols[L.n_cols + c] = R.cols[c];
-  a.n_left_cols = L.n_cols; a.n_out_cols = nd.n_proj;
-  for (u32 c = 0; c < nd.n_proj; c++) a.proj[c] = nd.proj[c];
-  a.build_is_left = build_left ? 1 : 0;
-  a.probe_outer = probe_outer ? 1u : 0u;
-  a.n_keys = nd.d.n_keys;
-  u32 build_keys[RDFGPU_MAX_KEYS] = {}, probe_keys[RDFGPU_MAX_KEYS] = {};
-  for (u32 k = 0; k < a.n_keys; k++) {
-    build_keys[k] = build_left ? nd.d.left_keys[k] : nd.d.right_keys[k];
-    probe_keys[k] = build_left ? nd.d.right_keys[k] : nd.d.left_keys[k];
-    a.build_key[k] = B.cols[build_keys[k]];
-    a.probe_key[k] = P.cols[probe_keys[k]];
-  }
-  a.n_build_dev = B.n_dev; a.n_build_cap = B.cap; a.n_probe_dev = P.n_dev; a.n_probe_cap = P.cap;
-  if (B.cap >= (1ull << 30)) fail(RDFGPU_ERR_UNSUPPORTED, "build side of %llu rows", (unsigned long long)B.cap);
-  u32 slots = 64;
-  while (slots < 2 * B.cap) slots <<= 1;
-  bool use_part = false; PartArgs part{};
-  // LDS copy per workgroup vs ONE table in HBM/L2: the LDS form pays the build once per workgroup and, above
-  // ~16 KiB of table, costs occupancy (a 128 KiB table = one workgroup per CU = latency-bound probes).
-  const u64 lds_limit = std::min<u64>(opt.v[RDFGPU_OPT_LDS_MAX_BUILD], kLdsJoinMaxBuild);
-  const bool global_table = B.cap > lds_limit;
-  // Every lane of a wave waits for the longest chain among its 64 probes, so short chains matter more than a
-  // small table: LDS tables get load <= 0.25 and at least 2048 slots (16 KiB), HBM tables under 1 MiB load <= 0.125.
-  if (!global_table) { while ((slots < 4 * B.cap || slots < 2048) && slots < 2 * kLdsJoinMaxBuild) slots <<= 1; }
-  else { while (slots < 8 * B.cap && (u64)slots * sizeof(uint2) < (1u << 20)) slots <<= 1; }
-  a.tbl_mask = slots - 1;
-  // The HBM table of a build side that is a pure slice of the store (a param-free scan: label, simProperty…) is the
-  // same for every plan until the store changes: it is built once per store version and kept on the store.
-  bool build_now = false;
-  if (global_table) {
-    const bool cacheable = B.stable_id != 0 && B.n_dev == nullptr && !opt.on(RDFGPU_OPT_NO_TABLE_CACHE);
-    if (cacheable) {
-      SliceKey sk; sk.n_keys = a.n_keys; sk.rows = B.cap;
-      for (u32 k = 0; k < a.n_keys; k++) sk.key[k] = a.build_key[k];
-      SliceTable* st = store->slice_table(sk);
-      cur_build_table = st;
-      std::unique_lock<std::mutex> building(store->slice_build_mu);
-      // Dense forms first (one single key over a dense id range): direct-address if the keys are unique, CSR if not.
-      // Decided once per slice; costs a few small kernels and host syncs at that time, nothing afterwards.
-      if (!st->dense_tried && a.n_keys == 1 && !opt.on(RDFGPU_OPT_NO_DIRECT_TABLE)) build_dense_table(st, a.build_key[0], B.cap);
-      if (st->csr_off) {
-        a.csr_off = st->csr_off; a.csr_rows = st->csr_rows; a.direct_min = st->kmin; a.direct_n = st->kn;
-        // lanes per probe row: a small probe side with a large fan-out is spread over the chip
-        // (first execution: the table's mean rows per key stands in for the unknown fan-out)
-        const u64 fan = nd.has_last ? nd.last_rows / (P.cap ? P.cap : 1) : B.cap / (st->kn ? st->kn : 1);
-        // measured on the BSBM candidate join (fan-out 111): 8 lanes per row is best at 75 k and at 1.2 M probe rows alike
-        // (a tiny probe side — a single query's constants — is latency-bound instead: spread each row over up to a whole wave)
-        const bool tiny = P.cap < 4096;
-        u32 rl = 0;
-        while (rl < (tiny ? 6u : 3u) && ((tiny ? 2ull : 16ull) << rl) <= fan && (P.cap << (rl + 1)) <= (1ull << 25)) rl++;
-        if (opt.v[RDFGPU_OPT_CSR_ROW_LANES_LOG2]) rl = (u32)std::min<u64>(6, opt.v[RDFGPU_OPT_CSR_ROW_LANES_LOG2] - 1);
-        if (probe_outer) rl = 0;   // (one lane per probe row: the row's null-extended candidate is produced once)
-        a.row_lanes_log2 = rl;
-      } else if (st->direct) {
-        a.direct = st->direct; a.direct_min = st->kmin; a.direct_n = st->kn;
-      } else {
-        if (!st->slots || st->mask != a.tbl_mask) {   // build the hash form now, under the lock, and publish it only when complete
-          if (st->slots) { store->table_free(st->slots); st->slots = nullptr; }
-          void* mem = store->table_alloc<uint2>(slots);
-          metrics.tables_built++;
-          a.gslots = static_cast<uint2*>(mem);
-          RDFGPU_HIP(hipMemsetAsync(a.gslots, 0xFF, (size_t)slots * sizeof(uint2), stream));
-          timed(KC_GJOIN_BUILD, 0, B.cap, B.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0, [&] { launch_gjoin_build(a, stream); });
-          RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-          st->slots = mem; st->mask = a.tbl_mask;
-          }
-        a.gslots = static_cast<uint2*>(st->slots);
-      }
-    } else if (a.n_keys <= 2 && !probe_filter && !post_filter && !opt.on(RDFGPU_OPT_NO_PARTITIONED_JOIN) && B.cap >= opt.v[RDFGPU_OPT_PARTITION_MIN_BUILD] &&
-               B.cap < (1ull << 31) && P.cap < (1ull << 31)) {
-      use_part = true;     // radix-partition both sides; every partition's table is built in LDS (part_join.hip)
-    } else {
-      // a large probe side pays for two host round trips with every probe that hits a 4-byte entry in L2 instead of an 8-byte slot beyond it
-      bool direct_built = false;
-      if (a.n_keys == 1 && B.n_dev == nullptr && B.cap >= 4096 && P.cap >= (1ull << 22) && !nd.transient_direct_failed && !opt.on(RDFGPU_OPT_NO_DIRECT_TABLE)) {
-        direct_built = build_transient_direct(a, B.cap);
-        nd.transient_direct_failed = !direct_built;
-      }
-      if (!direct_built) {
-        a.gslots = scratch<uint2>(slots);
-        build_now = true;
-        RDFGPU_HIP(hipMemsetAsync(a.gslots, 0xFF, (size_t)slots * sizeof(uint2), stream));
-      }
-    }
-  }
-  if (P.cap >= (1ull << 32)) fail(RDFGPU_ERR_UNSUPPORTED, "probe side of %llu rows", (unsigned long long)P.cap);
-  {
-    // Candidate queue per wave: a full queue costs one output reservation (a same-address atomic, ~88 per
-    // microsecond chip-wide), an oversized one costs occupancy (8 queues x 8 B x entries of LDS per workgroup).
-    // Sized from the matches a wave can expect out of one tile (64 x rows-per-lane probe rows), which is what a
-    // workgroup of an HBM-table join sees in its whole life; "expected" = the previous execution's cardinality
-    // when known, else one match per probe row.  A direct-address table has at most one match per row.
-    const u32 q_env = (u32)opt.v[RDFGPU_OPT_JOIN_WAVE_Q];
-    const u64 per_tile = 64ull * (u64)lds_join_items(P.cap << a.row_lanes_log2, global_table);
-    const u64 expect = nd.has_last ? nd.last_rows : P.cap;
-    u64 want = a.direct ? per_tile : (expect * per_tile * 3 / 2) / (P.cap ? P.cap : 1);
-    u32 q = 256;
-    while (q < want && q < 1024) q <<= 1;
-    if (!global_table && (size_t)slots * sizeof(uint2) > 64 * 1024) q = 256;
-    a.wave_q = q_env ? q_env : q;
-    // partitioned join: a sparse output (the previous execution found less than one match per 8 probe rows) needs no deep queues —
-    // 52 KB of LDS per workgroup instead of 64: three workgroups per CU instead of two
-    if (use_part) a.wave_q = nd.has_last && !nd.last_scaled && nd.last_rows * 8 < P.cap ? 64 : 256;
-  }
-  a.probe_col_base = build_left ? L.n_cols : 0;
-  a.has_filter = (u32)nd.shape;   // 0 none / 1 generic VM / 3 window
-  if (nd.shape == 1) a.prog = upload_program(nd.prog);
-  if (nd.shape == 2) { a.idp.a = nd.prog.nodes[0].u; a.idp.b = nd.prog.nodes[1].u; a.idp.is_eq = nd.prog.nodes[2].op == RDFGPU_EX_ID_EQ; }
-  if (nd.shape == 3) {
-    const rdfgpu_expr_node* e = nd.prog.nodes;
-    auto lit = [&](u32 o) { TvLiteral l{}; l.lo = e[o + 4].lo; l.hi = e[o + 4].hi; l.aux = e[o + 4].u; l.tag = e[o + 4].tag; l.flags = e[o + 4].flags;
-                            l.arith_sub = e[o + 5].op == RDFGPU_EX_SUB; l.cmp_op = e[o + 6].op; return l; };
-    a.win.x0 = e[0].u; a.win.y0 = e[2].u; a.win.x1 = e[8].u; a.win.y1 = e[10].u;
-    a.win.l0 = lit(0); a.win.l1 = lit(8);
-  }
-  a.has_probe_filter = probe_filter ? (probe_filter->shape == 1 ? 1u : 2u) : 0u;
-  if (probe_filter) {
-    if (probe_filter->shape == 1) {
-      const rdfgpu_expr_node* e = probe_filter->prog.nodes;
-      a.pid.col = a.probe_col_base + e[0].u; a.pid.lit = e[1].u; a.pid.is_eq = e[2].op == RDFGPU_EX_ID_EQ;
-    } else a.probe_prog = upload_program(probe_filter->prog);
-  }
-  if (post_filter) {   // FilterExec of the build side's input, columns relative to that input
-    const rdfgpu_expr_node* e = post_filter->prog.nodes;
-    a.has_post = 1;
-    a.post.col = (build_left ? 0 : L.n_cols) + e[0].u; a.post.lit = e[1].u; a.post.is_eq = e[2].op == RDFGPU_EX_ID_EQ;
-  }
-  a.tt = typed_table();
-  a.stream_direct = opt.on(RDFGPU_OPT_NO_STREAM_JOIN) ? 0u : 1u;
-  if (left_join) a.visited = scratch<u8>(L.cap);
-  u64* n_out = new_counter();
-  u32* overflow = reinterpret_cast<u32*>(new_counter());
-  a.n_out_dev = n_out; a.overflow = overflow;
-  const u64 tail = left_join ? L.cap : 0;
-
-  // columns the kernel reads on the probe side: keys ∪ projected ∪ filter columns
-  u32 probe_cols = 0, build_payload = 0;
-  {
-    bool pu[kMaxCols] = {}, bu[kMaxCols] = {};
-    const u32 nl = L.n_cols;
-    auto mark = [&](u32 c) { const bool from_left = c < nl; const u32 local = from_left ? c : c - nl; ((from_left == build_left) ? bu : pu)[local] = true; };
-    for (u32 k = 0; k < a.n_keys; k++) { pu[probe_keys[k]] = true; }
-    for (u32 c = 0; c < nd.n_proj; c++) mark(nd.proj[c]);
-    for (u32 i = 0; i < nd.prog.n; i++) if (nd.prog.nodes[i].op == RDFGPU_EX_COLUMN) mark(nd.prog.nodes[i].u);
-    if (probe_filter) for (u32 i = 0; i < probe_filter->prog.n; i++) if (probe_filter->prog.nodes[i].op == RDFGPU_EX_COLUMN) pu[probe_filter->prog.nodes[i].u] = true;
-    for (u32 k = 0; k < a.n_keys; k++) bu[build_keys[k]] = false;
-    for (bool b : pu) probe_cols += b;
-    for (bool b : bu) build_payload += b;
-  }
-  // SURVEY §8d hash join: 4(k+p_b)N_b + 8N_b + 4(k+p_p)N_p + 8N_p + 4 c_o N_o  (the 8-byte slot lives in LDS here)
-  const u64 fixed = (4ull * (a.n_keys + build_payload) + 8) * B.cap;
-
-  if (use_part) {
-    flush_pending_oj();
-    // output of the previous execution (none: single pass): above ~50 M rows the reservations of a single pass (one
-    // same-address atomic per 256 rows, ~88 per microsecond) cost more than walking every partition twice
-    const u64 expect_out = nd.has_last ? nd.last_rows : 0;
-    part.two_pass = expect_out >= opt.v[RDFGPU_OPT_PARTITION_TWO_PASS_ROWS] ? 1u : 0u;
-    if (part.two_pass && nd.shape == 2 && !left_join) {   // `build column <=|!=> probe column`: decided during the walk (part_join.hip, INL)
-      auto from_build = [&](u32 c) { return (c < L.n_cols) == build_left; };
-      const u32 ca = nd.prog.nodes[0].u, cb = nd.prog.nodes[1].u;
-      if (from_build(ca) != from_build(cb)) { part.inl_build = a.cols[from_build(ca) ? ca : cb]; part.inl_probe = a.cols[from_build(ca) ? cb : ca]; }
-    }
-    prepare_partitions(a, B, P, part);   // the build half of this HashJoinExec: inside the operator, every execution
-  }
-  // SURVEY 8d hash-join bytes of a partitioned join: both sides' key + payload columns and one 8-byte slot per row, the output;
-  // the partition passes are in the time of the operator, not in its bytes
-  const u64 part_fixed = (4ull * (a.n_keys + build_payload) + 8) * B.cap;
-  bool stream_values_tried = false;
-  auto launch_join = [&](int kc_lds, u64 fixed_bytes, u64 out_bytes_per_row) {
-    if (use_part) timed(KC_PART_JOIN, part_fixed, P.cap, P.n_dev, 4ull * probe_cols + 8, n_out, 0, out_bytes_per_row, [&] { launch_part_join(a, part, stream); });
-    else {
-      const bool streamed = a.stream_direct && direct_stream_join_ok(a);
-      // the streaming form over a direct table, window filter on ONE build column against probe columns, a probe side large enough to pay
-      // for a kernel and a host round trip: that column decoded per KEY (a.key_vals), once per execution
-      if (streamed && !stream_values_tried && a.direct && a.has_filter == 3 && a.has_probe_filter == 0 && B.n_dev == nullptr && a.tt.n_ids != 0 &&
-          direct_stream_join_items(P.cap) == 8 && P.cap >= (1ull << 22) && !opt.on(RDFGPU_OPT_NO_VALUE_TABLES)) {
-        stream_values_tried = true;
-        auto from_build = [&](u32 c) { return (c < L.n_cols) == build_left; };
-        if (a.win.x0 == a.win.x1 && from_build(a.win.x0) && !from_build(a.win.y0) && !from_build(a.win.y1)) {
-          long long* vals = scratch<long long>(a.direct_n);
-          u32* bad = reinterpret_cast<u32*>(new_counter());
-          launch_fill_i64(vals, INT64_MIN, a.direct_n, stream);
-          launch_direct_values(a.build_key[0], a.cols[a.win.x0], B.cap, a.direct_min, a.direct_n, a.tt, vals, bad, stream);
-          u32 is_bad = 0;
-          RDFGPU_HIP(hipMemcpyAsync(&is_bad, bad, sizeof(u32), hipMemcpyDeviceToHost, stream));
-          RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-          if (!is_bad) {
-            a.key_vals = vals; metrics.tables_built++;
-            a.stream_need_build_row = (a.has_post && from_build(a.post.col)) ? 1u : 0u;
-            for (u32 c = 0; c < nd.n_proj; c++) if (from_build(nd.proj[c])) a.stream_need_build_row = 1u;
-          }
-        }
-      }
-      timed(streamed ? (int)KC_STREAM_JOIN : kc_lds, fixed_bytes, P.cap, P.n_dev, 4ull * probe_cols + 8, n_out, 0, out_bytes_per_row, [&] { launch_lds_join(a, stream); });
-    }
-  };
-  if (build_now)   // build pass: keys read + one 8-byte slot written per build row
-    timed(KC_GJOIN_BUILD, 0, B.cap, B.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0, [&] { launch_gjoin_build(a, stream); });
+  LdsJoin j(nd, L, R, build_left, probe_filter, post_filter);
+  LdsJoinArgs& a = j.a;
+  if (j.B.cap >= (1ull << 30)) fail(RDFGPU_ERR_UNSUPPORTED, "build side of %llu rows", (unsigned long long)j.B.cap);
+  lds_join_args(j);
+  j.table = choose_join_table(j);
+  if (j.P.cap >= (1ull << 32)) fail(RDFGPU_ERR_UNSUPPORTED, "probe side of %llu rows", (unsigned long long)j.P.cap);
+  size_wave_queue(j);
+  if (j.left_join) a.visited = scratch<u8>(L.cap);
+  a.n_out_dev = new_counter();
+  a.overflow = reinterpret_cast<u32*>(new_counter());
+  j.tail = j.left_join ? L.cap : 0;
+  if (j.table == JoinTable::ScratchHash)   // build pass: keys read + one 8-byte slot written per build row
+    timed(KC_GJOIN_BUILD, 0, j.B.cap, j.B.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0, [&] { launch_gjoin_build(a, stream); });
   // Speculative mode (re-execution of a plan whose previous run is known): the output is sized from the
   // previous cardinality of this operator and NOTHING is waited for — the exact count stays on the device,
   // the overflow flag is checked once at the end of the plan (Plan::execute), which re-runs exactly if any
@@ -1890,131 +1660,339 @@ DevTable Plan::exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R,
   // about its mean rows per key, a hash table is assumed unique-ish — so the join can run without a host round
   // trip as well; the overflow flag at the end of the plan catches a wrong guess (exact re-run).
   u64 first_guess = 0;
-  if (speculative && !nd.has_last && !left_join && !opt.on(RDFGPU_OPT_NO_FIRST_RUN_SPECULATION)) {
-    if (a.direct) first_guess = P.cap;
-    else if (a.csr_off) first_guess = 2 * P.cap * ((B.cap + a.direct_n - 1) / (a.direct_n ? a.direct_n : 1)) + 1024;
-    else first_guess = P.cap + 1024;
+  if (speculative && !nd.has_last && !j.left_join && !opt.on(RDFGPU_OPT_NO_FIRST_RUN_SPECULATION)) {
+    if (a.direct) first_guess = j.P.cap;
+    else if (a.csr_off) first_guess = 2 * j.P.cap * ((j.B.cap + a.direct_n - 1) / (a.direct_n ? a.direct_n : 1)) + 1024;
+    else first_guess = j.P.cap + 1024;
   }
-  if (speculative && (nd.has_last || first_guess)) {
-    // a fusable run of follow-up lookups above this join (Plan::plan_chain) executes inside this join's resolve
-    // phase: the output is then the TOP node's, sized from the top node's history
-    NodeInfo* size_node = &nd;
-    u64 stage_bytes = 0;
-    BandArgs band{}; bool use_band = false;
-    if (pending_chain && pending_chain->base == &nd && !pending_chain->consumed && global_table && !use_part && !left_join && !probe_outer && !probe_filter && nd.shape != 1 &&
-        apply_chain(*pending_chain, nd, L, R, build_left, a, stage_bytes, &band, &use_band)) {
-      pending_chain->consumed = true;
-      size_node = pending_chain->top;
-      t.n_cols = a.n_out_cols;
+  const bool spec = speculative && (nd.has_last || first_guess);
+  // a fusable run of follow-up lookups above this join (Plan::plan_chain) executes inside this join's resolve
+  // phase: the output is then the TOP node's, sized from the top node's history
+  NodeInfo* size_node = &nd;
+  u64 stage_bytes = 0;
+  BandArgs band{}; bool use_band = false;
+  if (spec && pending_chain && pending_chain->base == &nd && !pending_chain->consumed && j.global_table && j.table != JoinTable::Partitioned && !j.left_join &&
+      !j.probe_outer && !probe_filter && nd.shape != 1 && apply_chain(*pending_chain, nd, L, R, build_left, j.slice, a, stage_bytes, &band, &use_band)) {
+    pending_chain->consumed = true;
+    size_node = pending_chain->top;
+    j.t.n_cols = a.n_out_cols;
+  }
+  // the probe side is read from here on: only the band join takes an ordered slice join's held-back write pass (exec_band_join)
+  if (!use_band) flush_pending_oj();
+  if (j.table == JoinTable::Partitioned) {
+    // output of the previous execution (none: single pass): above ~50 M rows the reservations of a single pass (one
+    // same-address atomic per 256 rows, ~88 per microsecond) cost more than walking every partition twice
+    const u64 expect_out = nd.has_last ? nd.last_rows : 0;
+    j.part.two_pass = expect_out >= opt.v[RDFGPU_OPT_PARTITION_TWO_PASS_ROWS] ? 1u : 0u;
+    if (j.part.two_pass && nd.shape == 2 && !j.left_join) {   // `build column <=|!=> probe column`: decided during the walk (part_join.hip, INL)
+      const u32 ca = nd.prog.nodes[0].u, cb = nd.prog.nodes[1].u;
+      if (on_build_side(a, ca) != on_build_side(a, cb)) { j.part.inl_build = a.cols[on_build_side(a, ca) ? ca : cb]; j.part.inl_probe = a.cols[on_build_side(a, ca) ? cb : ca]; }
     }
-    if (!use_band) flush_pending_oj();   // (only the band join takes an ordered slice join's held-back write pass)
-    const bool chained = a.n_chain != 0;
-    const u64 spec_cap = nd.has_last ? std::max<u64>(1024, size_node->last_rows + size_node->last_rows / (size_node->last_scaled ? 2 : 4) + 256)   // 25 % head room over the previous run (50 % over an extrapolation)
+    prepare_partitions(a, j.B, j.P, j.part);   // the build half of this HashJoinExec: inside the operator, every execution
+  }
+  return spec ? run_speculative(j, first_guess, *size_node, stage_bytes, use_band ? &band : nullptr) : run_exact(j);
+}
+
+// The kernel arguments that do not depend on the build side's table: both inputs' columns, the keys, the join filter, the fused
+// probe-side filter, the build-side filter kept as a conjunct, and the columns each side reads (bytes).
+void Plan::lds_join_args(LdsJoin& j) {
+  const NodeInfo& nd = j.nd; const DevTable& L = j.L; const DevTable& R = j.R;
+  LdsJoinArgs& a = j.a;
+  j.t.n_cols = nd.n_proj;
+  for (u32 c = 0; c < L.n_cols; c++) a.cols[c] = L.cols[c];
+  for (u32 c = 0; c < R.n_cols; c++) a.cols[L.n_cols + c] = R.cols[c];
+  a.n_left_cols = L.n_cols; a.n_out_cols = nd.n_proj;
+  for (u32 c = 0; c < nd.n_proj; c++) a.proj[c] = nd.proj[c];
+  a.build_is_left = j.build_left ? 1 : 0;
+  a.probe_outer = j.probe_outer ? 1u : 0u;
+  a.n_keys = nd.d.n_keys;
+  for (u32 k = 0; k < a.n_keys; k++) {
+    j.build_keys[k] = j.build_left ? nd.d.left_keys[k] : nd.d.right_keys[k];
+    j.probe_keys[k] = j.build_left ? nd.d.right_keys[k] : nd.d.left_keys[k];
+    a.build_key[k] = j.B.cols[j.build_keys[k]];
+    a.probe_key[k] = j.P.cols[j.probe_keys[k]];
+  }
+  a.n_build_dev = j.B.n_dev; a.n_build_cap = j.B.cap; a.n_probe_dev = j.P.n_dev; a.n_probe_cap = j.P.cap;
+  a.probe_col_base = j.build_left ? L.n_cols : 0;
+  a.has_filter = (u32)nd.shape;   // 0 none / 1 generic VM / 2 id (in)equality / 3 window
+  if (nd.shape == 1) a.prog = upload_program(nd.prog);
+  if (nd.shape == 2) { a.idp.a = nd.prog.nodes[0].u; a.idp.b = nd.prog.nodes[1].u; a.idp.is_eq = nd.prog.nodes[2].op == RDFGPU_EX_ID_EQ; }
+  if (nd.shape == 3) {
+    const rdfgpu_expr_node* e = nd.prog.nodes;
+    a.win.x0 = e[0].u; a.win.y0 = e[2].u; a.win.x1 = e[8].u; a.win.y1 = e[10].u;
+    a.win.l0 = window_literal(e, 0); a.win.l1 = window_literal(e, 8);
+  }
+  const NodeInfo* pf = j.probe_filter;
+  a.has_probe_filter = pf ? (pf->shape == 1 ? 1u : 2u) : 0u;
+  if (pf) {
+    if (pf->shape == 1) {
+      const rdfgpu_expr_node* e = pf->prog.nodes;
+      a.pid.col = a.probe_col_base + e[0].u; a.pid.lit = e[1].u; a.pid.is_eq = e[2].op == RDFGPU_EX_ID_EQ;
+    } else a.probe_prog = upload_program(pf->prog);
+  }
+  if (j.post_filter) {   // FilterExec of the build side's input, columns relative to that input
+    const rdfgpu_expr_node* e = j.post_filter->prog.nodes;
+    a.has_post = 1;
+    a.post.col = (j.build_left ? 0 : L.n_cols) + e[0].u; a.post.lit = e[1].u; a.post.is_eq = e[2].op == RDFGPU_EX_ID_EQ;
+  }
+  a.tt = typed_table();
+  a.stream_direct = opt.on(RDFGPU_OPT_NO_STREAM_JOIN) ? 0u : 1u;
+  // columns the kernel reads on the probe side: keys ∪ projected ∪ filter columns
+  bool pu[kMaxCols] = {}, bu[kMaxCols] = {};
+  auto mark = [&](u32 c) { (on_build_side(a, c) ? bu : pu)[c < L.n_cols ? c : c - L.n_cols] = true; };
+  for (u32 k = 0; k < a.n_keys; k++) pu[j.probe_keys[k]] = true;
+  for (u32 c = 0; c < nd.n_proj; c++) mark(nd.proj[c]);
+  for (u32 i = 0; i < nd.prog.n; i++) if (nd.prog.nodes[i].op == RDFGPU_EX_COLUMN) mark(nd.prog.nodes[i].u);
+  if (pf) for (u32 i = 0; i < pf->prog.n; i++) if (pf->prog.nodes[i].op == RDFGPU_EX_COLUMN) pu[pf->prog.nodes[i].u] = true;
+  for (u32 k = 0; k < a.n_keys; k++) bu[j.build_keys[k]] = false;
+  for (bool b : pu) j.probe_cols += b;
+  for (bool b : bu) j.build_payload += b;
+  j.build_bytes = (4ull * (a.n_keys + j.build_payload) + 8) * j.B.cap;
+}
+
+// Which table the join probes, built now where it has to be: the kernels this triggers run here, before the probe.
+JoinTable Plan::choose_join_table(LdsJoin& j) {
+  const NodeInfo& nd = j.nd;
+  const DevTable& B = j.B; const DevTable& P = j.P;
+  LdsJoinArgs& a = j.a;
+  u32& slots = j.slots;
+  while (slots < 2 * B.cap) slots <<= 1;
+  // LDS copy per workgroup vs ONE table in HBM/L2: the LDS form pays the build once per workgroup and, above
+  // ~16 KiB of table, costs occupancy (a 128 KiB table = one workgroup per CU = latency-bound probes).
+  const u64 lds_limit = std::min<u64>(opt.v[RDFGPU_OPT_LDS_MAX_BUILD], kLdsJoinMaxBuild);
+  j.global_table = B.cap > lds_limit;
+  // Every lane of a wave waits for the longest chain among its 64 probes, so short chains matter more than a
+  // small table: LDS tables get load <= 0.25 and at least 2048 slots (16 KiB), HBM tables under 1 MiB load <= 0.125.
+  if (!j.global_table) { while ((slots < 4 * B.cap || slots < 2048) && slots < 2 * kLdsJoinMaxBuild) slots <<= 1; }
+  else { while (slots < 8 * B.cap && (u64)slots * sizeof(uint2) < (1u << 20)) slots <<= 1; }
+  a.tbl_mask = slots - 1;
+  if (!j.global_table) return JoinTable::Lds;
+  // The HBM table of a build side that is a pure slice of the store (a param-free scan: label, simProperty…) is the
+  // same for every plan until the store changes: it is built once per store version and kept on the store.
+  if (B.stable_id != 0 && B.n_dev == nullptr && !opt.on(RDFGPU_OPT_NO_TABLE_CACHE)) {
+    SliceKey sk; sk.n_keys = a.n_keys; sk.rows = B.cap;
+    for (u32 k = 0; k < a.n_keys; k++) sk.key[k] = a.build_key[k];
+    SliceTable* st = store->slice_table(sk);
+    j.slice = st;
+    std::unique_lock<std::mutex> building(store->slice_build_mu);
+    // Dense forms first (one single key over a dense id range): direct-address if the keys are unique, CSR if not.
+    // Decided once per slice; costs a few small kernels and host syncs at that time, nothing afterwards.
+    if (!st->dense_tried && a.n_keys == 1 && !opt.on(RDFGPU_OPT_NO_DIRECT_TABLE)) build_dense_table(st, a.build_key[0], B.cap);
+    if (st->csr_off) {
+      a.csr_off = st->csr_off; a.csr_rows = st->csr_rows; a.direct_min = st->kmin; a.direct_n = st->kn;
+      // lanes per probe row: a small probe side with a large fan-out is spread over the chip
+      // (first execution: the table's mean rows per key stands in for the unknown fan-out)
+      const u64 fan = nd.has_last ? nd.last_rows / (P.cap ? P.cap : 1) : B.cap / (st->kn ? st->kn : 1);
+      // measured on the BSBM candidate join (fan-out 111): 8 lanes per row is best at 75 k and at 1.2 M probe rows alike
+      // (a tiny probe side — a single query's constants — is latency-bound instead: spread each row over up to a whole wave)
+      const bool tiny = P.cap < 4096;
+      u32 rl = 0;
+      while (rl < (tiny ? 6u : 3u) && ((tiny ? 2ull : 16ull) << rl) <= fan && (P.cap << (rl + 1)) <= (1ull << 25)) rl++;
+      if (opt.v[RDFGPU_OPT_CSR_ROW_LANES_LOG2]) rl = (u32)std::min<u64>(6, opt.v[RDFGPU_OPT_CSR_ROW_LANES_LOG2] - 1);
+      if (j.probe_outer) rl = 0;   // (one lane per probe row: the row's null-extended candidate is produced once)
+      a.row_lanes_log2 = rl;
+      return JoinTable::SliceCsr;
+    }
+    if (st->direct) { a.direct = st->direct; a.direct_min = st->kmin; a.direct_n = st->kn; return JoinTable::SliceDirect; }
+    if (!st->slots || st->mask != a.tbl_mask) {   // build the hash form now, under the lock, and publish it only when complete
+      if (st->slots) { store->table_free(st->slots); st->slots = nullptr; }
+      void* mem = store->table_alloc<uint2>(slots);
+      metrics.tables_built++;
+      a.gslots = static_cast<uint2*>(mem);
+      RDFGPU_HIP(hipMemsetAsync(a.gslots, 0xFF, (size_t)slots * sizeof(uint2), stream));
+      timed(KC_GJOIN_BUILD, 0, B.cap, B.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0, [&] { launch_gjoin_build(a, stream); });
+      RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+      st->slots = mem; st->mask = a.tbl_mask;
+    }
+    a.gslots = static_cast<uint2*>(st->slots);
+    return JoinTable::SliceHash;
+  }
+  if (a.n_keys <= 2 && !j.probe_filter && !j.post_filter && !opt.on(RDFGPU_OPT_NO_PARTITIONED_JOIN) && B.cap >= opt.v[RDFGPU_OPT_PARTITION_MIN_BUILD] &&
+      B.cap < (1ull << 31) && P.cap < (1ull << 31))
+    return JoinTable::Partitioned;
+  // The direct-address form for a build side that is NOT cached (RDFGPU_OPT_NO_TABLE_CACHE, or an intermediate with a host-known row
+  // count): built inside this execution, in scratch memory, when the single key turns out unique over a dense id range.  4 bytes per ID
+  // instead of 8 bytes per SLOT at load <= 0.5: the 285 k-row property slices of BSBM-100M are 1.1 MB (resident in every XCD's L2)
+  // instead of an 8 MB hash table that 0.54 G random probes fetch from the Infinity Cache line by line.  A large probe side pays for
+  // the two host round trips with every probe that hits a 4-byte entry in L2 instead of an 8-byte slot beyond it.
+  if (a.n_keys == 1 && B.n_dev == nullptr && B.cap >= 4096 && P.cap >= (1ull << 22) && !j.nd.transient_direct_failed && !opt.on(RDFGPU_OPT_NO_DIRECT_TABLE)) {
+    const DirectTable d = build_direct(a.build_key[0], B.cap, 4 * B.cap + 1024, false);   // (sparse ids: not even tried)
+    j.nd.transient_direct_failed = !d.direct;
+    if (d.direct) { metrics.tables_built++; a.direct = d.direct; a.direct_min = d.kmin; a.direct_n = d.kn; return JoinTable::TransientDirect; }
+  }
+  a.gslots = scratch<uint2>(slots);   // (filled by the build pass in exec_lds_join)
+  RDFGPU_HIP(hipMemsetAsync(a.gslots, 0xFF, (size_t)slots * sizeof(uint2), stream));
+  return JoinTable::ScratchHash;
+}
+
+// Candidate queue per wave: a full queue costs one output reservation (a same-address atomic, ~88 per
+// microsecond chip-wide), an oversized one costs occupancy (8 queues x 8 B x entries of LDS per workgroup).
+// Sized from the matches a wave can expect out of one tile (64 x rows-per-lane probe rows), which is what a
+// workgroup of an HBM-table join sees in its whole life; "expected" = the previous execution's cardinality
+// when known, else one match per probe row.  A direct-address table has at most one match per row.
+void Plan::size_wave_queue(LdsJoin& j) {
+  const NodeInfo& nd = j.nd;
+  const u64 np = j.P.cap;
+  LdsJoinArgs& a = j.a;
+  const u32 q_env = (u32)opt.v[RDFGPU_OPT_JOIN_WAVE_Q];
+  const u64 per_tile = 64ull * (u64)lds_join_items(np << a.row_lanes_log2, j.global_table);
+  const u64 expect = nd.has_last ? nd.last_rows : np;
+  const u64 want = a.direct ? per_tile : (expect * per_tile * 3 / 2) / (np ? np : 1);
+  u32 q = 256;
+  while (q < want && q < 1024) q <<= 1;
+  if (!j.global_table && (size_t)j.slots * sizeof(uint2) > 64 * 1024) q = 256;
+  a.wave_q = q_env ? q_env : q;
+  // partitioned join: a sparse output (the previous execution found less than one match per 8 probe rows) needs no deep queues —
+  // 52 KB of LDS per workgroup instead of 64: three workgroups per CU instead of two
+  if (j.table == JoinTable::Partitioned) a.wave_q = nd.has_last && !nd.last_scaled && nd.last_rows * 8 < np ? 64 : 256;
+}
+
+// One launch of the join kernel: the partitioned join, the streaming form over a direct table, or lds_join_kernel.  Bytes: the
+// build side's when every workgroup builds the table, `stage_bytes` of a fused chain, `out_bytes_per_row` per output row.
+void Plan::run_join_kernel(LdsJoin& j, u64 stage_bytes, u64 out_bytes_per_row) {
+  LdsJoinArgs& a = j.a;
+  const DevTable& B = j.B; const DevTable& P = j.P;
+  // SURVEY 8d hash-join bytes of a partitioned join: both sides' key + payload columns and one 8-byte slot per row, the output;
+  // the partition passes are in the time of the operator, not in its bytes
+  if (j.table == JoinTable::Partitioned) {
+    timed(KC_PART_JOIN, j.build_bytes, P.cap, P.n_dev, 4ull * j.probe_cols + 8, a.n_out_dev, 0, out_bytes_per_row, [&] { launch_part_join(a, j.part, stream); });
+    return;
+  }
+  const bool streamed = a.stream_direct && direct_stream_join_ok(a);
+  // the streaming form over a direct table, window filter on ONE build column against probe columns, a probe side large enough to pay
+  // for a kernel and a host round trip: that column decoded per KEY (a.key_vals), once per execution
+  if (streamed && !j.stream_values_tried && a.direct && a.has_filter == 3 && a.has_probe_filter == 0 && B.n_dev == nullptr && a.tt.n_ids != 0 &&
+      direct_stream_join_items(P.cap) == 8 && P.cap >= (1ull << 22) && !opt.on(RDFGPU_OPT_NO_VALUE_TABLES)) {
+    j.stream_values_tried = true;
+    if (a.win.x0 == a.win.x1 && on_build_side(a, a.win.x0) && !on_build_side(a, a.win.y0) && !on_build_side(a, a.win.y1)) {
+      long long* vals = scratch<long long>(a.direct_n);
+      u32* bad = reinterpret_cast<u32*>(new_counter());
+      launch_fill_i64(vals, INT64_MIN, a.direct_n, stream);
+      launch_direct_values(a.build_key[0], a.cols[a.win.x0], B.cap, a.direct_min, a.direct_n, a.tt, vals, bad, stream);
+      if (!read_back<u32>(bad)) {
+        a.key_vals = vals; metrics.tables_built++;
+        a.stream_need_build_row = (a.has_post && on_build_side(a, a.post.col)) ? 1u : 0u;
+        for (u32 c = 0; c < j.nd.n_proj; c++) if (on_build_side(a, j.nd.proj[c])) a.stream_need_build_row = 1u;
+      }
+    }
+  }
+  const int kc = streamed ? (int)KC_STREAM_JOIN
+                          : lds_join_class(a.has_filter, a.has_probe_filter, lds_join_items(P.cap << a.row_lanes_log2, j.global_table), lds_join_mode(a), a.n_chain != 0);
+  timed(kc, (j.global_table ? 0 : j.build_bytes) + stage_bytes, P.cap, P.n_dev, 4ull * j.probe_cols + 8, a.n_out_dev, 0, out_bytes_per_row, [&] { launch_lds_join(a, stream); });
+}
+
+// Speculative mode: the output sized from history (`size_node`: this join's, or the top node's of a fused chain) or from the
+// table form's guess; nothing is waited for.  `band`: the fused chain runs as a band join.
+DevTable Plan::run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node, u64 stage_bytes, BandArgs* band) {
+  LdsJoinArgs& a = j.a;
+  DevTable& t = j.t;
+  const u64 spec_cap = j.nd.has_last ? std::max<u64>(1024, size_node.last_rows + size_node.last_rows / (size_node.last_scaled ? 2 : 4) + 256)   // 25 % head room over the previous run (50 % over an extrapolation)
                                      : std::max<u64>(1024, first_guess);
-    a.out_cap = spec_cap;
-    for (u32 c = 0; c < a.n_out_cols; c++) { a.out[c] = scratch<u32>(spec_cap + tail); t.cols[c] = a.out[c]; }
-    if (left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, L.cap, stream));
-    // A small table against a CSR slice that is sorted by another column, with an output about as large as the slice:
-    // the matches are emitted in the slice's order (ordered_join.hip) — what consumes them partitioned by that column
-    // (the band join above) then has nothing to sort; the chain's look-ups by table columns run once per table row.
-    bool use_ordered = false;
-    if (!use_band && !probe_outer && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN) && a.csr_off && !a.range_rows && !left_join && a.has_filter == 0 && !a.has_probe_filter && !a.has_post &&
-        a.n_keys == 1 && B.sorted_col >= 0 && (u32)B.sorted_col != build_keys[0] && !B.n_dev && B.stable_id && B.cap < (1ull << 32) && P.cap <= (1ull << 24) &&
-        size_node->has_last && size_node->last_rows * 8 >= B.cap) {
-      use_ordered = true;
-      for (u32 s = 0; s < a.n_chain; s++) if (a.chain[s].key.src != 0 || a.chain[s].fs != 0) use_ordered = false;
-      u32 from_table = 0;   // output columns taken from the table row or a stage row travel in its packed record: at most 8
-      for (u32 c = 0; c < a.n_out_cols; c++) {
-        if (chained) from_table += a.chain_out[c].src != 1;
-        else { const u32 pc = a.proj[c]; from_table += ((pc < a.n_left_cols) == (a.build_is_left != 0)) ? 0u : 1u; }
-      }
-      if (from_table > 8 || a.n_out_cols > kOjMaxOutCols) use_ordered = false;
-    }
-    if (use_ordered) {
-      OrderedJoinArgs o{};
-      o.build_key = a.build_key[0]; o.n_build = B.cap;
-      o.probe_key = a.probe_key[0]; o.n_probe_dev = P.n_dev; o.n_probe_cap = P.cap;
-      o.kmin = a.direct_min; o.kn = a.direct_n;
-      o.head = scratch<uint2>(a.direct_n); o.next = scratch<u32>(P.cap);
-      RDFGPU_HIP(hipMemsetAsync(o.head, 0xFF, (size_t)a.direct_n * sizeof(uint2), stream));
-      o.n_stages = a.n_chain;
-      for (u32 s = 0; s < a.n_chain; s++) o.stage[s] = OrderedJoinStage{a.chain[s].key.ptr, a.chain[s].direct, a.chain[s].kmin, a.chain[s].kn, scratch<u32>(P.cap)};
-      o.n_out_cols = a.n_out_cols;
-      u32 n_words = 0;
-      for (u32 c = 0; c < a.n_out_cols; c++) {
-        if (chained) o.out_ref[c] = a.chain_out[c];
-        else { const u32 pc = a.proj[c]; const bool from_left = pc < a.n_left_cols; o.out_ref[c] = ColRef{a.cols[pc], (from_left == (a.build_is_left != 0)) ? 1u : 0u, 0u}; }
-        o.out[c] = a.out[c];
-        o.out_slot[c] = o.out_ref[c].src == 1 ? (u8)0xFF : (u8)n_words++;
-        if (o.out_ref[c].src == 1 && o.out_ref[c].ptr == B.cols[B.sorted_col] && t.sorted_col < 0) { t.sorted_col = (int)c; t.key_min = B.key_min; t.key_max = B.key_max; }
-      }
-      o.n_rec = n_words > 4 ? 2u : 1u;
-      o.trec = scratch<uint4>(P.cap * o.n_rec);
-      o.out_cap = spec_cap; o.n_out_dev = n_out; o.overflow = overflow;
-      const u64 tiles = ordered_join_tiles(B.cap);
-      o.tile_count = scratch<u32>(tiles + 1); o.tile_off = scratch<u32>(tiles + 1);
-      o.row_head = scratch<u32>(B.cap); o.row_cnt = scratch<unsigned char>(B.cap);
-      const size_t tb = scan_temp_bytes(tiles + 1);
-      void* temp = scratch<unsigned char>(tb);
-      timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
-      timed(KC_OJ_COUNT, 0, B.cap, nullptr, 4, nullptr, 0, 0, [&] { launch_ordered_join_count(o, stream); });
-      timed(scan_class(tiles + 1), 0, tiles + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(o.tile_count, o.tile_off, tiles + 1, temp, tb, stream); });
-      // the consumer is a band join that (last time) found this output sorted by its key and needed nothing else of it: the write
-      // pass is held back — that join has it write its row records instead of this table (exec_band_join), anything else flushes it
-      const int consumer = size_node->parent;
-      if (consumer >= 0 && nodes[consumer].band_takes_records && !pending_oj.active && t.sorted_col >= 0) {
-        pending_oj.active = true; pending_oj.o = o; pending_oj.first_col = a.out[0]; pending_oj.n_build = B.cap; pending_oj.n_chain = a.n_chain;
-      } else timed(KC_OJ_WRITE, 0, B.cap, nullptr, 4, n_out, 0, 8ull * a.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
-    }
-    else if (use_band) { cur_band_node = &nd; exec_band_join(a, band, B, P, 4ull * (1 + build_payload), 4ull * probe_cols); cur_band_node = nullptr; }
-    else launch_join(lds_join_class(a.has_filter, a.has_probe_filter, lds_join_items(P.cap << a.row_lanes_log2, global_table), use_part ? kJoinTableLds : lds_join_mode(a), chained),
-                     (global_table ? 0 : fixed) + stage_bytes, 4ull * a.n_out_cols);
-    spec_checks.push_back({size_node, (u32)(n_out - counters), left_join});
-    t.cap = spec_cap + tail; t.n_dev = n_out;
-    if (left_join) {
-      JoinArgs ja{};
-      for (u32 c = 0; c < L.n_cols; c++) ja.left[c] = L.cols[c];
-      ja.n_left_cols = L.n_cols; ja.n_right_cols = R.n_cols; ja.n_out_cols = nd.n_proj;
-      for (u32 c = 0; c < nd.n_proj; c++) { ja.proj[c] = nd.proj[c]; ja.out[c] = a.out[c]; }
-      ja.n_left_dev = L.n_dev; ja.n_left_cap = L.cap;
-      ja.visited = a.visited; ja.n_out_dev = n_out; ja.matched_total = spec_cap + tail;
-      timed(KC_LEFT_TAIL, 0, L.cap, L.n_dev, 1, nullptr, 0, 0, [&] { launch_join_left_unmatched(ja, stream); });
-    }
-    return t;
+  a.out_cap = spec_cap;
+  for (u32 c = 0; c < a.n_out_cols; c++) { a.out[c] = scratch<u32>(spec_cap + j.tail); t.cols[c] = a.out[c]; }
+  if (j.left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, j.L.cap, stream));
+  if (band) exec_band_join(j.nd, j.slice, a, *band, j.B, j.P, 4ull * (1 + j.build_payload), 4ull * j.probe_cols);
+  else if (!run_ordered_join(j, size_node, spec_cap)) run_join_kernel(j, stage_bytes, 4ull * a.n_out_cols);
+  spec_checks.push_back({&size_node, (u32)(a.n_out_dev - counters), j.left_join});
+  t.cap = spec_cap + j.tail; t.n_dev = a.n_out_dev;
+  if (j.left_join) left_join_tail(j.nd, j.L, j.R, a.out, a.visited, a.n_out_dev, spec_cap + j.tail);
+  return t;
+}
+
+// A small table against a CSR slice that is sorted by another column, with an output about as large as the slice:
+// the matches are emitted in the slice's order (ordered_join.hip) — what consumes them partitioned by that column
+// (the band join above) then has nothing to sort; the chain's look-ups by table columns run once per table row.
+// false: the join does not have that shape (nothing launched).
+bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap) {
+  const LdsJoinArgs& a = j.a;
+  const DevTable& B = j.B; const DevTable& P = j.P;
+  if (j.probe_outer || opt.on(RDFGPU_OPT_NO_ORDERED_JOIN) || !a.csr_off || a.range_rows || j.left_join || a.has_filter != 0 || a.has_probe_filter || a.has_post ||
+      a.n_keys != 1 || B.sorted_col < 0 || (u32)B.sorted_col == j.build_keys[0] || B.n_dev || !B.stable_id || B.cap >= (1ull << 32) || P.cap > (1ull << 24) ||
+      !size_node.has_last || size_node.last_rows * 8 < B.cap)
+    return false;
+  for (u32 s = 0; s < a.n_chain; s++) if (a.chain[s].key.src != 0 || a.chain[s].fs != 0) return false;
+  u32 from_table = 0;   // output columns taken from the table row or a stage row travel in its packed record: at most 8
+  for (u32 c = 0; c < a.n_out_cols; c++) from_table += a.n_chain ? a.chain_out[c].src != 1 : !on_build_side(a, a.proj[c]);
+  if (from_table > 8 || a.n_out_cols > kOjMaxOutCols) return false;
+  DevTable& t = j.t;
+  OrderedJoinArgs o{};
+  o.build_key = a.build_key[0]; o.n_build = B.cap;
+  o.probe_key = a.probe_key[0]; o.n_probe_dev = P.n_dev; o.n_probe_cap = P.cap;
+  o.kmin = a.direct_min; o.kn = a.direct_n;
+  o.head = scratch<uint2>(a.direct_n); o.next = scratch<u32>(P.cap);
+  RDFGPU_HIP(hipMemsetAsync(o.head, 0xFF, (size_t)a.direct_n * sizeof(uint2), stream));
+  o.n_stages = a.n_chain;
+  for (u32 s = 0; s < a.n_chain; s++) o.stage[s] = OrderedJoinStage{a.chain[s].key.ptr, a.chain[s].direct, a.chain[s].kmin, a.chain[s].kn, scratch<u32>(P.cap)};
+  o.n_out_cols = a.n_out_cols;
+  u32 n_words = 0;
+  for (u32 c = 0; c < a.n_out_cols; c++) {
+    if (a.n_chain) o.out_ref[c] = a.chain_out[c];
+    else { const u32 pc = a.proj[c]; o.out_ref[c] = ColRef{a.cols[pc], on_build_side(a, pc) ? 1u : 0u, 0u}; }
+    o.out[c] = a.out[c];
+    o.out_slot[c] = o.out_ref[c].src == 1 ? (u8)0xFF : (u8)n_words++;
+    if (o.out_ref[c].src == 1 && o.out_ref[c].ptr == B.cols[B.sorted_col] && t.sorted_col < 0) { t.sorted_col = (int)c; t.key_min = B.key_min; t.key_max = B.key_max; }
   }
-  flush_pending_oj();
+  o.n_rec = n_words > 4 ? 2u : 1u;
+  o.trec = scratch<uint4>(P.cap * o.n_rec);
+  o.out_cap = spec_cap; o.n_out_dev = a.n_out_dev; o.overflow = a.overflow;
+  const u64 tiles = ordered_join_tiles(B.cap);
+  o.tile_count = scratch<u32>(tiles + 1); o.tile_off = scratch<u32>(tiles + 1);
+  o.row_head = scratch<u32>(B.cap); o.row_cnt = scratch<unsigned char>(B.cap);
+  const size_t tb = scan_temp_bytes(tiles + 1);
+  void* temp = scratch<unsigned char>(tb);
+  timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
+  timed(KC_OJ_COUNT, 0, B.cap, nullptr, 4, nullptr, 0, 0, [&] { launch_ordered_join_count(o, stream); });
+  timed(scan_class(tiles + 1), 0, tiles + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(o.tile_count, o.tile_off, tiles + 1, temp, tb, stream); });
+  // the consumer is a band join that (last time) found this output sorted by its key and needed nothing else of it: the write
+  // pass is held back — that join has it write its row records instead of this table (exec_band_join), anything else flushes it
+  const int consumer = size_node.parent;
+  if (consumer >= 0 && nodes[consumer].band_takes_records && !pending_oj.active && t.sorted_col >= 0) {
+    pending_oj.active = true; pending_oj.o = o; pending_oj.first_col = a.out[0]; pending_oj.n_build = B.cap; pending_oj.n_chain = a.n_chain;
+  } else timed(KC_OJ_WRITE, 0, B.cap, nullptr, 4, a.n_out_dev, 0, 8ull * a.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
+  return true;
+}
+
+// Exact mode: the output sized from the table form, the count read back; a second attempt with room for all if it did not fit.
+DevTable Plan::run_exact(LdsJoin& j) {
+  NodeInfo& nd = j.nd;
+  LdsJoinArgs& a = j.a;
+  const DevTable& B = j.B; const DevTable& P = j.P;
+  DevTable& t = j.t;
   u64 out_cap = P.cap < 1024 ? 1024 : P.cap;   // optimistic: at most one match per probe row on average
   if (a.csr_off) out_cap = std::max<u64>(out_cap, 2 * P.cap * ((B.cap + a.direct_n - 1) / (a.direct_n ? a.direct_n : 1)) + 1024);   // CSR: twice the mean rows per key
   u64 total = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
     a.out_cap = out_cap;
-    for (u32 c = 0; c < nd.n_proj; c++) { a.out[c] = scratch<u32>(out_cap + tail); t.cols[c] = a.out[c]; }
-    if (left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, L.cap, stream));
-    launch_join(lds_join_class(a.has_filter, a.has_probe_filter, lds_join_items(P.cap << a.row_lanes_log2, global_table), use_part ? kJoinTableLds : lds_join_mode(a)),
-                global_table ? 0 : fixed, 4ull * nd.n_proj);
-    const u32 i0 = (u32)(n_out - counters);
-    RDFGPU_HIP(hipMemcpyAsync(ctx->counters_host + i0, counters + i0, 2 * sizeof(u64), hipMemcpyDeviceToHost, stream));
-    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+    for (u32 c = 0; c < nd.n_proj; c++) { a.out[c] = scratch<u32>(out_cap + j.tail); t.cols[c] = a.out[c]; }
+    if (j.left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, j.L.cap, stream));
+    run_join_kernel(j, 0, 4ull * nd.n_proj);
+    const u32 i0 = (u32)(a.n_out_dev - counters);
+    read_back(ctx->counters_host + i0, counters + i0, 2 * sizeof(u64));
     total = ctx->counters_host[i0];
     const bool ovf = (ctx->counters_host[i0 + 1] & 0xFFFFFFFFull) != 0;
     if (!ovf) break;
     if (attempt == 1) fail(RDFGPU_ERR_DEVICE, "LDS join overflowed its exact-size output");
     out_cap = total;   // the count is exact even when the writes did not fit: run again with room for all
-    RDFGPU_HIP(hipMemsetAsync(n_out, 0, 2 * sizeof(u64), stream));
+    RDFGPU_HIP(hipMemsetAsync(a.n_out_dev, 0, 2 * sizeof(u64), stream));
   }
   nd.last_rows = total; nd.has_last = true; nd.last_scaled = false;   // history for the next (speculative) execution
-  t.cap = total + tail;
-  if (!left_join) { if (total == 0) t.cap = 0; return t; }
-  // left join tail: unmatched build rows, nulls on the right
+  t.cap = total + j.tail;
+  if (!j.left_join) { if (total == 0) t.cap = 0; return t; }
+  left_join_tail(nd, j.L, j.R, a.out, a.visited, a.n_out_dev, 0);
+  t.n_dev = a.n_out_dev;
+  return t;
+}
+
+// Left join tail: the build (left) rows no probe row visited, nulls on the right, appended at the device count `n_out_dev`.
+// `matched_total`: the capacity of the output columns when the count is not known on the host (0 = unchecked).
+void Plan::left_join_tail(const NodeInfo& nd, const DevTable& L, const DevTable& R, u32* const* out, u8* visited, u64* n_out_dev, u64 matched_total) {
   JoinArgs ja{};
   for (u32 c = 0; c < L.n_cols; c++) ja.left[c] = L.cols[c];
   ja.n_left_cols = L.n_cols; ja.n_right_cols = R.n_cols; ja.n_out_cols = nd.n_proj;
-  for (u32 c = 0; c < nd.n_proj; c++) { ja.proj[c] = nd.proj[c]; ja.out[c] = a.out[c]; }
+  for (u32 c = 0; c < nd.n_proj; c++) { ja.proj[c] = nd.proj[c]; ja.out[c] = out[c]; }
   ja.n_left_dev = L.n_dev; ja.n_left_cap = L.cap;
-  ja.visited = a.visited; ja.n_out_dev = n_out;
+  ja.visited = visited; ja.n_out_dev = n_out_dev; ja.matched_total = matched_total;
   timed(KC_LEFT_TAIL, 0, L.cap, L.n_dev, 1, nullptr, 0, 0, [&] { launch_join_left_unmatched(ja, stream); });
-  t.n_dev = n_out;
-  return t;
 }
 
 // Radix partitioning of both sides of a HashJoinExec by the top bits of the key hash (part_join.hip): per side one pass
@@ -2097,7 +2075,8 @@ void Plan::prepare_partitions(const LdsJoinArgs& a, const DevTable& B, const Dev
 // to move once (compulsory): decode reads the probe columns and writes the records, the mask kernel reads the records
 // and the group entries with their stage look-ups and writes one bit per pair, the emit kernel reads the bits and
 // writes the output.
-void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const DevTable& P, u64 build_bytes_per_row, u64 probe_bytes_per_row) {
+void Plan::exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& a, BandArgs& b, const DevTable& B, const DevTable& P, u64 build_bytes_per_row,
+                          u64 probe_bytes_per_row) {
   const u32 kn = a.direct_n;
   const u64 np = P.cap, nb = B.cap;
   // the probe side arrives sorted by the key (an ordered slice join below, ordered_join.hip): nothing to partition.  Keys
@@ -2107,7 +2086,7 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
   b.presorted = presorted ? 1u : 0u;
   // the full-semantics pass is launched when the previous execution met a row that needed it (or there was none); a row that
   // needs it after all is caught at the end of the plan like any failed speculation
-  const bool skip_slow = speculative && cur_band_node && cur_band_node->band_ran && cur_band_node->band_slow_rows == 0;
+  const bool skip_slow = speculative && base.band_ran && base.band_slow_rows == 0;
   // The probe side is the held-back output of an ordered slice join (Plan::pending_oj): if everything this join reads of it
   // travels in that join's packed table record — the window operands, the id operand, the rows' output values — and its key is
   // the slice's sorted column, that join writes this join's row records itself (OjBandFuse) and the table in between is never
@@ -2130,11 +2109,11 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
     ok = ok && fuse.key_col != nullptr;
     if (ok) fused = true; else flush_pending_oj();
   }
-  if (cur_band_node) cur_band_node->band_takes_records = presorted && skip_slow && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN);
+  base.band_takes_records = presorted && skip_slow && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN);
   // small probe side, not sorted: counting sort on the key (band_scatter_kernel) instead of rocPRIM's radix sort; a larger one
   // when the previous execution found it piecewise sorted (>= 4 rows per run of equal neighbouring keys: the N sorted runs
   // a repartition delivers) — one atomic per run, rows of a run scattered together
-  const u64 runs_seen = cur_band_node ? (cur_band_node->band_run_stats & 0xFFFFFFFFull) : 0, run_rows = cur_band_node ? (cur_band_node->band_run_stats >> 32) : 0;
+  const u64 runs_seen = base.band_run_stats & 0xFFFFFFFFull, run_rows = base.band_run_stats >> 32;
   const bool counting = !presorted && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN) && (np <= (1ull << 21) || (runs_seen && run_rows >= 4 * runs_seen));
   if (counting) {
     b.key_hist = scratch<u32>((u64)kn + 2); b.key_cursor = scratch<u32>((u64)kn + 2);
@@ -2175,11 +2154,11 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
     put(&nb, 8);
   }
   bool have_entries = false;
-  const bool cache_entries = cur_build_table && B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_TABLE_CACHE);
+  const bool cache_entries = B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_TABLE_CACHE);
   std::unique_lock<std::mutex> entries_lock(store->slice_build_mu, std::defer_lock);
   if (cache_entries) {
     entries_lock.lock();
-    for (const auto& e : cur_build_table->band_entries) if (e.key == ekey) { b.et = e.et; for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = e.eo[u]; have_entries = true; }
+    for (const auto& e : build_table->band_entries) if (e.key == ekey) { b.et = e.et; for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = e.eo[u]; have_entries = true; }
   }
   b.n_entries = nb;
   if (!have_entries) {
@@ -2197,7 +2176,7 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
     }
   }
   // the build side, once: per row its columns + stage look-ups read, 16 B of operands + the output values written
-  const bool own_entries = cache_entries && cur_build_table->band_entries.size() < 8;
+  const bool own_entries = cache_entries && build_table->band_entries.size() < 8;
   if (own_entries) {
     b.et = store->table_alloc<uint4>(nb + 64);
     for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = store->table_alloc<u32>(nb);
@@ -2207,18 +2186,18 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
     for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = scratch<u32>(nb);
   }
   timed(KC_BAND_ENTRIES, 0, nb, B.n_dev, entry_bytes + 4ull * b.n_entry_cols + 16 + 4ull * b.n_entry_cols, nullptr, 0, 0, [&] { launch_band_entries(b, stream); });
-    if (cache_entries && cur_build_table->band_entries.size() < 8) {   // publish only when complete
+    if (cache_entries && build_table->band_entries.size() < 8) {   // publish only when complete
       RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
       SliceTable::BandEntries e{ekey, b.et, {nullptr, nullptr, nullptr, nullptr}};
       for (u32 u = 0; u < b.n_entry_cols; u++) e.eo[u] = b.eo[u];
-      cur_build_table->band_entries.push_back(e);
+      build_table->band_entries.push_back(e);
     }
   }
   if (entries_lock.owns_lock()) entries_lock.unlock();
   // per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
   b.poff = scratch<u32>((u64)kn + 2);
   // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
-  const u64 cmax = (cur_build_table->csr_max_group + 63) / 64;
+  const u64 cmax = (build_table->csr_max_group + 63) / 64;
   const u64 max_blocks = cmax * (np / 64 + 1) + nb / 64 + kn + 1;
   if (max_blocks >= (1ull << 31)) fail(RDFGPU_ERR_UNSUPPORTED, "band join of %llu blocks", (unsigned long long)max_blocks);
   b.max_blocks = (u32)max_blocks;
@@ -2226,9 +2205,7 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
   if (fused) {
     const OrderedJoinArgs& o = pending_oj.o;
     pending_oj.active = false;
-    // the packed pair test reads 8 bytes of window, the id operand and at most one output value per row: 16 bytes per match instead of 32
-    fuse.compact = (b.pack16 && b.n_row_cols <= 1 && skip_slow && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT)) ? 1 : 0;
-    b.compact = fuse.compact;
+    fuse.compact = b.compact;   // (16 bytes per match instead of 32)
     // `entry id != row id` by entry index: the band join's groups are the rows of the very slice the ordered join streamed (same sorted column, same
     // rows, identity CSR), the entry's id is that join's build key, the row's id its probe key — equal keys are what made the match, and a store slice
     // holds every (key, sorted column) pair once: the only entry of the group whose id equals the row's is the slice row the match came from
@@ -2253,8 +2230,8 @@ void Plan::exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const 
   b.boff = scratch<u32>((u64)kn + 1);
   // the block kernels launch one wave per block: sized from the previous execution's count (+ 25 %), not from the upper bound
   b.n_blocks_out = new_counter();
-  band_block_counters.push_back({cur_band_node, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters), skip_slow});
-  const u64 hist = cur_band_node ? cur_band_node->band_blocks : 0;
+  band_block_counters.push_back({&base, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters), skip_slow});
+  const u64 hist = base.band_blocks;
   b.launch_blocks = (u32)std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks);
   b.bdesc = scratch<uint4>(max_blocks);
   b.masks = scratch<u64>(max_blocks * 64);

@@ -58,6 +58,42 @@ struct PendingOj { bool active = false; OrderedJoinArgs o{}; const u32* first_co
 
 struct BoundTable { std::vector<const u32*> cols; u64 n_rows = 0; bool bound = false; };
 
+// The table an LDS join probes (Plan::choose_join_table).
+enum class JoinTable {
+  Lds,                                 // built by every workgroup in its own LDS
+  SliceCsr, SliceDirect, SliceHash,    // a store slice's table, built once per store version and kept on the store
+  Partitioned,                         // both sides radix-partitioned, every partition's table built in LDS (part_join.hip)
+  TransientDirect, ScratchHash         // direct-address / hash table in HBM, built inside this execution
+};
+
+// One HashJoinExec on the LDS-join path while it is set up and run (Plan::exec_lds_join and its steps).
+struct LdsJoin {
+  NodeInfo& nd;
+  const DevTable& L; const DevTable& R;
+  const bool build_left;
+  const DevTable& B; const DevTable& P;
+  const NodeInfo* probe_filter;        // a FilterExec of the probe side run inside the probe
+  const NodeInfo* post_filter;         // a FilterExec of the build side kept as a conjunct of the join filter
+  // a LEFT join built on its right input preserves its PROBE side (choose_build_left): for everything below it is an inner join whose
+  // kernel adds one null-extended row per unmatched probe row — no visited flags, no tail pass
+  const bool probe_outer, left_join;
+  LdsJoinArgs a{};
+  u32 build_keys[RDFGPU_MAX_KEYS] = {}, probe_keys[RDFGPU_MAX_KEYS] = {};
+  u32 probe_cols = 0, build_payload = 0;   // columns the kernel reads on the probe side; build columns besides the keys
+  u64 build_bytes = 0;                     // SURVEY §8d hash join, build half: 4(k+p_b)N_b + 8N_b (the 8-byte slot in LDS)
+  u32 slots = 64;                          // hash table slots (LDS or HBM)
+  bool global_table = false;               // one table in HBM / L2 instead of a copy per workgroup in LDS
+  JoinTable table = JoinTable::Lds;
+  SliceTable* slice = nullptr;             // the store-level tables of a slice build side
+  PartArgs part{};
+  u64 tail = 0;                            // left join: output rows reserved for the unmatched build rows
+  bool stream_values_tried = false;
+  DevTable t;                              // the output
+  LdsJoin(NodeInfo& n, const DevTable& l, const DevTable& r, bool bl, const NodeInfo* pf, const NodeInfo* post)
+      : nd(n), L(l), R(r), build_left(bl), B(bl ? l : r), P(bl ? r : l), probe_filter(pf), post_filter(post),
+        probe_outer(n.d.join_type == RDFGPU_JOIN_LEFT && !bl), left_join(n.d.join_type == RDFGPU_JOIN_LEFT && bl) {}
+};
+
 // Kernel classes for per-kernel timing; names are what rocprofv3 --kernel-trace prints.
 enum KernelClass {
   KC_LOCATE, KC_SCAN_COUNT, KC_SCAN_WRITE, KC_FILTER_ID, KC_FILTER_TV, KC_FILTER_VM, KC_CROSS, KC_JOIN_BUILD,
@@ -127,11 +163,9 @@ struct Plan {
   std::vector<SpecCheck> spec_checks;
   struct BandBlockCounter { NodeInfo* node; u32 counter; u32 slow_counter; u32 runs_counter; bool slow_skipped; };
   std::vector<BandBlockCounter> band_block_counters;   // device-side block counts of this execution's band joins -> NodeInfo::band_blocks
-  NodeInfo* cur_band_node = nullptr;                   // the base join whose band join is being set up
   std::vector<PendingLaunch> pending;
   std::vector<DevTable> memo; std::vector<char> memo_valid;   // node results of the current execution
   ChainRequest* pending_chain = nullptr;                        // set while the base join of a fusable chain executes
-  SliceTable* cur_build_table = nullptr;                        // the store-level table of the join being set up (if any)
   PendingOj pending_oj;
   void flush_pending_oj();
   u32 events_used = 0;
@@ -156,19 +190,31 @@ struct Plan {
   DevTable exec_join(NodeInfo& nd);
   DevTable exec_topk(NodeInfo& nd);
   DevTable apply_filter(NodeInfo& nd, const DevTable& in);
+  bool keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const;
   DevTable exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R, bool build_left, const NodeInfo* probe_filter, const NodeInfo* post_filter = nullptr);
+  void lds_join_args(LdsJoin& j);
+  JoinTable choose_join_table(LdsJoin& j);
+  void size_wave_queue(LdsJoin& j);
+  void run_join_kernel(LdsJoin& j, u64 stage_bytes, u64 out_bytes_per_row);
+  DevTable run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node, u64 stage_bytes, BandArgs* band);
+  bool run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap);
+  DevTable run_exact(LdsJoin& j);
+  void left_join_tail(const NodeInfo& nd, const DevTable& L, const DevTable& R, u32* const* out, u8* visited, u64* n_out_dev, u64 matched_total);
   bool plan_chain(NodeInfo& top, ChainRequest& req);
+  struct DirectTable { bool dense = false; u32 kmin = 0, kn = 0; u32* direct = nullptr; u32* flags = nullptr; };
+  DirectTable build_direct(const u32* key, u64 n, u64 max_range, bool cached);
   void build_dense_table(SliceTable* st, const u32* key, u64 n);
-  bool build_transient_direct(LdsJoinArgs& a, u64 n);
-  bool apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& L, const DevTable& R, bool build_left, LdsJoinArgs& a, u64& stage_bytes, BandArgs* band, bool* use_band);
+  bool apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& L, const DevTable& R, bool build_left, SliceTable* build_table, LdsJoinArgs& a, u64& stage_bytes, BandArgs* band, bool* use_band);
   void prepare_partitions(const LdsJoinArgs& a, const DevTable& B, const DevTable& P, PartArgs& pa);
-  void exec_band_join(LdsJoinArgs& a, BandArgs& b, const DevTable& B, const DevTable& P, u64 build_bytes_per_row, u64 probe_bytes_per_row);
+  void exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& a, BandArgs& b, const DevTable& B, const DevTable& P, u64 build_bytes_per_row, u64 probe_bytes_per_row);
   bool choose_build_left(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf, bool lpost = false, bool rpost = false) const;
   void release_intermediates();
   template <class T> T* scratch(u64 n);
   u64* new_counter();
   const ExprProgram* upload_program(const ExprProgram& p);
-  u64 read_u64(const u64* dev);
+  // one host round trip: `bytes` of device memory copied to `host`, then the stream waited for
+  void read_back(void* host, const void* dev, size_t bytes);
+  template <class T> T read_back(const void* dev) { T v{}; read_back(&v, dev, sizeof v); return v; }
   // brackets one launch with HIP events when timing is on
   template <class F>
   void timed(int kc, u64 fixed_bytes, u64 rows_cap, const u64* rows_dev, u64 bytes_per_row,

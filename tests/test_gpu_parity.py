@@ -1785,6 +1785,41 @@ def test_plan_outlives_its_store_handle(torch_cuda):
     plan.close()
 
 
+@pytest.mark.parametrize("option", ["NO_INDEX_JOIN", "NO_BAND_JOIN"])
+def test_held_back_ordered_join_output_after_an_option_change(bsbm_stores, torch_cuda, option):
+    """The ordered slice join of the batched Q5 holds its write pass back once the band join above it has taken its records
+    (NodeInfo::band_takes_records, kept across executions).  An option set on the plan afterwards routes that join elsewhere:
+    NO_INDEX_JOIN makes the held-back table the BUILD side of a hash table built in the step, NO_BAND_JOIN the probe side of an
+    ordinary index join.  Either way the write pass has to run before the table is read: the bindings stay the oracle's."""
+    ds, gs, os_ = bsbm_stores
+    rng = np.random.default_rng(11)
+    # more parameter rows than the productFeature slice has (the constants' first join builds on the slice, ordered), few of them
+    # products: the constants table (~7.5 k rows) stays smaller than the slice, so under NO_INDEX_JOIN the candidate join builds on it
+    n_rows, n_prod = 40_000, 400
+    xs = ds.feature_base + rng.integers(0, ds.n_features, n_rows)                       # ids that are no product's
+    xs[rng.choice(n_rows, n_prod, replace=False)] = [ds.product(int(i)) for i in rng.choice(ds.n_products, n_prod, replace=False)]
+    params = [np.arange(1, n_rows + 1, dtype=np.uint32), xs.astype(np.uint32)]
+    keep, ptrs = table_on_device(torch_cuda, params)
+    desc = bsbm.q5_batch_plan(ds)
+    exp, n_exp, _ = os_.execute(desc, [params])
+    plan = gs.plan(desc).enable_kernel_timing(True)
+    plan.bind_table(0, ptrs, n_rows)
+    fused = False
+    for _ in range(6):
+        got = plan.execute().fetch()
+        np.testing.assert_array_equal(ku.multiset(got), ku.multiset(exp, n_exp))
+        fused = fused or any("oj_write_band_kernel" in k[0] for k in plan.kernel_stats())
+    assert fused or ENGINE_TOGGLED
+    plan.set_option(option, 1)
+    got = plan.execute().fetch()
+    np.testing.assert_array_equal(ku.multiset(got), ku.multiset(exp, n_exp))
+    names = {k[0] for k in plan.kernel_stats()}
+    if not ENGINE_TOGGLED:
+        assert plan.metrics().exact_reruns == 0 and any("oj_write_kernel" in k for k in names), sorted(names)   # the held-back pass ran on its own
+        if option == "NO_INDEX_JOIN":
+            assert any("gjoin_build_kernel" in k for k in names), sorted(names)
+
+
 def test_tables_rebuilt_inside_a_fused_execution(torch_cuda):
     """rdfgpu_store_drop_tables (what any extend / remove does to the cached join tables): a plan with history keeps its fused
     form — the tables it needs are built inside the next execution, which still runs the ordered slice join + band join and
