@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RDFGPU_ABI_VERSION 3u
+#define RDFGPU_ABI_VERSION 4u
 
 /* ------------------------------------------------------------------------------------ */
 /* 0. Status codes                                                                       */
@@ -326,9 +326,9 @@ typedef struct rdfgpu_expr_node {
 enum {
   RDFGPU_NODE_DATA_SOURCE = 1, /* DataSourceExec(MemQuadPatternDataSource), pattern_data_source.rs:21-58  */
   RDFGPU_NODE_FILTER = 2,      /* FilterExec: keep rows whose predicate is true; optional projection       */
-  RDFGPU_NODE_HASH_JOIN = 3,   /* HashJoinExec(CollectLeft), inner | left, NullEqualsNothing, filter, projection */
+  RDFGPU_NODE_HASH_JOIN = 3,   /* HashJoinExec(CollectLeft), inner | left | left semi | left anti, NullEqualsNothing, filter, projection */
   RDFGPU_NODE_CROSS_JOIN = 4,  /* CrossJoinExec                                                            */
-  RDFGPU_NODE_NESTED_LOOP_JOIN = 5, /* NestedLoopJoinExec: inner | left with a filter and no equi keys     */
+  RDFGPU_NODE_NESTED_LOOP_JOIN = 5, /* NestedLoopJoinExec: inner | left | left semi | left anti, no equi keys */
   RDFGPU_NODE_PROJECTION = 6,  /* ProjectionExec of plain columns                                          */
   RDFGPU_NODE_TABLE = 7,       /* bindings supplied by the caller (device columns), e.g. all-gathered rows */
   RDFGPU_NODE_TOPK = 8,        /* The operators directly above the path in the reference's explore plans (SURVEY §8f-3,
@@ -360,7 +360,19 @@ enum { RDFGPU_SORT_BY_ID = 0, RDFGPU_SORT_BY_TERM = 1,
                                     cast of BSBM explore Q10's ORDER BY yields an error = null for them).  Exact for Q10, whose
                                     prices are xsd:double literals; a decimal's cast goes through its lexical form in the
                                     reference and through the Decimal -> Double conversion here.                            */ };
-enum { RDFGPU_JOIN_INNER = 0, RDFGPU_JOIN_LEFT = 1 };
+enum { RDFGPU_JOIN_INNER = 0, RDFGPU_JOIN_LEFT = 1,
+       /* ABI 4: JoinType::LeftSemi / JoinType::LeftAnti of HashJoinExec and NestedLoopJoinExec (CROSS_JOIN stays inner-only) — what
+          FILTER EXISTS / FILTER NOT EXISTS become (correlated subqueries, lib/logical/src/expr_builder_context.rs:197-300, decorrelated
+          by DataFusion) and what MINUS becomes (LeftAnti, lib/logical/src/minus/rewrite.rs:58-130).
+          Output schema: the LEFT input's columns only; the node's projection indexes the left columns (at most 16); the join filter
+          still sees [left cols, right cols].
+          Rows: each left row appears at most once — it appears (SEMI) / does not appear (ANTI) when at least one right row matches it:
+          equal on every key and the filter evaluates to exactly true (null or false is not a match).  Keys are NullEqualsNothing: a
+          left row with a null (id 0) key never matches, so ANTI keeps it and SEMI drops it.
+          NestedLoopJoinExec without a filter: SEMI keeps every left row when the right input has at least one row, ANTI keeps every
+          left row when it has none (the EXISTS lowering for patterns that share no variable).
+          Row order unspecified, as for the other joins; duplicate left rows are all kept.                                         */
+       RDFGPU_JOIN_LEFT_SEMI = 2, RDFGPU_JOIN_LEFT_ANTI = 3 };
 #define RDFGPU_MAX_KEYS 4u
 #define RDFGPU_MAX_COLUMNS 16u
 #define RDFGPU_NO_PROJECTION 0xFFFFFFFFu
@@ -592,6 +604,7 @@ enum {
   RDFGPU_OPT_NO_STREAM_JOIN,            /* flag: joins against a direct-address table always take the generic queueing kernel (no register-resident streaming form) */
   RDFGPU_OPT_PARTITION_ROWS,            /* value: build rows per partition a partitioned join aims for (0 = automatic: 1024)   */
   RDFGPU_OPT_PARTITION_SLOTS,           /* value: slots of a partition's LDS table, a power of two from 1024 to 8192 (0 = automatic: 4096); a partition with more than slots / 2 build rows is joined chunk by chunk */
+  RDFGPU_OPT_NO_SEMI_LDS,               /* flag: semi / anti joins never build their set of right rows in LDS (the HBM set, built per execution) */
   RDFGPU_OPT__COUNT
 };
 int rdfgpu_store_set_option(rdfgpu_store* store, uint32_t option, uint64_t value);

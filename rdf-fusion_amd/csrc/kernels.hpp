@@ -252,6 +252,36 @@ void preload_tu_join_fs0();
 void preload_tu_join_fs1();
 void preload_tu_join_fs2();
 void preload_tu_join_fs3();
+// ---- LeftSemi / LeftAnti joins (semi_join.hip): one verdict per left row, the right input is only looked up ----
+// The right input is the table: a {key0, row + 1} open-addressing set in LDS (built by every workgroup) or in HBM (semi_build
+// kernel), or, for NestedLoopJoinExec, staged tile by tile through LDS.  A left row survives when some right row equals it on every
+// key (NullEqualsNothing) and passes the join filter with exactly `true` (semi), or when none does (anti).
+enum SemiForm { kSemiLds = 0, kSemiHbm = 1, kSemiNested = 2 };
+enum SemiFilter { kSemiNoFilter = 0, kSemiVm = 1, kSemiIdPair = 2 };
+constexpr u32 kSemiLdsMaxBuild = kLdsJoinMaxBuild;   // 16384 slots x 8 B = 128 KiB of LDS
+struct SemiJoinArgs {
+  const u32* cols[2 * kMaxCols];   // [left cols, right cols]: what the join filter sees
+  u32 n_left_cols, n_right_cols;
+  u32* out[kMaxCols];
+  u32 n_out_cols;
+  u32 proj[kMaxCols];              // into the left cols
+  u32 n_keys;
+  const u32* left_key[RDFGPU_MAX_KEYS];
+  const u32* right_key[RDFGPU_MAX_KEYS];
+  const u64* n_left_dev; u64 n_left_cap;
+  const u64* n_right_dev; u64 n_right_cap;
+  u32 tbl_mask;                    // slots - 1 (power of two >= 2 x right rows)
+  unsigned long long* gslots;      // kSemiHbm: the table in HBM (zeroed before the build)
+  IdPairFilter idp;                // kSemiIdPair
+  const ExprProgram* prog;         // kSemiVm (device copy)
+  TypedTable tt;
+  u64* n_out_dev;
+};
+void launch_semi_build(const SemiJoinArgs& a, bool dedupe, hipStream_t s);
+void launch_semi_join(const SemiJoinArgs& a, int form, bool anti, int filter, hipStream_t s);
+size_t semi_join_lds_bytes(const SemiJoinArgs& a, int form);
+void preload_tu_semi_join();
+
 void launch_lds_join(const LdsJoinArgs& a, hipStream_t s);
 // stream_join.hip: the same operator against a direct-address table as a streaming pass (launch_lds_join routes to it when a.stream_direct)
 bool direct_stream_join_ok(const LdsJoinArgs& a);

@@ -289,7 +289,8 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
       case RDFGPU_NODE_HASH_JOIN: case RDFGPU_NODE_CROSS_JOIN: case RDFGPU_NODE_NESTED_LOOP_JOIN: {
         const NodeInfo& l = child(r.left, "left");
         const NodeInfo& rr = child(r.right, "right");
-        if (r.join_type != RDFGPU_JOIN_INNER && r.join_type != RDFGPU_JOIN_LEFT) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: join type %u", i, r.join_type);
+        const bool semi = r.join_type == RDFGPU_JOIN_LEFT_SEMI || r.join_type == RDFGPU_JOIN_LEFT_ANTI;
+        if (r.join_type != RDFGPU_JOIN_INNER && r.join_type != RDFGPU_JOIN_LEFT && !semi) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: join type %u", i, r.join_type);
         if (r.kind == RDFGPU_NODE_HASH_JOIN) {
           if (r.n_keys == 0 || r.n_keys > RDFGPU_MAX_KEYS) fail(RDFGPU_ERR_INVALID, "node %u: HashJoinExec needs 1..%u keys", i, RDFGPU_MAX_KEYS);
           for (u32 k = 0; k < r.n_keys; k++)
@@ -298,7 +299,8 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
         if (r.kind == RDFGPU_NODE_CROSS_JOIN && (r.expr_len || r.join_type != RDFGPU_JOIN_INNER)) fail(RDFGPU_ERR_INVALID, "node %u: CrossJoinExec takes no filter / join type", i);
         if (l.width + rr.width > 2u * kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
         load_program(nd, d, l.width + rr.width, "join filter", plan->regex_dev, plan->str_consts_dev);
-        load_projection(nd, d, l.width + rr.width, "join");
+        // a semi / anti join outputs the left columns only: its projection indexes them (the filter still sees both sides)
+        load_projection(nd, d, semi ? l.width : l.width + rr.width, "join");
         nd.shape = detect_join_filter_shape(nd.prog, plan->opt.on(RDFGPU_OPT_FORCE_GENERIC_VM));
         if (l.width > (u32)kMaxCols || rr.width > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
         break;
@@ -566,7 +568,9 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::oj_probe_kernel", "rdfgpu::oj_count_kernel", "void rdfgpu::oj_write_kernel",
       "void rdfgpu::filter_write_kernel", "rdfgpu::part_keys_kernel", "void rdfgpu::part_join_kernel",
       "rdfgpu::oj_band_records_kernel", "rdfgpu::oj_write_band_kernel", "void rdfgpu::small_scan_kernel",
-      "rdfgpu::part_pass (hist + scan + scatter)", "void rdfgpu::stream_join_kernel"};
+      "rdfgpu::part_pass (hist + scan + scatter)", "void rdfgpu::stream_join_kernel", "void rdfgpu::semi_build_kernel",
+      "void rdfgpu::semi_join_kernel<0, false", "void rdfgpu::semi_join_kernel<0, true", "void rdfgpu::semi_join_kernel<1, false",
+      "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -833,7 +837,10 @@ DevTable Plan::exec_node(u32 idx) {
       for (u32 c = 0; c < nd.n_proj; c++) t.cols[c] = in.cols[nd.proj[c]];
       break;
     }
-    case RDFGPU_NODE_HASH_JOIN: case RDFGPU_NODE_CROSS_JOIN: case RDFGPU_NODE_NESTED_LOOP_JOIN: t = exec_join(nd); break;
+    case RDFGPU_NODE_HASH_JOIN: case RDFGPU_NODE_CROSS_JOIN: case RDFGPU_NODE_NESTED_LOOP_JOIN:
+      // semi / anti joins leave before anything of exec_join (chain planning, filter fusion, side choice) sees them
+      t = nd.d.join_type == RDFGPU_JOIN_LEFT_SEMI || nd.d.join_type == RDFGPU_JOIN_LEFT_ANTI ? exec_semi_join(nd) : exec_join(nd);
+      break;
     case RDFGPU_NODE_TOPK: t = exec_topk(nd); break;
     case RDFGPU_NODE_CLOSURE: {
       const DevTable in = exec_node((u32)nd.d.left);
@@ -1120,6 +1127,86 @@ DevTable Plan::exec_topk(NodeInfo& nd) {
   return t;
 }
 
+// HashJoinExec / NestedLoopJoinExec with JoinType::LeftSemi / LeftAnti (semi_join.hip).  The output has at most as many rows as the
+// left input: a table of cap L.cap whose count stays on the device, like a FilterExec's — no speculation, no overflow, no re-run.
+// The right input (the existence side) is the table, the left rows probe it: a set built by every workgroup in LDS when the right
+// input is small, else one set in HBM built in this execution; a NestedLoopJoinExec streams the right rows through LDS.
+DevTable Plan::exec_semi_join(NodeInfo& nd) {
+  const bool anti = nd.d.join_type == RDFGPU_JOIN_LEFT_ANTI;
+  // the inputs are sub-plans of their own (a chain pending above must not leak into them)
+  ChainRequest* const for_this_join = pending_chain;
+  pending_chain = nullptr;
+  const DevTable L = exec_node((u32)nd.d.left);
+  const DevTable R = exec_node((u32)nd.d.right);
+  pending_chain = for_this_join;
+  flush_pending_oj();   // a held-back ordered-join write must have happened before either input is read
+  DevTable t;
+  t.n_cols = nd.n_proj;
+  if (L.cap == 0) { t.cap = 0; return t; }
+  const bool hash = nd.d.kind == RDFGPU_NODE_HASH_JOIN;
+  const bool right_empty = R.cap == 0;
+  // the verdict is the same for every left row when the right input is empty (nothing matches), or for a nested-loop join without a
+  // filter over a right input whose row count the host knows: the left rows, projected, without a launch
+  if (right_empty || (!hash && nd.prog.n == 0 && R.n_dev == nullptr)) {
+    const bool keep_all = right_empty ? anti : !anti;
+    if (!keep_all) { t.cap = 0; return t; }
+    t.cap = L.cap; t.n_dev = L.n_dev;
+    for (u32 c = 0; c < nd.n_proj; c++) t.cols[c] = L.cols[nd.proj[c]];
+    return t;
+  }
+  if (L.cap >= 0xFFFFFFF0ull || R.cap >= 0x7FFFFFFFull) fail(RDFGPU_ERR_UNSUPPORTED, "semi / anti join of %llu x %llu rows", (unsigned long long)L.cap, (unsigned long long)R.cap);
+  SemiJoinArgs a{};
+  for (u32 c = 0; c < L.n_cols; c++) a.cols[c] = L.cols[c];
+  for (u32 c = 0; c < R.n_cols; c++) a.cols[L.n_cols + c] = R.cols[c];
+  a.n_left_cols = L.n_cols; a.n_right_cols = R.n_cols;
+  a.n_out_cols = nd.n_proj;
+  for (u32 c = 0; c < nd.n_proj; c++) { a.proj[c] = nd.proj[c]; a.out[c] = scratch<u32>(L.cap); t.cols[c] = a.out[c]; }
+  a.n_keys = hash ? nd.d.n_keys : 0;
+  for (u32 k = 0; k < a.n_keys; k++) { a.left_key[k] = L.cols[nd.d.left_keys[k]]; a.right_key[k] = R.cols[nd.d.right_keys[k]]; }
+  a.n_left_dev = L.n_dev; a.n_left_cap = L.cap; a.n_right_dev = R.n_dev; a.n_right_cap = R.cap;
+  a.tt = typed_table();
+  a.n_out_dev = new_counter();
+  int filter = kSemiNoFilter;
+  u32 left_fcols = 0;   // distinct left columns the filter reads (compulsory bytes)
+  if (nd.prog.n) {
+    bool used[2 * kMaxCols] = {};
+    for (u32 i = 0; i < nd.prog.n; i++) if (nd.prog.nodes[i].op == RDFGPU_EX_COLUMN) used[nd.prog.nodes[i].u] = true;
+    for (u32 c = 0; c < L.n_cols; c++) left_fcols += used[c];
+    if (nd.shape == 2) {   // `col <ID_EQ | ID_NEQ> col`
+      filter = kSemiIdPair;
+      a.idp = IdPairFilter{nd.prog.nodes[0].u, nd.prog.nodes[1].u, nd.prog.nodes[2].op == RDFGPU_EX_ID_EQ ? 1u : 0u};
+    } else {
+      filter = kSemiVm;
+      a.prog = upload_program(nd.prog);
+    }
+  }
+  int form = kSemiNested;
+  u64 build_bytes = 0;
+  if (hash) {
+    const u64 lds_max = std::min<u64>(opt.v[RDFGPU_OPT_LDS_MAX_BUILD], kSemiLdsMaxBuild);
+    form = R.cap <= lds_max && !opt.on(RDFGPU_OPT_NO_SEMI_LDS) ? kSemiLds : kSemiHbm;
+    u64 slots = 64;
+    while (slots < 2 * R.cap) slots <<= 1;
+    a.tbl_mask = (u32)(slots - 1);
+    // build half: the right keys read once, one 8-byte slot written per row
+    build_bytes = (4ull * a.n_keys + 8) * R.cap;
+    if (form == kSemiHbm) {
+      a.gslots = scratch<unsigned long long>(slots);
+      RDFGPU_HIP(hipMemsetAsync(a.gslots, 0, slots * sizeof(unsigned long long), stream));
+      timed(KC_SEMI_BUILD, 0, R.cap, R.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0, [&] { launch_semi_build(a, filter == kSemiNoFilter, stream); });
+      build_bytes = 0;
+    }
+  } else {
+    build_bytes = 4ull * R.n_cols * R.cap;   // the right rows staged once (re-reads of them come from L2)
+  }
+  // compulsory bytes: 4·(k + c)·N_left (keys and left filter columns) + 4·c_out·N_out (the survivors' columns, read and written:
+  // 8 per cell) + the build's; right columns of candidates are not counted (their number depends on the data)
+  timed(semi_join_class(form, anti), build_bytes, L.cap, L.n_dev, 4ull * (a.n_keys + left_fcols), a.n_out_dev, 0, 8ull * nd.n_proj,
+        [&] { launch_semi_join(a, form, anti, filter, stream); });
+  t.cap = L.cap; t.n_dev = a.n_out_dev;
+  return t;
+}
+
 // Which input the hash join builds on.  A left join must build on the preserved (left) side.  An inner join builds
 // on the smaller input — unless exactly one input is a pure slice of the store (the same rows on every execution
 // until the store changes) and the other one is no larger: the slice's join table (direct-address / CSR / hash) is
@@ -1194,7 +1281,7 @@ bool Plan::plan_chain(NodeInfo& top, ChainRequest& req) {
       const u32 cs = (u32)(side == 0 ? d.left : d.right), co = (u32)(side == 0 ? d.right : d.left);
       const NodeInfo& sn = nodes[cs]; const NodeInfo& on = nodes[co];
       if (sn.d.kind != RDFGPU_NODE_DATA_SOURCE || sources[sn.source].has_residual) continue;
-      if (on.d.kind != RDFGPU_NODE_HASH_JOIN || on.refs != 1) continue;
+      if (on.d.kind != RDFGPU_NODE_HASH_JOIN || on.d.join_type > RDFGPU_JOIN_LEFT || on.refs != 1) continue;   // (a semi / anti join is no chain base)
       const DevTable S = exec_node(cs);   // a slice: no launch
       if (S.cap == 0 || S.stable_id == 0) continue;
       SliceKey sk; sk.n_keys = 1; sk.rows = S.cap; sk.key[0] = S.cols[side == 0 ? d.left_keys[0] : d.right_keys[0]];

@@ -105,13 +105,17 @@ enum KernelClass {
   KC_BAND_SLOW, KC_RADIX_SORT, KC_BAND_BOUNDS, KC_BAND_BLOCKS, KC_BAND_DECODE, KC_BAND_MASK, KC_BAND_EMIT, KC_BAND_ENTRIES, KC_BAND_DESC, KC_BAND_PT, KC_BAND_ROWS,
   KC_FILTER_BITS_ID, KC_FILTER_BITS_TV, KC_FILTER_BITS_VERDICT, KC_FILTER_BITS_VALUE, KC_VALUE_VERDICTS, KC_VALUE_RUNS, KC_RUN_SCAN, KC_RUN_COPY, KC_OJ_PROBE, KC_OJ_COUNT, KC_OJ_WRITE, KC_FILTER_WRITE,
   KC_PART_KEYS, KC_PART_JOIN, KC_OJ_BAND_RECORDS, KC_OJ_WRITE_BAND, KC_SMALL_SCAN, KC_PART_PASS, KC_STREAM_JOIN,
-  KC_LDS_JOIN0,                      // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
+  KC_SEMI_BUILD, KC_SEMI_JOIN0,      // 6 names: semi_join_kernel<form 0 / 1, anti>, semi_nested_kernel<anti> (semi_join_class)
+  KC_SEMI_JOIN_END = KC_SEMI_JOIN0 + 6,
+  KC_LDS_JOIN0 = KC_SEMI_JOIN_END,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
 const char* kernel_class_name(int kc);
 inline int lds_join_class(u32 fs, u32 pfs, int items, int mode, bool chain = false) {
   return KC_LDS_JOIN0 + (int)((((fs * 3 + pfs) * 2 + (items == 4 ? 0 : 1)) * 4 + mode) * 2) + (chain ? 1 : 0);
 }
+
+inline int semi_join_class(int form, bool anti) { return KC_SEMI_JOIN0 + form * 2 + (anti ? 1 : 0); }
 
 struct KernelStat { u32 launches = 0; double ms = 0; u64 bytes = 0; u64 rows = 0; };
 
@@ -189,6 +193,7 @@ struct Plan {
   DevTable exec_filter(NodeInfo& nd);
   DevTable exec_join(NodeInfo& nd);
   DevTable exec_topk(NodeInfo& nd);
+  DevTable exec_semi_join(NodeInfo& nd);
   DevTable apply_filter(NodeInfo& nd, const DevTable& in);
   bool keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const;
   DevTable exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R, bool build_left, const NodeInfo* probe_filter, const NodeInfo* post_filter = nullptr);

@@ -399,14 +399,22 @@ class PlanBuilder:
         n = abi.PlanNode(kind=abi.NODE_PROJECTION, left=child, right=-1)
         return self._push(n, self._proj(n, columns, self.width[child]), self._projected(self.names[child], columns))
 
+    def _join_output(self, left, right, join_type):
+        """Columns a join outputs before its projection: [left, right], or the left ones only for LeftSemi / LeftAnti."""
+        if join_type in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI):
+            return self.width[left], self.names[left]
+        return self.width[left] + self.width[right], self.names[left] + self.names[right]
+
     def hash_join(self, left, right, on, join_type=abi.JOIN_INNER, filter=None, projection=None):
+        """HashJoinExec(CollectLeft).  join_type LEFT_SEMI / LEFT_ANTI: the output is the left columns (the projection indexes
+        them); the filter still sees [left cols, right cols]."""
         n = abi.PlanNode(kind=abi.NODE_HASH_JOIN, left=left, right=right, join_type=join_type)
         n.n_keys = len(on)
         for k, (l, r) in enumerate(on):
             n.left_keys[k], n.right_keys[k] = l, r
         self._expr(n, filter)
-        return self._push(n, self._proj(n, projection, self.width[left] + self.width[right]),
-                          self._projected(self.names[left] + self.names[right], projection))
+        width, names = self._join_output(left, right, join_type)
+        return self._push(n, self._proj(n, projection, width), self._projected(names, projection))
 
     def cross_join(self, left, right):
         n = abi.PlanNode(kind=abi.NODE_CROSS_JOIN, left=left, right=right, join_type=abi.JOIN_INNER)
@@ -416,8 +424,8 @@ class PlanBuilder:
     def nested_loop_join(self, left, right, join_type=abi.JOIN_INNER, filter=None, projection=None):
         n = abi.PlanNode(kind=abi.NODE_NESTED_LOOP_JOIN, left=left, right=right, join_type=join_type)
         self._expr(n, filter)
-        return self._push(n, self._proj(n, projection, self.width[left] + self.width[right]),
-                          self._projected(self.names[left] + self.names[right], projection))
+        width, names = self._join_output(left, right, join_type)
+        return self._push(n, self._proj(n, projection, width), self._projected(names, projection))
 
     def table(self, slot, n_cols, names=None):
         n = abi.PlanNode(kind=abi.NODE_TABLE, left=-1, right=-1, table_slot=slot, table_cols=n_cols)
@@ -481,6 +489,49 @@ class PlanBuilder:
         keep = list(range(len(ln))) + [len(ln) + i for i, v in enumerate(rn) if v not in ln]
         return self.hash_join(left, right, on, join_type=join_type, filter=filter, projection=keep)
 
+    # -- EXISTS / NOT EXISTS / MINUS lowering -----------------------------------------------------
+    def _semi_anti(self, left, right, anti, nullable, minus):
+        ln, rn = self.names[left], self.names[right]
+        shared = sorted(v for v in ln if v in rn)
+        jt = abi.JOIN_LEFT_ANTI if anti else abi.JOIN_LEFT_SEMI
+        if not any(v in nullable for v in shared):
+            on = [(ln.index(v), rn.index(v)) for v in shared]
+            return self.hash_join(left, right, on, join_type=jt)
+        w = len(ln)
+        f = None
+        for v in shared:
+            c = IS_COMPATIBLE(col(ln.index(v)), col(w + rn.index(v)))
+            f = c if f is None else AND(f, c)
+        if minus:
+            some = None
+            for v in shared:
+                b = AND(BOUND(col(ln.index(v))), BOUND(col(w + rn.index(v))))
+                some = b if some is None else OR(some, b)
+            f = AND(f, some)
+        return self.nested_loop_join(left, right, jt, filter=f)
+
+    def sparql_exists(self, outer, inner, negate=False, nullable=()):
+        """FILTER EXISTS { inner } (negate: FILTER NOT EXISTS) over `outer`: the correlated subquery of
+        lib/logical/src/expr_builder_context.rs:197-300, as DataFusion decorrelates it into a LeftSemi / LeftAnti join whose
+        output is `outer`'s columns.  S = the variables `outer` and `inner` share:
+          - S empty: the test is whether `inner` has any row at all — a NestedLoopJoinExec without a filter;
+          - no variable of S nullable: a hash join on every variable of S, in sorted order (the correlation predicates
+            `outer.v = inner.v`, :275-276, become the equi-keys);
+          - some variable of S in `nullable`: IS_COMPATIBLE per shared variable, AND-ed, as the join filter of a
+            NestedLoopJoinExec (no equi-keys are left)."""
+        if not any(v in self.names[inner] for v in self.names[outer]):
+            return self.nested_loop_join(outer, inner, abi.JOIN_LEFT_ANTI if negate else abi.JOIN_LEFT_SEMI)
+        return self._semi_anti(outer, inner, negate, set(nullable), minus=False)
+
+    def sparql_minus(self, left, right, nullable=()):
+        """left MINUS right (lib/logical/src/minus/rewrite.rs:58-130): a LeftAnti join.  No shared variable: `left` unchanged
+        (:62-64).  Shared variables all non-nullable: anti join on them.  Otherwise a NestedLoopJoinExec whose filter is the AND
+        over S of IS_COMPATIBLE(l.v, r.v), AND-ed with the OR over S of BOUND(l.v) AND BOUND(r.v) (:93-135: a right row that binds
+        none of the shared variables removes nothing)."""
+        if not any(v in self.names[right] for v in self.names[left]):
+            return left
+        return self._semi_anti(left, right, True, set(nullable), minus=True)
+
 
 # ----------------------------------------------------------------------------------------------
 # plan display, in the reference's format (bench/tests/plans/snapshots/*.snap; DataSourceExec lines as
@@ -488,6 +539,7 @@ class PlanBuilder:
 # ----------------------------------------------------------------------------------------------
 _BIN = {abi.EX_GT: "GT", abi.EX_LT: "LT", abi.EX_GEQ: "GEQ", abi.EX_LEQ: "LEQ", abi.EX_EQ: "EQ", abi.EX_ADD: "ADD", abi.EX_SUB: "SUB",
         abi.EX_IS_COMPATIBLE: "IS_COMPATIBLE"}
+_JOIN_TYPE_NAMES = {abi.JOIN_INNER: "Inner", abi.JOIN_LEFT: "Left", abi.JOIN_LEFT_SEMI: "LeftSemi", abi.JOIN_LEFT_ANTI: "LeftAnti"}
 _UN = {abi.EX_ENC_TV: "ENC_TV", abi.EX_EBV: "EBV", abi.EX_BOUND: "BOUND", abi.EX_BOOL_AS_TV: "BOOLEAN_AS_TERM"}
 
 
@@ -559,7 +611,7 @@ def explain(pb, root, choose_index=None):
             return
         if n.kind in (abi.NODE_HASH_JOIN, abi.NODE_NESTED_LOOP_JOIN):
             ln, rn = pb.names[n.left], pb.names[n.right]
-            jt = "Inner" if n.join_type == abi.JOIN_INNER else "Left"
+            jt = _JOIN_TYPE_NAMES[n.join_type]
             head = "HashJoinExec: mode=CollectLeft" if n.kind == abi.NODE_HASH_JOIN else "NestedLoopJoinExec:"
             sep = ", " if n.kind == abi.NODE_HASH_JOIN else " "
             text = f"{head}{sep}join_type={jt}"
@@ -574,7 +626,7 @@ def explain(pb, root, choose_index=None):
                 both = ln + rn
                 fake = [abi.ExprNode(e.op, e.tag, e.flags, 0, renum[e.u] if e.op == abi.EX_COLUMN else e.u, e.lo, e.hi) for e in ex]
                 text += ", filter=" + format_expr(fake, [both[c] for c in used])
-            lines.append(f"{pad}{text}{proj(i, ln + rn)}")
+            lines.append(f"{pad}{text}{proj(i, ln if n.join_type in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI) else ln + rn)}")
             walk(n.left, depth + 1); walk(n.right, depth + 1)
             return
         if n.kind == abi.NODE_CROSS_JOIN:
