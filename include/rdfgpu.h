@@ -347,12 +347,65 @@ enum {
   RDFGPU_NODE_UNION = 9,       /* UnionExec: the rows of `left` followed by the rows of `right` (bag union; both inputs have
                                   the same columns) — SPARQL UNION as planned in BSBM Explore - Q4 / Q11 (Execution Plan).snap;
                                   optional projection */
-  RDFGPU_NODE_CLOSURE = 10     /* KleenePlusClosureExec (lib/physical/src/paths/kleene_plus/physical.rs:94-157, 246-384): `left` yields
+  RDFGPU_NODE_CLOSURE = 10,    /* KleenePlusClosureExec (lib/physical/src/paths/kleene_plus/physical.rs:94-157, 246-384): `left` yields
                                   the inner paths (graph, start, end) — graph 0 = default graph; the output is the SET of all paths
                                   of one or more inner paths chained end-to-start: within one graph (join_type = 0), or continuing
                                   through the inner paths of any graph while keeping the first path's graph (join_type = 1 =
                                   allow_cross_graph_paths).  A null start / end is an execution error, as in the reference. */
+  /* ABI 4 addendum (backward compatible: new enum values and functions, no struct changed) */
+  RDFGPU_NODE_AGGREGATE = 11   /* AggregateExec(mode=Single) over object-id group columns — what the BSBM Business Intelligence plans put
+                                  on top of their join trees (bench/tests/plans/snapshots/..Business Intelligence - Q1..Q8 (Execution
+                                  Plan).snap).  Encoding: left = input; n_keys (0..RDFGPU_MAX_KEYS) group columns in left_keys[];
+                                  table_cols = number of aggregates (0..RDFGPU_MAX_AGGREGATES); table_slot = offset into the u32 pool of
+                                  table_cols pairs (RDFGPU_AGG_*, input column); n_proj must be RDFGPU_NO_PROJECTION.  Output columns: the
+                                  keys in order, then the aggregates.  Two rows are one group when their key ids are equal; id 0
+                                  (unbound) is a key value like any other (SQL GROUP BY puts NULLs in a group of their own).  With 0 keys
+                                  there is exactly one output row, even over an empty input; with keys an empty input gives no row.  Row
+                                  order unspecified.  A node without aggregates (a DISTINCT over its keys, BI Q4's `AggregateExec:
+                                  gby=[feature], aggr=[]`) outputs object ids only and may appear anywhere in a plan; a node WITH
+                                  aggregates must be the plan's root (their values are not object ids and cannot flow into another
+                                  operator), anywhere else it is RDFGPU_ERR_UNSUPPORTED at compile.  An input of 2^32 rows or more fails
+                                  the execute with RDFGPU_ERR_UNSUPPORTED.  The aggregate values leave through rdfgpu_plan_agg_*;
+                                  rdfgpu_plan_result_info / _device / _fetch report the key columns only.                              */
 };
+/*
+ * Aggregate functions of RDFGPU_NODE_AGGREGATE (ABI 4 addendum).  The reference plans SPARQL aggregates in
+ * lib/logical/src/expr_builder.rs:700-760 onto its own accumulators (lib/functions/src/aggregates/); the input of SUM / AVG is
+ * ENC_TV of an object-id column (the expression VM has no casts: BSBM BI's `AVG(xsd:float(xsd:string(?price)))` stays on the host).
+ *   COUNT_STAR      rows of the group, as xsd:integer: DataFusion count(*) then INT64_AS_TERM (graph_pattern_rewriter.rs:311-313)
+ *   COUNT           rows whose input id is not 0 (unbound), xsd:integer
+ *   COUNT_DISTINCT  distinct non-zero ids of the input column in the group, xsd:integer (expr_builder.rs:724-733: count_distinct over
+ *                   the ids; two ids are two terms)
+ *   SUM             aggregates/sum.rs:34-73.  The sum starts as xsd:integer 0.  A value that is not numeric, unbound ones included, is
+ *                   skipped (sum.rs:52 has no `else`; the reference's behaviour, not the SPARQL spec's).  Kinds promote as in
+ *                   NumericPair::with_casts_from (lib/model/src/xsd/numeric.rs:127-): int / integer, then decimal, then float, then
+ *                   double; the result kind is the widest kind seen in the group.  An integer result outside i64 is the error value,
+ *                   and so is a decimal result outside the i128 x 10^-18 range.
+ *   AVG             aggregates/avg.rs:43-134.  The sum starts as xsd:DECIMAL 0, so an all-integer group averages to a decimal:
+ *                   AVG(1, 2) = 1.5.  Every row of the group is counted (avg.rs:59); one value that is not numeric or unbound makes
+ *                   the result the error value (avg.rs:63-78).  A count of 0 gives xsd:integer 0 (only the zero-key group over an empty
+ *                   input has one).  Decimal results are Decimal::checked_div(sum, count) (lib/model/src/xsd/decimal.rs:131-162),
+ *                   restated bit-exactly: the dividend is scaled by 10 while it stays inside i128, the divisor's trailing zeros are
+ *                   stripped, two truncating divisions, and a scale beyond 10^38 is the error value.  Float results divide by
+ *                   f32(count), double results by f64(count).
+ * Exactness.  Counts and every integer / decimal sum are exact and independent of row order (each value's i128 is added as 32-bit limbs
+ * into u64 counters, carried and range-checked once per group: exact up to 2^32 rows per group).  The reference adds float and double
+ * values one after the other in row order, so its result depends on that order; here the order is the device's, and the result satisfies
+ *     |result - exact sum| <= n * eps * sum(|x_i|) + eta,  eps = 2^-24 and eta = 2^-149 for a float result, 2^-53 and 2^-1074 for a double one
+ * where x_i is each value as the reference casts it (to f32 for a float result, to f64 for a double one), n the group's numeric values and
+ * eta the spacing of the subnormals (a rounding near zero is absolute, not relative).  AVG divides that sum once more, correctly rounded.
+ * The reference's integer / decimal overflow can depend on order too (a prefix overflows, the total does not); here the TOTAL decides.
+ * Not on the device — refused with RDFGPU_ERR_UNSUPPORTED at compile, never answered differently: MIN, MAX, SAMPLE, GROUP_CONCAT (MIN / MAX
+ * keep the first value's error state, so their result depends on row order when a group holds unbound values, min.rs:42-53), SUM / AVG
+ * with DISTINCT, COUNT(DISTINCT *), more than RDFGPU_MAX_KEYS keys or RDFGPU_MAX_AGGREGATES aggregates.
+ */
+enum {
+  RDFGPU_AGG_COUNT_STAR = 1, RDFGPU_AGG_COUNT = 2, RDFGPU_AGG_COUNT_DISTINCT = 3, RDFGPU_AGG_SUM = 4, RDFGPU_AGG_AVG = 5,
+  /* reserved, RDFGPU_ERR_UNSUPPORTED at compile */
+  RDFGPU_AGG_MIN = 6, RDFGPU_AGG_MAX = 7, RDFGPU_AGG_SAMPLE = 8, RDFGPU_AGG_GROUP_CONCAT = 9,
+  RDFGPU_AGG_SUM_DISTINCT = 10, RDFGPU_AGG_AVG_DISTINCT = 11, RDFGPU_AGG_COUNT_DISTINCT_STAR = 12
+};
+#define RDFGPU_MAX_AGGREGATES 8u
 enum { RDFGPU_SORT_BY_ID = 0, RDFGPU_SORT_BY_TERM = 1,
        RDFGPU_SORT_BY_DOUBLE = 2 /* ENC_SORT of a numeric value: the sortable encoding orders numerics by Double::from(Numeric)
                                     (lib/encoding/src/sortable_term/builder.rs:36-39, lib/model/src/xsd/double.rs:92-102) in IEEE
@@ -464,10 +517,33 @@ int rdfgpu_plan_result_device(rdfgpu_plan* plan, const uint32_t** cols, uint32_t
 /* Copies the whole result to caller-owned host columns (each with room for n_rows). */
 int rdfgpu_plan_fetch(rdfgpu_plan* plan, uint32_t* const* host_cols, uint32_t n_cols);
 /*
+ * ABI 4 addendum: the aggregate values of a RDFGPU_NODE_AGGREGATE root, one per result row and aggregate (row i of aggregate a belongs
+ * to row i of the key columns).  24 bytes each:
+ *   tag RDFGPU_TV_INTEGER   lo = the value (counts, integer sums)
+ *   tag RDFGPU_TV_DECIMAL   (lo, hi) = the i128 value * 10^18
+ *   tag RDFGPU_TV_FLOAT     lo = the IEEE-754 binary32 bits (zero-extended);  RDFGPU_TV_DOUBLE: lo = the binary64 bits
+ *   tag RDFGPU_TV_NULL      the error value
+ * The host turns integers into xsd:integer terms (INT64_AS_TERM) and the rest into typed literals.
+ */
+typedef struct rdfgpu_agg_value {
+  int64_t lo;
+  int64_t hi;
+  uint8_t tag;
+  uint8_t reserved[7];
+} rdfgpu_agg_value;
+/* Number of aggregate columns of the executed result (0 unless the root is an RDFGPU_NODE_AGGREGATE with aggregates). */
+int rdfgpu_plan_agg_count(rdfgpu_plan* plan, uint32_t* n_aggs);
+/* Copies aggregate `agg` of every result row (n_rows of rdfgpu_plan_result_info) to caller-owned host memory. */
+int rdfgpu_plan_agg_fetch(rdfgpu_plan* plan, uint32_t agg, rdfgpu_agg_value* host);
+/* Device pointer of aggregate `agg` (n_rows values; valid until the next execute / destroy of this plan; NULL when there are no rows). */
+int rdfgpu_plan_agg_device(rdfgpu_plan* plan, uint32_t agg, const rdfgpu_agg_value** values);
+/*
  * SendableRecordBatchStream::poll_next (stream.rs:39-63): exports the next batch of at
  * most batch_size rows as an Arrow struct array of UInt32 children (format "+s" / "I");
  * id 0 becomes a null.  Never yields an empty batch (scan.rs:195-198).  Returns
- * RDFGPU_END once drained.  `schema` may be NULL.
+ * RDFGPU_END once drained.  `schema` may be NULL.  ABI 4 addendum: after the key columns, each
+ * aggregate of an RDFGPU_NODE_AGGREGATE root is one more child, a struct "+s" of
+ * tag: uint8 "C", lo: int64 "l", hi: int64 "l" (rdfgpu_agg_value), null where the tag is 0.
  */
 int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSchema* schema);
 /* Restarts the batch stream over the current result. */
@@ -605,6 +681,7 @@ enum {
   RDFGPU_OPT_PARTITION_ROWS,            /* value: build rows per partition a partitioned join aims for (0 = automatic: 1024)   */
   RDFGPU_OPT_PARTITION_SLOTS,           /* value: slots of a partition's LDS table, a power of two from 1024 to 8192 (0 = automatic: 4096); a partition with more than slots / 2 build rows is joined chunk by chunk */
   RDFGPU_OPT_NO_SEMI_LDS,               /* flag: semi / anti joins never build their set of right rows in LDS (the HBM set, built per execution) */
+  RDFGPU_OPT_NO_AGG_LDS,                /* flag (ABI 4 addendum): AggregateExec never keeps per-workgroup partial accumulators in LDS (every row adds into the HBM accumulators) */
   RDFGPU_OPT__COUNT
 };
 int rdfgpu_store_set_option(rdfgpu_store* store, uint32_t option, uint64_t value);

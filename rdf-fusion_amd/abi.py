@@ -34,7 +34,14 @@ NT_IRI, NT_BNODE, NT_SIMPLE, NT_LANG, NT_TYPED = 1, 2, 3, 4, 5   # rdfgpu_ntripl
 
 # plan nodes
 (NODE_DATA_SOURCE, NODE_FILTER, NODE_HASH_JOIN, NODE_CROSS_JOIN, NODE_NESTED_LOOP_JOIN,
- NODE_PROJECTION, NODE_TABLE, NODE_TOPK, NODE_UNION, NODE_CLOSURE) = range(1, 11)
+ NODE_PROJECTION, NODE_TABLE, NODE_TOPK, NODE_UNION, NODE_CLOSURE, NODE_AGGREGATE) = range(1, 12)
+# aggregate functions of NODE_AGGREGATE (ABI 4 addendum); MIN .. COUNT_DISTINCT_STAR are reserved and refused at compile
+(AGG_COUNT_STAR, AGG_COUNT, AGG_COUNT_DISTINCT, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_SAMPLE, AGG_GROUP_CONCAT,
+ AGG_SUM_DISTINCT, AGG_AVG_DISTINCT, AGG_COUNT_DISTINCT_STAR) = range(1, 13)
+AGG_NAMES = {AGG_COUNT_STAR: "COUNT(*)", AGG_COUNT: "COUNT", AGG_COUNT_DISTINCT: "COUNT(DISTINCT)", AGG_SUM: "SUM", AGG_AVG: "AVG",
+             AGG_MIN: "MIN", AGG_MAX: "MAX", AGG_SAMPLE: "SAMPLE", AGG_GROUP_CONCAT: "GROUP_CONCAT", AGG_SUM_DISTINCT: "SUM(DISTINCT)",
+             AGG_AVG_DISTINCT: "AVG(DISTINCT)", AGG_COUNT_DISTINCT_STAR: "COUNT(DISTINCT *)"}
+MAX_AGGREGATES = 8
 SORT_BY_ID, SORT_BY_TERM, SORT_BY_DOUBLE = 0, 1, 2
 JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
 MAX_KEYS = 4
@@ -48,7 +55,7 @@ OPTION_NAMES = ["FORCE_GENERIC_VM", "NO_JOIN_REORDER", "NO_SPECULATION", "NO_FIR
                 "NO_TABLE_CACHE", "NO_INDEX_JOIN", "NO_CHAIN_FUSION", "NO_VALUE_TABLES", "NO_RANGE_INDEX", "NO_FILTER_FUSION",
                 "NO_LDS_JOIN", "NO_GLOBAL_TABLE_JOIN", "NO_DIRECT_TABLE", "NO_BAND_JOIN", "NO_PARTITIONED_JOIN", "NO_VALUE_VERDICTS", "NO_PRIMING", "NO_ORDERED_JOIN", "NO_BAND_PACK16", "NO_RUN_COPY", "NO_RANGE_PARTITION",
                 "LDS_MAX_BUILD", "CSR_ROW_LANES_LOG2", "JOIN_WAVE_Q", "PARTITION_MIN_BUILD", "PARTITION_TWO_PASS_ROWS", "NO_OWN_PARTITION_PASS", "NO_BAND_COMPACT", "NO_PROBE_OUTER_JOIN", "NO_STREAM_JOIN", "PARTITION_ROWS", "PARTITION_SLOTS",
-                "NO_SEMI_LDS"]
+                "NO_SEMI_LDS", "NO_AGG_LDS"]
 OPTIONS = {name: i for i, name in enumerate(OPTION_NAMES)}
 
 
@@ -60,6 +67,11 @@ class Config(C.Structure):
 class TypedValue(C.Structure):
     _fields_ = [("lo", C.c_int64), ("aux", C.c_uint32), ("tag", C.c_uint8), ("flags", C.c_uint8),
                 ("reserved", C.c_uint16)]
+
+
+class AggValue(C.Structure):
+    """rdfgpu_agg_value: tag TV_INTEGER lo = value; TV_DECIMAL (lo, hi) = i128 * 10^18; TV_FLOAT / TV_DOUBLE lo = IEEE bits; TV_NULL = error"""
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("tag", C.c_uint8), ("reserved", C.c_uint8 * 7)]
 
 
 class ScanInstruction(C.Structure):
@@ -141,6 +153,7 @@ ArrowArray._fields_ = [
 assert C.sizeof(TypedValue) == 16
 assert C.sizeof(ScanInstruction) == 16
 assert C.sizeof(ExprNode) == 24
+assert C.sizeof(AggValue) == 24
 
 # every symbol include/rdfgpu.h declares (the CPU test-suite checks the .so exports them all)
 EXPORTED_SYMBOLS = [
@@ -150,6 +163,7 @@ EXPORTED_SYMBOLS = [
     "rdfgpu_store_read_index",
     "rdfgpu_plan_compile", "rdfgpu_plan_destroy", "rdfgpu_plan_bind_table", "rdfgpu_plan_execute",
     "rdfgpu_plan_result_info", "rdfgpu_plan_result_device", "rdfgpu_plan_fetch", "rdfgpu_plan_next",
+    "rdfgpu_plan_agg_count", "rdfgpu_plan_agg_fetch", "rdfgpu_plan_agg_device",
     "rdfgpu_plan_rewind", "rdfgpu_plan_decode_terms", "rdfgpu_ntriples_parse", "rdfgpu_ntriples_info", "rdfgpu_ntriples_terms", "rdfgpu_ntriples_decoded_info", "rdfgpu_ntriples_decoded", "rdfgpu_ntriples_columns", "rdfgpu_ntriples_destroy", "rdfgpu_plan_metrics", "rdfgpu_plan_selected_index", "rdfgpu_plan_stream",
     "rdfgpu_plan_enable_kernel_timing", "rdfgpu_plan_kernel_stats",
     "rdfgpu_plan_pushdown_filters", "rdfgpu_plan_set_dynamic_filters", "rdfgpu_plan_source_predicate",

@@ -181,6 +181,36 @@ int rdfgpu_plan_fetch(rdfgpu_plan* plan, uint32_t* const* host_cols, uint32_t n_
   ABI_END
 }
 
+int rdfgpu_plan_agg_count(rdfgpu_plan* plan, uint32_t* n_aggs) {
+  ABI_BEGIN
+  Plan* p = P(plan);
+  if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  if (n_aggs) *n_aggs = (uint32_t)p->agg_out.size();
+  ABI_END
+}
+int rdfgpu_plan_agg_fetch(rdfgpu_plan* plan, uint32_t agg, rdfgpu_agg_value* host) {
+  ABI_BEGIN
+  Plan* p = P(plan);
+  if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  if (agg >= p->agg_out.size()) fail(RDFGPU_ERR_INVALID, "aggregate %u of %zu", agg, p->agg_out.size());
+  p->store->activate();
+  if (p->result_rows) {
+    if (!host) fail(RDFGPU_ERR_INVALID, "null host buffer");
+    RDFGPU_HIP(hipMemcpyAsync(host, p->agg_out[agg], p->result_rows * sizeof(rdfgpu_agg_value), hipMemcpyDeviceToHost, p->stream));
+  }
+  RDFGPU_HIP(hipStreamSynchronize(p->stream));
+  ABI_END
+}
+int rdfgpu_plan_agg_device(rdfgpu_plan* plan, uint32_t agg, const rdfgpu_agg_value** values) {
+  ABI_BEGIN
+  Plan* p = P(plan);
+  if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  if (agg >= p->agg_out.size()) fail(RDFGPU_ERR_INVALID, "aggregate %u of %zu", agg, p->agg_out.size());
+  if (!values) fail(RDFGPU_ERR_INVALID, "null out pointer");
+  *values = p->result_rows ? p->agg_out[agg] : nullptr;
+  ABI_END
+}
+
 // Arrow C Data Interface export -----------------------------------------------------------------
 namespace {
 struct ChildPriv { void* buffers[3] = {nullptr, nullptr, nullptr}; };
@@ -192,6 +222,13 @@ void release_child_array(struct ArrowArray* a) {
   a->release = nullptr;
 }
 struct StructPriv { const void* buffers[1]; struct ArrowArray** children; u32 n; };
+void release_struct_array(struct ArrowArray* a);
+void release_agg_array(struct ArrowArray* a) {   // a struct array that owns its validity bitmap
+  if (!a || !a->release) return;
+  std::free(const_cast<void*>(static_cast<StructPriv*>(a->private_data)->buffers[0]));
+  static_cast<StructPriv*>(a->private_data)->buffers[0] = nullptr;
+  release_struct_array(a);
+}
 void release_struct_array(struct ArrowArray* a) {
   if (!a || !a->release) return;
   StructPriv* pr = static_cast<StructPriv*>(a->private_data);
@@ -210,6 +247,57 @@ void release_schema(struct ArrowSchema* s) {
   }
   s->release = nullptr;
 }
+// One aggregate column of a batch: struct<tag: uint8, lo: int64, hi: int64>, null where the tag is RDFGPU_TV_NULL.
+ArrowArray* export_leaf(int64_t len, void* data, uint8_t* valid, int64_t nulls) {
+  ArrowArray* ch = new ArrowArray();
+  std::memset(ch, 0, sizeof *ch);
+  ChildPriv* cp = new ChildPriv();
+  cp->buffers[0] = valid; cp->buffers[1] = data;
+  ch->length = len; ch->null_count = nulls; ch->n_buffers = 2;
+  ch->buffers = const_cast<const void**>(reinterpret_cast<void**>(cp->buffers));
+  ch->release = release_child_array; ch->private_data = cp;
+  return ch;
+}
+ArrowArray* export_agg(const rdfgpu_agg_value* v, u64 len) {
+  uint8_t* tag = static_cast<uint8_t*>(std::malloc(len ? len : 1));
+  int64_t* lo = static_cast<int64_t*>(std::malloc(len ? len * 8 : 8));
+  int64_t* hi = static_cast<int64_t*>(std::malloc(len ? len * 8 : 8));
+  uint8_t* valid = static_cast<uint8_t*>(std::calloc((len + 7) / 8 + 1, 1));
+  int64_t nulls = 0;
+  for (u64 i = 0; i < len; i++) {
+    tag[i] = v[i].tag; lo[i] = v[i].lo; hi[i] = v[i].hi;
+    if (v[i].tag == RDFGPU_TV_NULL) nulls++; else valid[i >> 3] |= (uint8_t)(1u << (i & 7));
+  }
+  StructPriv* sp = new StructPriv();
+  sp->buffers[0] = valid; sp->n = 3; sp->children = new ArrowArray*[3];
+  sp->children[0] = export_leaf((int64_t)len, tag, nullptr, 0);
+  sp->children[1] = export_leaf((int64_t)len, lo, nullptr, 0);
+  sp->children[2] = export_leaf((int64_t)len, hi, nullptr, 0);
+  ArrowArray* a = new ArrowArray();
+  std::memset(a, 0, sizeof *a);
+  a->length = (int64_t)len; a->null_count = nulls; a->n_buffers = 1; a->buffers = sp->buffers;
+  a->n_children = 3; a->children = sp->children;
+  a->release = release_agg_array; a->private_data = sp;
+  return a;
+}
+ArrowSchema* agg_schema(const char* name) {
+  static const char* const names[3] = {"tag", "lo", "hi"};
+  static const char* const formats[3] = {"C", "l", "l"};
+  SchemaPriv* pr = new SchemaPriv();
+  pr->n = 3; pr->children = new ArrowSchema*[3]; pr->names = nullptr;
+  for (u32 c = 0; c < 3; c++) {
+    ArrowSchema* cs = new ArrowSchema();
+    std::memset(cs, 0, sizeof *cs);
+    cs->format = formats[c]; cs->name = names[c]; cs->flags = 2;
+    cs->release = release_schema; cs->private_data = nullptr;
+    pr->children[c] = cs;
+  }
+  ArrowSchema* s = new ArrowSchema();
+  std::memset(s, 0, sizeof *s);
+  s->format = "+s"; s->name = name; s->flags = 2; s->n_children = 3; s->children = pr->children;
+  s->release = release_schema; s->private_data = pr;
+  return s;
+}
 }  // namespace
 
 int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSchema* schema) {
@@ -219,10 +307,11 @@ int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSche
     p->ensure_host_copy();
     if (p->cursor >= p->result_rows) return RDFGPU_END;   // never an empty batch (scan.rs:195-198)
     const u64 len = std::min<u64>(p->store->batch_size, p->result_rows - p->cursor);
-    const u32 nc = p->result.n_cols;
+    const u32 nk = p->result.n_cols, na = (u32)p->host_aggs.size(), nc = nk + na;
     StructPriv* sp = new StructPriv();
     sp->buffers[0] = nullptr; sp->n = nc; sp->children = new ArrowArray*[nc ? nc : 1];
-    for (u32 c = 0; c < nc; c++) {
+    for (u32 c = nk; c < nc; c++) sp->children[c] = export_agg(p->host_aggs[c - nk].data() + p->cursor, len);
+    for (u32 c = 0; c < nk; c++) {
       ArrowArray* ch = new ArrowArray();
       std::memset(ch, 0, sizeof *ch);
       ChildPriv* cp = new ChildPriv();
@@ -251,9 +340,10 @@ int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSche
       SchemaPriv* pr = new SchemaPriv();
       pr->n = nc; pr->children = new ArrowSchema*[nc ? nc : 1]; pr->names = new std::string[nc ? nc : 1];
       for (u32 c = 0; c < nc; c++) {
+        pr->names[c] = "c" + std::to_string(c);
+        if (c >= nk) { pr->children[c] = agg_schema(pr->names[c].c_str()); continue; }
         ArrowSchema* cs = new ArrowSchema();
         std::memset(cs, 0, sizeof *cs);
-        pr->names[c] = "c" + std::to_string(c);
         cs->format = "I"; cs->name = pr->names[c].c_str(); cs->flags = 2 /* ARROW_FLAG_NULLABLE */;
         cs->release = release_schema; cs->private_data = nullptr;
         pr->children[c] = cs;

@@ -1,0 +1,354 @@
+// aggregate.hip — AggregateExec(mode=Single) over object-id group columns: COUNT(*), COUNT, COUNT(DISTINCT), SUM, AVG (include/rdfgpu.h,
+// RDFGPU_NODE_AGGREGATE; lib/functions/src/aggregates/sum.rs:34-73, avg.rs:43-134).
+//
+// Three passes over the input, the group count read back once in between (it sizes the accumulators):
+//   agg_groups_kernel  every row finds its key tuple in one open-addressing table in HBM (slot = row + 1 of the row that claimed it; a
+//                      row whose tuple is there already only reads).  A claiming row takes the next dense group index: the claims of a
+//                      1024-row tile are compacted with ballot + mbcnt behind ONE counter reservation per workgroup and tile.
+//   agg_accum_kernel   every row adds into its group's accumulator words.  Rows of a wave are consecutive rows, so runs of equal
+//                      neighbouring groups (clustered join output, one hot group) are summed within the wave first and only the run's
+//                      head lane issues the atomic (Guideline 12).  When every group's words fit in 64 KiB, each workgroup keeps
+//                      partials in LDS and merges them into HBM once; otherwise (or with NO_AGG_LDS) the atomics go to HBM directly.
+//   agg_final_kernel   one lane per group: the key ids from the group's first row, every aggregate's rdfgpu_agg_value.
+//
+// Accumulator words of one group (u64, structure of arrays: word w of group g at acc[w * groups + g]):
+//   word 0                  rows of the group (COUNT(*), AVG's count)
+//   COUNT / COUNT DISTINCT  1 word: rows with a bound id / first insertions of (group, id) into the aggregate's set
+//   SUM / AVG               11 words: kinds seen (bit 0 int/integer, 1 decimal, 2 float, 3 double, 4 not numeric or unbound); the integer
+//                           values as sums of their two 32-bit limbs + the number of negative ones; the decimal values (i128 x 10^18) as
+//                           sums of their four 32-bit limbs + the number of negative ones; the sum of the values cast to f64; the sum of the
+//                           values cast to f32, kept in f64.
+// A limb sum of up to 2^32 rows fits a u64, and two's complement makes the exact total sum(limb_i * 2^(32 i)) - negatives * 2^64 (2^128):
+// integer and decimal results are exact and do not depend on row order.  Float and double results are the f64 sums, in the device's
+// order (the header states the bound).
+#include "join_device.hpp"
+
+namespace rdfgpu {
+
+constexpr int kAggBlock = 256;
+constexpr int kAggItems = 4;                        // rows per lane and tile of the group pass: one reservation per 1024 rows
+constexpr u32 kAggTile = (u32)kAggBlock * kAggItems;
+constexpr u32 kGroupNone = 0xFFFFFFFFu;
+enum : u32 { kKindInt = 1, kKindDec = 2, kKindFloat = 4, kKindDouble = 8, kKindOther = 16 };
+
+// ---- pass 1 ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ Keys agg_keys(const AggArgs& a, u64 row) {
+  Keys k;
+#pragma unroll
+  for (u32 q = 0; q < RDFGPU_MAX_KEYS; q++) k.k[q] = q < a.n_keys ? a.key[q][row] : 0u;   // id 0 is a key value like any other
+  return k;
+}
+__device__ __forceinline__ bool agg_keys_equal(const AggArgs& a, u64 row, const Keys& k) {
+  bool eq = true;
+#pragma unroll
+  for (u32 q = 0; q < RDFGPU_MAX_KEYS; q++) if (q < a.n_keys) eq = eq && a.key[q][row] == k.k[q];
+  return eq;
+}
+
+__global__ __launch_bounds__(kAggBlock) void agg_groups_kernel(const AggArgs a) {
+  __shared__ u32 wave_tot[kAggBlock / 64];
+  __shared__ u64 wg_base;
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 n = live_rows(a.n_dev, a.cap);
+  const u64 n_tiles = (n + kAggTile - 1) / kAggTile;
+  for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    u64 row[kAggItems]; u32 slot[kAggItems]; bool won[kAggItems];
+#pragma unroll
+    for (int it = 0; it < kAggItems; it++) {
+      row[it] = tile * kAggTile + (u64)it * kAggBlock + tid;
+      won[it] = false; slot[it] = 0;
+      if (row[it] >= n) continue;
+      const Keys k = agg_keys(a, row[it]);
+      u32 h = hash_keys4(k, a.n_keys) & a.slot_mask;
+      for (;;) {   // load factor <= 0.5: an empty slot exists
+        u32 cur = a.slots[h];   // slots are written once: a stale read can only be a 0, which the CAS settles
+        if (cur == 0) {
+          cur = atomicCAS(a.slots + h, 0u, (u32)row[it] + 1u);
+          if (cur == 0) { won[it] = true; break; }
+        }
+        if (agg_keys_equal(a, cur - 1, k)) break;
+        h = (h + 1) & a.slot_mask;
+      }
+      slot[it] = h;
+      a.row_slot[row[it]] = h;
+    }
+    unsigned long long mask[kAggItems]; u32 off[kAggItems]; u32 wtot = 0;
+#pragma unroll
+    for (int it = 0; it < kAggItems; it++) { mask[it] = __ballot(won[it]); off[it] = wtot; wtot += (u32)__popcll(mask[it]); }
+    if (lane == 0) wave_tot[wave] = wtot;
+    __syncthreads();
+    if (tid == 0) {
+      u32 total = 0;
+      for (int w = 0; w < kAggBlock / 64; w++) { const u32 t = wave_tot[w]; wave_tot[w] = total; total += t; }
+      wg_base = total ? atomicAdd((unsigned long long*)a.n_groups_dev, (unsigned long long)total) : 0ull;
+    }
+    __syncthreads();
+    const u64 base = wg_base + wave_tot[wave];
+#pragma unroll
+    for (int it = 0; it < kAggItems; it++) {
+      if (!won[it]) continue;
+      const u32 gid = (u32)(base + off[it] + lane_prefix(mask[it]));
+      a.slot_gid[slot[it]] = gid;
+      a.rep_row[gid] = (u32)row[it];
+    }
+    __syncthreads();   // wave_tot / wg_base are reused by the next tile
+  }
+}
+
+// ---- pass 2 ---------------------------------------------------------------------------------------------------------------------
+// A lane's run: the lanes [lane, end) of its wave hold rows of the same group; the head lane (first of the run) issues the atomic.
+struct AggRun { u32 lane, end; bool head; bool merge; };
+
+template <class T, class Op>
+__device__ __forceinline__ T run_reduce(T v, const AggRun& r, Op op) {
+  if (!r.merge) return v;   // (uniform: no run of the wave is longer than one lane)
+#pragma unroll
+  for (u32 off = 1; off < 64; off <<= 1) {
+    const T o = __shfl_down(v, off);
+    if (r.lane + off < r.end) v = op(v, o);
+  }
+  return v;
+}
+__device__ __forceinline__ void acc_add(unsigned long long* acc, u64 at, unsigned long long v, const AggRun& r) {
+  v = run_reduce(v, r, [](unsigned long long x, unsigned long long y) { return x + y; });
+  if (r.head && v) atomicAdd(acc + at, v);
+}
+__device__ __forceinline__ void acc_or(unsigned long long* acc, u64 at, unsigned long long v, const AggRun& r) {
+  v = run_reduce(v, r, [](unsigned long long x, unsigned long long y) { return x | y; });
+  if (r.head && v) atomicOr(acc + at, v);
+}
+__device__ __forceinline__ void acc_add_f64(unsigned long long* acc, u64 at, double v, const AggRun& r) {
+  v = run_reduce(v, r, [](double x, double y) { return __dadd_rn(x, y); });
+  if (r.head && v != 0.0) unsafeAtomicAdd(reinterpret_cast<double*>(acc + at), v);
+}
+
+// First insertion of (g, id) into the COUNT DISTINCT set.
+__device__ __forceinline__ bool dset_insert(unsigned long long* set, u32 mask, u32 g, u32 id) {
+  const unsigned long long e = ((unsigned long long)g << 32) | id;
+  Keys k; k.k[0] = g; k.k[1] = id; k.k[2] = 0; k.k[3] = 0;
+  u32 h = hash_keys4(k, 2) & mask;
+  for (;;) {
+    unsigned long long cur = set[h];
+    if (cur == e) return false;
+    if (cur == 0ull) {
+      cur = atomicCAS(set + h, 0ull, e);
+      if (cur == 0ull) return true;
+      if (cur == e) return false;
+    }
+    h = (h + 1) & mask;
+  }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) {
+  extern __shared__ unsigned long long lacc[];
+  const u32 tid = threadIdx.x, lane = tid & 63;
+  const u64 n = live_rows(a.n_dev, a.cap);
+  const u32 G = a.n_groups;
+  unsigned long long* acc = a.acc;
+  if constexpr (LDS) {
+    for (u32 i = tid; i < a.n_words * G; i += kAggBlock) lacc[i] = 0ull;
+    __syncthreads();
+    acc = lacc;
+  }
+  for (u64 base = (u64)blockIdx.x * kAggBlock; base < n; base += (u64)gridDim.x * kAggBlock) {
+    const u64 row = base + tid;
+    const bool valid = row < n;
+    const u32 g = !valid ? kGroupNone : a.n_keys ? a.slot_gid[a.row_slot[row]] : 0u;
+    const u32 prev = __shfl_up(g, 1);
+    const bool head = lane == 0 || prev != g;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long after = heads & ~((2ull << lane) - 1ull);   // heads of later lanes (lane 63: 2 << 63 wraps to 0, none)
+    AggRun r{lane, after ? (u32)__ffsll((long long)after) - 1u : 64u, head && valid, heads != ~0ull};
+    acc_add(acc, g, 1ull, r);   // word 0: rows of the group
+    for (u32 i = 0; i < a.n_aggs; i++) {
+      const u32 fn = a.fn[i];
+      if (fn == RDFGPU_AGG_COUNT_STAR) continue;
+      const u64 w = (u64)a.word0[i] * G + (valid ? g : 0u);
+      const u32 id = valid ? a.in[i][row] : 0u;
+      if (fn == RDFGPU_AGG_COUNT) { acc_add(acc, w, id != 0, r); continue; }
+      if (fn == RDFGPU_AGG_COUNT_DISTINCT) { acc_add(acc, w, id != 0 && dset_insert(a.dset[i], a.dset_mask, g, id), r); continue; }
+      // SUM / AVG: ENC_TV of the id, one 16-byte gather
+      const Val v = enc_tv(a.tt, id);
+      const int k = num_kind(v.tag);
+      u32 kind = k == NK_NONE ? kKindOther : k == NK_DECIMAL ? kKindDec : k == NK_FLOAT ? kKindFloat : k == NK_DOUBLE ? kKindDouble : kKindInt;
+      if (!valid) kind = 0;
+      const bool is_int = kind == kKindInt, is_dec = kind == kKindDec, num = valid && k != NK_NONE;
+      const u64 ix = is_int ? (u64)v.lo : 0ull;
+      const u64 d0 = is_dec ? (u64)v.lo : 0ull, d1 = is_dec ? (u64)v.hi : 0ull;
+      acc_or(acc, w, kind, r);
+      acc_add(acc, w + 1ull * G, ix & 0xFFFFFFFFull, r);
+      acc_add(acc, w + 2ull * G, ix >> 32, r);
+      acc_add(acc, w + 3ull * G, is_int && v.lo < 0, r);
+      acc_add(acc, w + 4ull * G, d0 & 0xFFFFFFFFull, r);
+      acc_add(acc, w + 5ull * G, d0 >> 32, r);
+      acc_add(acc, w + 6ull * G, d1 & 0xFFFFFFFFull, r);
+      acc_add(acc, w + 7ull * G, d1 >> 32, r);
+      acc_add(acc, w + 8ull * G, is_dec && v.hi < 0, r);
+      acc_add_f64(acc, w + 9ull * G, num ? to_f64(v, k) : 0.0, r);
+      acc_add_f64(acc, w + 10ull * G, num ? (double)to_f32(v, k) : 0.0, r);
+    }
+  }
+  if constexpr (LDS) {   // merge this workgroup's partials once (same layout: the LDS form holds every group)
+    __syncthreads();
+    for (u32 i = tid; i < a.n_words * G; i += kAggBlock) {
+      const unsigned long long v = lacc[i];
+      if (v == 0ull) continue;
+      const u8 op = a.word_op[i / G];
+      if (op == kAggOr) atomicOr(a.acc + i, v);
+      else if (op == kAggAddF64) unsafeAtomicAdd(reinterpret_cast<double*>(a.acc + i), __longlong_as_double((long long)v));
+      else atomicAdd(a.acc + i, v);
+    }
+  }
+}
+
+// ---- pass 3 ---------------------------------------------------------------------------------------------------------------------
+// 256-bit two's complement, enough for sum(limb_i * 2^(32 i)) over 2^32 rows and for the integer part scaled by 10^18.
+struct Wide { u64 w[4]; };
+__device__ __forceinline__ void wide_add(Wide& x, const Wide& y) {
+  u64 carry = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) { const u128_t s = (u128_t)x.w[i] + y.w[i] + carry; x.w[i] = (u64)s; carry = (u64)(s >> 64); }
+}
+__device__ __forceinline__ Wide wide_shifted(u64 v, u32 bits) {   // v << bits, bits a multiple of 32 below 192
+  Wide r{{0, 0, 0, 0}};
+  const u32 word = bits / 64, b = bits % 64;
+  r.w[word] = v << b;
+  if (b && word + 1 < 4) r.w[word + 1] = v >> (64 - b);
+  return r;
+}
+__device__ __forceinline__ Wide wide_neg(Wide x) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) x.w[i] = ~x.w[i];
+  wide_add(x, Wide{{1, 0, 0, 0}});
+  return x;
+}
+__device__ __forceinline__ void wide_mul(Wide& x, u64 m) {   // modulo 2^256: exact for the signed values here
+  u64 carry = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) { const u128_t p = (u128_t)x.w[i] * m + carry; x.w[i] = (u64)p; carry = (u64)(p >> 64); }
+}
+__device__ __forceinline__ bool wide_fits(const Wide& x, int words) {   // fits a signed integer of `words` 64-bit words
+  const u64 ext = (x.w[words - 1] >> 63) ? ~0ull : 0ull;
+  for (int i = words; i < 4; i++) if (x.w[i] != ext) return false;
+  return true;
+}
+
+__device__ __forceinline__ u128_t u128_div(u128_t n, u128_t d) {   // shift-subtract: no 128-bit division libcall on the device
+  u128_t q = 0, r = 0;
+  for (int i = 127; i >= 0; i--) {
+    r = (r << 1) | ((n >> i) & 1);
+    if (r >= d) { r -= d; q |= (u128_t)1 << i; }
+  }
+  return q;
+}
+// Decimal::checked_div(sum, Decimal::from(count)), lib/model/src/xsd/decimal.rs:131-162, count > 0.
+__device__ __forceinline__ bool decimal_div_count(i128_t left, u64 count, i128_t& out) {
+  const bool neg = left < 0;
+  u128_t m = neg ? (u128_t)0 - (u128_t)left : (u128_t)left;
+  u32 shift_left = 0;
+  if (m != 0) {   // `while let Some(r) = left.checked_mul(10)`: |left| * 10 stays inside i128 (for both signs) iff |left| <= (2^127 - 1) / 10
+    const u128_t lim = ((u128_t)0x0CCCCCCCCCCCCCCCull << 64) | (u128_t)0xCCCCCCCCCCCCCCCCull;
+    while (m <= lim) { m *= 10u; shift_left++; }
+  }
+  u64 right = count; u32 tz = 0;   // count * 10^18 with its trailing zeros stripped: shift_right = 18 + tz
+  while (right % 10u == 0) { right /= 10u; tz++; }
+  const u32 shift = shift_left + tz;   // (shift_left + shift_right) - 18
+  if (shift > 38) return false;        // 10_i128.checked_pow(shift) overflows
+  u128_t p = 1;
+  for (u32 i = 0; i < shift; i++) p *= 10u;
+  const u128_t q = u128_div(u128_div(m, right), p);   // two truncating divisions (toward zero: on the magnitude)
+  out = (i128_t)(neg ? (u128_t)0 - q : q);
+  return true;
+}
+
+__device__ __forceinline__ void put(rdfgpu_agg_value* o, u32 g, u8 tag, long long lo, long long hi) {
+  long long* p = reinterpret_cast<long long*>(o + g);
+  p[0] = lo; p[1] = hi; p[2] = (long long)tag;   // (tag, reserved bytes = 0)
+}
+
+__global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
+  const u32 G = a.n_groups;
+  const u32 g = blockIdx.x * kAggBlock + threadIdx.x;
+  if (g >= G) return;
+  if (a.n_keys) {
+    const u32 rep = a.rep_row[g];
+    for (u32 q = 0; q < a.n_keys; q++) a.out_key[q][g] = a.key[q][rep];
+  }
+  const u64 rows = a.acc[g];
+  for (u32 i = 0; i < a.n_aggs; i++) {
+    const u32 fn = a.fn[i];
+    rdfgpu_agg_value* o = a.out[i];
+    if (fn == RDFGPU_AGG_COUNT_STAR) { put(o, g, RDFGPU_TV_INTEGER, (long long)rows, 0); continue; }
+    const unsigned long long* w = a.acc + (u64)a.word0[i] * G + g;
+    if (fn == RDFGPU_AGG_COUNT || fn == RDFGPU_AGG_COUNT_DISTINCT) { put(o, g, RDFGPU_TV_INTEGER, (long long)w[0], 0); continue; }
+    const u32 kinds = (u32)w[0];
+    const bool avg = fn == RDFGPU_AGG_AVG;
+    if (avg && rows == 0) { put(o, g, RDFGPU_TV_INTEGER, 0, 0); continue; }                   // avg.rs: count 0 => integer 0
+    if (avg && (kinds & kKindOther)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }            // avg.rs:63-78
+    const double f64 = __longlong_as_double((long long)w[9 * (u64)G]);
+    const double f32s = __longlong_as_double((long long)w[10 * (u64)G]);
+    if (kinds & kKindDouble) {
+      const double v = avg ? __ddiv_rn(f64, (double)rows) : f64;
+      put(o, g, RDFGPU_TV_DOUBLE, __double_as_longlong(v), 0); continue;
+    }
+    if (kinds & kKindFloat) {
+      const float s = (float)f32s;
+      const float v = avg ? __fdiv_rn(s, (float)rows) : s;
+      put(o, g, RDFGPU_TV_FLOAT, (long long)(u64)__float_as_uint(v), 0); continue;
+    }
+    // exact integer part I = L0 + L1 * 2^32 - negatives * 2^64
+    Wide I = wide_shifted(w[1 * (u64)G], 0);
+    wide_add(I, wide_shifted(w[2 * (u64)G], 32));
+    wide_add(I, wide_neg(wide_shifted(w[3 * (u64)G], 64)));
+    if (!avg && !(kinds & kKindDec)) {   // sum.rs: starts as integer 0, integers only
+      if (wide_fits(I, 1)) put(o, g, RDFGPU_TV_INTEGER, (long long)I.w[0], 0); else put(o, g, RDFGPU_TV_NULL, 0, 0);
+      continue;
+    }
+    // decimal: D = sum(limb_i * 2^(32 i)) - negatives * 2^128, plus I * 10^18
+    Wide D = wide_shifted(w[4 * (u64)G], 0);
+    wide_add(D, wide_shifted(w[5 * (u64)G], 32));
+    wide_add(D, wide_shifted(w[6 * (u64)G], 64));
+    wide_add(D, wide_shifted(w[7 * (u64)G], 96));
+    wide_add(D, wide_neg(wide_shifted(w[8 * (u64)G], 128)));
+    wide_mul(I, 1000000000000000000ull);
+    wide_add(D, I);
+    if (!wide_fits(D, 2)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }
+    i128_t sum = (i128_t)(((u128_t)D.w[1] << 64) | (u128_t)D.w[0]);
+    if (avg && !decimal_div_count(sum, rows, sum)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }
+    put(o, g, RDFGPU_TV_DECIMAL, (long long)(u64)(u128_t)sum, (long long)(u64)((u128_t)sum >> 64));
+  }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------
+void launch_agg_groups(const AggArgs& a, hipStream_t s) {
+  u64 g = (a.cap + kAggTile - 1) / kAggTile;
+  if (g > 16384) g = 16384;
+  hipLaunchKernelGGL(agg_groups_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  RDFGPU_HIP(hipGetLastError());
+}
+
+void launch_agg_accum(const AggArgs& a, hipStream_t s) {
+  u64 g = (a.cap + kAggBlock - 1) / kAggBlock;
+  if (a.lds) {
+    const size_t lds = (size_t)a.n_words * a.n_groups * sizeof(unsigned long long);
+    if (lds > kAggLdsBytes) fail(RDFGPU_ERR_INVALID, "aggregate: %zu bytes of LDS partials", lds);
+    if (g > 512) g = 512;   // every workgroup zeroes and merges all partials: enough of them to fill the part, not one per tile
+    hipLaunchKernelGGL(agg_accum_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+  } else {
+    if (g > 16384) g = 16384;
+    hipLaunchKernelGGL(agg_accum_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  }
+  RDFGPU_HIP(hipGetLastError());
+}
+
+void launch_agg_final(const AggArgs& a, hipStream_t s) {
+  const u64 g = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
+  hipLaunchKernelGGL(agg_final_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  RDFGPU_HIP(hipGetLastError());
+}
+
+// (kernels.hpp, preload_code_objects: the runtime loads a translation unit's code object at the first use of one of its kernels)
+void preload_tu_aggregate() { hipFuncAttributes at; RDFGPU_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void*>(agg_final_kernel))); }
+
+}  // namespace rdfgpu

@@ -282,6 +282,43 @@ void launch_semi_join(const SemiJoinArgs& a, int form, bool anti, int filter, hi
 size_t semi_join_lds_bytes(const SemiJoinArgs& a, int form);
 void preload_tu_semi_join();
 
+// ---- AggregateExec(mode=Single) (aggregate.hip): GROUP BY object-id columns with COUNT / COUNT DISTINCT / SUM / AVG ----
+// Pass 1 (agg_groups_kernel) gives every row a dense group index through one open-addressing table of key tuples in HBM; pass 2
+// (agg_accum_kernel) adds every row into its group's accumulators — per-workgroup LDS partials merged once when the groups fit, else
+// straight into HBM — after summing runs of equal neighbouring groups within the wave; pass 3 (agg_final_kernel) is one lane per group.
+constexpr u32 kAggSumWords = 11;          // accumulator words of a SUM / AVG per group (aggregate.hip)
+constexpr u32 kAggMaxWords = 1 + RDFGPU_MAX_AGGREGATES * kAggSumWords;
+constexpr size_t kAggLdsBytes = 65536;    // LDS partials of one workgroup
+enum AggWordOp : u8 { kAggAdd = 0, kAggOr = 1, kAggAddF64 = 2 };
+struct AggArgs {
+  u32 n_keys;
+  const u32* key[RDFGPU_MAX_KEYS];
+  const u64* n_dev; u64 cap;                     // input rows: the device count when n_dev, else cap
+  u32 n_aggs;
+  u32 fn[RDFGPU_MAX_AGGREGATES];                 // RDFGPU_AGG_*
+  const u32* in[RDFGPU_MAX_AGGREGATES];          // input column (COUNT_STAR: unused)
+  u32 word0[RDFGPU_MAX_AGGREGATES];              // first accumulator word of each aggregate (word 0 = rows of the group)
+  u32 n_words;
+  u8 word_op[kAggMaxWords];                      // how each word is merged (AggWordOp)
+  unsigned long long* acc;                       // [n_words x n_groups], word w of group g at acc[w * n_groups + g]
+  unsigned long long* dset[RDFGPU_MAX_AGGREGATES];   // COUNT_DISTINCT: set of (group << 32 | id), 0 = empty
+  u32 dset_mask;
+  TypedTable tt;
+  u32* slots; u32 slot_mask;                     // group table: row + 1 of the row that claimed the slot (0 = empty)
+  u32* row_slot;                                 // per input row: its group's slot
+  u32* slot_gid;                                 // per claimed slot: the dense group index
+  u32* rep_row;                                  // per group: the row that claimed it
+  u64* n_groups_dev;
+  u32 n_groups;                                  // known on the host before passes 2 and 3
+  u32 lds;                                       // pass 2: 1 = LDS partials per workgroup
+  u32* out_key[RDFGPU_MAX_KEYS];
+  rdfgpu_agg_value* out[RDFGPU_MAX_AGGREGATES];
+};
+void launch_agg_groups(const AggArgs& a, hipStream_t s);
+void launch_agg_accum(const AggArgs& a, hipStream_t s);
+void launch_agg_final(const AggArgs& a, hipStream_t s);
+void preload_tu_aggregate();
+
 void launch_lds_join(const LdsJoinArgs& a, hipStream_t s);
 // stream_join.hip: the same operator against a direct-address table as a streaming pass (launch_lds_join routes to it when a.stream_direct)
 bool direct_stream_join_ok(const LdsJoinArgs& a);

@@ -261,6 +261,8 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
     const rdfgpu_plan_node& r = nd.d;
     auto child = [&](int32_t c, const char* what) -> const NodeInfo& {
       if (c < 0 || (u32)c >= i) fail(RDFGPU_ERR_INVALID, "node %u: %s child %d must precede the node", i, what, c);
+      if (plan->nodes[c].d.kind == RDFGPU_NODE_AGGREGATE && plan->nodes[c].n_aggs)   // aggregate values are not object ids
+        fail(RDFGPU_ERR_UNSUPPORTED, "node %u: input %d is an AggregateExec with aggregates, which must be the plan's root", i, c);
       return plan->nodes[c];
     };
     switch (r.kind) {
@@ -341,6 +343,36 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
           if (!covered) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: TopK output column %u is neither the group nor a sort key by id", i, nd.proj[q]);
         }
         nd.width = nd.n_proj;
+        break;
+      }
+      case RDFGPU_NODE_AGGREGATE: {   // AggregateExec(mode=Single), ..Business Intelligence - Q8 (Execution Plan).snap
+        const NodeInfo& c = child(r.left, "input");
+        if (r.n_keys > RDFGPU_MAX_KEYS) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u group columns (at most %u)", i, r.n_keys, RDFGPU_MAX_KEYS);
+        if (r.table_cols > RDFGPU_MAX_AGGREGATES) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u aggregates (at most %u)", i, r.table_cols, RDFGPU_MAX_AGGREGATES);
+        if (r.n_proj != RDFGPU_NO_PROJECTION) fail(RDFGPU_ERR_INVALID, "node %u: AggregateExec takes no projection", i);
+        if (r.n_keys + r.table_cols == 0) fail(RDFGPU_ERR_INVALID, "node %u: AggregateExec without group columns and aggregates", i);
+        for (u32 k = 0; k < r.n_keys; k++)
+          if (r.left_keys[k] >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: group column %u out of range", i, r.left_keys[k]);
+        if (r.table_cols && ((u64)r.table_slot + 2ull * r.table_cols > d->n_pool || !d->pool)) fail(RDFGPU_ERR_INVALID, "node %u: aggregate list outside the pool", i);
+        for (u32 a = 0; a < r.table_cols; a++) {
+          const u32 fn = d->pool[r.table_slot + 2 * a], in = d->pool[r.table_slot + 2 * a + 1];
+          switch (fn) {
+            case RDFGPU_AGG_COUNT_STAR: break;
+            case RDFGPU_AGG_COUNT: case RDFGPU_AGG_COUNT_DISTINCT: case RDFGPU_AGG_SUM: case RDFGPU_AGG_AVG:
+              if (in >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, in, c.width);
+              break;
+            case RDFGPU_AGG_MIN: case RDFGPU_AGG_MAX: case RDFGPU_AGG_SAMPLE: case RDFGPU_AGG_GROUP_CONCAT:
+              fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: MIN / MAX / SAMPLE / GROUP_CONCAT are not on the device (MIN / MAX keep the first "
+                                           "value's error state, min.rs:42-53: their result depends on row order)", i, a);
+            case RDFGPU_AGG_SUM_DISTINCT: case RDFGPU_AGG_AVG_DISTINCT: case RDFGPU_AGG_COUNT_DISTINCT_STAR:
+              fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: SUM / AVG with DISTINCT and COUNT(DISTINCT *) are not on the device", i, a);
+            default: fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: unknown function %u", i, a, fn);
+          }
+          nd.agg_fn[a] = fn; nd.agg_col[a] = fn == RDFGPU_AGG_COUNT_STAR ? 0 : in;
+        }
+        nd.n_aggs = r.table_cols;
+        if (nd.n_aggs && i != d->root) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: an AggregateExec with aggregates must be the plan's root (node %u)", i, d->root);
+        nd.width = r.n_keys;   // the id columns; the aggregates leave through rdfgpu_plan_agg_*
         break;
       }
       default: fail(RDFGPU_ERR_INVALID, "node %u: unknown kind %u", i, r.kind);
@@ -570,7 +602,8 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::oj_band_records_kernel", "rdfgpu::oj_write_band_kernel", "void rdfgpu::small_scan_kernel",
       "rdfgpu::part_pass (hist + scan + scatter)", "void rdfgpu::stream_join_kernel", "void rdfgpu::semi_build_kernel",
       "void rdfgpu::semi_join_kernel<0, false", "void rdfgpu::semi_join_kernel<0, true", "void rdfgpu::semi_join_kernel<1, false",
-      "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true"};
+      "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true",
+      "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -714,6 +747,7 @@ void Plan::execute() {
   events_used = 2;   // events 0/1 bracket the whole execute
   pending.clear();
   host_valid = false; cursor = 0; executed = false;
+  agg_out.clear();
   const hipEvent_t ev_start = ctx->event(0), ev_stop = ctx->event(1);
   RDFGPU_HIP(hipEventRecord(ev_start, stream));
   RDFGPU_HIP(hipMemsetAsync(counters, 0, 256 * sizeof(u64), stream));
@@ -842,6 +876,7 @@ DevTable Plan::exec_node(u32 idx) {
       t = nd.d.join_type == RDFGPU_JOIN_LEFT_SEMI || nd.d.join_type == RDFGPU_JOIN_LEFT_ANTI ? exec_semi_join(nd) : exec_join(nd);
       break;
     case RDFGPU_NODE_TOPK: t = exec_topk(nd); break;
+    case RDFGPU_NODE_AGGREGATE: t = exec_aggregate(nd); break;
     case RDFGPU_NODE_CLOSURE: {
       const DevTable in = exec_node((u32)nd.d.left);
       const u64 n = in.n_dev && in.cap ? read_back<u64>(in.n_dev) : in.cap;
@@ -1204,6 +1239,77 @@ DevTable Plan::exec_semi_join(NodeInfo& nd) {
   timed(semi_join_class(form, anti), build_bytes, L.cap, L.n_dev, 4ull * (a.n_keys + left_fcols), a.n_out_dev, 0, 8ull * nd.n_proj,
         [&] { launch_semi_join(a, form, anti, filter, stream); });
   t.cap = L.cap; t.n_dev = a.n_out_dev;
+  return t;
+}
+
+// AggregateExec(mode=Single) (aggregate.hip): group pass, one read-back of the group count (it sizes the accumulators and is the
+// output's row count), accumulate pass, one lane per group to finish.  Over a zero-key aggregate there is one group and no group pass.
+// Compulsory bytes: per input row 4 per key column, 4 + 16 per SUM / AVG input (id + typed value), 4 per COUNT / COUNT
+// DISTINCT input; per output group 4 per key column + 24 per aggregate.
+DevTable Plan::exec_aggregate(NodeInfo& nd) {
+  ChainRequest* const for_this = pending_chain;   // the input is a sub-plan of its own
+  pending_chain = nullptr;
+  const DevTable in = exec_node((u32)nd.d.left);
+  pending_chain = for_this;
+  flush_pending_oj();   // a held-back ordered-join write must have happened before the input is read
+  if (in.cap >= (1ull << 32)) fail(RDFGPU_ERR_UNSUPPORTED, "AggregateExec over %llu rows (at most 2^32 - 1)", (unsigned long long)in.cap);
+  AggArgs a{};
+  a.n_keys = nd.d.n_keys;
+  for (u32 k = 0; k < a.n_keys; k++) a.key[k] = in.cols[nd.d.left_keys[k]];
+  a.n_dev = in.n_dev; a.cap = in.cap;
+  a.n_aggs = nd.n_aggs;
+  a.n_words = 1;
+  a.word_op[0] = kAggAdd;
+  u64 accum_row_bytes = 0;
+  bool distinct = false;
+  for (u32 i = 0; i < a.n_aggs; i++) {
+    const u32 fn = nd.agg_fn[i];
+    a.fn[i] = fn; a.in[i] = fn == RDFGPU_AGG_COUNT_STAR ? nullptr : in.cols[nd.agg_col[i]];
+    a.word0[i] = a.n_words;
+    const u32 words = fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? kAggSumWords : 1;
+    for (u32 w = 0; w < words; w++) a.word_op[a.n_words + w] = words == 1 ? kAggAdd : w == 0 ? kAggOr : w >= 9 ? kAggAddF64 : kAggAdd;
+    a.n_words += words;
+    accum_row_bytes += fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? 20 : 4;
+    distinct = distinct || fn == RDFGPU_AGG_COUNT_DISTINCT;
+  }
+  a.tt = typed_table();
+  const u64 cap = in.cap;
+  u64 slots = 64;
+  while (slots < 2 * cap && slots < (1ull << 32)) slots <<= 1;
+  u64 G = 1;
+  if (a.n_keys) {
+    G = 0;
+    if (cap) {
+      a.slots = scratch<u32>(slots); a.slot_mask = (u32)(slots - 1);
+      a.row_slot = scratch<u32>(cap); a.slot_gid = scratch<u32>(slots); a.rep_row = scratch<u32>(cap);
+      a.n_groups_dev = new_counter();
+      RDFGPU_HIP(hipMemsetAsync(a.slots, 0, slots * sizeof(u32), stream));
+      timed(KC_AGG_GROUPS, 0, cap, in.n_dev, 4ull * a.n_keys, nullptr, 0, 0, [&] { launch_agg_groups(a, stream); });
+      G = read_back<u64>(a.n_groups_dev);
+    }
+  }
+  a.n_groups = (u32)G;
+  DevTable t;
+  t.n_cols = a.n_keys; t.cap = G;
+  for (u32 k = 0; k < a.n_keys; k++) { a.out_key[k] = scratch<u32>(G); t.cols[k] = a.out_key[k]; }
+  for (u32 i = 0; i < a.n_aggs; i++) a.out[i] = scratch<rdfgpu_agg_value>(G);
+  if (&nd == &nodes[root]) agg_out.assign(a.out, a.out + a.n_aggs);
+  if (G == 0) return t;
+  a.acc = scratch<unsigned long long>(a.n_words * G);
+  RDFGPU_HIP(hipMemsetAsync(a.acc, 0, a.n_words * G * sizeof(unsigned long long), stream));
+  if (cap) {
+    if (distinct) {
+      a.dset_mask = (u32)(slots - 1);
+      for (u32 i = 0; i < a.n_aggs; i++) {
+        if (a.fn[i] != RDFGPU_AGG_COUNT_DISTINCT) continue;
+        a.dset[i] = scratch<unsigned long long>(slots);
+        RDFGPU_HIP(hipMemsetAsync(a.dset[i], 0, slots * sizeof(unsigned long long), stream));
+      }
+    }
+    a.lds = !opt.on(RDFGPU_OPT_NO_AGG_LDS) && (u64)a.n_words * G * sizeof(unsigned long long) <= kAggLdsBytes;
+    timed(a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
+  }
+  timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
   return t;
 }
 
@@ -2357,6 +2463,11 @@ void Plan::ensure_host_copy() {
   for (u32 c = 0; c < result.n_cols; c++) {
     host_cols[c].resize(result_rows);
     if (result_rows) RDFGPU_HIP(hipMemcpyAsync(host_cols[c].data(), result.cols[c], result_rows * 4, hipMemcpyDeviceToHost, stream));
+  }
+  host_aggs.assign(agg_out.size(), std::vector<rdfgpu_agg_value>());
+  for (size_t i = 0; i < agg_out.size(); i++) {
+    host_aggs[i].resize(result_rows);
+    if (result_rows) RDFGPU_HIP(hipMemcpyAsync(host_aggs[i].data(), agg_out[i], result_rows * sizeof(rdfgpu_agg_value), hipMemcpyDeviceToHost, stream));
   }
   RDFGPU_HIP(hipStreamSynchronize(stream));
   host_valid = true;

@@ -43,6 +43,7 @@ struct NodeInfo {
   u64 band_run_stats = 0;                      // sampled rows << 32 | runs of equal neighbouring probe keys (a piecewise sorted probe side takes the counting partition)
   int parent = -1;                             // the one operator consuming this node (-1: the root, or several)
   bool band_takes_records = false;             // this node's band join found its probe side presorted by an ordered slice join below and needed no slow pass: next time that join may write the row records itself
+  u32 n_aggs = 0; u32 agg_fn[RDFGPU_MAX_AGGREGATES] = {}, agg_col[RDFGPU_MAX_AGGREGATES] = {};   // AggregateExec: (RDFGPU_AGG_*, input column)
   bool band_ran = false; u64 band_slow_rows = 0;   // .. and how many of its probe rows needed the full typed-value semantics                    // .. extrapolated from a priming run over a prefix of the bound tables
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
@@ -107,7 +108,8 @@ enum KernelClass {
   KC_PART_KEYS, KC_PART_JOIN, KC_OJ_BAND_RECORDS, KC_OJ_WRITE_BAND, KC_SMALL_SCAN, KC_PART_PASS, KC_STREAM_JOIN,
   KC_SEMI_BUILD, KC_SEMI_JOIN0,      // 6 names: semi_join_kernel<form 0 / 1, anti>, semi_nested_kernel<anti> (semi_join_class)
   KC_SEMI_JOIN_END = KC_SEMI_JOIN0 + 6,
-  KC_LDS_JOIN0 = KC_SEMI_JOIN_END,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
+  KC_AGG_GROUPS = KC_SEMI_JOIN_END, KC_AGG_ACCUM_HBM, KC_AGG_ACCUM_LDS, KC_AGG_FINAL,
+  KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
 const char* kernel_class_name(int kc);
@@ -176,6 +178,8 @@ struct Plan {
   KernelStat kstats[KC__N];
   // Arrow batch stream over a host copy of the result
   std::vector<std::vector<u32>> host_cols; bool host_valid = false; u64 cursor = 0;
+  // aggregate values of an AggregateExec root (result_rows each), on the device and their host copy
+  std::vector<rdfgpu_agg_value*> agg_out; std::vector<std::vector<rdfgpu_agg_value>> host_aggs;
 
   ~Plan();
   // the store's typed-value table with this execution's run-time error word attached (the last counter slot)
@@ -194,6 +198,7 @@ struct Plan {
   DevTable exec_join(NodeInfo& nd);
   DevTable exec_topk(NodeInfo& nd);
   DevTable exec_semi_join(NodeInfo& nd);
+  DevTable exec_aggregate(NodeInfo& nd);
   DevTable apply_filter(NodeInfo& nd, const DevTable& in);
   bool keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const;
   DevTable exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R, bool build_left, const NodeInfo* probe_filter, const NodeInfo* post_filter = nullptr);

@@ -83,6 +83,9 @@ def load_library():
     lib.rdfgpu_plan_result_device.argtypes = [vp, C.POINTER(vp), C.c_uint32]
     lib.rdfgpu_plan_fetch.argtypes = [vp, C.POINTER(vp), C.c_uint32]
     lib.rdfgpu_plan_next.argtypes = [vp, C.POINTER(abi.ArrowArray), C.POINTER(abi.ArrowSchema)]
+    lib.rdfgpu_plan_agg_count.argtypes = [vp, u32p]
+    lib.rdfgpu_plan_agg_fetch.argtypes = [vp, C.c_uint32, vp]
+    lib.rdfgpu_plan_agg_device.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     lib.rdfgpu_plan_rewind.argtypes = [vp]
     lib.rdfgpu_ntriples_parse.argtypes = [C.c_int32, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(vp)]
     lib.rdfgpu_ntriples_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -509,6 +512,30 @@ class GpuPlan:
         _check(self._lib.rdfgpu_plan_fetch(self._h, ptrs, c))
         return cols
 
+    def agg_count(self):
+        """Aggregate columns of the executed result (an AggregateExec root with aggregates; 0 otherwise)."""
+        n = C.c_uint32()
+        _check(self._lib.rdfgpu_plan_agg_count(self._h, C.byref(n)))
+        return n.value
+
+    def fetch_aggregate(self, agg):
+        """Aggregate `agg` of every result row as a numpy structured array of rdfgpu_agg_value (fields lo, hi, tag)."""
+        n, _ = self.result_info()
+        out = np.zeros(n, AGG_DTYPE)
+        _check(self._lib.rdfgpu_plan_agg_fetch(self._h, agg, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def aggregate_device(self, agg):
+        """Device pointer of aggregate `agg` (result_info()[0] rdfgpu_agg_value, 24 bytes each; 0 when there are no rows)."""
+        p = C.c_void_p()
+        _check(self._lib.rdfgpu_plan_agg_device(self._h, agg, C.byref(p)))
+        return p.value or 0
+
+    def aggregate_values(self, agg):
+        """Aggregate `agg` as Python values: int (xsd:integer), fractions.Fraction (xsd:decimal), float (xsd:float / xsd:double),
+        None (the error value)."""
+        return [agg_value(int(v["tag"]), int(v["lo"]), int(v["hi"])) for v in self.fetch_aggregate(agg)]
+
     def batches(self):
         """Drains the Arrow batch stream; yields pyarrow StructArrays of UInt32 children."""
         import pyarrow as pa
@@ -605,3 +632,21 @@ class GpuPlan:
         out = C.c_void_p()
         _check(self._lib.rdfgpu_plan_stream(self._h, C.byref(out)))
         return out.value
+AGG_DTYPE = np.dtype([("lo", "<i8"), ("hi", "<i8"), ("tag", "u1"), ("reserved", "u1", (7,))])
+
+
+def agg_value(tag, lo, hi=0):
+    """One rdfgpu_agg_value as a Python value: int for xsd:integer, fractions.Fraction for xsd:decimal (the i128 / 10^18), float for
+    xsd:float / xsd:double, None for the error value."""
+    from fractions import Fraction
+    lo &= (1 << 64) - 1
+    if tag == abi.TV_INTEGER:
+        return lo - (1 << 64) if lo >= 1 << 63 else lo
+    if tag == abi.TV_DECIMAL:
+        v = ((hi & ((1 << 64) - 1)) << 64) | lo
+        return Fraction(v - (1 << 128) if v >= 1 << 127 else v, 10 ** 18)
+    if tag == abi.TV_FLOAT:
+        return float(np.array([lo & 0xFFFFFFFF], np.uint32).view(np.float32)[0])
+    if tag == abi.TV_DOUBLE:
+        return float(np.array([lo], np.uint64).view(np.float64)[0])
+    return None

@@ -465,6 +465,24 @@ class PlanBuilder:
         n = abi.PlanNode(kind=abi.NODE_CLOSURE, left=left, right=-1, join_type=1 if allow_cross_graph_paths else 0)
         return self._push(n, self._proj(n, None, 3), self.names[left])
 
+    def aggregate(self, left, group_by, aggregates=()):
+        """AggregateExec(mode=Single): GROUP BY the id columns `group_by` (0 to 4) with `aggregates` = [(abi.AGG_*, input column), ...]
+        (at most 8; AGG_COUNT_STAR takes no column: None).  Output: the keys in order, then the aggregates, named like DataFusion's
+        display (`COUNT(y)`).  Only the key columns are ids: a node with aggregates must be the plan's root."""
+        group_by = [int(c) for c in group_by]
+        aggregates = [(int(fn), None if c is None else int(c)) for fn, c in aggregates]
+        names = self.names[left]
+        n = abi.PlanNode(kind=abi.NODE_AGGREGATE, left=left, right=-1, n_keys=len(group_by), table_cols=len(aggregates),
+                         table_slot=len(self.pool))
+        for k, c in enumerate(group_by[:abi.MAX_KEYS]):
+            n.left_keys[k] = c
+        n.n_keys = len(group_by)           # (more than MAX_KEYS is the library's to refuse)
+        for fn, c in aggregates:
+            self.pool.extend([fn, 0 if c is None else c])
+        n.n_proj = abi.NO_PROJECTION
+        out = [names[c] for c in group_by] + [_agg_label(fn, None if c is None else names[c]) for fn, c in aggregates]
+        return self._push(n, len(out), out)
+
     def build(self, root):
         return PlanDescription(self.nodes, self.exprs, self.pool, root, list(self.width), list(self.regexes))
 
@@ -541,6 +559,16 @@ _BIN = {abi.EX_GT: "GT", abi.EX_LT: "LT", abi.EX_GEQ: "GEQ", abi.EX_LEQ: "LEQ", 
         abi.EX_IS_COMPATIBLE: "IS_COMPATIBLE"}
 _JOIN_TYPE_NAMES = {abi.JOIN_INNER: "Inner", abi.JOIN_LEFT: "Left", abi.JOIN_LEFT_SEMI: "LeftSemi", abi.JOIN_LEFT_ANTI: "LeftAnti"}
 _UN = {abi.EX_ENC_TV: "ENC_TV", abi.EX_EBV: "EBV", abi.EX_BOUND: "BOUND", abi.EX_BOOL_AS_TV: "BOOLEAN_AS_TERM"}
+
+
+def _agg_label(fn, column, at=None):
+    """An aggregate as DataFusion names it: COUNT(*), COUNT(y), COUNT(DISTINCT y), SUM(y), AVG(y) (`y@1` with the column index)."""
+    arg = "*" if column is None else (column if at is None else f"{column}@{at}")
+    if fn == abi.AGG_COUNT_STAR:
+        return "COUNT(*)"
+    if fn in (abi.AGG_COUNT_DISTINCT, abi.AGG_SUM_DISTINCT, abi.AGG_AVG_DISTINCT):
+        return f"{abi.AGG_NAMES[fn].split('(')[0]}(DISTINCT {arg})"
+    return f"{abi.AGG_NAMES.get(fn, f'AGG{fn}')}({arg})"
 
 
 def format_expr(nodes, names):
@@ -635,6 +663,16 @@ def explain(pb, root, choose_index=None):
             return
         if n.kind == abi.NODE_TABLE:
             lines.append(f"{pad}BoundTableExec: slot={n.table_slot}, columns=[{', '.join(pb.names[i])}]")
+            return
+        if n.kind == abi.NODE_AGGREGATE:
+            full = pb.names[n.left]
+            gby = ", ".join(f"{full[n.left_keys[k]]}@{n.left_keys[k]} as {full[n.left_keys[k]]}" for k in range(min(n.n_keys, abi.MAX_KEYS)))
+            aggs = []
+            for a in range(n.table_cols):
+                fn, c = pb.pool[n.table_slot + 2 * a], pb.pool[n.table_slot + 2 * a + 1]
+                aggs.append(_agg_label(fn, None if fn == abi.AGG_COUNT_STAR else full[c], c))
+            lines.append(f"{pad}AggregateExec: mode=Single, gby=[{gby}], aggr=[{', '.join(aggs)}]")
+            walk(n.left, depth + 1)
             return
         name = {abi.NODE_PROJECTION: "ProjectionExec", abi.NODE_TOPK: "SortExec: TopK", abi.NODE_UNION: "UnionExec",
                 abi.NODE_CLOSURE: "KleenePlusClosureExec"}[n.kind]
