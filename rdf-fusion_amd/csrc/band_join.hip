@@ -203,7 +203,11 @@ __global__ __launch_bounds__(256) void oj_band_records_kernel(const OrderedJoinA
   uint4 rec; u32 flags;
   band_row_record(b, iy0, iy1, x, rec, flags);
   if (flags & 1u) atomicAdd(b.slow_rows, 1u);
-  if (f.compact) { f.brec[r] = make_uint4(rec.x, rec.y, x, word(f.row_slot[0])); return; }   // (packed form: rec.z / .w are unused; a flagged row's record passes nothing)
+  if (f.compact) {   // (packed form: rec.z / .w are unused; a flagged row's record passes nothing)
+    const uint4 rc = make_uint4(rec.x, rec.y, x, word(f.row_slot[0]));
+    if (f.key_rec) f.key_rec[key - a.kmin] = rc; else f.brec[r] = rc;   // (in place: by key — one table row per key, or the plan re-runs)
+    return;
+  }
   f.brec[2 * r] = rec;
   f.brec[2 * r + 1] = make_uint4(x, flags, word(f.row_slot[0]), word(f.row_slot[1]));
 }
@@ -390,7 +394,7 @@ __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
   const uint4 d = b.bdesc[blk];
   const u32 eb = __builtin_amdgcn_readfirstlane(d.x), ne = __builtin_amdgcn_readfirstlane(d.y);
   const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
-  uint4 rec = PACK ? make_uint4(0x0001FFFFu, 0u, 0u, 0u) : make_uint4(kBandInvalidLo, 0u, 1u, 0u);   // (nothing passes; PACK: the decode pass stored the packed form)
+  uint4 rec = PACK ? make_uint4(kBandPackedNone, 0u, 0u, 0u) : make_uint4(kBandInvalidLo, 0u, 1u, 0u);   // (nothing passes; PACK: the decode pass stored the packed form)
   u32 x = 0;
   if (lane < nr) { rec = b.rec_s[rb + lane]; if (NEQ) x = b.compact ? rec.z : b.aux_s[rb + lane].x; }   // (compact: the 16-byte record carries the id operand itself)
   // The block's 64 entries go through LDS: lane e fetches entry e (one coalesced 1 KB load per block), every test then reads

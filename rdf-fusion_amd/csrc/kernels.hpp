@@ -341,6 +341,8 @@ struct OrderedJoinArgs {
   u64 out_cap; u64* n_out_dev; u32* overflow;
   u32* tile_count; u32* tile_off;                                      // per 1024-row tile of the slice (+ 1) and their exclusive scan
   u32* row_head; unsigned char* row_cnt;                               // per slice row, from the count pass: first table row of its chain, chain length (capped at 255: longer chains are re-walked)
+  u32* multi_rows;                                                     // table rows hung behind an existing chain head (null: not counted): a chain of 2+ rows rules out the in-place band records
+  uint4* key_rec;                                                      // in place (OjInPlace): [kn] the band record of each key's table row, filled with one that passes nothing by the probe pass
 };
 struct BandArgs;
 // The ordered slice join feeding a band join (band_join.hip) writes the band join's ROW RECORDS itself: the windows, the id
@@ -356,9 +358,15 @@ struct OjBandFuse {
   u8 y0_slot[2], y1_slot[2], neq_slot, row_slot[2];   // words of the packed table record holding the window operands / id operand / output values (0xFF: none)
   u8 self_index;                     // the record's id-operand word holds the match's SLICE ROW instead (BandArgs::neq_self)
   u8 compact;                        // one 16-byte record per table row and match {lo pair, width pair, id operand, output value 0} instead of {record, aux} (BandArgs::compact)
+  uint4* key_rec;                    // in place: the records by KEY (OrderedJoinArgs::key_rec) instead of by table row in brec — a slice row gathers its record in one step
 };
 void launch_oj_band_records(const OrderedJoinArgs& a, const BandArgs& b, const OjBandFuse& f, hipStream_t s);
 void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, hipStream_t s);
+// In place: no key of the multimap has more than one table row, and the band join's groups are the slice's own rows (OjBandFuse::self_index).
+// The band join's probe rows are then the slice's rows themselves — rec_s[slice row] = the record of its chain's one table row, or one
+// that passes nothing — and poff is the slice's CSR offsets: no count pass, no scan, no compaction.  (A tag: an overload of the kernel.)
+struct OjInPlace {};
+void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, OjInPlace, hipStream_t s);
 u64 ordered_join_tiles(u64 n_build);
 void launch_ordered_join_probe(const OrderedJoinArgs& a, hipStream_t s);
 void launch_ordered_join_count(const OrderedJoinArgs& a, hipStream_t s);
@@ -417,6 +425,7 @@ void launch_part_join(const LdsJoinArgs& a, const PartArgs& pa, hipStream_t s);
 constexpr u32 kBandMaxSideCols = 4;   // output columns taken from the group entry; from the probe row: kBandMaxRowCols
 constexpr u32 kBandMaxRowCols = 2;    // (they travel inside the row's 32-byte record)
 constexpr u32 kBandMaxGroup = 512;    // largest CSR group (rows of one key) the path accepts: 8 chunks of 64 entries
+constexpr u32 kBandPackedNone = 0x0001FFFFu;   // word x of a packed (pack16) row record that passes nothing: window 0 empty (band_pack_interval)
 struct BandWin {              // one integer window stage: lo(row) <= x(entry) <= hi(row)
   const u32* key_col;         // build column holding the stage's key
   const long long* val; u32 vkmin, vkn;   // x = val[key - vkmin] (INT64_MIN = no row)

@@ -24,6 +24,8 @@ constexpr u32 kOjTile = kOjBlock * kOjRounds;
 // table row -> its stage rows, and into the multimap when every stage has a row (inner joins: no stage row, no match)
 __global__ __launch_bounds__(256) void oj_probe_kernel(const OrderedJoinArgs a) {
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a.key_rec)   // (the records pass fills in the keys that have a table row)
+    for (u64 z = r; z < a.kn; z += (u64)gridDim.x * blockDim.x) a.key_rec[z] = make_uint4(kBandPackedNone, 0u, 0u, 0u);
   const u64 n = live_rows(a.n_probe_dev, a.n_probe_cap);
   if (r >= n) return;
   const u32 key = a.probe_key[r];
@@ -54,9 +56,11 @@ __global__ __launch_bounds__(256) void oj_probe_kernel(const OrderedJoinArgs a) 
   if (a.n_rec > 1) a.trec[r * a.n_rec + 1] = make_uint4(w[4], w[5], w[6], w[7]);
   const u32 old = atomicExch(&a.head[d].x, (u32)r);
   a.next[r] = old;
-  if (old != kNil) atomicAdd(&a.head[d].y, 1u);    // rows of a key beyond its first (0xFFFFFFFF + 1 = 0): the count pass reads chain head
-}                                                  // and length with ONE 8-byte gather (its gathers are what it is bound by); a key with
-                                                   // one row — the common case — costs one atomic here
+  if (old != kNil) {   // rows of a key beyond its first (0xFFFFFFFF + 1 = 0): the count pass reads chain head and length with ONE 8-byte
+    atomicAdd(&a.head[d].y, 1u);                   // gather (its gathers are what it is bound by); a key with one row — the common case —
+    if (a.multi_rows) atomicAdd(a.multi_rows, 1u);   // costs one atomic here, and nothing for the multi-row counter
+  }
+}
 __global__ __launch_bounds__(kOjBlock) void oj_count_kernel(const OrderedJoinArgs a) {
   __shared__ u32 wave_tot[kOjBlock / 64];
   const u64 base = (u64)blockIdx.x * kOjTile;
@@ -251,13 +255,43 @@ __global__ __launch_bounds__(kOjBlock) void oj_write_band_kernel(const OrderedJo
     f.aux_s[pos] = r1;
   }
 }
+// In place (kernels.hpp OjInPlace): every key of the multimap holds at most one table row, so the band join's probe row at slice
+// row i IS slice row i — with the record of its key's table row (z = i: the row's own entry, BandArgs::neq_self), or one that
+// passes nothing when the key has none.  One streaming pass over the slice's join-key column, ONE 16-byte gather per row from the
+// records by key (4.6 MB at 285 K products; through head[] to a record by table row it took two dependent gathers), 16 bytes
+// written per row; kOjRounds rows per lane, every round's loads issued before the first is used.  A key with more rows is counted
+// by oj_probe_kernel (multi_rows): the plan then re-runs exactly and takes the counted route.
+__global__ __launch_bounds__(kOjBlock) void oj_write_band_kernel(const OrderedJoinArgs a, const OjBandFuse f, OjInPlace) {
+  const u64 base = (u64)blockIdx.x * kOjTile + threadIdx.x;
+  u32 dk[kOjRounds];
+#pragma unroll
+  for (int it = 0; it < kOjRounds; it++) {
+    const u64 row = base + (u64)it * kOjBlock;
+    const u32 key = row < a.n_build ? a.build_key[row] : 0u;
+    const u32 d = key - a.kmin;
+    dk[it] = key != 0 && d < a.kn ? d : kNil;
+  }
+  uint4 rc[kOjRounds];
+#pragma unroll
+  for (int it = 0; it < kOjRounds; it++) rc[it] = dk[it] != kNil ? f.key_rec[dk[it]] : make_uint4(kBandPackedNone, 0u, 0u, 0u);
+#pragma unroll
+  for (int it = 0; it < kOjRounds; it++) {
+    const u64 row = base + (u64)it * kOjBlock;
+    rc[it].z = (u32)row;
+    if (row < a.n_build) f.rec_s[row] = rc[it];
+  }
+}
 void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, hipStream_t s) {
   hipLaunchKernelGGL(oj_write_band_kernel, dim3((unsigned)ordered_join_tiles(a.n_build)), dim3(kOjBlock), 0, s, a, f);
 }
+void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, OjInPlace tag, hipStream_t s) {
+  if (a.n_build) hipLaunchKernelGGL(oj_write_band_kernel, dim3((unsigned)ordered_join_tiles(a.n_build)), dim3(kOjBlock), 0, s, a, f, tag);
+}
 
 void launch_ordered_join_probe(const OrderedJoinArgs& a, hipStream_t s) {
-  if (!a.n_probe_cap) return;
-  hipLaunchKernelGGL(oj_probe_kernel, dim3((unsigned)((a.n_probe_cap + 255) / 256)), dim3(256), 0, s, a);
+  const u64 n = a.key_rec && a.kn > a.n_probe_cap ? a.kn : a.n_probe_cap;   // (key_rec: one lane per key fills it, whatever the number of table rows)
+  if (!n) return;
+  hipLaunchKernelGGL(oj_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
 }
 u64 ordered_join_tiles(u64 n_build) { return (n_build + kOjTile - 1) / kOjTile; }
 void launch_ordered_join_count(const OrderedJoinArgs& a, hipStream_t s) {

@@ -600,7 +600,8 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::oj_probe_kernel", "rdfgpu::oj_count_kernel", "void rdfgpu::oj_write_kernel",
       "void rdfgpu::filter_write_kernel", "rdfgpu::part_keys_kernel", "void rdfgpu::part_join_kernel",
       "rdfgpu::oj_band_records_kernel", "rdfgpu::oj_write_band_kernel", "void rdfgpu::small_scan_kernel",
-      "rdfgpu::part_pass (hist + scan + scatter)", "void rdfgpu::stream_join_kernel", "void rdfgpu::semi_build_kernel",
+      "rdfgpu::part_pass (hist + scan + scatter)", "void rdfgpu::stream_join_kernel",
+      "rdfgpu::oj_write_band_kernel(rdfgpu::OrderedJoinArgs, rdfgpu::OjBandFuse, rdfgpu::OjInPlace)", "void rdfgpu::semi_build_kernel",
       "void rdfgpu::semi_join_kernel<0, false", "void rdfgpu::semi_join_kernel<0, true", "void rdfgpu::semi_join_kernel<1, false",
       "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true",
       "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel"};
@@ -755,6 +756,7 @@ void Plan::execute() {
   spec_checks.clear();
   pending_oj.active = false;
   band_block_counters.clear();
+  oj_chain_counters.clear();
   memo.assign(nodes.size(), DevTable{}); memo_valid.assign(nodes.size(), 0);
   speculative = allow_speculation && !opt.on(RDFGPU_OPT_NO_SPECULATION);
 
@@ -823,14 +825,19 @@ void Plan::execute() {
   }
   bool slow_missed = false;
   for (const BandBlockCounter& c : band_block_counters) {
-    c.node->band_blocks = ctx->counters_host[c.counter];
+    c.node->band_blocks = c.known_blocks ? c.known_blocks : ctx->counters_host[c.counter];
     c.node->band_slow_rows = ctx->counters_host[c.slow_counter] & 0xFFFFFFFFull;
     c.node->band_run_stats = ctx->counters_host[c.runs_counter];
     c.node->band_ran = true;
     if (c.slow_skipped && c.node->band_slow_rows) slow_missed = true;   // rows with non-integer operands, and their pass was not launched
   }
+  bool in_place_missed = false;
+  for (const OjChainCounter& c : oj_chain_counters) {
+    c.node->band_multi_rows = ctx->counters_host[c.counter] & 0xFFFFFFFFull;
+    if (c.in_place && c.node->band_multi_rows) in_place_missed = true;   // a key with 2+ table rows: the in-place records held one of them
+  }
   // speculative joins: did every output fit the size taken from the previous run?
-  bool spec_failed = slow_missed;
+  bool spec_failed = slow_missed || in_place_missed;
   for (const SpecCheck& c : spec_checks) {
     if ((ctx->counters_host[c.counter + 1] & 0xFFFFFFFFull) != 0) spec_failed = true;
     else { c.node->last_rows = ctx->counters_host[c.counter]; c.node->has_last = true; c.node->last_scaled = false; }
@@ -1612,9 +1619,29 @@ bool Plan::keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTabl
 // The held-back write pass of an ordered slice join, run after all: its consumer turned out not to take the band join's records.
 void Plan::flush_pending_oj() {
   if (!pending_oj.active) return;
+  count_pending_oj();
   pending_oj.active = false;
   const OrderedJoinArgs& o = pending_oj.o;
   timed(KC_OJ_WRITE, 0, pending_oj.n_build, nullptr, 4, o.n_out_dev, 0, 8ull * o.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
+}
+
+// The count pass of an ordered slice join and the scan of its per-tile counts: where every match goes.
+void Plan::count_ordered_join(OrderedJoinArgs& o) {
+  const u64 tiles = ordered_join_tiles(o.n_build);
+  o.tile_count = scratch<u32>(tiles + 1); o.tile_off = scratch<u32>(tiles + 1);
+  o.row_head = scratch<u32>(o.n_build); o.row_cnt = scratch<unsigned char>(o.n_build);
+  const size_t tb = scan_temp_bytes(tiles + 1);
+  void* temp = scratch<unsigned char>(tb);
+  timed(KC_OJ_COUNT, 0, o.n_build, nullptr, 4, nullptr, 0, 0, [&] { launch_ordered_join_count(o, stream); });
+  timed(scan_class(tiles + 1), 0, tiles + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(o.tile_count, o.tile_off, tiles + 1, temp, tb, stream); });
+}
+// The held-back ordered slice join skipped its count pass for an in-place band join that does not take it after all: it runs now,
+// and so does the check of the count its write pass will write.
+void Plan::count_pending_oj() {
+  if (!pending_oj.active || pending_oj.counted) return;
+  pending_oj.counted = true;
+  count_ordered_join(pending_oj.o);
+  spec_checks.push_back(pending_oj.check);
 }
 
 DevTable Plan::exec_join(NodeInfo& nd) {
@@ -2086,7 +2113,9 @@ DevTable Plan::run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node,
   if (j.left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, j.L.cap, stream));
   if (band) exec_band_join(j.nd, j.slice, a, *band, j.B, j.P, 4ull * (1 + j.build_payload), 4ull * j.probe_cols);
   else if (!run_ordered_join(j, size_node, spec_cap)) run_join_kernel(j, stage_bytes, 4ull * a.n_out_cols);
-  spec_checks.push_back({&size_node, (u32)(a.n_out_dev - counters), j.left_join});
+  const SpecCheck check{&size_node, (u32)(a.n_out_dev - counters), j.left_join};
+  if (pending_oj.active && !pending_oj.counted && pending_oj.o.n_out_dev == a.n_out_dev) pending_oj.check = check;   // nothing writes that count unless the count pass runs after all
+  else spec_checks.push_back(check);
   t.cap = spec_cap + j.tail; t.n_dev = a.n_out_dev;
   if (j.left_join) left_join_tail(j.nd, j.L, j.R, a.out, a.visited, a.n_out_dev, spec_cap + j.tail);
   return t;
@@ -2128,19 +2157,21 @@ bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap)
   o.n_rec = n_words > 4 ? 2u : 1u;
   o.trec = scratch<uint4>(P.cap * o.n_rec);
   o.out_cap = spec_cap; o.n_out_dev = a.n_out_dev; o.overflow = a.overflow;
-  const u64 tiles = ordered_join_tiles(B.cap);
-  o.tile_count = scratch<u32>(tiles + 1); o.tile_off = scratch<u32>(tiles + 1);
-  o.row_head = scratch<u32>(B.cap); o.row_cnt = scratch<unsigned char>(B.cap);
-  const size_t tb = scan_temp_bytes(tiles + 1);
-  void* temp = scratch<unsigned char>(tb);
-  timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
-  timed(KC_OJ_COUNT, 0, B.cap, nullptr, 4, nullptr, 0, 0, [&] { launch_ordered_join_count(o, stream); });
-  timed(scan_class(tiles + 1), 0, tiles + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(o.tile_count, o.tile_off, tiles + 1, temp, tb, stream); });
   // the consumer is a band join that (last time) found this output sorted by its key and needed nothing else of it: the write
-  // pass is held back — that join has it write its row records instead of this table (exec_band_join), anything else flushes it
+  // pass is held back — that join has it write its row records instead of this table (exec_band_join), anything else flushes it.
+  // If that join also read the slice's rows in place last time and no key had two table rows, the count pass waits as well:
+  // the in-place records do not need it (OjInPlace); whatever else takes the table runs it first (count_pending_oj)
   const int consumer = size_node.parent;
-  if (consumer >= 0 && nodes[consumer].band_takes_records && !pending_oj.active && t.sorted_col >= 0) {
+  const bool held = consumer >= 0 && nodes[consumer].band_takes_records && !pending_oj.active && t.sorted_col >= 0;
+  // (NO_BAND_COMPACT switches it off: the in-place records are the 16-byte ones)
+  const bool in_place = held && nodes[consumer].band_in_place && nodes[consumer].band_multi_rows == 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT);
+  if (held) o.multi_rows = reinterpret_cast<u32*>(new_counter());
+  if (in_place) o.key_rec = scratch<uint4>(a.direct_n);
+  timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
+  if (!in_place) count_ordered_join(o);
+  if (held) {
     pending_oj.active = true; pending_oj.o = o; pending_oj.first_col = a.out[0]; pending_oj.n_build = B.cap; pending_oj.n_chain = a.n_chain;
+    pending_oj.counted = !in_place; pending_oj.rows_seen = size_node.last_rows;
   } else timed(KC_OJ_WRITE, 0, B.cap, nullptr, 4, a.n_out_dev, 0, 8ull * a.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
   return true;
 }
@@ -2326,7 +2357,23 @@ void Plan::exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& 
   b.compact = (b.pack16 && b.n_row_cols <= 1 && skip_slow && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT)) ? 1u : 0u;
   if (!presorted) { b.skey_in = scratch<u32>(np); b.sval_in = scratch<u32>(np); b.rec = scratch<uint4>((b.compact ? 1 : 2) * np); }
   b.skey = skey; b.perm = perm;
-  b.rec_s = scratch<uint4>(np); b.aux_s = scratch<uint4>(np);
+  if (fused) {
+    const OrderedJoinArgs& o = pending_oj.o;
+    fuse.compact = b.compact;   // (16 bytes per match instead of 32)
+    // `entry id != row id` by entry index: the band join's groups are the rows of the very slice the ordered join streamed (same sorted column, same
+    // rows, identity CSR), the entry's id is that join's build key, the row's id its probe key — equal keys are what made the match, and a store slice
+    // holds every (key, sorted column) pair once: the only entry of the group whose id equals the row's is the slice row the match came from
+    fuse.self_index = 0;
+    if (fuse.compact && b.has_neq && !b.neq_is_eq && b.csr_rows == nullptr && a.build_key[0] == fuse.key_col && B.cap == pending_oj.n_build &&
+        b.neq_build == o.build_key && B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT))
+      for (u32 c = 0; c < o.n_out_cols; c++)
+        if (o.out[c] == b.neq_probe && o.out_slot[c] != 0xFFu && o.out_ref[c].src == 0 && o.out_ref[c].ptr == o.probe_key) fuse.self_index = 1;
+    b.neq_self = fuse.self_index;
+  }
+  // In place (OjInPlace): the ordered join below skipped its count pass, and the slice it streamed IS this join's build side — the probe rows of key k
+  // are then the group's own slice rows csr_off[k] .. csr_off[k + 1), each with the record of its one table row, and the blocks are the slice's
+  // (cached below with the entries).  Anything else counts the matches now and compacts them (the write-band pass).
+  bool in_place = fused && !pending_oj.counted && fuse.self_index;
   b.slow_rows = reinterpret_cast<u32*>(new_counter());
   b.run_stats = reinterpret_cast<unsigned long long*>(new_counter());
   const size_t stb = sort_u32_temp_bytes(np, bits);
@@ -2386,47 +2433,69 @@ void Plan::exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& 
       build_table->band_entries.push_back(e);
     }
   }
-  if (entries_lock.owns_lock()) entries_lock.unlock();
-  // per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
-  b.poff = scratch<u32>((u64)kn + 2);
-  // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
+  // In place: the band join's rows of key k are the CSR group k itself (poff = csr_off), so its blocks depend on the slice alone — laid out once per
+  // store version beside the entries (same key, same lock), their exact number read back, published when complete; by the first execution
+  // that could take the route, so that the first one that does finds them.  The route pays for every slice row, matched or not, and for
+  // ceil(E/64)² blocks per key: it is taken when the ordered join's last measured rows cover at least half of the slice, and when the block
+  // count, bounded here in 64 bits (sum over keys of ceil(E/64)² <= cmax · (rows / 64 + keys)), stays below 2^31 — the device counts in 32
   const u64 cmax = (build_table->csr_max_group + 63) / 64;
-  const u64 max_blocks = cmax * (np / 64 + 1) + nb / 64 + kn + 1;
+  const bool layout_fits = cmax * (nb / 64 + kn) < (1ull << 31);
+  SliceTable::BandEntries* layout = nullptr;
+  if (fused && fuse.self_index && cache_entries && layout_fits && pending_oj.rows_seen * 2 >= nb)
+    for (auto& e : build_table->band_entries) if (e.key == ekey) layout = &e;
+  in_place = in_place && layout != nullptr;   // (entries that could not be cached: the counted route)
+  if (layout && !layout->boff) {
+    u32* boff = store->table_alloc<u32>((u64)kn + 1);
+    const size_t tb = band_blocks_scan_temp_bytes(kn);
+    void* temp = scratch<unsigned char>(tb);
+    timed(scan_class((u64)kn + 1), 12ull * kn, (u64)kn + 1, nullptr, 4, nullptr, 0, 0, [&] { band_blocks_scan(a.csr_off, a.csr_off, kn, boff, temp, tb, stream); });
+    const u32 n = read_back<u32>(boff + kn);
+    BandArgs d = b;
+    d.poff = const_cast<u32*>(a.csr_off); d.boff = boff; d.bdesc = store->table_alloc<uint4>(n); d.max_blocks = n; d.n_blocks_out = nullptr;
+    timed(KC_BAND_DESC, 12ull * kn, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_desc(d, stream); });
+    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+    layout->boff = boff; layout->bdesc = d.bdesc; layout->n_blocks = n;
+    metrics.tables_built++;
+  }
+  const SliceTable::BandEntries lay = layout ? *layout : SliceTable::BandEntries{};   // (a copy: the list may grow once the lock is released)
+  if (entries_lock.owns_lock()) entries_lock.unlock();
+  base.band_in_place = layout != nullptr;   // (the route is available: next time the ordered join below may leave its matches uncounted)
+  if (fused && !in_place) count_pending_oj();
+  const u64 nrows = in_place ? nb : np;            // probe rows of the block kernels: the slice's own (in place) or the matches
+  b.rec_s = scratch<uint4>(nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(nrows);
+  // per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
+  b.poff = in_place ? const_cast<u32*>(a.csr_off) : scratch<u32>((u64)kn + 2);
+  // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
+  const u64 max_blocks = in_place ? lay.n_blocks : cmax * (np / 64 + 1) + nb / 64 + kn + 1;
   if (max_blocks >= (1ull << 31)) fail(RDFGPU_ERR_UNSUPPORTED, "band join of %llu blocks", (unsigned long long)max_blocks);
   b.max_blocks = (u32)max_blocks;
   b.bcount = scratch<u32>(max_blocks + 1); b.bofs = scratch<u32>(max_blocks + 1);   // (bcount is zeroed by the decode pass: a memset is two more launches, ~10 us of launch gap each on this part)
   if (fused) {
     const OrderedJoinArgs& o = pending_oj.o;
     pending_oj.active = false;
-    fuse.compact = b.compact;   // (16 bytes per match instead of 32)
-    // `entry id != row id` by entry index: the band join's groups are the rows of the very slice the ordered join streamed (same sorted column, same
-    // rows, identity CSR), the entry's id is that join's build key, the row's id its probe key — equal keys are what made the match, and a store slice
-    // holds every (key, sorted column) pair once: the only entry of the group whose id equals the row's is the slice row the match came from
-    fuse.self_index = 0;
-    if (fuse.compact && b.has_neq && !b.neq_is_eq && b.csr_rows == nullptr && a.build_key[0] == fuse.key_col && B.cap == pending_oj.n_build &&
-        b.neq_build == o.build_key && B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT))
-      for (u32 c = 0; c < o.n_out_cols; c++)
-        if (o.out[c] == b.neq_probe && o.out_slot[c] != 0xFFu && o.out_ref[c].src == 0 && o.out_ref[c].ptr == o.probe_key) fuse.self_index = 1;
-    b.neq_self = fuse.self_index;
-    fuse.brec = scratch<uint4>((fuse.compact ? 1 : 2) * o.n_probe_cap);
+    oj_chain_counters.push_back({&base, (u32)(reinterpret_cast<u64*>(o.multi_rows) - counters), in_place});
+    fuse.key_rec = in_place ? o.key_rec : nullptr;
+    fuse.brec = in_place ? nullptr : scratch<uint4>((fuse.compact ? 1 : 2) * o.n_probe_cap);
     fuse.rec_s = b.rec_s; fuse.aux_s = b.aux_s; fuse.poff = b.poff; fuse.bcount = b.bcount; fuse.max_blocks = b.max_blocks;
     fuse.kmin = b.kmin; fuse.kn = b.kn;
     // per table row: its packed record read + two typed-value gathers + 32 B written; per slice row the count pass's 5 bytes + its
-    // key; per match a 32-byte record gathered and stored
+    // key; per match a 32-byte record gathered and stored (in place: per slice row its key read, its key's 16-byte record gathered and stored)
     const u64 rec_bytes = fuse.compact ? 16 : 32;
     timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
-    timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });
+    if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
+    else timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });
   } else
   timed(KC_BAND_DECODE, 0, np, P.n_dev, 4 + 4ull * (b.n_win + b.has_neq) + 9ull * b.n_win + 24 + 8, nullptr, 0, 0, [&] { launch_band_decode(b, stream); });
   // the partition pass: in the time, not in the algorithmic bytes
   if (!presorted && !counting) timed(KC_RADIX_SORT, 0, np, nullptr, 0, nullptr, 0, 0, [&] { sort_pairs_u32_u32(b.skey_in, skey, b.sval_in, perm, np, bits, stemp, stb, stream); });
-  b.boff = scratch<u32>((u64)kn + 1);
-  // the block kernels launch one wave per block: sized from the previous execution's count (+ 25 %), not from the upper bound
+  b.boff = in_place ? lay.boff : scratch<u32>((u64)kn + 1);
+  // the block kernels launch one wave per block: sized from the previous execution's count (+ 25 %), not from the upper bound (in place: exactly)
   b.n_blocks_out = new_counter();
-  band_block_counters.push_back({&base, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters), skip_slow});
+  band_block_counters.push_back({&base, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters), skip_slow,
+                                 in_place ? max_blocks : 0});
   const u64 hist = base.band_blocks;
-  b.launch_blocks = (u32)std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks);
-  b.bdesc = scratch<uint4>(max_blocks);
+  b.launch_blocks = (u32)(in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
+  b.bdesc = in_place ? lay.bdesc : scratch<uint4>(max_blocks);
   b.masks = scratch<u64>(max_blocks * 64);
   const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn));
   void* temp = scratch<unsigned char>(tb);
@@ -2435,12 +2504,15 @@ void Plan::exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& 
     RDFGPU_HIP(hipMemcpyAsync(b.key_cursor, b.poff, ((size_t)kn + 1) * sizeof(u32), hipMemcpyDeviceToDevice, stream));
     timed(KC_BAND_ROWS, 0, np, P.n_dev, 8 + 32 + 32, nullptr, 0, 0, [&] { launch_band_scatter(b, stream); });
   } else if (!presorted) timed(KC_BAND_BOUNDS, 0, np, nullptr, 4, nullptr, 0, 0, [&] { launch_band_bounds(skey, np, kn, b.poff, stream); });   // (presorted: the decode pass wrote poff)
-  timed(scan_class((u64)kn + 1), 12ull * kn, (u64)kn + 1, nullptr, 4, nullptr, 0, 0, [&] { band_blocks_scan(a.csr_off, b.poff, kn, b.boff, temp, tb, stream); });   // (blocks per key: the scan's input iterator)
-  timed(KC_BAND_DESC, 12ull * kn, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_desc(b, stream); });
+  if (!in_place) {
+    timed(scan_class((u64)kn + 1), 12ull * kn, (u64)kn + 1, nullptr, 4, nullptr, 0, 0, [&] { band_blocks_scan(a.csr_off, b.poff, kn, b.boff, temp, tb, stream); });   // (blocks per key: the scan's input iterator)
+    timed(KC_BAND_DESC, 12ull * kn, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_desc(b, stream); });
+  }
   if (!presorted && !counting) timed(KC_BAND_ROWS, 0, np, P.n_dev, 4 + 32 + 32, nullptr, 0, 0, [&] { launch_band_rows(b, stream); });
   // per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count
   // is not known on the host
-  timed(KC_BAND_MASK, 16ull * nb, np, P.n_dev, b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  const u64* const nrows_dev = in_place ? nullptr : P.n_dev;
+  timed(KC_BAND_MASK, 16ull * nb, nrows, nrows_dev, b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
   if (!skip_slow) {
     // the full-semantics pass needs the chain's literals and columns: the fused join kernel's argument block, by pointer
     static_assert(sizeof(LdsJoinArgs) <= ExecContext::kArgBytes, "argument staging slot too small");
@@ -2452,7 +2524,7 @@ void Plan::exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& 
     timed(KC_BAND_SLOW, 0, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_slow(a_dev, b, stream); });
   }
   timed(scan_class(max_blocks + 1), 0, max_blocks + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.bcount, b.bofs, max_blocks + 1, temp, tb, stream); });
-  timed(KC_BAND_EMIT, 4ull * b.n_entry_cols * nb, np, P.n_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
+  timed(KC_BAND_EMIT, 4ull * b.n_entry_cols * nb, nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
 }
 
 void Plan::ensure_host_copy() {

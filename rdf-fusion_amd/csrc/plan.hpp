@@ -44,6 +44,8 @@ struct NodeInfo {
   int parent = -1;                             // the one operator consuming this node (-1: the root, or several)
   bool band_takes_records = false;             // this node's band join found its probe side presorted by an ordered slice join below and needed no slow pass: next time that join may write the row records itself
   u32 n_aggs = 0; u32 agg_fn[RDFGPU_MAX_AGGREGATES] = {}, agg_col[RDFGPU_MAX_AGGREGATES] = {};   // AggregateExec: (RDFGPU_AGG_*, input column)
+  bool band_in_place = false;                  // the ordered slice join below wrote this band join's records with the slice's rows as its own entries
+  u64 band_multi_rows = 0;                     // .. and met this many table rows behind another of the same key (0: next time it may skip its count pass)
   bool band_ran = false; u64 band_slow_rows = 0;   // .. and how many of its probe rows needed the full typed-value semantics                    // .. extrapolated from a priming run over a prefix of the bound tables
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
@@ -55,7 +57,10 @@ struct ChainRequest { NodeInfo* top = nullptr; NodeInfo* base = nullptr; std::ve
 
 // An ordered slice join whose write pass is held back: its consumer, a band join, may have it write the band join's row
 // records instead of the output table (OjBandFuse); anything else flushes it (Plan::flush_pending_oj) first.
-struct PendingOj { bool active = false; OrderedJoinArgs o{}; const u32* first_col = nullptr; u64 n_build = 0; u32 n_chain = 0; };
+// counted = false: its count pass has not run either (the band join may read the slice's rows in place, OjInPlace); whatever
+// else takes the table runs it first (Plan::count_pending_oj) and registers `check`, the check of the count it writes.
+// rows_seen: that join's last measured output rows (how much of the slice the band join's in-place form would leave idle).
+struct PendingOj { bool active = false; OrderedJoinArgs o{}; const u32* first_col = nullptr; u64 n_build = 0; u32 n_chain = 0; bool counted = true; SpecCheck check{}; u64 rows_seen = 0; };
 
 struct BoundTable { std::vector<const u32*> cols; u64 n_rows = 0; bool bound = false; };
 
@@ -105,7 +110,7 @@ enum KernelClass {
   KC_FILTER_VERDICT, KC_REGEX_VERDICTS, KC_UNION,
   KC_BAND_SLOW, KC_RADIX_SORT, KC_BAND_BOUNDS, KC_BAND_BLOCKS, KC_BAND_DECODE, KC_BAND_MASK, KC_BAND_EMIT, KC_BAND_ENTRIES, KC_BAND_DESC, KC_BAND_PT, KC_BAND_ROWS,
   KC_FILTER_BITS_ID, KC_FILTER_BITS_TV, KC_FILTER_BITS_VERDICT, KC_FILTER_BITS_VALUE, KC_VALUE_VERDICTS, KC_VALUE_RUNS, KC_RUN_SCAN, KC_RUN_COPY, KC_OJ_PROBE, KC_OJ_COUNT, KC_OJ_WRITE, KC_FILTER_WRITE,
-  KC_PART_KEYS, KC_PART_JOIN, KC_OJ_BAND_RECORDS, KC_OJ_WRITE_BAND, KC_SMALL_SCAN, KC_PART_PASS, KC_STREAM_JOIN,
+  KC_PART_KEYS, KC_PART_JOIN, KC_OJ_BAND_RECORDS, KC_OJ_WRITE_BAND, KC_SMALL_SCAN, KC_PART_PASS, KC_STREAM_JOIN, KC_OJ_WRITE_BAND_IN_PLACE,
   KC_SEMI_BUILD, KC_SEMI_JOIN0,      // 6 names: semi_join_kernel<form 0 / 1, anti>, semi_nested_kernel<anti> (semi_join_class)
   KC_SEMI_JOIN_END = KC_SEMI_JOIN0 + 6,
   KC_AGG_GROUPS = KC_SEMI_JOIN_END, KC_AGG_ACCUM_HBM, KC_AGG_ACCUM_LDS, KC_AGG_FINAL,
@@ -167,13 +172,17 @@ struct Plan {
   bool priming = false, primed = false;   // the first execution over big bound tables is preceded by one over their first rows (Plan::prime)
   void prime();
   std::vector<SpecCheck> spec_checks;
-  struct BandBlockCounter { NodeInfo* node; u32 counter; u32 slow_counter; u32 runs_counter; bool slow_skipped; };
-  std::vector<BandBlockCounter> band_block_counters;   // device-side block counts of this execution's band joins -> NodeInfo::band_blocks
+  struct BandBlockCounter { NodeInfo* node; u32 counter; u32 slow_counter; u32 runs_counter; bool slow_skipped; u64 known_blocks; };
+  std::vector<BandBlockCounter> band_block_counters;   // device-side block counts of this execution's band joins -> NodeInfo::band_blocks (known_blocks != 0: counted on the host)
+  struct OjChainCounter { NodeInfo* node; u32 counter; bool in_place; };
+  std::vector<OjChainCounter> oj_chain_counters;       // the multi-row counts of the ordered slice joins that wrote band records -> NodeInfo::band_multi_rows
   std::vector<PendingLaunch> pending;
   std::vector<DevTable> memo; std::vector<char> memo_valid;   // node results of the current execution
   ChainRequest* pending_chain = nullptr;                        // set while the base join of a fusable chain executes
   PendingOj pending_oj;
   void flush_pending_oj();
+  void count_pending_oj();
+  void count_ordered_join(OrderedJoinArgs& o);
   u32 events_used = 0;
   KernelStat kstats[KC__N];
   // Arrow batch stream over a host copy of the result

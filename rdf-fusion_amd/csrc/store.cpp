@@ -265,7 +265,7 @@ void Store::drop_slice_tables() {
     table_free(t.direct); table_free(t.csr_off); table_free(t.csr_rows); table_free(t.slots);
     for (auto& v : t.values) table_free(v.val);
     for (auto& r : t.ranges) { table_free(r.rows); table_free(r.vals); table_free(r.link); }
-    for (auto& e : t.band_entries) { table_free(e.et); for (u32* p : e.eo) table_free(p); }
+    for (auto& e : t.band_entries) { table_free(e.et); for (u32* p : e.eo) table_free(p); table_free(e.boff); table_free(e.bdesc); }
     for (auto& v : t.value_starts) table_free(v.lo);
   }
   slice_tables.clear();

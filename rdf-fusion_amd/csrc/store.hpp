@@ -103,7 +103,9 @@ struct SliceTable {
   std::vector<RangeIndex> ranges;
   // a CSR table's rows decoded for one band-join chain (band_join.hip: the pair test's operands and the entries' output
   // values, in CSR order): a function of the store's slices and the chain's constants only — `key` spells them out
-  struct BandEntries { std::string key; uint4* et; u32* eo[4]; };
+  // boff / bdesc: the block layout of a band join that reads the slice's rows in place (its rows of key k are the CSR group k
+  // itself: poff = csr_off), a function of the slice alone; built by the first such execution, n_blocks exact (null: not yet)
+  struct BandEntries { std::string key; uint4* et; u32* eo[4]; u32* boff = nullptr; uint4* bdesc = nullptr; u32 n_blocks = 0; };
   std::vector<BandEntries> band_entries;
   // the slice as the sorted input of a FILTER on its sort column (kernels.hip, run-copy form): lo[i] = first row whose id is >= first + i
   // (i = 0 .. span): where every distinct id's run starts — a function of the slice alone
