@@ -729,6 +729,20 @@ void Plan::prime() {
   }
 }
 
+// The measurements this execution's band joins left in the counters -> NodeInfo::band.  true: one of them speculated wrongly.
+bool Plan::record_band_history() {
+  bool missed = false;
+  for (const BandFeedback& f : band_feedback) {
+    BandHistory& h = f.node->band;
+    h.ran = true; h.blocks = f.known_blocks ? f.known_blocks : ctx->counters_host[f.blocks];
+    h.slow_rows = ctx->counters_host[f.slow_rows] & 0xFFFFFFFFull; h.run_stats = ctx->counters_host[f.run_stats];
+    if (f.slow_skipped && h.slow_rows) missed = true;   // rows with non-integer operands, and their pass was not launched
+    if (f.multi_rows >= 0) h.multi_rows = ctx->counters_host[f.multi_rows] & 0xFFFFFFFFull;
+    if (f.multi_rows >= 0 && f.in_place && h.multi_rows) missed = true;   // a key with 2+ table rows: the in-place records held one of them
+  }
+  return missed;
+}
+
 void Plan::execute() {
   if (!primed && !priming) prime();
   store->activate();
@@ -755,8 +769,7 @@ void Plan::execute() {
 
   spec_checks.clear();
   pending_oj.active = false;
-  band_block_counters.clear();
-  oj_chain_counters.clear();
+  band_feedback.clear();
   memo.assign(nodes.size(), DevTable{}); memo_valid.assign(nodes.size(), 0);
   speculative = allow_speculation && !opt.on(RDFGPU_OPT_NO_SPECULATION);
 
@@ -823,21 +836,8 @@ void Plan::execute() {
                                                "a float / double / decimal SUBSTR position, or a comparison with a string that has no bytes on the device");
     fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with a per-row pattern: a row's pattern literal was not announced in the plan's pattern table");
   }
-  bool slow_missed = false;
-  for (const BandBlockCounter& c : band_block_counters) {
-    c.node->band_blocks = c.known_blocks ? c.known_blocks : ctx->counters_host[c.counter];
-    c.node->band_slow_rows = ctx->counters_host[c.slow_counter] & 0xFFFFFFFFull;
-    c.node->band_run_stats = ctx->counters_host[c.runs_counter];
-    c.node->band_ran = true;
-    if (c.slow_skipped && c.node->band_slow_rows) slow_missed = true;   // rows with non-integer operands, and their pass was not launched
-  }
-  bool in_place_missed = false;
-  for (const OjChainCounter& c : oj_chain_counters) {
-    c.node->band_multi_rows = ctx->counters_host[c.counter] & 0xFFFFFFFFull;
-    if (c.in_place && c.node->band_multi_rows) in_place_missed = true;   // a key with 2+ table rows: the in-place records held one of them
-  }
-  // speculative joins: did every output fit the size taken from the previous run?
-  bool spec_failed = slow_missed || in_place_missed;
+  // speculative joins: did the band joins take the right route, did every output fit the size taken from the previous run?
+  bool spec_failed = record_band_history();
   for (const SpecCheck& c : spec_checks) {
     if ((ctx->counters_host[c.counter + 1] & 0xFFFFFFFFull) != 0) spec_failed = true;
     else { c.node->last_rows = ctx->counters_host[c.counter]; c.node->has_last = true; c.node->last_scaled = false; }
@@ -1419,19 +1419,27 @@ bool Plan::plan_chain(NodeInfo& top, ChainRequest& req) {
   return true;
 }
 
-// Resolves the chain against the base join's inputs; false (nothing changed in `a` that matters) if some column cannot
-// be addressed the way the kernel needs.
-bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& L, const DevTable& R, bool build_left, SliceTable* build_table, LdsJoinArgs& a,
-                       u64& stage_bytes, BandArgs* band, bool* use_band) {
-  std::vector<ColRef> cur(base.n_proj);
+// Resolves the chain against the base join `j` and leaves it in j.a: as a band join where it has that shape (j.use_band, j.band), else with the range index
+// of its first stage where that applies.  false (j.a.n_chain stays 0: the stages written so far are not read) if some column cannot be addressed the way the kernel needs.
+bool Plan::apply_chain(const ChainRequest& req, LdsJoin& j) {
+  if (!resolve_chain(req, j)) return false;
+  j.use_band = chain_band_args(req, j);
+  if (!j.use_band) chain_range_index(j, j.a.chain[0]);
+  j.a.n_chain = (u32)req.links.size(); j.a.n_out_cols = (u32)j.chain_cols.size();
+  for (size_t k = 0; k < j.chain_cols.size(); k++) j.a.chain_out[k] = j.chain_cols[k];
+  return true;
+}
+
+// The chain's stages bottom-up (j.a.chain): each stage's key, table, filter operands and output columns (j.chain_cols) as references to base columns or to its own slice's.
+bool Plan::resolve_chain(const ChainRequest& req, LdsJoin& j) {
+  const NodeInfo& base = j.nd; std::vector<ColRef>& cur = j.chain_cols;
+  cur.resize(base.n_proj);
   for (u32 k = 0; k < base.n_proj; k++) {
-    const u32 c = base.proj[k];
-    const bool from_left = c < L.n_cols;
-    cur[k] = ColRef{from_left ? L.cols[c] : R.cols[c - L.n_cols], (from_left == build_left) ? 1u : 0u, 0u};
+    const u32 col = base.proj[k];
+    const bool from_left = col < j.L.n_cols;
+    cur[k] = ColRef{from_left ? j.L.cols[col] : j.R.cols[col - j.L.n_cols], (from_left == j.build_left) ? 1u : 0u, 0u};
   }
-  ChainStage stages[kMaxChain];
-  const SliceTable::ValueColumn* stage_vc[kMaxChain] = {nullptr, nullptr, nullptr};
-  stage_bytes = 0;
+  j.stage_bytes = 0;
   for (size_t t = 0; t < req.links.size(); t++) {
     const ChainLink& ln = req.links[t];
     const NodeInfo& N = *ln.node;
@@ -1439,14 +1447,13 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
     const u32 prev_w = ln.slice_is_left ? nodes[N.d.right].width : wl;
     if (prev_w != cur.size()) return false;
     bool bad = false;
-    auto resolve = [&](u32 c) -> ColRef {
-      const bool in_left = c < wl; const u32 local = in_left ? c : c - wl;
+    auto resolve = [&](u32 col) -> ColRef {
+      const bool in_left = col < wl; const u32 local = in_left ? col : col - wl;
       if (in_left == ln.slice_is_left) { if (local >= ln.slice.n_cols) { bad = true; return ColRef{}; } return ColRef{ln.slice.cols[local], 2u + (u32)t, 0u}; }
       if (local >= cur.size()) { bad = true; return ColRef{}; }
       return cur[local];
     };
-    ChainStage& st = stages[t];
-    std::memset(&st, 0, sizeof st);
+    ChainStage& st = j.a.chain[t]; std::memset(&st, 0, sizeof st);
     const u32 prev_key = ln.slice_is_left ? N.d.right_keys[0] : N.d.left_keys[0];
     if (prev_key >= cur.size()) return false;
     st.key = cur[prev_key];
@@ -1465,144 +1472,132 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
       st.l0 = window_literal(e, 0); st.l1 = window_literal(e, 8);
     } else return false;
     for (u32 q = 0; q < n_fcols; q++) if (st.f[q].src > 1 && st.f[q].src != 2u + (u32)t) return false;   // base columns or this stage's
-    // integer window whose x operand is a column of this stage's slice and whose y operands are base columns: use the
-    // slice's decoded value table (built once per store version, kept with the direct table)
+    // integer window whose x operand is a column of this stage's slice and whose y operands are base columns: use the slice's decoded value table
     if (st.fs == 3 && st.f[0].src == 2u + (u32)t && st.f[2].src == st.f[0].src && st.f[2].ptr == st.f[0].ptr && st.f[1].src <= 1 && st.f[3].src <= 1 &&
         !opt.on(RDFGPU_OPT_NO_VALUE_TABLES)) {
-      SliceTable* tab = const_cast<SliceTable*>(ln.table);
-      std::unique_lock<std::mutex> building(store->slice_build_mu);
-      SliceTable::ValueColumn* vc = nullptr;
-      for (auto& v : tab->values) if (v.col == st.f[0].ptr) vc = &v;
-      if (!vc) {
-        const u32 key_local = ln.slice_is_left ? N.d.left_keys[0] : N.d.right_keys[0];
-        long long* val = store->table_alloc<long long>(tab->kn);
-        metrics.tables_built++;
-        u32* bad = reinterpret_cast<u32*>(new_counter());
-        launch_fill_i64(val, INT64_MIN, tab->kn, stream);
-        launch_direct_values(ln.slice.cols[key_local], st.f[0].ptr, ln.slice.cap, tab->kmin, tab->kn, typed_table(), val, bad, stream);
-        if (read_back<u32>(bad)) { store->table_free(val); val = nullptr; }
-        SliceTable::ValueColumn fresh{st.f[0].ptr, val, val != nullptr};
-        if (val) {   // value range: the bias of the band join's 32-bit window intervals
-          long long* mm = reinterpret_cast<long long*>(new_counter()); (void)new_counter();
-          const long long init[2] = {INT64_MAX, INT64_MIN + 1};
-          RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, stream));
-          launch_val_minmax(val, tab->kn, mm, stream);
-          long long got[2];
-          read_back(got, mm, sizeof got);
-          fresh.vmin = got[0]; fresh.vmax = got[1];
-        }
-        tab->values.push_back(fresh);
-        vc = &tab->values.back();
-      }
-      if (vc->usable) { st.val = vc->val; stage_vc[t] = vc; }
+      const SliceTable::ValueColumn vc = slice_value_column(ln, st.f[0].ptr);
+      if (vc.usable) { st.val = vc.val; j.chain_vc[t] = vc; }
     }
     std::vector<ColRef> next(N.n_proj);
     for (u32 k = 0; k < N.n_proj; k++) next[k] = resolve(N.proj[k]);
     if (bad) return false;
     cur.swap(next);
-    stage_bytes += base.last_rows * (8ull + 4ull * n_fcols);   // per candidate: key + table slot + filter operands (estimate)
+    j.stage_bytes += base.last_rows * (8ull + 4ull * n_fcols);   // per candidate: key + table slot + filter operands (estimate)
   }
-  if (cur.size() != req.top->n_proj || cur.size() > (size_t)kMaxCols) return false;
-  // Band join (band_join.hip): when the groups of the CSR base are small, every stage hangs off a BUILD column and the
-  // stage filters are integer windows between a stage value and probe columns, the chain runs group by group — both
-  // sides partitioned by the key, the pair tests in registers — instead of probe row by probe row.
-  *use_band = false;
-  if (band && a.csr_off && build_table && !opt.on(RDFGPU_OPT_NO_BAND_JOIN) && arg_slots_used < ExecContext::kArgSlots) {
-    const DevTable& B = build_left ? L : R; const DevTable& Pp = build_left ? R : L;
-    BandArgs b{};
-    bool ok = a.n_keys == 1 && (a.has_filter == 0 || a.has_filter == 2) && a.has_probe_filter == 0 && a.visited == nullptr;
-    if (ok && a.has_filter == 2) {
-      const bool ab = on_build_side(a, a.idp.a), bb = on_build_side(a, a.idp.b);
-      ok = ab != bb;
-      if (ok) { b.has_neq = 1; b.neq_is_eq = a.idp.is_eq; b.neq_build = a.cols[ab ? a.idp.a : a.idp.b]; b.neq_probe = a.cols[ab ? a.idp.b : a.idp.a]; }
-    }
-    if (ok && a.has_post) {
-      ok = on_build_side(a, a.post.col);
-      b.has_post = 1; b.post_col = a.cols[a.post.col]; b.post_lit = a.post.lit; b.post_is_eq = a.post.is_eq;
-    }
-    b.n_stages = (u32)req.links.size();
-    bool pack16 = !opt.on(RDFGPU_OPT_NO_BAND_PACK16);
-    for (size_t t = 0; ok && t < req.links.size(); t++) {
-      const ChainStage& st = stages[t];
-      ok = st.key.src == 1 && (st.fs == 0 || st.fs == 3);
-      if (!ok) break;
-      b.stage[t] = BandStage{st.key.ptr, st.direct, st.kmin, st.kn};
-      if (st.fs == 0) continue;
-      const SliceTable::ValueColumn* vc = stage_vc[t];
-      ok = st.val != nullptr && vc && b.n_win < 2 && st.f[1].src == 0 && st.f[3].src == 0 && range_op(st.l0.cmp_op) && range_op(st.l1.cmp_op) &&
-           vc->vmin <= vc->vmax && (unsigned long long)(vc->vmax - vc->vmin) < 0xFFFFFFE0ull;
-      if (!ok) break;
-      BandWin& w = b.win[b.n_win++];
-      if ((unsigned long long)(vc->vmax - vc->vmin) > 65530ull) pack16 = false;   // biased values 1 .. range + 1 have to fit 16 bits
-      w.key_col = st.key.ptr; w.val = st.val; w.vkmin = st.kmin; w.vkn = st.kn; w.vbase = vc->vmin;
-      w.y0 = st.f[1].ptr; w.y1 = st.f[3].ptr; w.l0 = st.l0; w.l1 = st.l1; w.stage = (u32)t;
-    }
-    b.pack16 = pack16 ? 1u : 0u;
-    for (size_t k = 0; ok && k < cur.size(); k++) {
-      if (cur[k].src == 0) { ok = b.n_row_cols < kBandMaxRowCols; if (ok) { b.out_from_row[k] = 1; b.out_sel[k] = (u8)b.n_row_cols; b.row_col[b.n_row_cols++] = cur[k].ptr; } }
-      else { ok = b.n_entry_cols < kBandMaxSideCols; if (ok) { b.out_from_row[k] = 0; b.out_sel[k] = (u8)(2 + b.n_entry_cols); b.entry_col[b.n_entry_cols++] = cur[k]; } }
-    }
-    if (ok) {   // group sizes: the largest decides (one wave joins a whole group), measured once per table
-      SliceTable* tab = build_table;
-      std::unique_lock<std::mutex> building(store->slice_build_mu);
-      if (tab->csr_max_group == 0) {
-        u32* mx = reinterpret_cast<u32*>(new_counter());
-        launch_csr_max_group(a.csr_off, a.direct_n, mx, stream);
-        const u32 got = read_back<u32>(mx);
-        tab->csr_max_group = got ? got : 1;
-      }
-      ok = tab->csr_max_group <= kBandMaxGroup && B.cap >= 4ull * a.direct_n && Pp.cap * 4 >= a.direct_n && Pp.cap < (1ull << 31);
-    }
-    if (ok) { *band = b; *use_band = true; }
+  return cur.size() == req.top->n_proj && cur.size() <= (size_t)kMaxCols;
+}
+
+// {min, max} of the i64 values `launch(slots)` folds into two counter slots, read back in one host round trip.
+template <class F> void Plan::device_minmax_i64(long long (&got)[2], F&& launch) {
+  long long* mm = reinterpret_cast<long long*>(new_counter()); (void)new_counter();   // {min, max}: two slots
+  const long long init[2] = {INT64_MAX, INT64_MIN + 1};
+  RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, stream));
+  launch(mm);
+  read_back(got, mm, sizeof got);
+}
+
+// The decoded value table of column `col` of a chain link's slice: found (one entry per column: pushed only after a failed look-up under the same lock) or built now, once per store version.  A copy: the list may grow.
+SliceTable::ValueColumn Plan::slice_value_column(const ChainLink& ln, const u32* col) {
+  SliceTable* tab = const_cast<SliceTable*>(ln.table);
+  std::unique_lock<std::mutex> building(store->slice_build_mu);
+  for (const auto& v : tab->values) if (v.col == col) return v;
+  const u32 key_local = ln.slice_is_left ? ln.node->d.left_keys[0] : ln.node->d.right_keys[0];
+  long long* val = store->table_alloc<long long>(tab->kn); metrics.tables_built++;
+  u32* bad = reinterpret_cast<u32*>(new_counter());
+  launch_fill_i64(val, INT64_MIN, tab->kn, stream);
+  launch_direct_values(ln.slice.cols[key_local], col, ln.slice.cap, tab->kmin, tab->kn, typed_table(), val, bad, stream);
+  if (read_back<u32>(bad)) { store->table_free(val); val = nullptr; }
+  SliceTable::ValueColumn fresh{col, val, val != nullptr};
+  if (val) {   // value range: the bias of the band join's 32-bit window intervals
+    long long got[2]; device_minmax_i64(got, [&](long long* mm) { launch_val_minmax(val, tab->kn, mm, stream); });
+    fresh.vmin = got[0]; fresh.vmax = got[1];
   }
-  // Range index: a CSR base whose first stage is an integer window (GT / LT / GEQ / LEQ) between the stage's decoded
-  // value and probe-side columns expands, per probe row, only the part of the key's group whose value can pass —
-  // the group is kept sorted by that value (built once per store version, kept with the CSR table).
-  if (!*use_band) {
-    const ChainStage& s0 = stages[0];
-    const DevTable& B = build_left ? L : R;
-    if (a.csr_off && build_table && s0.val && s0.fs == 3 && s0.key.src == 1 && s0.f[1].src == 0 && s0.f[3].src == 0 &&
-        range_op(s0.l0.cmp_op) && range_op(s0.l1.cmp_op) && !opt.on(RDFGPU_OPT_NO_RANGE_INDEX)) {
-      SliceTable* tab = build_table;
-      std::unique_lock<std::mutex> building(store->slice_build_mu);
-      SliceTable::RangeIndex* ri = nullptr;
-      for (auto& r : tab->ranges) if (r.val == s0.val && r.link_col == s0.key.ptr) ri = &r;
-      if (!ri) {
-        SliceTable::RangeIndex fresh{s0.val, s0.key.ptr, nullptr, nullptr, 0, nullptr, false};
-        const u64 n = B.cap;
-        long long* mm = reinterpret_cast<long long*>(new_counter()); (void)new_counter();   // {min, max}: two slots
-        const long long init[2] = {INT64_MAX, INT64_MIN + 1};
-        RDFGPU_HIP(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, stream));
-        launch_range_minmax(s0.key.ptr, a.csr_rows, n, s0.val, s0.kmin, s0.kn, mm, stream);
-        long long got[2];
-        read_back(got, mm, sizeof got);
-        if (got[0] <= got[1] && (unsigned long long)(got[1] - got[0]) < 0xFFFFFFF0ull && n < (1ull << 32)) {
-          u64* key_in = scratch<u64>(n); u64* key_out = scratch<u64>(n); u32* rows_in = scratch<u32>(n);
-          fresh.rows = store->table_alloc<u32>(n);
-          fresh.vals = store->table_alloc<u32>(n);
-          metrics.tables_built++;
-          fresh.vbase = got[0];
-          launch_range_keys(a.build_key[0], a.direct_min, s0.key.ptr, a.csr_rows, n, s0.val, s0.kmin, s0.kn, got[0], key_in, rows_in, stream);
-          const size_t tb = sort_temp_bytes(n);
-          void* temp = scratch<unsigned char>(tb);
-          sort_pairs_u64_u32(key_in, key_out, rows_in, fresh.rows, n, temp, tb, stream);
-          launch_range_decode(key_out, n, fresh.vals, stream);
-          fresh.link = store->table_alloc<u32>(n);
-          launch_gather_u32(s0.key.ptr, fresh.rows, fresh.link, n, stream);   // the link column in index order
-          RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-          fresh.usable = true;
-        }
-        tab->ranges.push_back(fresh);
-        ri = &tab->ranges.back();
-      }
-      if (ri->usable) { a.range_rows = ri->rows; a.range_vals = ri->vals; a.range_vbase = ri->vbase; a.range_link = ri->link; a.range_link_col = ri->link_col; }
-    }
+  tab->values.push_back(fresh);
+  return fresh;
+}
+
+// Band join (band_join.hip): when the groups of the CSR base are small, every stage hangs off a BUILD column and the stage filters are integer windows between a stage value
+// and probe columns, the chain runs group by group — both sides partitioned by the key, the pair tests in registers — instead of probe row by probe row.  true: j.band is filled.
+bool Plan::chain_band_args(const ChainRequest& req, LdsJoin& j) {
+  const LdsJoinArgs& a = j.a; BandArgs b{};
+  if (!a.csr_off || !j.slice || opt.on(RDFGPU_OPT_NO_BAND_JOIN) || arg_slots_used >= ExecContext::kArgSlots) return false;
+  if (a.n_keys != 1 || (a.has_filter != 0 && a.has_filter != 2) || a.has_probe_filter != 0 || a.visited != nullptr) return false;
+  if (a.has_filter == 2) {
+    const bool ab = on_build_side(a, a.idp.a), bb = on_build_side(a, a.idp.b);
+    if (ab == bb) return false;
+    b.has_neq = 1; b.neq_is_eq = a.idp.is_eq; b.neq_build = a.cols[ab ? a.idp.a : a.idp.b]; b.neq_probe = a.cols[ab ? a.idp.b : a.idp.a];
   }
-  a.n_chain = (u32)req.links.size();
-  for (size_t t = 0; t < req.links.size(); t++) a.chain[t] = stages[t];
-  for (size_t k = 0; k < cur.size(); k++) a.chain_out[k] = cur[k];
-  a.n_out_cols = (u32)cur.size();
+  if (a.has_post) {
+    if (!on_build_side(a, a.post.col)) return false;
+    b.has_post = 1; b.post_col = a.cols[a.post.col]; b.post_lit = a.post.lit; b.post_is_eq = a.post.is_eq;
+  }
+  b.n_stages = (u32)req.links.size();
+  bool pack16 = !opt.on(RDFGPU_OPT_NO_BAND_PACK16);
+  for (size_t t = 0; t < req.links.size(); t++) {
+    const ChainStage& st = a.chain[t];
+    if (st.key.src != 1 || (st.fs != 0 && st.fs != 3)) return false;
+    b.stage[t] = BandStage{st.key.ptr, st.direct, st.kmin, st.kn};
+    if (st.fs == 0) continue;
+    const SliceTable::ValueColumn& vc = j.chain_vc[t];
+    if (st.val == nullptr || b.n_win >= 2 || st.f[1].src != 0 || st.f[3].src != 0 || !range_op(st.l0.cmp_op) || !range_op(st.l1.cmp_op) ||
+        vc.vmin > vc.vmax || (unsigned long long)(vc.vmax - vc.vmin) >= 0xFFFFFFE0ull) return false;
+    BandWin& w = b.win[b.n_win++];
+    if ((unsigned long long)(vc.vmax - vc.vmin) > 65530ull) pack16 = false;   // biased values 1 .. range + 1 have to fit 16 bits
+    w.key_col = st.key.ptr; w.val = st.val; w.vkmin = st.kmin; w.vkn = st.kn; w.vbase = vc.vmin;
+    w.y0 = st.f[1].ptr; w.y1 = st.f[3].ptr; w.l0 = st.l0; w.l1 = st.l1; w.stage = (u32)t;
+  }
+  b.pack16 = pack16 ? 1u : 0u;
+  for (size_t k = 0; k < j.chain_cols.size(); k++) {
+    const ColRef& col = j.chain_cols[k];
+    if (col.src == 0 ? b.n_row_cols >= kBandMaxRowCols : b.n_entry_cols >= kBandMaxSideCols) return false;
+    if (col.src == 0) { b.out_from_row[k] = 1; b.out_sel[k] = (u8)b.n_row_cols; b.row_col[b.n_row_cols++] = col.ptr; }
+    else { b.out_from_row[k] = 0; b.out_sel[k] = (u8)(2 + b.n_entry_cols); b.entry_col[b.n_entry_cols++] = col; }
+  }
+  // group sizes: the largest decides (one wave joins a whole group)
+  if (csr_max_group(j.slice, a) > kBandMaxGroup || j.B.cap < 4ull * a.direct_n || j.P.cap * 4 < a.direct_n || j.P.cap >= (1ull << 31)) return false;
+  j.band = b;
   return true;
+}
+
+// Rows of the largest group of a slice's CSR table: measured once per table, under the lock.
+u32 Plan::csr_max_group(SliceTable* tab, const LdsJoinArgs& a) {
+  std::unique_lock<std::mutex> building(store->slice_build_mu);
+  if (tab->csr_max_group) return tab->csr_max_group;
+  u32* mx = reinterpret_cast<u32*>(new_counter());
+  launch_csr_max_group(a.csr_off, a.direct_n, mx, stream);
+  return tab->csr_max_group = std::max(1u, read_back<u32>(mx));
+}
+
+// Range index: a CSR base whose first stage `s0` is an integer window (GT / LT / GEQ / LEQ) between the stage's decoded value and probe-side columns expands, per probe row,
+// only the part of the key's group whose value can pass — the group is kept sorted by that value (found on the CSR table or built now, once per store version, under the lock).
+void Plan::chain_range_index(LdsJoin& j, const ChainStage& s0) {
+  LdsJoinArgs& a = j.a;
+  if (!a.csr_off || !j.slice || !s0.val || s0.fs != 3 || s0.key.src != 1 || s0.f[1].src != 0 || s0.f[3].src != 0 ||
+      !range_op(s0.l0.cmp_op) || !range_op(s0.l1.cmp_op) || opt.on(RDFGPU_OPT_NO_RANGE_INDEX)) return;
+  std::unique_lock<std::mutex> building(store->slice_build_mu);
+  SliceTable::RangeIndex* ri = nullptr;
+  for (auto& r : j.slice->ranges) if (r.val == s0.val && r.link_col == s0.key.ptr) ri = &r;
+  if (!ri) {
+    SliceTable::RangeIndex fresh{s0.val, s0.key.ptr, nullptr, nullptr, 0, nullptr, false};
+    const u64 n = j.B.cap;
+    long long got[2]; device_minmax_i64(got, [&](long long* mm) { launch_range_minmax(s0.key.ptr, a.csr_rows, n, s0.val, s0.kmin, s0.kn, mm, stream); });
+    if (got[0] <= got[1] && (unsigned long long)(got[1] - got[0]) < 0xFFFFFFF0ull && n < (1ull << 32)) {
+      u64* key_in = scratch<u64>(n); u64* key_out = scratch<u64>(n); u32* rows_in = scratch<u32>(n);
+      fresh.rows = store->table_alloc<u32>(n); fresh.vals = store->table_alloc<u32>(n);
+      metrics.tables_built++; fresh.vbase = got[0];
+      launch_range_keys(a.build_key[0], a.direct_min, s0.key.ptr, a.csr_rows, n, s0.val, s0.kmin, s0.kn, got[0], key_in, rows_in, stream);
+      const size_t tb = sort_temp_bytes(n); void* temp = scratch<unsigned char>(tb);
+      sort_pairs_u64_u32(key_in, key_out, rows_in, fresh.rows, n, temp, tb, stream);
+      launch_range_decode(key_out, n, fresh.vals, stream);
+      fresh.link = store->table_alloc<u32>(n);
+      launch_gather_u32(s0.key.ptr, fresh.rows, fresh.link, n, stream);   // the link column in index order
+      RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+      fresh.usable = true;
+    }
+    j.slice->ranges.push_back(fresh);
+    ri = &j.slice->ranges.back();
+  }
+  if (ri->usable) { a.range_rows = ri->rows; a.range_vals = ri->vals; a.range_vbase = ri->vbase; a.range_link = ri->link; a.range_link_col = ri->link_col; }
 }
 
 // The held-back write pass of an ordered slice join runs before anything reads its table, except the band join that consumes
@@ -1610,7 +1605,7 @@ bool Plan::apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& 
 // the records last time (the sides as exec_join chooses them below).  exec_lds_join then hands it on to the band join or runs
 // it just before the probe side is read.
 bool Plan::keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const {
-  if (!nd.band_takes_records || nd.d.kind != RDFGPU_NODE_HASH_JOIN || left_join || lf || rf || opt.on(RDFGPU_OPT_NO_LDS_JOIN)) return false;
+  if (!nd.band.takes_records || nd.d.kind != RDFGPU_NODE_HASH_JOIN || left_join || lf || rf || opt.on(RDFGPU_OPT_NO_LDS_JOIN)) return false;
   const bool build_left = choose_build_left(nd, L, R, false, false, false);
   const DevTable& B = build_left ? L : R; const DevTable& P = build_left ? R : L;
   return (B.cap <= kLdsJoinMaxBuild || !opt.on(RDFGPU_OPT_NO_GLOBAL_TABLE_JOIN)) && P.cols[0] == pending_oj.first_col && B.cols[0] != pending_oj.first_col;
@@ -1889,16 +1884,14 @@ DevTable Plan::exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R,
   // a fusable run of follow-up lookups above this join (Plan::plan_chain) executes inside this join's resolve
   // phase: the output is then the TOP node's, sized from the top node's history
   NodeInfo* size_node = &nd;
-  u64 stage_bytes = 0;
-  BandArgs band{}; bool use_band = false;
   if (spec && pending_chain && pending_chain->base == &nd && !pending_chain->consumed && j.global_table && j.table != JoinTable::Partitioned && !j.left_join &&
-      !j.probe_outer && !probe_filter && nd.shape != 1 && apply_chain(*pending_chain, nd, L, R, build_left, j.slice, a, stage_bytes, &band, &use_band)) {
+      !j.probe_outer && !probe_filter && nd.shape != 1 && apply_chain(*pending_chain, j)) {
     pending_chain->consumed = true;
     size_node = pending_chain->top;
     j.t.n_cols = a.n_out_cols;
   }
   // the probe side is read from here on: only the band join takes an ordered slice join's held-back write pass (exec_band_join)
-  if (!use_band) flush_pending_oj();
+  if (!j.use_band) flush_pending_oj();
   if (j.table == JoinTable::Partitioned) {
     // output of the previous execution (none: single pass): above ~50 M rows the reservations of a single pass (one
     // same-address atomic per 256 rows, ~88 per microsecond) cost more than walking every partition twice
@@ -1910,7 +1903,7 @@ DevTable Plan::exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R,
     }
     prepare_partitions(a, j.B, j.P, j.part);   // the build half of this HashJoinExec: inside the operator, every execution
   }
-  return spec ? run_speculative(j, first_guess, *size_node, stage_bytes, use_band ? &band : nullptr) : run_exact(j);
+  return spec ? run_speculative(j, first_guess, *size_node) : run_exact(j);
 }
 
 // The kernel arguments that do not depend on the build side's table: both inputs' columns, the keys, the join filter, the fused
@@ -2102,8 +2095,8 @@ void Plan::run_join_kernel(LdsJoin& j, u64 stage_bytes, u64 out_bytes_per_row) {
 }
 
 // Speculative mode: the output sized from history (`size_node`: this join's, or the top node's of a fused chain) or from the
-// table form's guess; nothing is waited for.  `band`: the fused chain runs as a band join.
-DevTable Plan::run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node, u64 stage_bytes, BandArgs* band) {
+// table form's guess; nothing is waited for.  j.use_band: the fused chain runs as a band join.
+DevTable Plan::run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node) {
   LdsJoinArgs& a = j.a;
   DevTable& t = j.t;
   const u64 spec_cap = j.nd.has_last ? std::max<u64>(1024, size_node.last_rows + size_node.last_rows / (size_node.last_scaled ? 2 : 4) + 256)   // 25 % head room over the previous run (50 % over an extrapolation)
@@ -2111,8 +2104,8 @@ DevTable Plan::run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node,
   a.out_cap = spec_cap;
   for (u32 c = 0; c < a.n_out_cols; c++) { a.out[c] = scratch<u32>(spec_cap + j.tail); t.cols[c] = a.out[c]; }
   if (j.left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, j.L.cap, stream));
-  if (band) exec_band_join(j.nd, j.slice, a, *band, j.B, j.P, 4ull * (1 + j.build_payload), 4ull * j.probe_cols);
-  else if (!run_ordered_join(j, size_node, spec_cap)) run_join_kernel(j, stage_bytes, 4ull * a.n_out_cols);
+  if (j.use_band) exec_band_join(j);
+  else if (!run_ordered_join(j, size_node, spec_cap)) run_join_kernel(j, j.stage_bytes, 4ull * a.n_out_cols);
   const SpecCheck check{&size_node, (u32)(a.n_out_dev - counters), j.left_join};
   if (pending_oj.active && !pending_oj.counted && pending_oj.o.n_out_dev == a.n_out_dev) pending_oj.check = check;   // nothing writes that count unless the count pass runs after all
   else spec_checks.push_back(check);
@@ -2162,15 +2155,15 @@ bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap)
   // If that join also read the slice's rows in place last time and no key had two table rows, the count pass waits as well:
   // the in-place records do not need it (OjInPlace); whatever else takes the table runs it first (count_pending_oj)
   const int consumer = size_node.parent;
-  const bool held = consumer >= 0 && nodes[consumer].band_takes_records && !pending_oj.active && t.sorted_col >= 0;
+  const bool held = consumer >= 0 && nodes[consumer].band.takes_records && !pending_oj.active && t.sorted_col >= 0;
   // (NO_BAND_COMPACT switches it off: the in-place records are the 16-byte ones)
-  const bool in_place = held && nodes[consumer].band_in_place && nodes[consumer].band_multi_rows == 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT);
+  const bool in_place = held && nodes[consumer].band.in_place && nodes[consumer].band.multi_rows == 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT);
   if (held) o.multi_rows = reinterpret_cast<u32*>(new_counter());
   if (in_place) o.key_rec = scratch<uint4>(a.direct_n);
   timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
   if (!in_place) count_ordered_join(o);
   if (held) {
-    pending_oj.active = true; pending_oj.o = o; pending_oj.first_col = a.out[0]; pending_oj.n_build = B.cap; pending_oj.n_chain = a.n_chain;
+    pending_oj.active = true; pending_oj.o = o; pending_oj.first_col = a.out[0]; pending_oj.n_build = B.cap;
     pending_oj.counted = !in_place; pending_oj.rows_seen = size_node.last_rows;
   } else timed(KC_OJ_WRITE, 0, B.cap, nullptr, 4, a.n_out_dev, 0, 8ull * a.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
   return true;
@@ -2294,237 +2287,211 @@ void Plan::prepare_partitions(const LdsJoinArgs& a, const DevTable& B, const Dev
   } else side(P, a.probe_key, pa.ppart, pa.pstart, kr);
 }
 
-// The fused chain as a key-partitioned band join (band_join.hip).  `a` is complete (chain, output columns, out_cap,
-// counters); everything allocated here is scratch of this execution.  Bytes recorded per kernel = what that kernel has
-// to move once (compulsory): decode reads the probe columns and writes the records, the mask kernel reads the records
-// and the group entries with their stage look-ups and writes one bit per pair, the emit kernel reads the bits and
-// writes the output.
-void Plan::exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& a, BandArgs& b, const DevTable& B, const DevTable& P, u64 build_bytes_per_row,
-                          u64 probe_bytes_per_row) {
-  const u32 kn = a.direct_n;
-  const u64 np = P.cap, nb = B.cap;
-  // the probe side arrives sorted by the key (an ordered slice join below, ordered_join.hip): nothing to partition.  Keys
-  // below the table's range would map to "joins nothing" (= kn, the largest) out of order: the slice's id range rules that out.
-  bool presorted = false;
-  if (P.sorted_col >= 0 && P.cols[P.sorted_col] == a.probe_key[0] && P.key_min >= std::max<u32>(1u, a.direct_min) && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN)) presorted = true;
-  b.presorted = presorted ? 1u : 0u;
-  // the full-semantics pass is launched when the previous execution met a row that needed it (or there was none); a row that
-  // needs it after all is caught at the end of the plan like any failed speculation
-  const bool skip_slow = speculative && base.band_ran && base.band_slow_rows == 0;
-  // The probe side is the held-back output of an ordered slice join (Plan::pending_oj): if everything this join reads of it
-  // travels in that join's packed table record — the window operands, the id operand, the rows' output values — and its key is
-  // the slice's sorted column, that join writes this join's row records itself (OjBandFuse) and the table in between is never
-  // written.  Otherwise its write pass runs now.
-  OjBandFuse fuse{}; bool fused = false;
-  if (pending_oj.active) {
-    const OrderedJoinArgs& o = pending_oj.o;
-    bool ok = presorted && skip_slow && P.cols[0] == pending_oj.first_col && P.n_cols == o.n_out_cols;
-    auto slot_of = [&](const u32* col, u8& slot) {      // the word of the packed record that holds output column `col`
-      slot = 0xFFu;
-      for (u32 c = 0; c < o.n_out_cols; c++) if (o.out[c] == col && o.out_slot[c] != 0xFFu) { slot = o.out_slot[c]; return true; }
-      return false;
-    };
-    fuse.y0_slot[0] = fuse.y0_slot[1] = fuse.y1_slot[0] = fuse.y1_slot[1] = fuse.neq_slot = fuse.row_slot[0] = fuse.row_slot[1] = 0xFFu;
-    for (u32 w = 0; ok && w < b.n_win; w++) ok = slot_of(b.win[w].y0, fuse.y0_slot[w]) && slot_of(b.win[w].y1, fuse.y1_slot[w]);
-    if (ok && b.has_neq) ok = slot_of(b.neq_probe, fuse.neq_slot);
-    for (u32 u = 0; ok && u < b.n_row_cols; u++) ok = slot_of(b.row_col[u], fuse.row_slot[u]);
-    fuse.key_col = nullptr;
-    for (u32 c = 0; ok && c < o.n_out_cols; c++) if (o.out[c] == a.probe_key[0] && o.out_slot[c] == 0xFFu && o.out_ref[c].src == 1) fuse.key_col = o.out_ref[c].ptr;
-    ok = ok && fuse.key_col != nullptr;
-    if (ok) fused = true; else flush_pending_oj();
+// The fused chain as a key-partitioned band join (band_join.hip).  j.a is complete (chain, output columns, out_cap, counters), j.band holds what apply_chain
+// resolved; everything allocated here is scratch of this execution.  Bytes recorded per kernel = what that kernel has to move once (compulsory).  The route flags
+// (BandJoin says what each means) are all set here, before the first launch; in_place alone has to wait for band_slice_tables, which finds or builds the layout it needs.
+void Plan::exec_band_join(LdsJoin& j) {
+  BandJoin bj(j);
+  BandHistory& hist = j.nd.band; const DevTable& P = j.P; const bool ordered = !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN);
+  bj.presorted = ordered && P.sorted_col >= 0 && P.cols[P.sorted_col] == j.a.probe_key[0] && P.key_min >= std::max<u32>(1u, j.a.direct_min);
+  bj.skip_slow = speculative && hist.ran && hist.slow_rows == 0;   // a row that needs the pass after all is caught at the end of the plan like any failed speculation
+  const u64 runs_seen = hist.run_stats & 0xFFFFFFFFull, run_rows = hist.run_stats >> 32;
+  bj.counting = !bj.presorted && ordered && (bj.np <= (1ull << 21) || (runs_seen && run_rows >= 4 * runs_seen));
+  bj.cache_entries = j.B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_TABLE_CACHE);
+  // the packed pair test reads 8 bytes of window, the id operand and at most one output value per row: 16 bytes per row instead of 32 whenever no full-semantics pass will want the flags
+  j.band.compact = (j.band.pack16 && j.band.n_row_cols <= 1 && bj.skip_slow && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT)) ? 1u : 0u;
+  bj.fused = take_pending_oj(bj);     // not fused: that join's write pass has run by now
+  hist.takes_records = bj.presorted && bj.skip_slow && ordered;
+  band_probe_side(bj);
+  band_slice_tables(bj);
+  hist.in_place = bj.lay.boff != nullptr;   // the layout exists: next time the ordered join below may leave its matches uncounted
+  // In place: the ordered join below skipped its count pass, and the slice it streamed IS this join's build side.  Anything else counts the matches now and compacts them (the write-band pass).
+  bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place;
+  if (bj.fused && !bj.in_place) count_pending_oj();
+  band_row_records(bj);
+  band_blocks_and_emit(bj);
+}
+
+// The probe side is the held-back output of an ordered slice join (Plan::pending_oj).  true: everything this join reads of it travels in that join's packed
+// table record and its key is the slice's sorted column, so that join writes this join's row records itself (bj.fuse).  Otherwise its write pass runs now.
+bool Plan::take_pending_oj(BandJoin& bj) {
+  if (!pending_oj.active) return false;
+  const LdsJoinArgs& a = bj.j.a; const DevTable& B = bj.j.B; const DevTable& P = bj.j.P; BandArgs& b = bj.j.band; OjBandFuse& fuse = bj.fuse; const OrderedJoinArgs& o = pending_oj.o;
+  bool ok = bj.presorted && bj.skip_slow && P.cols[0] == pending_oj.first_col && P.n_cols == o.n_out_cols;
+  auto slot_of = [&](const u32* col, u8& slot) {      // the word of the packed record that holds output column `col`
+    slot = 0xFFu;
+    for (u32 c = 0; c < o.n_out_cols; c++) if (o.out[c] == col && o.out_slot[c] != 0xFFu) { slot = o.out_slot[c]; return true; }
+    return false;
+  };
+  fuse.y0_slot[0] = fuse.y0_slot[1] = fuse.y1_slot[0] = fuse.y1_slot[1] = fuse.neq_slot = fuse.row_slot[0] = fuse.row_slot[1] = 0xFFu;
+  for (u32 w = 0; ok && w < b.n_win; w++) ok = slot_of(b.win[w].y0, fuse.y0_slot[w]) && slot_of(b.win[w].y1, fuse.y1_slot[w]);
+  if (ok && b.has_neq) ok = slot_of(b.neq_probe, fuse.neq_slot);
+  for (u32 u = 0; ok && u < b.n_row_cols; u++) ok = slot_of(b.row_col[u], fuse.row_slot[u]);
+  for (u32 c = 0; ok && c < o.n_out_cols; c++) if (o.out[c] == a.probe_key[0] && o.out_slot[c] == 0xFFu && o.out_ref[c].src == 1) fuse.key_col = o.out_ref[c].ptr;
+  if (!ok || fuse.key_col == nullptr) { flush_pending_oj(); return false; }
+  fuse.compact = b.compact;   // (16 bytes per match instead of 32)
+  // self_index, `entry id != row id` by entry index: the band join's groups are the rows of the very slice the ordered join streamed (same sorted column, same rows, identity CSR),
+  // the entry's id is that join's build key, the row's id its probe key — equal keys are what made the match, and a store slice holds every (key, sorted column) pair once:
+  // the only entry of the group whose id equals the row's is the slice row the match came from
+  if (fuse.compact && b.has_neq && !b.neq_is_eq && a.csr_rows == nullptr && a.build_key[0] == fuse.key_col && B.cap == pending_oj.n_build &&
+      b.neq_build == o.build_key && B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT))
+    for (u32 c = 0; c < o.n_out_cols; c++)
+      if (o.out[c] == b.neq_probe && o.out_slot[c] != 0xFFu && o.out_ref[c].src == 0 && o.out_ref[c].ptr == o.probe_key) fuse.self_index = 1;
+  b.neq_self = fuse.self_index;
+  return true;
+}
+
+// The kernel arguments that repeat the LDS join's (table, probe side, output), and what partitions the probe rows by the key: the counting
+// sort's key histogram or the radix sort's pairs and temp, the unsorted rows' records, the two counts the row passes leave behind.
+void Plan::band_probe_side(BandJoin& bj) {
+  const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band;
+  if (bj.counting) {
+    b.key_hist = scratch<u32>((u64)bj.kn + 2); b.key_cursor = scratch<u32>((u64)bj.kn + 2);
+    RDFGPU_HIP(hipMemsetAsync(b.key_hist, 0, ((size_t)bj.kn + 2) * sizeof(u32), stream));
   }
-  base.band_takes_records = presorted && skip_slow && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN);
-  // small probe side, not sorted: counting sort on the key (band_scatter_kernel) instead of rocPRIM's radix sort; a larger one
-  // when the previous execution found it piecewise sorted (>= 4 rows per run of equal neighbouring keys: the N sorted runs
-  // a repartition delivers) — one atomic per run, rows of a run scattered together
-  const u64 runs_seen = base.band_run_stats & 0xFFFFFFFFull, run_rows = base.band_run_stats >> 32;
-  const bool counting = !presorted && !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN) && (np <= (1ull << 21) || (runs_seen && run_rows >= 4 * runs_seen));
-  if (counting) {
-    b.key_hist = scratch<u32>((u64)kn + 2); b.key_cursor = scratch<u32>((u64)kn + 2);
-    RDFGPU_HIP(hipMemsetAsync(b.key_hist, 0, ((size_t)kn + 2) * sizeof(u32), stream));
-  }
-  b.csr_off = a.csr_off; b.csr_rows = a.csr_rows; b.kmin = a.direct_min; b.kn = kn;
-  b.probe_key = a.probe_key[0]; b.n_probe_dev = P.n_dev; b.n_probe_cap = np;
-  b.tt = a.tt;
-  b.n_out_cols = a.n_out_cols; b.out_cap = a.out_cap; b.n_out_dev = a.n_out_dev; b.overflow = a.overflow;
-  for (u32 c = 0; c < a.n_out_cols; c++) b.out[c] = a.out[c];
-  u32 bits = 1;
-  while ((1ull << bits) <= kn) bits++;            // keys 0 .. kn (kn = joins nothing)
-  u32* skey = scratch<u32>(np); u32* perm = scratch<u32>(np);
-  if (presorted) { b.skey_in = skey; b.sval_in = perm; b.rec = nullptr; }
-  // the packed pair test reads 8 bytes of window, the id operand and at most one output value per row: 16 bytes per row instead of 32
-  // whenever no full-semantics pass will want the flags (decode pass and ordered-join records alike)
-  b.compact = (b.pack16 && b.n_row_cols <= 1 && skip_slow && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT)) ? 1u : 0u;
-  if (!presorted) { b.skey_in = scratch<u32>(np); b.sval_in = scratch<u32>(np); b.rec = scratch<uint4>((b.compact ? 1 : 2) * np); }
-  b.skey = skey; b.perm = perm;
-  if (fused) {
-    const OrderedJoinArgs& o = pending_oj.o;
-    fuse.compact = b.compact;   // (16 bytes per match instead of 32)
-    // `entry id != row id` by entry index: the band join's groups are the rows of the very slice the ordered join streamed (same sorted column, same
-    // rows, identity CSR), the entry's id is that join's build key, the row's id its probe key — equal keys are what made the match, and a store slice
-    // holds every (key, sorted column) pair once: the only entry of the group whose id equals the row's is the slice row the match came from
-    fuse.self_index = 0;
-    if (fuse.compact && b.has_neq && !b.neq_is_eq && b.csr_rows == nullptr && a.build_key[0] == fuse.key_col && B.cap == pending_oj.n_build &&
-        b.neq_build == o.build_key && B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT))
-      for (u32 c = 0; c < o.n_out_cols; c++)
-        if (o.out[c] == b.neq_probe && o.out_slot[c] != 0xFFu && o.out_ref[c].src == 0 && o.out_ref[c].ptr == o.probe_key) fuse.self_index = 1;
-    b.neq_self = fuse.self_index;
-  }
-  // In place (OjInPlace): the ordered join below skipped its count pass, and the slice it streamed IS this join's build side — the probe rows of key k
-  // are then the group's own slice rows csr_off[k] .. csr_off[k + 1), each with the record of its one table row, and the blocks are the slice's
-  // (cached below with the entries).  Anything else counts the matches now and compacts them (the write-band pass).
-  bool in_place = fused && !pending_oj.counted && fuse.self_index;
-  b.slow_rows = reinterpret_cast<u32*>(new_counter());
-  b.run_stats = reinterpret_cast<unsigned long long*>(new_counter());
-  const size_t stb = sort_u32_temp_bytes(np, bits);
-  void* stemp = scratch<unsigned char>(stb);
-  u64 entry_bytes = build_bytes_per_row + (a.csr_rows ? 4 : 0) + (a.has_post ? 4 : 0);
-  for (u32 t = 0; t < a.n_chain; t++) entry_bytes += 4 + (a.chain[t].val ? 8 : 0);
-  // The decoded entries depend on the store's slices and the chain's constants only: kept with the slice's CSR table
-  // (per store version, like every other join table), so a steady-state step does not decode 5.4 M build rows again.
-  std::string ekey;
-  {
-    auto put = [&](const void* p, size_t n) { ekey.append(reinterpret_cast<const char*>(p), n); };
-    put(&b.csr_off, sizeof b.csr_off); put(&b.csr_rows, sizeof b.csr_rows); put(&b.kmin, 4); put(&b.kn, 4); put(&b.n_stages, 4); put(&b.n_win, 4);
-    for (u32 t = 0; t < b.n_stages; t++) put(&b.stage[t], sizeof(BandStage));
-    for (u32 w = 0; w < b.n_win; w++) { put(&b.win[w].key_col, sizeof(void*)); put(&b.win[w].val, sizeof(void*)); put(&b.win[w].vkmin, 4); put(&b.win[w].vkn, 4); put(&b.win[w].vbase, 8); }
-    put(&b.has_post, 4); put(&b.post_lit, 4); put(&b.post_is_eq, 4); put(&b.post_col, sizeof(void*)); put(&b.has_neq, 4); put(&b.neq_build, sizeof(void*));
-    put(&b.n_entry_cols, 4);
-    for (u32 u = 0; u < b.n_entry_cols; u++) { put(&b.entry_col[u].ptr, sizeof(void*)); put(&b.entry_col[u].src, 4); }
-    put(&nb, 8);
-  }
-  bool have_entries = false;
-  const bool cache_entries = B.stable_id != 0 && !opt.on(RDFGPU_OPT_NO_TABLE_CACHE);
-  std::unique_lock<std::mutex> entries_lock(store->slice_build_mu, std::defer_lock);
-  if (cache_entries) {
-    entries_lock.lock();
-    for (const auto& e : build_table->band_entries) if (e.key == ekey) { b.et = e.et; for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = e.eo[u]; have_entries = true; }
-  }
-  b.n_entries = nb;
-  if (!have_entries) {
+  b.presorted = bj.presorted ? 1u : 0u; b.tt = a.tt;
+  b.csr_off = a.csr_off; b.csr_rows = a.csr_rows; b.kmin = a.direct_min; b.kn = bj.kn; b.n_entries = bj.nb;
+  b.probe_key = a.probe_key[0]; b.n_probe_dev = bj.j.P.n_dev; b.n_probe_cap = bj.np;
+  b.n_out_cols = a.n_out_cols; b.out_cap = a.out_cap; b.n_out_dev = a.n_out_dev; b.overflow = a.overflow; for (u32 c = 0; c < a.n_out_cols; c++) b.out[c] = a.out[c];
+  b.skey = bj.skey = scratch<u32>(bj.np); b.perm = bj.perm = scratch<u32>(bj.np);
+  if (bj.presorted) { b.skey_in = bj.skey; b.sval_in = bj.perm; b.rec = nullptr; }
+  else { b.skey_in = scratch<u32>(bj.np); b.sval_in = scratch<u32>(bj.np); b.rec = scratch<uint4>((b.compact ? 1 : 2) * bj.np); }
+  b.slow_rows = reinterpret_cast<u32*>(new_counter()); b.run_stats = reinterpret_cast<unsigned long long*>(new_counter());
+  while ((1ull << bj.sort_bits) <= bj.kn) bj.sort_bits++;            // keys 0 .. kn (kn = joins nothing)
+  bj.sort_temp_bytes = sort_u32_temp_bytes(bj.np, bj.sort_bits); bj.sort_temp = scratch<unsigned char>(bj.sort_temp_bytes);
+}
+
+// The two tables a band join keeps on its build slice's SliceTable (per store version, like every other join table): found or built under
+// ONE hold of the lock, taken only when they are kept at all; each is published only once the stream has been waited for, and the layout is
+// copied before the lock goes.  bj.ekey: the bytes the decoded entries depend on, the store's slices and the chain's constants.
+void Plan::band_slice_tables(BandJoin& bj) {
+  const BandArgs& b = bj.j.band;
+  auto put = [&](const void* p, size_t n) { bj.ekey.append(reinterpret_cast<const char*>(p), n); };
+  put(&b.csr_off, sizeof b.csr_off); put(&b.csr_rows, sizeof b.csr_rows); put(&b.kmin, 4); put(&b.kn, 4); put(&b.n_stages, 4); put(&b.n_win, 4);
+  for (u32 t = 0; t < b.n_stages; t++) put(&b.stage[t], sizeof(BandStage));
+  for (u32 w = 0; w < b.n_win; w++) { put(&b.win[w].key_col, sizeof(void*)); put(&b.win[w].val, sizeof(void*)); put(&b.win[w].vkmin, 4); put(&b.win[w].vkn, 4); put(&b.win[w].vbase, 8); }
+  put(&b.has_post, 4); put(&b.post_lit, 4); put(&b.post_is_eq, 4); put(&b.post_col, sizeof(void*)); put(&b.has_neq, 4); put(&b.neq_build, sizeof(void*));
+  put(&b.n_entry_cols, 4); for (u32 u = 0; u < b.n_entry_cols; u++) { put(&b.entry_col[u].ptr, sizeof(void*)); put(&b.entry_col[u].src, 4); }
+  put(&bj.nb, 8);
+  std::unique_lock<std::mutex> building(store->slice_build_mu, std::defer_lock);
+  if (bj.cache_entries) building.lock();
+  band_entries(bj);
+  if (const SliceTable::BandEntries* layout = band_layout(bj)) bj.lay = *layout;
+}
+
+// The build side's decoded entries (the pair test's operands, the entries' output values), found on the slice's table (keys are unique there: an entry is
+// pushed only after a failed look-up under the same lock) or built: a steady-state step does not decode 5.4 M build rows again.  The caller holds the lock when bj.cache_entries.
+void Plan::band_entries(BandJoin& bj) {
+  const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band; SliceTable* tab = bj.j.slice;
+  if (bj.cache_entries) for (const auto& e : tab->band_entries) if (e.key == bj.ekey) { b.et = e.et; for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = e.eo[u]; return; }
   // stages all keyed by one build column: their look-ups once per distinct key value instead of once per entry
-  {
-    const u32* kc = a.n_chain ? b.stage[0].key_col : nullptr;
-    bool same = kc != nullptr;
-    u64 lo = ~0ull, hi = 0;
-    for (u32 t = 0; t < b.n_stages; t++) { same = same && b.stage[t].key_col == kc; lo = std::min<u64>(lo, b.stage[t].kmin); hi = std::max<u64>(hi, (u64)b.stage[t].kmin + b.stage[t].kn); }
-    for (u32 w = 0; w < b.n_win; w++) same = same && b.win[w].key_col == kc;
-    if (same && hi > lo && hi - lo <= (64ull << 20) && hi - lo <= 8 * nb + 1024) {
-      b.pt_min = (u32)lo; b.pt_n = (u32)(hi - lo); b.pt_key_col = kc;
-      b.pt = scratch<uint4>(2ull * b.pt_n);
-      timed(KC_BAND_PT, 0, b.pt_n, nullptr, 4ull * b.n_stages + 8ull * b.n_win + 4ull * b.n_entry_cols + 32, nullptr, 0, 0, [&] { launch_band_pt(b, stream); });
-    }
+  const u32* kc = a.n_chain ? b.stage[0].key_col : nullptr;
+  bool same = kc != nullptr; u64 lo = ~0ull, hi = 0;
+  for (u32 t = 0; t < b.n_stages; t++) { same = same && b.stage[t].key_col == kc; lo = std::min<u64>(lo, b.stage[t].kmin); hi = std::max<u64>(hi, (u64)b.stage[t].kmin + b.stage[t].kn); }
+  for (u32 w = 0; w < b.n_win; w++) same = same && b.win[w].key_col == kc;
+  if (same && hi > lo && hi - lo <= (64ull << 20) && hi - lo <= 8 * bj.nb + 1024) {
+    b.pt_min = (u32)lo; b.pt_n = (u32)(hi - lo); b.pt_key_col = kc; b.pt = scratch<uint4>(2ull * b.pt_n);
+    timed(KC_BAND_PT, 0, b.pt_n, nullptr, 4ull * b.n_stages + 8ull * b.n_win + 4ull * b.n_entry_cols + 32, nullptr, 0, 0, [&] { launch_band_pt(b, stream); });
   }
   // the build side, once: per row its columns + stage look-ups read, 16 B of operands + the output values written
-  const bool own_entries = cache_entries && build_table->band_entries.size() < 8;
-  if (own_entries) {
-    b.et = store->table_alloc<uint4>(nb + 64);
-    for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = store->table_alloc<u32>(nb);
-    metrics.tables_built++;
-  } else {
-    b.et = scratch<uint4>(nb + 64);                  // padded: the pair test reads whole groups of 8 entries
-    for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = scratch<u32>(nb);
+  u64 entry_bytes = 4ull * (1 + bj.j.build_payload) + (a.csr_rows ? 4 : 0) + (a.has_post ? 4 : 0);
+  for (u32 t = 0; t < a.n_chain; t++) entry_bytes += 4 + (a.chain[t].val ? 8 : 0);
+  const bool own_entries = bj.cache_entries && tab->band_entries.size() < 8;   // kept on the slice, else scratch of this execution
+  b.et = own_entries ? store->table_alloc<uint4>(bj.nb + 64) : scratch<uint4>(bj.nb + 64);   // padded: the pair test reads whole groups of 8 entries
+  for (u32 u = 0; u < b.n_entry_cols; u++) b.eo[u] = own_entries ? store->table_alloc<u32>(bj.nb) : scratch<u32>(bj.nb);
+  timed(KC_BAND_ENTRIES, 0, bj.nb, bj.j.B.n_dev, entry_bytes + 4ull * b.n_entry_cols + 16 + 4ull * b.n_entry_cols, nullptr, 0, 0, [&] { launch_band_entries(b, stream); });
+  if (own_entries) {   // publish only when complete
+    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++; metrics.tables_built++;
+    SliceTable::BandEntries e{bj.ekey, b.et, {nullptr, nullptr, nullptr, nullptr}};
+    for (u32 u = 0; u < b.n_entry_cols; u++) e.eo[u] = b.eo[u];
+    tab->band_entries.push_back(e);
   }
-  timed(KC_BAND_ENTRIES, 0, nb, B.n_dev, entry_bytes + 4ull * b.n_entry_cols + 16 + 4ull * b.n_entry_cols, nullptr, 0, 0, [&] { launch_band_entries(b, stream); });
-    if (cache_entries && build_table->band_entries.size() < 8) {   // publish only when complete
-      RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-      SliceTable::BandEntries e{ekey, b.et, {nullptr, nullptr, nullptr, nullptr}};
-      for (u32 u = 0; u < b.n_entry_cols; u++) e.eo[u] = b.eo[u];
-      build_table->band_entries.push_back(e);
-    }
-  }
-  // In place: the band join's rows of key k are the CSR group k itself (poff = csr_off), so its blocks depend on the slice alone — laid out once per
-  // store version beside the entries (same key, same lock), their exact number read back, published when complete; by the first execution
-  // that could take the route, so that the first one that does finds them.  The route pays for every slice row, matched or not, and for
-  // ceil(E/64)² blocks per key: it is taken when the ordered join's last measured rows cover at least half of the slice, and when the block
-  // count, bounded here in 64 bits (sum over keys of ceil(E/64)² <= cmax · (rows / 64 + keys)), stays below 2^31 — the device counts in 32
-  const u64 cmax = (build_table->csr_max_group + 63) / 64;
-  const bool layout_fits = cmax * (nb / 64 + kn) < (1ull << 31);
+}
+
+// In place: the band join's rows of key k are the CSR group k itself (poff = csr_off), so its blocks depend on the slice alone — laid out once per store version beside the
+// entries (same key, same lock), their exact number read back, published when complete; by the first execution that could take the route, so that the first one that does finds
+// them.  The route pays for every slice row, matched or not, and for ceil(E/64)² blocks per key: it is taken when the ordered join's last measured rows cover at least half of the
+// slice, and when the block count, bounded here in 64 bits (sum over keys of ceil(E/64)² <= cmax · (rows / 64 + keys)), stays below 2^31 — the device counts in 32.
+// Null: the route is not available (entries that could not be cached among the reasons: the counted route); a layout returned has its boff.
+SliceTable::BandEntries* Plan::band_layout(BandJoin& bj) {
+  const LdsJoinArgs& a = bj.j.a; const u32 kn = bj.kn;
   SliceTable::BandEntries* layout = nullptr;
-  if (fused && fuse.self_index && cache_entries && layout_fits && pending_oj.rows_seen * 2 >= nb)
-    for (auto& e : build_table->band_entries) if (e.key == ekey) layout = &e;
-  in_place = in_place && layout != nullptr;   // (entries that could not be cached: the counted route)
+  if (bj.fused && bj.fuse.self_index && bj.cache_entries && bj.cmax * (bj.nb / 64 + kn) < (1ull << 31) && pending_oj.rows_seen * 2 >= bj.nb)
+    for (auto& e : bj.j.slice->band_entries) if (e.key == bj.ekey) layout = &e;
   if (layout && !layout->boff) {
     u32* boff = store->table_alloc<u32>((u64)kn + 1);
-    const size_t tb = band_blocks_scan_temp_bytes(kn);
-    void* temp = scratch<unsigned char>(tb);
+    const size_t tb = band_blocks_scan_temp_bytes(kn); void* temp = scratch<unsigned char>(tb);
     timed(scan_class((u64)kn + 1), 12ull * kn, (u64)kn + 1, nullptr, 4, nullptr, 0, 0, [&] { band_blocks_scan(a.csr_off, a.csr_off, kn, boff, temp, tb, stream); });
     const u32 n = read_back<u32>(boff + kn);
-    BandArgs d = b;
-    d.poff = const_cast<u32*>(a.csr_off); d.boff = boff; d.bdesc = store->table_alloc<uint4>(n); d.max_blocks = n; d.n_blocks_out = nullptr;
+    BandArgs d = bj.j.band; d.poff = const_cast<u32*>(a.csr_off); d.boff = boff; d.bdesc = store->table_alloc<uint4>(n); d.max_blocks = n; d.n_blocks_out = nullptr;
     timed(KC_BAND_DESC, 12ull * kn, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_desc(d, stream); });
     RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
-    layout->boff = boff; layout->bdesc = d.bdesc; layout->n_blocks = n;
-    metrics.tables_built++;
+    layout->boff = boff; layout->bdesc = d.bdesc; layout->n_blocks = n; metrics.tables_built++;
   }
-  const SliceTable::BandEntries lay = layout ? *layout : SliceTable::BandEntries{};   // (a copy: the list may grow once the lock is released)
-  if (entries_lock.owns_lock()) entries_lock.unlock();
-  base.band_in_place = layout != nullptr;   // (the route is available: next time the ordered join below may leave its matches uncounted)
-  if (fused && !in_place) count_pending_oj();
-  const u64 nrows = in_place ? nb : np;            // probe rows of the block kernels: the slice's own (in place) or the matches
-  b.rec_s = scratch<uint4>(nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(nrows);
-  // per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
+  return layout;
+}
+
+// The probe rows' records in key order, with the rows per key (poff) and the blocks' counts zeroed: written by the ordered slice join below (fused; in place: one per slice row), else decoded from the probe columns.
+void Plan::band_row_records(BandJoin& bj) {
+  const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band; OjBandFuse& fuse = bj.fuse;
+  const u32 kn = bj.kn; const u64 np = bj.np, nb = bj.nb; const bool in_place = bj.in_place;
+  bj.nrows = in_place ? nb : np; b.rec_s = scratch<uint4>(bj.nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(bj.nrows);
   b.poff = in_place ? const_cast<u32*>(a.csr_off) : scratch<u32>((u64)kn + 2);
   // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
-  const u64 max_blocks = in_place ? lay.n_blocks : cmax * (np / 64 + 1) + nb / 64 + kn + 1;
-  if (max_blocks >= (1ull << 31)) fail(RDFGPU_ERR_UNSUPPORTED, "band join of %llu blocks", (unsigned long long)max_blocks);
-  b.max_blocks = (u32)max_blocks;
-  b.bcount = scratch<u32>(max_blocks + 1); b.bofs = scratch<u32>(max_blocks + 1);   // (bcount is zeroed by the decode pass: a memset is two more launches, ~10 us of launch gap each on this part)
-  if (fused) {
-    const OrderedJoinArgs& o = pending_oj.o;
-    pending_oj.active = false;
-    oj_chain_counters.push_back({&base, (u32)(reinterpret_cast<u64*>(o.multi_rows) - counters), in_place});
-    fuse.key_rec = in_place ? o.key_rec : nullptr;
-    fuse.brec = in_place ? nullptr : scratch<uint4>((fuse.compact ? 1 : 2) * o.n_probe_cap);
-    fuse.rec_s = b.rec_s; fuse.aux_s = b.aux_s; fuse.poff = b.poff; fuse.bcount = b.bcount; fuse.max_blocks = b.max_blocks;
-    fuse.kmin = b.kmin; fuse.kn = b.kn;
-    // per table row: its packed record read + two typed-value gathers + 32 B written; per slice row the count pass's 5 bytes + its
-    // key; per match a 32-byte record gathered and stored (in place: per slice row its key read, its key's 16-byte record gathered and stored)
-    const u64 rec_bytes = fuse.compact ? 16 : 32;
-    timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
-    if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
-    else timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });
-  } else
-  timed(KC_BAND_DECODE, 0, np, P.n_dev, 4 + 4ull * (b.n_win + b.has_neq) + 9ull * b.n_win + 24 + 8, nullptr, 0, 0, [&] { launch_band_decode(b, stream); });
-  // the partition pass: in the time, not in the algorithmic bytes
-  if (!presorted && !counting) timed(KC_RADIX_SORT, 0, np, nullptr, 0, nullptr, 0, 0, [&] { sort_pairs_u32_u32(b.skey_in, skey, b.sval_in, perm, np, bits, stemp, stb, stream); });
-  b.boff = in_place ? lay.boff : scratch<u32>((u64)kn + 1);
-  // the block kernels launch one wave per block: sized from the previous execution's count (+ 25 %), not from the upper bound (in place: exactly)
-  b.n_blocks_out = new_counter();
-  band_block_counters.push_back({&base, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters), skip_slow,
-                                 in_place ? max_blocks : 0});
-  const u64 hist = base.band_blocks;
-  b.launch_blocks = (u32)(in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
-  b.bdesc = in_place ? lay.bdesc : scratch<uint4>(max_blocks);
-  b.masks = scratch<u64>(max_blocks * 64);
-  const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn));
-  void* temp = scratch<unsigned char>(tb);
-  if (counting) {   // poff = exclusive scan of the rows per key (entry kn = the rows that join something); then the scatter
+  bj.max_blocks = in_place ? bj.lay.n_blocks : bj.cmax * (np / 64 + 1) + nb / 64 + kn + 1;
+  if (bj.max_blocks >= (1ull << 31)) fail(RDFGPU_ERR_UNSUPPORTED, "band join of %llu blocks", (unsigned long long)bj.max_blocks);
+  b.max_blocks = (u32)bj.max_blocks; b.bcount = scratch<u32>(bj.max_blocks + 1); b.bofs = scratch<u32>(bj.max_blocks + 1);   // (bcount is zeroed by the decode pass: a memset is two more launches, ~10 us of launch gap each on this part)
+  // decode, per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
+  if (!bj.fused) return timed(KC_BAND_DECODE, 0, np, bj.j.P.n_dev, 4 + 4ull * (b.n_win + b.has_neq) + 9ull * b.n_win + 24 + 8, nullptr, 0, 0, [&] { launch_band_decode(b, stream); });
+  const OrderedJoinArgs& o = pending_oj.o; pending_oj.active = false;
+  fuse.key_rec = in_place ? o.key_rec : nullptr;
+  fuse.brec = in_place ? nullptr : scratch<uint4>((fuse.compact ? 1 : 2) * o.n_probe_cap);
+  fuse.rec_s = b.rec_s; fuse.aux_s = b.aux_s; fuse.poff = b.poff; fuse.bcount = b.bcount; fuse.max_blocks = b.max_blocks; fuse.kmin = b.kmin; fuse.kn = b.kn;
+  // per table row: its packed record read + two typed-value gathers + 32 B written; per slice row the count pass's 5 bytes + its key; per match a 32-byte record gathered and stored (in place: per slice row its key read, its key's 16-byte record gathered and stored)
+  const u64 rec_bytes = fuse.compact ? 16 : 32;
+  timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
+  if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
+  else timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });
+}
+
+// The blocks (64 entries x 64 rows) and what runs over them.  First the radix sort of a probe side that came neither sorted nor small (in the time, not in the algorithmic bytes:
+// SURVEY 8d), the blocks' buffers, the launch of the block kernels sized from the previous execution's count (+ 25 %), not from the upper bound (in place: exactly), where this execution
+// leaves its own counts, the rows per key and the blocks of every key laid out; then the pair test, the full-semantics pass where rows may need it, the scan of the blocks' counts, the output rows.
+void Plan::band_blocks_and_emit(BandJoin& bj) {
+  const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band;
+  const u32 kn = bj.kn; const u64 np = bj.np, nb = bj.nb, max_blocks = bj.max_blocks;
+  if (!bj.presorted && !bj.counting) timed(KC_RADIX_SORT, 0, np, nullptr, 0, nullptr, 0, 0, [&] { sort_pairs_u32_u32(b.skey_in, bj.skey, b.sval_in, bj.perm, np, bj.sort_bits, bj.sort_temp, bj.sort_temp_bytes, stream); });
+  b.boff = bj.in_place ? bj.lay.boff : scratch<u32>((u64)kn + 1); b.n_blocks_out = new_counter();
+  // the multi-row count is the ordered join's (pending_oj.o stays as it was when that join was taken over); a band join that was not fused has none
+  band_feedback.push_back({&bj.j.nd, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters),
+                           bj.fused ? (int)(reinterpret_cast<u64*>(pending_oj.o.multi_rows) - counters) : -1, bj.skip_slow, bj.in_place, bj.in_place ? max_blocks : 0});
+  const u64 hist = bj.j.nd.band.blocks; b.launch_blocks = (u32)(bj.in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
+  b.bdesc = bj.in_place ? bj.lay.bdesc : scratch<uint4>(max_blocks); b.masks = scratch<u64>(max_blocks * 64);
+  const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn)); void* temp = scratch<unsigned char>(tb);
+  if (bj.counting) {   // poff = exclusive scan of the rows per key (entry kn = the rows that join something); then the scatter
     timed(scan_class((u64)kn + 1), 0, (u64)kn + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.key_hist, b.poff, (u64)kn + 1, temp, tb, stream); });
     RDFGPU_HIP(hipMemcpyAsync(b.key_cursor, b.poff, ((size_t)kn + 1) * sizeof(u32), hipMemcpyDeviceToDevice, stream));
-    timed(KC_BAND_ROWS, 0, np, P.n_dev, 8 + 32 + 32, nullptr, 0, 0, [&] { launch_band_scatter(b, stream); });
-  } else if (!presorted) timed(KC_BAND_BOUNDS, 0, np, nullptr, 4, nullptr, 0, 0, [&] { launch_band_bounds(skey, np, kn, b.poff, stream); });   // (presorted: the decode pass wrote poff)
-  if (!in_place) {
+    timed(KC_BAND_ROWS, 0, np, bj.j.P.n_dev, 8 + 32 + 32, nullptr, 0, 0, [&] { launch_band_scatter(b, stream); });
+  } else if (!bj.presorted) timed(KC_BAND_BOUNDS, 0, np, nullptr, 4, nullptr, 0, 0, [&] { launch_band_bounds(bj.skey, np, kn, b.poff, stream); });   // (presorted: the decode pass wrote poff)
+  if (!bj.in_place) {
     timed(scan_class((u64)kn + 1), 12ull * kn, (u64)kn + 1, nullptr, 4, nullptr, 0, 0, [&] { band_blocks_scan(a.csr_off, b.poff, kn, b.boff, temp, tb, stream); });   // (blocks per key: the scan's input iterator)
     timed(KC_BAND_DESC, 12ull * kn, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_desc(b, stream); });
   }
-  if (!presorted && !counting) timed(KC_BAND_ROWS, 0, np, P.n_dev, 4 + 32 + 32, nullptr, 0, 0, [&] { launch_band_rows(b, stream); });
-  // per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count
-  // is not known on the host
-  const u64* const nrows_dev = in_place ? nullptr : P.n_dev;
-  timed(KC_BAND_MASK, 16ull * nb, nrows, nrows_dev, b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
-  if (!skip_slow) {
+  if (!bj.presorted && !bj.counting) timed(KC_BAND_ROWS, 0, np, bj.j.P.n_dev, 4 + 32 + 32, nullptr, 0, 0, [&] { launch_band_rows(b, stream); });
+  // pair test, per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count is not known on the host
+  const u64* const nrows_dev = bj.in_place ? nullptr : bj.j.P.n_dev;
+  timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  if (!bj.skip_slow) {
     // the full-semantics pass needs the chain's literals and columns: the fused join kernel's argument block, by pointer
     static_assert(sizeof(LdsJoinArgs) <= ExecContext::kArgBytes, "argument staging slot too small");
     const u32 slot = arg_slots_used++;
     LdsJoinArgs* a_host = reinterpret_cast<LdsJoinArgs*>(ctx->args_host + (size_t)slot * ExecContext::kArgBytes);
     LdsJoinArgs* a_dev = reinterpret_cast<LdsJoinArgs*>(ctx->args_dev + (size_t)slot * ExecContext::kArgBytes);
-    *a_host = a;
-    RDFGPU_HIP(hipMemcpyAsync(a_dev, a_host, sizeof(LdsJoinArgs), hipMemcpyHostToDevice, stream));
+    *a_host = a; RDFGPU_HIP(hipMemcpyAsync(a_dev, a_host, sizeof(LdsJoinArgs), hipMemcpyHostToDevice, stream));
     timed(KC_BAND_SLOW, 0, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_slow(a_dev, b, stream); });
   }
   timed(scan_class(max_blocks + 1), 0, max_blocks + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.bcount, b.bofs, max_blocks + 1, temp, tb, stream); });
-  timed(KC_BAND_EMIT, 4ull * b.n_entry_cols * nb, nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
+  timed(KC_BAND_EMIT, 4ull * b.n_entry_cols * nb, bj.nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
 }
 
 void Plan::ensure_host_copy() {

@@ -26,6 +26,16 @@ struct SourceInfo {               // one DataSourceExec
   bool dynamic_dirty = false;     // the effective instructions have to be derived again before the next execute
 };
 
+// What the band join based on a node keeps from one execution to the next: measurements, written by Plan::record_band_history, and two route flags.
+struct BandHistory {
+  bool ran = false; u64 slow_rows = 0;   // record_band_history: it ran; probe rows that needed the full typed-value semantics.  exec_band_join: ran and 0 = the full-semantics pass is not launched
+  u64 blocks = 0;               // record_band_history: its blocks (counted on the device; in place: known on the host).  exec_band_join sizes the block kernels' launch from it
+  u64 run_stats = 0;            // record_band_history: sampled rows << 32 | runs of equal neighbouring probe keys.  exec_band_join: a piecewise sorted probe side takes the counting partition
+  u64 multi_rows = 0;           // record_band_history: table rows the ordered slice join that wrote this join's records met behind another of the same key.  run_ordered_join: 0 = it may skip its count pass
+  bool takes_records = false;   // exec_band_join: the probe side came presorted from an ordered slice join and no row needed the slow pass.  run_ordered_join / keeps_pending_oj: that join holds its write pass back
+  bool in_place = false;        // exec_band_join: the slice's block layout is cached, the in-place route is available.  run_ordered_join reads it with multi_rows
+};
+
 struct NodeInfo {
   rdfgpu_plan_node d;
   u32 width = 0;                  // output columns
@@ -37,16 +47,11 @@ struct NodeInfo {
   int source = -1;                // index into Plan::sources
   u32 refs = 0;                   // how many operators consume this node
   u64 last_rows = 0; bool has_last = false;   // output cardinality of the previous execution (speculative sizing)
-  bool last_scaled = false;
+  bool last_scaled = false;                    // .. extrapolated from a priming run over a prefix of the bound tables (Plan::prime), not measured
   bool transient_direct_failed = false;        // a build side that is not cached turned out not to be unique and dense: do not try the direct-address form again
-  u64 band_blocks = 0;                         // blocks of the band join based on this node in its previous execution (launch sizing)
-  u64 band_run_stats = 0;                      // sampled rows << 32 | runs of equal neighbouring probe keys (a piecewise sorted probe side takes the counting partition)
   int parent = -1;                             // the one operator consuming this node (-1: the root, or several)
-  bool band_takes_records = false;             // this node's band join found its probe side presorted by an ordered slice join below and needed no slow pass: next time that join may write the row records itself
   u32 n_aggs = 0; u32 agg_fn[RDFGPU_MAX_AGGREGATES] = {}, agg_col[RDFGPU_MAX_AGGREGATES] = {};   // AggregateExec: (RDFGPU_AGG_*, input column)
-  bool band_in_place = false;                  // the ordered slice join below wrote this band join's records with the slice's rows as its own entries
-  u64 band_multi_rows = 0;                     // .. and met this many table rows behind another of the same key (0: next time it may skip its count pass)
-  bool band_ran = false; u64 band_slow_rows = 0;   // .. and how many of its probe rows needed the full typed-value semantics                    // .. extrapolated from a priming run over a prefix of the bound tables
+  BandHistory band;                            // the band join based on this node, if there was one
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
 
@@ -60,7 +65,7 @@ struct ChainRequest { NodeInfo* top = nullptr; NodeInfo* base = nullptr; std::ve
 // counted = false: its count pass has not run either (the band join may read the slice's rows in place, OjInPlace); whatever
 // else takes the table runs it first (Plan::count_pending_oj) and registers `check`, the check of the count it writes.
 // rows_seen: that join's last measured output rows (how much of the slice the band join's in-place form would leave idle).
-struct PendingOj { bool active = false; OrderedJoinArgs o{}; const u32* first_col = nullptr; u64 n_build = 0; u32 n_chain = 0; bool counted = true; SpecCheck check{}; u64 rows_seen = 0; };
+struct PendingOj { bool active = false; OrderedJoinArgs o{}; const u32* first_col = nullptr; u64 n_build = 0; bool counted = true; SpecCheck check{}; u64 rows_seen = 0; };
 
 struct BoundTable { std::vector<const u32*> cols; u64 n_rows = 0; bool bound = false; };
 
@@ -94,10 +99,29 @@ struct LdsJoin {
   PartArgs part{};
   u64 tail = 0;                            // left join: output rows reserved for the unmatched build rows
   bool stream_values_tried = false;
+  u64 stage_bytes = 0;                     // a fused chain of lookups above this join (Plan::apply_chain): what its stages read (estimate)
+  std::vector<ColRef> chain_cols; SliceTable::ValueColumn chain_vc[kMaxChain] = {};   // .. its output columns (bottom-up, while it is resolved into a.chain / a.chain_out); the decoded value table a stage's window reads (a copy; val == nullptr: none)
+  BandArgs band{}; bool use_band = false;  // the chain runs as a band join (Plan::exec_band_join), with these arguments
   DevTable t;                              // the output
   LdsJoin(NodeInfo& n, const DevTable& l, const DevTable& r, bool bl, const NodeInfo* pf, const NodeInfo* post)
       : nd(n), L(l), R(r), build_left(bl), B(bl ? l : r), P(bl ? r : l), probe_filter(pf), post_filter(post),
         probe_outer(n.d.join_type == RDFGPU_JOIN_LEFT && !bl), left_join(n.d.join_type == RDFGPU_JOIN_LEFT && bl) {}
+};
+
+// One band join while it is set up and run (Plan::exec_band_join and its steps): the fused chain of `j`, its kernel arguments (left by apply_chain) in j.band.
+struct BandJoin {
+  LdsJoin& j; const u32 kn; const u64 np, nb, cmax;   // keys of the build side's CSR table (key kn = joins nothing); probe rows (capacity), build rows; 64-entry pieces of its largest group
+  bool presorted = false;              // route: the probe side arrives sorted by the key (an ordered slice join below): nothing to partition.  Its keys may not lie below the table's range: they would map to "joins nothing" (= kn, the largest) out of order
+  bool skip_slow = false;              // route: the previous execution met no row that needed the full-semantics pass: it is not launched
+  bool counting = false;               // route: not sorted, but small or piecewise sorted (>= 4 rows per run of equal neighbouring keys last time, the N sorted runs a repartition delivers): counting sort on the key, one atomic per run, instead of the radix sort
+  bool fused = false;                  // route: the held-back ordered slice join below writes this join's row records itself (OjBandFuse)
+  bool in_place = false;               // route: .. without counting its matches: the rows of key k are the slice's own CSR group k (OjInPlace)
+  bool cache_entries = false;          // the build side is a store slice: its decoded entries and block layout are kept on its SliceTable
+  OjBandFuse fuse{};                   // fused: where the ordered join's packed record holds what this join reads of a row
+  std::string ekey; SliceTable::BandEntries lay{};   // what the decoded entries depend on, spelt out (SliceTable::BandEntries::key); a copy of the slice's in-place block layout (boff == nullptr: there is none, the route is closed)
+  u64 nrows = 0, max_blocks = 0;       // probe rows of the block kernels (in place: the slice's own rows); upper bound of the blocks (in place: exact)
+  u32* skey = nullptr; u32* perm = nullptr; u32 sort_bits = 1; void* sort_temp = nullptr; size_t sort_temp_bytes = 0;   // the radix sort of the probe keys (its output pairs, key bits, temp): allocated by band_probe_side, run by band_blocks_and_emit
+  BandJoin(LdsJoin& join) : j(join), kn(join.a.direct_n), np(join.P.cap), nb(join.B.cap), cmax((join.slice->csr_max_group + 63) / 64) {}
 };
 
 // Kernel classes for per-kernel timing; names are what rocprofv3 --kernel-trace prints.
@@ -172,10 +196,10 @@ struct Plan {
   bool priming = false, primed = false;   // the first execution over big bound tables is preceded by one over their first rows (Plan::prime)
   void prime();
   std::vector<SpecCheck> spec_checks;
-  struct BandBlockCounter { NodeInfo* node; u32 counter; u32 slow_counter; u32 runs_counter; bool slow_skipped; u64 known_blocks; };
-  std::vector<BandBlockCounter> band_block_counters;   // device-side block counts of this execution's band joins -> NodeInfo::band_blocks (known_blocks != 0: counted on the host)
-  struct OjChainCounter { NodeInfo* node; u32 counter; bool in_place; };
-  std::vector<OjChainCounter> oj_chain_counters;       // the multi-row counts of the ordered slice joins that wrote band records -> NodeInfo::band_multi_rows
+  // The counter slots a band join of this execution leaves its measurements in -> NodeInfo::band (known_blocks != 0: counted on the host; multi_rows < 0: not fused, no such count)
+  struct BandFeedback { NodeInfo* node; u32 blocks, slow_rows, run_stats; int multi_rows; bool slow_skipped, in_place; u64 known_blocks; };
+  std::vector<BandFeedback> band_feedback;
+  bool record_band_history();     // after the counters came back; true: a band join speculated wrongly (exact re-run)
   std::vector<PendingLaunch> pending;
   std::vector<DevTable> memo; std::vector<char> memo_valid;   // node results of the current execution
   ChainRequest* pending_chain = nullptr;                        // set while the base join of a fusable chain executes
@@ -215,7 +239,7 @@ struct Plan {
   JoinTable choose_join_table(LdsJoin& j);
   void size_wave_queue(LdsJoin& j);
   void run_join_kernel(LdsJoin& j, u64 stage_bytes, u64 out_bytes_per_row);
-  DevTable run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node, u64 stage_bytes, BandArgs* band);
+  DevTable run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node);
   bool run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap);
   DevTable run_exact(LdsJoin& j);
   void left_join_tail(const NodeInfo& nd, const DevTable& L, const DevTable& R, u32* const* out, u8* visited, u64* n_out_dev, u64 matched_total);
@@ -223,9 +247,14 @@ struct Plan {
   struct DirectTable { bool dense = false; u32 kmin = 0, kn = 0; u32* direct = nullptr; u32* flags = nullptr; };
   DirectTable build_direct(const u32* key, u64 n, u64 max_range, bool cached);
   void build_dense_table(SliceTable* st, const u32* key, u64 n);
-  bool apply_chain(const ChainRequest& req, NodeInfo& base, const DevTable& L, const DevTable& R, bool build_left, SliceTable* build_table, LdsJoinArgs& a, u64& stage_bytes, BandArgs* band, bool* use_band);
+  bool apply_chain(const ChainRequest& req, LdsJoin& j);   // its steps:
+  bool resolve_chain(const ChainRequest& req, LdsJoin& j); SliceTable::ValueColumn slice_value_column(const ChainLink& ln, const u32* col);
+  bool chain_band_args(const ChainRequest& req, LdsJoin& j); u32 csr_max_group(SliceTable* tab, const LdsJoinArgs& a);
+  void chain_range_index(LdsJoin& j, const ChainStage& s0); template <class F> void device_minmax_i64(long long (&got)[2], F&& launch);
   void prepare_partitions(const LdsJoinArgs& a, const DevTable& B, const DevTable& P, PartArgs& pa);
-  void exec_band_join(NodeInfo& base, SliceTable* build_table, LdsJoinArgs& a, BandArgs& b, const DevTable& B, const DevTable& P, u64 build_bytes_per_row, u64 probe_bytes_per_row);
+  void exec_band_join(LdsJoin& j);   // its steps, in order:
+  bool take_pending_oj(BandJoin& bj); void band_probe_side(BandJoin& bj); void band_row_records(BandJoin& bj); void band_blocks_and_emit(BandJoin& bj);
+  void band_slice_tables(BandJoin& bj); void band_entries(BandJoin& bj); SliceTable::BandEntries* band_layout(BandJoin& bj);
   bool choose_build_left(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf, bool lpost = false, bool rpost = false) const;
   void release_intermediates();
   template <class T> T* scratch(u64 n);

@@ -1788,7 +1788,7 @@ def test_plan_outlives_its_store_handle(torch_cuda):
 @pytest.mark.parametrize("option", ["NO_INDEX_JOIN", "NO_BAND_JOIN"])
 def test_held_back_ordered_join_output_after_an_option_change(bsbm_stores, torch_cuda, option):
     """The ordered slice join of the batched Q5 holds its write pass back once the band join above it has taken its records
-    (NodeInfo::band_takes_records, kept across executions).  An option set on the plan afterwards routes that join elsewhere:
+    (NodeInfo::band.takes_records, kept across executions).  An option set on the plan afterwards routes that join elsewhere:
     NO_INDEX_JOIN makes the held-back table the BUILD side of a hash table built in the step, NO_BAND_JOIN the probe side of an
     ordinary index join.  Either way the write pass has to run before the table is read: the bindings stay the oracle's."""
     ds, gs, os_ = bsbm_stores
