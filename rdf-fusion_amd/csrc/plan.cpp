@@ -1540,9 +1540,9 @@ bool Plan::chain_band_args(const ChainRequest& req, LdsJoin& j) {
     if (st.fs == 0) continue;
     const SliceTable::ValueColumn& vc = j.chain_vc[t];
     if (st.val == nullptr || b.n_win >= 2 || st.f[1].src != 0 || st.f[3].src != 0 || !range_op(st.l0.cmp_op) || !range_op(st.l1.cmp_op) ||
-        vc.vmin > vc.vmax || (unsigned long long)(vc.vmax - vc.vmin) >= 0xFFFFFFE0ull) return false;
+        vc.vmin > vc.vmax || (unsigned long long)vc.vmax - (unsigned long long)vc.vmin >= 0xFFFFFFE0ull) return false;   // (unsigned: the spread of two i64 may exceed i64)
     BandWin& w = b.win[b.n_win++];
-    if ((unsigned long long)(vc.vmax - vc.vmin) > 65530ull) pack16 = false;   // biased values 1 .. range + 1 have to fit 16 bits
+    if ((unsigned long long)vc.vmax - (unsigned long long)vc.vmin > 65530ull) pack16 = false;   // biased values 1 .. range + 1 have to fit 16 bits
     w.key_col = st.key.ptr; w.val = st.val; w.vkmin = st.kmin; w.vkn = st.kn; w.vbase = vc.vmin;
     w.y0 = st.f[1].ptr; w.y1 = st.f[3].ptr; w.l0 = st.l0; w.l1 = st.l1; w.stage = (u32)t;
   }
@@ -1581,7 +1581,7 @@ void Plan::chain_range_index(LdsJoin& j, const ChainStage& s0) {
     SliceTable::RangeIndex fresh{s0.val, s0.key.ptr, nullptr, nullptr, 0, nullptr, false};
     const u64 n = j.B.cap;
     long long got[2]; device_minmax_i64(got, [&](long long* mm) { launch_range_minmax(s0.key.ptr, a.csr_rows, n, s0.val, s0.kmin, s0.kn, mm, stream); });
-    if (got[0] <= got[1] && (unsigned long long)(got[1] - got[0]) < 0xFFFFFFF0ull && n < (1ull << 32)) {
+    if (got[0] <= got[1] && (unsigned long long)got[1] - (unsigned long long)got[0] < 0xFFFFFFF0ull && n < (1ull << 32)) {
       u64* key_in = scratch<u64>(n); u64* key_out = scratch<u64>(n); u32* rows_in = scratch<u32>(n);
       fresh.rows = store->table_alloc<u32>(n); fresh.vals = store->table_alloc<u32>(n);
       metrics.tables_built++; fresh.vbase = got[0];
