@@ -308,6 +308,38 @@ enum {
                                  language or with a's (string_literal.rs:80-95, else error); the part of a before the first occurrence
                                  of b with a's language — a VIEW of a, nothing is copied; b does not occur => the simple literal "".    */
   RDFGPU_EX_STRAFTER = 36,    /* same: STRAFTER, scalar/strings/str_after.rs — the part of a behind the first occurrence of b             */
+  /* ---- ABI 4 addendum: numeric expressions (new enum values only).  Every op is a pure per-row function of its operands and restates
+     the reference bit for bit: exact integer / i128 arithmetic or single correctly rounded IEEE operations, nothing fused.  They run in
+     the generic VM (FilterExec, join filters, and the input of SUM / AVG: RDFGPU_AGG_INPUT_EXPR). */
+  RDFGPU_EX_MUL = 37,         /* TV TV -> TV  scalar/numeric/mul.rs:50-76: both numeric, else error; kinds promote as for ADD.  int: i32 checked,
+                                 integer: i64 checked, float / double: one multiply; decimal: Decimal::checked_mul (lib/model/src/xsd/
+                                 decimal.rs:93-125) — both values lose their trailing decimal zeros, the zeros must make up the 18 fraction
+                                 digits (fewer => error: the product would need more precision, and so does 0 x 2.5 as written there), then a
+                                 checked i128 product and a checked multiply by 10^(zeros - 18).                                     */
+  RDFGPU_EX_DIV = 38,         /* TV TV -> TV  div.rs:51-80: int and integer pairs divide AS DECIMALS and yield a decimal; float / double: one
+                                 divide (x / 0 is inf or NaN, not an error); decimal: Decimal::checked_div (decimal.rs:131-163) — the dividend
+                                 is scaled by 10 while it stays inside i128, the divisor loses its trailing zeros, two truncating divisions; a
+                                 zero divisor, MIN / -1 and a scale beyond 10^38 => error.  The same code finishes a decimal AVG.       */
+  RDFGPU_EX_NEG = 39,         /* TV -> TV  unary_minus.rs (Numeric::neg, lib/model/src/xsd/numeric.rs:30-38): checked for int / integer / decimal
+                                 (-MIN => error), the sign bit flipped for float / double; not numeric => error.  Plan text: MINUS.     */
+  RDFGPU_EX_PLUS = 40,        /* TV -> TV  unary_plus.rs: a numeric value unchanged, anything else => error                                  */
+  RDFGPU_EX_ABS = 41,         /* TV -> TV  abs.rs (Numeric::abs, numeric.rs:20-28): checked like NEG, the sign bit cleared for float / double   */
+  RDFGPU_EX_ROUND = 42,       /* TV -> TV  round.rs:48-60: int / integer unchanged; float / double: Rust's `round`, half away from zero, the sign
+                                 of a zero result kept; decimal: Decimal::checked_round (decimal.rs:211-222), whose negative branch is
+                                 `-value % 10 > 5`: 2.5 rounds to 3 and -2.5 to -2, restated as written.                                */
+  RDFGPU_EX_CEIL = 43,        /* TV -> TV  ceil.rs:48-60: like ROUND with `ceil` / Decimal::checked_ceil (decimal.rs:228-238); CEIL(-0.5) = -0.0  */
+  RDFGPU_EX_FLOOR = 44,       /* TV -> TV  floor.rs: `floor` / Decimal::checked_floor (decimal.rs:244-254)                                  */
+  RDFGPU_EX_CAST = 45,        /* TV -> TV  the XSD constructor functions, scalar/conversion/cast_{boolean,int,integer,decimal,float,double}.rs:
+                                 48-62; `u` = the target tag: RDFGPU_TV_BOOLEAN, _INT, _INTEGER, _DECIMAL, _FLOAT or _DOUBLE (any other target:
+                                 RDFGPU_ERR_UNSUPPORTED at compile — xsd:string and xsd:dateTime casts are not on the device).  A boolean casts
+                                 to 0 / 1 of the target.  A numeric: to decimal from float / double by Decimal::try_from(Double) (decimal.rs:
+                                 420-435: v * 10^18 in f64 must lie in [-2^127, 2^127], then a truncating, SATURATING conversion; a float is
+                                 widened first); to integer / int through that decimal, a truncating division by 10^18 and a range check
+                                 (decimal.rs:464-494, integer.rs:267-287, int.rs:238-267); to double / float as the comparisons promote
+                                 (Decimal -> Double decimal.rs:445-462, Double -> Float `as f32`); to boolean `!= 0 && !NaN` (boolean.rs:51-84).
+                                 Named / blank nodes, language-tagged strings, dateTime / date / time, durations, other literals and null =>
+                                 error.  A SIMPLE LITERAL would have to be parsed: such a row fails the execute with RDFGPU_ERR_UNSUPPORTED
+                                 (the lexical parsers are not restated; never answered differently).                                  */
   RDFGPU_EX__COUNT
 };
 
@@ -357,7 +389,11 @@ enum {
                                   on top of their join trees (bench/tests/plans/snapshots/..Business Intelligence - Q1..Q8 (Execution
                                   Plan).snap).  Encoding: left = input; n_keys (0..RDFGPU_MAX_KEYS) group columns in left_keys[];
                                   table_cols = number of aggregates (0..RDFGPU_MAX_AGGREGATES); table_slot = offset into the u32 pool of
-                                  table_cols pairs (RDFGPU_AGG_*, input column); n_proj must be RDFGPU_NO_PROJECTION.  Output columns: the
+                                  table_cols pairs (RDFGPU_AGG_*, input); n_proj must be RDFGPU_NO_PROJECTION.  The input is a column of
+                                  `left`, or — SUM and AVG only — RDFGPU_AGG_INPUT_EXPR | the pool offset of two words (expr_off, expr_len)
+                                  naming a program in `exprs` over the input's columns that leaves a typed value (`SUM(?price * ?qty)`);
+                                  such an input of COUNT / COUNT_DISTINCT, and a program with REGEX / CONTAINS / STRSTARTS / STRENDS /
+                                  LANG_IN in it, is RDFGPU_ERR_UNSUPPORTED at compile.  Output columns: the
                                   keys in order, then the aggregates.  Two rows are one group when their key ids are equal; id 0
                                   (unbound) is a key value like any other (SQL GROUP BY puts NULLs in a group of their own).  With 0 keys
                                   there is exactly one output row, even over an empty input; with keys an empty input gives no row.  Row
@@ -371,7 +407,8 @@ enum {
 /*
  * Aggregate functions of RDFGPU_NODE_AGGREGATE (ABI 4 addendum).  The reference plans SPARQL aggregates in
  * lib/logical/src/expr_builder.rs:700-760 onto its own accumulators (lib/functions/src/aggregates/); the input of SUM / AVG is
- * ENC_TV of an object-id column (the expression VM has no casts: BSBM BI's `AVG(xsd:float(xsd:string(?price)))` stays on the host).
+ * ENC_TV of an object-id column, or an expression program (RDFGPU_AGG_INPUT_EXPR) whose error value counts as "not numeric", exactly
+ * as an unbound id does.  (A cast FROM A STRING is not on the device: BSBM BI's `AVG(xsd:float(xsd:string(?price)))` stays on the host.)
  *   COUNT_STAR      rows of the group, as xsd:integer: DataFusion count(*) then INT64_AS_TERM (graph_pattern_rewriter.rs:311-313)
  *   COUNT           rows whose input id is not 0 (unbound), xsd:integer
  *   COUNT_DISTINCT  distinct non-zero ids of the input column in the group, xsd:integer (expr_builder.rs:724-733: count_distinct over
@@ -406,6 +443,7 @@ enum {
   RDFGPU_AGG_SUM_DISTINCT = 10, RDFGPU_AGG_AVG_DISTINCT = 11, RDFGPU_AGG_COUNT_DISTINCT_STAR = 12
 };
 #define RDFGPU_MAX_AGGREGATES 8u
+#define RDFGPU_AGG_INPUT_EXPR 0x80000000u   /* bit 31 of an aggregate's input: the low 31 bits are the pool offset of (expr_off, expr_len) */
 enum { RDFGPU_SORT_BY_ID = 0, RDFGPU_SORT_BY_TERM = 1,
        RDFGPU_SORT_BY_DOUBLE = 2 /* ENC_SORT of a numeric value: the sortable encoding orders numerics by Double::from(Numeric)
                                     (lib/encoding/src/sortable_term/builder.rs:36-39, lib/model/src/xsd/double.rs:92-102) in IEEE

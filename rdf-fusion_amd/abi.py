@@ -30,7 +30,9 @@ NT_IRI, NT_BNODE, NT_SIMPLE, NT_LANG, NT_TYPED = 1, 2, 3, 4, 5   # rdfgpu_ntripl
 (EX_COLUMN, EX_LIT_ID, EX_LIT_TV, EX_ENC_TV, EX_GT, EX_LT, EX_GEQ, EX_LEQ, EX_EQ, EX_ADD, EX_SUB,
  EX_EBV, EX_ID_EQ, EX_ID_NEQ, EX_AND, EX_OR, EX_NOT, EX_IS_COMPATIBLE, EX_BOUND, EX_BOOL_AS_TV,
  EX_LIT_BOOL, EX_NEQ, EX_REGEX, EX_CONTAINS, EX_STRSTARTS, EX_STRENDS, EX_LANG_IN, EX_REGEX_VAR,
- EX_STR, EX_LIT_STR, EX_STRLEN, EX_SUBSTR, EX_UCASE, EX_LCASE, EX_STRBEFORE, EX_STRAFTER) = range(1, 37)
+ EX_STR, EX_LIT_STR, EX_STRLEN, EX_SUBSTR, EX_UCASE, EX_LCASE, EX_STRBEFORE, EX_STRAFTER,
+ EX_MUL, EX_DIV, EX_NEG, EX_PLUS, EX_ABS, EX_ROUND, EX_CEIL, EX_FLOOR, EX_CAST) = range(1, 46)
+CAST_TARGETS = (TV_BOOLEAN, TV_INT, TV_INTEGER, TV_DECIMAL, TV_FLOAT, TV_DOUBLE)   # EX_CAST's `u`; any other tag is refused at compile
 
 # plan nodes
 (NODE_DATA_SOURCE, NODE_FILTER, NODE_HASH_JOIN, NODE_CROSS_JOIN, NODE_NESTED_LOOP_JOIN,
@@ -42,6 +44,7 @@ AGG_NAMES = {AGG_COUNT_STAR: "COUNT(*)", AGG_COUNT: "COUNT", AGG_COUNT_DISTINCT:
              AGG_MIN: "MIN", AGG_MAX: "MAX", AGG_SAMPLE: "SAMPLE", AGG_GROUP_CONCAT: "GROUP_CONCAT", AGG_SUM_DISTINCT: "SUM(DISTINCT)",
              AGG_AVG_DISTINCT: "AVG(DISTINCT)", AGG_COUNT_DISTINCT_STAR: "COUNT(DISTINCT *)"}
 MAX_AGGREGATES = 8
+AGG_INPUT_EXPR = 0x80000000   # bit 31 of an aggregate's input: the low 31 bits are the pool offset of (expr_off, expr_len); SUM / AVG only
 SORT_BY_ID, SORT_BY_TERM, SORT_BY_DOUBLE = 0, 1, 2
 JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
 MAX_KEYS = 4

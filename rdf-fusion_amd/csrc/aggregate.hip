@@ -139,8 +139,19 @@ __device__ __forceinline__ bool dset_insert(unsigned long long* set, u32 mask, u
   }
 }
 
-template <bool LDS>
-__global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) {
+// Column `c` of the input, for an aggregate's program: `c` comes from the program (wave-uniform), and indexing the kernarg array with it
+// would copy the array to scratch — a chain of value selects over the pointers stays in SGPRs ("What the generic VM costs").
+__device__ __forceinline__ const u32* agg_col(const AggArgs& a, u32 c) {
+  const u32* p = a.col[0];
+#pragma unroll
+  for (u32 q = 1; q < (u32)kMaxCols; q++) p = c == q ? a.col[q] : p;
+  return p;
+}
+
+// EXPR: some SUM / AVG reads an expression (RDFGPU_AGG_INPUT_EXPR): that aggregate's value is its program's, evaluated by the VM.  A node
+// whose aggregates are all plain columns runs the instantiation without the VM in it.
+template <bool LDS, bool EXPR>
+__device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
   extern __shared__ unsigned long long lacc[];
   const u32 tid = threadIdx.x, lane = tid & 63;
   const u64 n = live_rows(a.n_dev, a.cap);
@@ -165,11 +176,15 @@ __global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) {
       const u32 fn = a.fn[i];
       if (fn == RDFGPU_AGG_COUNT_STAR) continue;
       const u64 w = (u64)a.word0[i] * G + (valid ? g : 0u);
-      const u32 id = valid ? a.in[i][row] : 0u;
+      u32 id;
+      if constexpr (EXPR) id = valid && a.in[i] ? a.in[i][row] : 0u;
+      else id = valid ? a.in[i][row] : 0u;
       if (fn == RDFGPU_AGG_COUNT) { acc_add(acc, w, id != 0, r); continue; }
       if (fn == RDFGPU_AGG_COUNT_DISTINCT) { acc_add(acc, w, id != 0 && dset_insert(a.dset[i], a.dset_mask, g, id), r); continue; }
-      // SUM / AVG: ENC_TV of the id, one 16-byte gather
-      const Val v = enc_tv(a.tt, id);
+      // SUM / AVG: ENC_TV of the id, one 16-byte gather — or the value of the aggregate's program (the branch is uniform)
+      Val v;
+      if constexpr (EXPR) v = a.prog[i] ? eval_program(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
+      else v = enc_tv(a.tt, id);
       const int k = num_kind(v.tag);
       u32 kind = k == NK_NONE ? kKindOther : k == NK_DECIMAL ? kKindDec : k == NK_FLOAT ? kKindFloat : k == NK_DOUBLE ? kKindDouble : kKindInt;
       if (!valid) kind = 0;
@@ -202,6 +217,9 @@ __global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) {
   }
 }
 
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) { agg_accum_rows<LDS, false>(a); }
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_expr_kernel(const AggArgs a) { agg_accum_rows<LDS, true>(a); }
+
 // ---- pass 3 ---------------------------------------------------------------------------------------------------------------------
 // 256-bit two's complement, enough for sum(limb_i * 2^(32 i)) over 2^32 rows and for the integer part scaled by 10^18.
 struct Wide { u64 w[4]; };
@@ -231,34 +249,6 @@ __device__ __forceinline__ void wide_mul(Wide& x, u64 m) {   // modulo 2^256: ex
 __device__ __forceinline__ bool wide_fits(const Wide& x, int words) {   // fits a signed integer of `words` 64-bit words
   const u64 ext = (x.w[words - 1] >> 63) ? ~0ull : 0ull;
   for (int i = words; i < 4; i++) if (x.w[i] != ext) return false;
-  return true;
-}
-
-__device__ __forceinline__ u128_t u128_div(u128_t n, u128_t d) {   // shift-subtract: no 128-bit division libcall on the device
-  u128_t q = 0, r = 0;
-  for (int i = 127; i >= 0; i--) {
-    r = (r << 1) | ((n >> i) & 1);
-    if (r >= d) { r -= d; q |= (u128_t)1 << i; }
-  }
-  return q;
-}
-// Decimal::checked_div(sum, Decimal::from(count)), lib/model/src/xsd/decimal.rs:131-162, count > 0.
-__device__ __forceinline__ bool decimal_div_count(i128_t left, u64 count, i128_t& out) {
-  const bool neg = left < 0;
-  u128_t m = neg ? (u128_t)0 - (u128_t)left : (u128_t)left;
-  u32 shift_left = 0;
-  if (m != 0) {   // `while let Some(r) = left.checked_mul(10)`: |left| * 10 stays inside i128 (for both signs) iff |left| <= (2^127 - 1) / 10
-    const u128_t lim = ((u128_t)0x0CCCCCCCCCCCCCCCull << 64) | (u128_t)0xCCCCCCCCCCCCCCCCull;
-    while (m <= lim) { m *= 10u; shift_left++; }
-  }
-  u64 right = count; u32 tz = 0;   // count * 10^18 with its trailing zeros stripped: shift_right = 18 + tz
-  while (right % 10u == 0) { right /= 10u; tz++; }
-  const u32 shift = shift_left + tz;   // (shift_left + shift_right) - 18
-  if (shift > 38) return false;        // 10_i128.checked_pow(shift) overflows
-  u128_t p = 1;
-  for (u32 i = 0; i < shift; i++) p *= 10u;
-  const u128_t q = u128_div(u128_div(m, right), p);   // two truncating divisions (toward zero: on the magnitude)
-  out = (i128_t)(neg ? (u128_t)0 - q : q);
   return true;
 }
 
@@ -315,7 +305,8 @@ __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
     wide_add(D, I);
     if (!wide_fits(D, 2)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }
     i128_t sum = (i128_t)(((u128_t)D.w[1] << 64) | (u128_t)D.w[0]);
-    if (avg && !decimal_div_count(sum, rows, sum)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }
+    // Decimal::checked_div(sum, Decimal::from(count)), expr_device.hpp (count > 0; count * 10^18 is below 2^92)
+    if (avg && !dec_checked_div(sum, (i128_t)rows * (i128_t)kDecOne, sum)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }
     put(o, g, RDFGPU_TV_DECIMAL, (long long)(u64)(u128_t)sum, (long long)(u64)((u128_t)sum >> 64));
   }
 }
@@ -334,10 +325,12 @@ void launch_agg_accum(const AggArgs& a, hipStream_t s) {
     const size_t lds = (size_t)a.n_words * a.n_groups * sizeof(unsigned long long);
     if (lds > kAggLdsBytes) fail(RDFGPU_ERR_INVALID, "aggregate: %zu bytes of LDS partials", lds);
     if (g > 512) g = 512;   // every workgroup zeroes and merges all partials: enough of them to fill the part, not one per tile
-    hipLaunchKernelGGL(agg_accum_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+    if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+    else hipLaunchKernelGGL(agg_accum_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
   } else {
     if (g > 16384) g = 16384;
-    hipLaunchKernelGGL(agg_accum_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+    if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+    else hipLaunchKernelGGL(agg_accum_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
   }
   RDFGPU_HIP(hipGetLastError());
 }

@@ -7,6 +7,10 @@
 //   GT/LT/.. lib/functions/src/scalar/comparison/*.rs via PartialOrd lib/model/src/typed_value.rs:162-261
 //   promotion lib/model/src/xsd/numeric.rs:127-201
 //   ADD/SUB  lib/functions/src/scalar/numeric/add.rs:40-86 (checked int/decimal, IEEE float/double)
+//   MUL/DIV  scalar/numeric/mul.rs:50-76, div.rs:51-80 over Decimal::checked_mul / checked_div (lib/model/src/xsd/decimal.rs:93-163)
+//   NEG/PLUS/ABS  unary_minus.rs, unary_plus.rs, abs.rs (lib/model/src/xsd/numeric.rs:20-38)
+//   ROUND/CEIL/FLOOR  round.rs:48-60, ceil.rs:48-60, floor.rs (decimal.rs:211-254; f32 / f64 round, ceil, floor)
+//   CAST     scalar/conversion/cast_{boolean,int,integer,decimal,float,double}.rs:48-62 and the From / TryFrom impls they call
 //   EBV      lib/functions/src/builtin/native/effective_boolean_value.rs:99-119
 //   AND/OR   SQL three-valued logic on native booleans (lib/logical/src/expr_builder_context.rs:393-434)
 #pragma once
@@ -40,7 +44,8 @@ struct TypedTable {
   uint32_t* rt_error;            // the executing plan's run-time error flags (null outside a plan): bit 0 a REGEX with a Perl
                                  // class / word boundary met a non-ASCII subject, bit 1 a per-row REGEX pattern was not announced,
                                  // bit 2 a string expression met what the device does not restate (case mapping of a non-ASCII
-                                 // string, a non-integer SUBSTR argument)
+                                 // string, a non-integer SUBSTR argument), bit 3 a numeric CAST met a simple literal (the lexical
+                                 // parsers are not restated)
 };
 
 // Value kinds on the evaluation stack.
@@ -59,6 +64,7 @@ struct Val {
 // and flags bits 4 / 5 an ASCII upper / lower case mapping applied when a byte is read.  Nothing is materialised.
 constexpr uint8_t kStrUpper = 0x10, kStrLower = 0x20;
 constexpr uint32_t kRtStringUnsupported = 4u;
+constexpr uint32_t kRtCastFromString = 8u;
 
 typedef __int128 i128_t;
 typedef unsigned __int128 u128_t;
@@ -239,6 +245,214 @@ __device__ __forceinline__ Val tv_arith(const Val& a, const Val& b, bool sub) {
       if (sub ? __builtin_sub_overflow(x, y, &z) : __builtin_add_overflow(x, y, &z)) return r;
       r.tag = RDFGPU_TV_DECIMAL; set_dec(r, z); return r; }
   }
+}
+
+// ---- decimals (i128 x 10^-18): multiply, divide, round — lib/model/src/xsd/decimal.rs:93-163, 211-254 ----
+// There is no 128-bit multiply-overflow or division libcall on the device: magnitudes over 64-bit limbs, the sign kept apart.
+// Out of line: every kernel that hosts the VM would otherwise carry the 128-step divisions in its own body.
+constexpr uint64_t kDecOne = 1000000000000000000ull;   // DECIMAL_PART_POW
+__device__ __forceinline__ u128_t i128_mag(i128_t v) { return v < 0 ? (u128_t)0 - (u128_t)v : (u128_t)v; }
+__device__ __forceinline__ bool i128_from_mag(bool neg, u128_t m, i128_t& out) {   // false: outside [-2^127, 2^127 - 1]
+  const u128_t top = (u128_t)1 << 127;
+  if (neg ? m > top : m >= top) return false;
+  out = (i128_t)(neg ? (u128_t)0 - m : m);
+  return true;
+}
+__device__ __forceinline__ bool u128_mul_checked(u128_t a, u128_t b, u128_t& out) {   // false: the product needs more than 128 bits
+  const uint64_t a0 = (uint64_t)a, a1 = (uint64_t)(a >> 64), b0 = (uint64_t)b, b1 = (uint64_t)(b >> 64);
+  if (a1 && b1) return false;
+  const u128_t cross = (u128_t)a1 * b0 + (u128_t)a0 * b1;   // (one of the two products is 0)
+  if (cross >> 64) return false;
+  const u128_t lo = (u128_t)a0 * b0;
+  out = lo + (cross << 64);
+  return out >= lo;
+}
+__device__ __forceinline__ u128_t u128_div(u128_t n, u128_t d) {   // shift-subtract, d != 0
+  u128_t q = 0, r = 0;
+  for (int i = 127; i >= 0; i--) {
+    r = (r << 1) | ((n >> i) & 1);
+    if (r >= d) { r -= d; q |= (u128_t)1 << i; }
+  }
+  return q;
+}
+__device__ __forceinline__ uint32_t u128_strip_zeros(u128_t& m) {   // `while v % 10 == 0 { v /= 10 }`, m != 0
+  uint32_t z = 0;
+  for (;;) { u128_t q = m; if (u128_divmod10(q) != 0) return z; m = q; z++; }
+}
+__device__ __forceinline__ u128_t u128_pow10(uint32_t e) { u128_t p = 1; for (uint32_t i = 0; i < e; i++) p *= 10u; return p; }   // e <= 38
+// i128::checked_mul
+__device__ __forceinline__ bool i128_mul_checked(i128_t x, i128_t y, i128_t& out) {
+  u128_t m;
+  return u128_mul_checked(i128_mag(x), i128_mag(y), m) && i128_from_mag((x < 0) != (y < 0), m, out);
+}
+// Decimal::checked_mul, decimal.rs:93-125: both values lose their trailing decimal zeros, the zeros must make up the 18 fraction digits
+// (a product that would need more precision is an error, and so is 0 x anything with fewer than 18 zeros: as written there)
+__device__ __noinline__ bool dec_checked_mul(i128_t left, i128_t right, i128_t& out) {
+  const bool neg = (left < 0) != (right < 0);
+  u128_t ml = i128_mag(left), mr = i128_mag(right);
+  const uint32_t zeros = (ml ? u128_strip_zeros(ml) : 0u) + (mr ? u128_strip_zeros(mr) : 0u);
+  if (zeros < 18u || zeros - 18u > 38u) return false;   // checked_sub; 10_i128.checked_pow
+  u128_t m; i128_t p;   // p: only its range check counts — `left.checked_mul(right)` must fit i128 before the scale is applied
+  if (!u128_mul_checked(ml, mr, m) || !i128_from_mag(neg, m, p)) return false;
+  return u128_mul_checked(m, u128_pow10(zeros - 18u), m) && i128_from_mag(neg, m, out);
+}
+// Decimal::checked_div, decimal.rs:131-163: the dividend is scaled by 10 while it stays inside i128, the divisor loses its trailing zeros,
+// two truncating divisions (toward zero: on the magnitudes); a zero divisor, MIN / -1 and a scale beyond 10^38 are errors
+__device__ __noinline__ bool dec_checked_div(i128_t left, i128_t right, i128_t& out) {
+  if (right == 0) return false;
+  const bool neg = (left < 0) != (right < 0);
+  u128_t ml = i128_mag(left), mr = i128_mag(right);
+  uint32_t shift_left = 0;
+  if (ml != 0) {   // `while let Some(r) = left.checked_mul(10)`: |left| * 10 stays inside i128 (for both signs) iff |left| <= (2^127 - 1) / 10
+    const u128_t lim = ((u128_t)0x0CCCCCCCCCCCCCCCull << 64) | (u128_t)0xCCCCCCCCCCCCCCCCull;
+    while (ml <= lim) { ml *= 10u; shift_left++; }
+  }
+  const uint32_t total = shift_left + u128_strip_zeros(mr);
+  if (total < 18u || total - 18u > 38u) return false;
+  const u128_t q = u128_div(ml, mr);
+  if (!neg && (q >> 127)) return false;   // MIN / -1
+  return i128_from_mag(neg, u128_div(q, u128_pow10(total - 18u)), out);
+}
+// Decimal::checked_round / checked_ceil / checked_floor, decimal.rs:211-254 (how: 0 round, 1 ceil, 2 floor).  Round's negative branch
+// is `-value % 10 > 5`: -2.5 rounds to -2, as written there.
+__device__ __noinline__ bool dec_checked_round(i128_t v, int how, i128_t& out) {
+  const bool neg = v < 0;
+  const u128_t m = i128_mag(v);
+  u128_t q;
+  if (how == 0) {
+    q = u128_div(m, kDecOne / 10u);                       // value / DECIMAL_PART_POW_MINUS_ONE
+    const uint32_t digit = u128_divmod10(q);
+    q += neg ? digit > 5u : digit >= 5u;
+  } else {
+    q = u128_div(m, kDecOne);
+    const bool frac = q * kDecOne != m;
+    if (frac && (how == 1) != neg) q += 1;                // ceil of a positive, floor of a negative: one step away from zero
+  }
+  i128_t whole;
+  return i128_from_mag(neg, q, whole) && i128_mul_checked(whole, (i128_t)kDecOne, out);
+}
+// TryFrom<Double> for Decimal, decimal.rs:420-435: in range (NaN fails both comparisons), then `as i128`: truncating and SATURATING
+__device__ __forceinline__ bool f64_to_dec(double v, i128_t& out) {
+  const double shifted = __dmul_rn(v, 1e18), top = 170141183460469231731687303715884105728.0;   // 2^127
+  if (!(-top <= shifted && shifted <= top)) return false;
+  const uint64_t bits = (uint64_t)__double_as_longlong(shifted);
+  const int e = (int)((bits >> 52) & 0x7FFu) - 1075;
+  const uint64_t man = (bits & 0xFFFFFFFFFFFFFull) | ((bits >> 52) & 0x7FFu ? 1ull << 52 : 0ull);
+  const u128_t mag = e >= 0 ? (u128_t)man << e : (e > -64 ? (u128_t)(man >> -e) : (u128_t)0);   // e <= 75 here
+  const bool neg = bits >> 63;
+  if (!neg && (mag >> 127)) { out = (i128_t)(((u128_t)1 << 127) - 1); return true; }
+  out = (i128_t)(neg ? (u128_t)0 - mag : mag);
+  return true;
+}
+
+// MUL / DIV, mul.rs:50-76, div.rs:51-80: kinds promote as for ADD; int and integer pairs DIVIDE as decimals
+__device__ __noinline__ Val tv_muldiv(Val a, Val b, bool div) {
+  const int ka = num_kind(a.tag), kb = num_kind(b.tag);
+  Val r = val_tv_null();
+  if (ka == NK_NONE || kb == NK_NONE) return r;
+  int k = pair_kind(ka, kb);
+  if (div && (k == NK_INT || k == NK_INTEGER)) k = NK_DECIMAL;
+  switch (k) {
+    case NK_INT: {
+      int32_t z;
+      if (__builtin_mul_overflow((int32_t)a.lo, (int32_t)b.lo, &z)) return r;
+      r.tag = RDFGPU_TV_INT; r.lo = z; return r; }
+    case NK_INTEGER: {
+      long long z;
+      if (__builtin_mul_overflow((long long)a.lo, (long long)b.lo, &z)) return r;
+      r.tag = RDFGPU_TV_INTEGER; r.lo = z; return r; }
+    case NK_FLOAT: {   // the quotient is formed in f64 and rounded once: exact for f32 operands, subnormal results included
+      const float x = to_f32(a, ka), y = to_f32(b, kb);
+      const float z = div ? (float)__ddiv_rn((double)x, (double)y) : __fmul_rn(x, y);
+      r.tag = RDFGPU_TV_FLOAT; r.lo = (int64_t)(uint64_t)__float_as_uint(z); return r; }
+    case NK_DOUBLE: {
+      const double x = to_f64(a, ka), y = to_f64(b, kb);
+      const double z = div ? __ddiv_rn(x, y) : __dmul_rn(x, y);
+      r.tag = RDFGPU_TV_DOUBLE; r.lo = __double_as_longlong(z); return r; }
+    default: {
+      i128_t z;
+      if (!(div ? dec_checked_div(to_dec(a, ka), to_dec(b, kb), z) : dec_checked_mul(to_dec(a, ka), to_dec(b, kb), z))) return r;
+      r.tag = RDFGPU_TV_DECIMAL; set_dec(r, z); return r; }
+  }
+}
+// f32 / f64 round: half away from zero, the sign of a zero result kept (Rust's `round`)
+__device__ __forceinline__ double f64_round(double x) {
+  const double t = trunc(x);
+  const double r = fabs(__dsub_rn(x, t)) >= 0.5 ? __dadd_rn(t, copysign(1.0, x)) : t;   // x - trunc(x) is exact
+  return copysign(r, x);
+}
+// NEG / PLUS / ABS / ROUND / CEIL / FLOOR: numeric.rs:20-38, round.rs:48-60, ceil.rs:48-60, floor.rs
+__device__ __noinline__ Val tv_unary_numeric(Val a, uint32_t op) {
+  const int k = num_kind(a.tag);
+  Val r = val_tv_null();
+  if (k == NK_NONE) return r;
+  if (op == RDFGPU_EX_PLUS) return a;
+  const bool neg_op = op == RDFGPU_EX_NEG, abs_op = op == RDFGPU_EX_ABS;
+  switch (k) {
+    case NK_INT: case NK_INTEGER: {
+      if (!neg_op && !abs_op) return a;                                            // ROUND / CEIL / FLOOR of an integer
+      if (a.lo >= 0 && abs_op) return a;
+      if (a.lo == (k == NK_INT ? (int64_t)INT32_MIN : INT64_MIN)) return r;        // checked_neg / checked_abs
+      a.lo = -a.lo; return a; }
+    case NK_FLOAT: {
+      uint32_t bits = (uint32_t)a.lo;
+      if (neg_op) bits ^= 0x80000000u;
+      else if (abs_op) bits &= 0x7FFFFFFFu;
+      else {
+        const double x = (double)__uint_as_float(bits);   // exact in f64, and so is the rounded value
+        bits = __float_as_uint((float)(op == RDFGPU_EX_ROUND ? f64_round(x) : op == RDFGPU_EX_CEIL ? ceil(x) : floor(x)));
+      }
+      a.lo = (int64_t)(uint64_t)bits; return a; }
+    case NK_DOUBLE: {
+      uint64_t bits = (uint64_t)a.lo;
+      if (neg_op) bits ^= 1ull << 63;
+      else if (abs_op) bits &= ~(1ull << 63);
+      else {
+        const double x = __longlong_as_double((long long)bits);
+        bits = (uint64_t)__double_as_longlong(op == RDFGPU_EX_ROUND ? f64_round(x) : op == RDFGPU_EX_CEIL ? ceil(x) : floor(x));
+      }
+      a.lo = (int64_t)bits; return a; }
+    default: {
+      const i128_t v = val_dec(a);
+      i128_t z;
+      if (neg_op || abs_op) {
+        if (abs_op && v >= 0) return a;
+        if (!i128_from_mag(false, i128_mag(v), z)) return r;                       // -MIN
+        if (neg_op && v > 0) z = -v;
+      } else if (!dec_checked_round(v, op == RDFGPU_EX_ROUND ? 0 : op == RDFGPU_EX_CEIL ? 1 : 2, z)) return r;
+      set_dec(a, z); return a; }
+  }
+}
+// CAST to boolean / int / integer / decimal / float / double, scalar/conversion/cast_*.rs:48-62.  Booleans cast as 0 / 1; floats reach
+// the integer kinds through Decimal::try_from (decimal.rs:420-435) and a truncating division (decimal.rs:464-494); a simple literal
+// would have to be parsed: the plan's run-time error, never answered differently.
+__device__ __noinline__ Val tv_cast(Val a, uint32_t target, uint32_t* rt_error) {
+  Val r = val_tv_null();
+  int k = num_kind(a.tag);
+  if (a.tag == RDFGPU_TV_BOOLEAN) { a.lo = a.lo != 0; k = NK_INTEGER; }
+  else if (a.tag == RDFGPU_TV_STRING && a.aux == 0) { if (rt_error) atomicOr(rt_error, kRtCastFromString); return r; }
+  else if (k == NK_NONE) return r;
+  r.tag = (uint8_t)target;
+  switch (target) {
+    case RDFGPU_TV_BOOLEAN:   // boolean.rs:51-84
+      r.lo = k == NK_FLOAT ? (__uint_as_float((uint32_t)a.lo) != 0.0f && !isnan(__uint_as_float((uint32_t)a.lo)))
+           : k == NK_DOUBLE ? (__longlong_as_double(a.lo) != 0.0 && !isnan(__longlong_as_double(a.lo)))
+           : k == NK_DECIMAL ? (a.lo | a.hi) != 0 : a.lo != 0;
+      return r;
+    case RDFGPU_TV_FLOAT: r.lo = (int64_t)(uint64_t)__float_as_uint(to_f32(a, k)); return r;
+    case RDFGPU_TV_DOUBLE: r.lo = __double_as_longlong(to_f64(a, k)); return r;
+    default: break;
+  }
+  i128_t d;
+  if (k == NK_FLOAT || k == NK_DOUBLE) { if (!f64_to_dec(to_f64(a, k), d)) return val_tv_null(); }
+  else d = to_dec(a, k);
+  if (target == RDFGPU_TV_DECIMAL) { set_dec(r, d); return r; }
+  const u128_t q = u128_div(i128_mag(d), kDecOne);   // below 2^68
+  const bool neg = d < 0;
+  const u128_t lim = target == RDFGPU_TV_INT ? (u128_t)1 << 31 : (u128_t)1 << 63;
+  if (neg ? q > lim : q >= lim) return val_tv_null();
+  r.lo = neg ? (int64_t)(0ull - (uint64_t)q) : (int64_t)(uint64_t)q;
+  return r;
 }
 
 // EBV, effective_boolean_value.rs:99-119 : 0 / 1 / 2 (error => null)
@@ -451,6 +665,10 @@ __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const Typed
                      : e.op == RDFGPU_EX_LEQ ? o <= 0 : e.op == RDFGPU_EX_EQ ? o == 0 : o != 0;
         v = val_tv_bool(r); break; }
       case RDFGPU_EX_ADD: case RDFGPU_EX_SUB: { const Val b = st[--sp]; const Val a = st[--sp]; v = tv_arith(a, b, e.op == RDFGPU_EX_SUB); break; }
+      case RDFGPU_EX_MUL: case RDFGPU_EX_DIV: { const Val b = st[--sp]; const Val a = st[--sp]; v = tv_muldiv(a, b, e.op == RDFGPU_EX_DIV); break; }
+      case RDFGPU_EX_NEG: case RDFGPU_EX_PLUS: case RDFGPU_EX_ABS: case RDFGPU_EX_ROUND: case RDFGPU_EX_CEIL: case RDFGPU_EX_FLOOR:
+        v = tv_unary_numeric(st[--sp], e.op); break;
+      case RDFGPU_EX_CAST: v = tv_cast(st[--sp], e.u, tt.rt_error); break;
       case RDFGPU_EX_EBV: v = val_bool(tv_ebv(st[--sp])); break;
       case RDFGPU_EX_REGEX: v = tv_regex(prog.regex[e.u], tt, st[--sp], -1, &prog); break;
       case RDFGPU_EX_REGEX_VAR: { const Val pat = st[--sp]; const Val val = st[--sp]; v = tv_regex_var(prog.regex, e.u, (uint32_t)e.lo, tt, val, pat, &prog); break; }

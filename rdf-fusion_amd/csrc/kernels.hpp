@@ -296,7 +296,10 @@ struct AggArgs {
   const u64* n_dev; u64 cap;                     // input rows: the device count when n_dev, else cap
   u32 n_aggs;
   u32 fn[RDFGPU_MAX_AGGREGATES];                 // RDFGPU_AGG_*
-  const u32* in[RDFGPU_MAX_AGGREGATES];          // input column (COUNT_STAR: unused)
+  const u32* in[RDFGPU_MAX_AGGREGATES];          // input column (COUNT_STAR and expression inputs: unused)
+  const ExprProgram* prog[RDFGPU_MAX_AGGREGATES];   // SUM / AVG over an expression (RDFGPU_AGG_INPUT_EXPR): its program (device copy), else null
+  const u32* col[kMaxCols];                      // .. the input's columns, which the programs read
+  u32 exprs;                                     // 1 = some aggregate has a program: pass 2 runs its VM instantiation
   u32 word0[RDFGPU_MAX_AGGREGATES];              // first accumulator word of each aggregate (word 0 = rows of the group)
   u32 n_words;
   u8 word_op[kAggMaxWords];                      // how each word is merged (AggWordOp)

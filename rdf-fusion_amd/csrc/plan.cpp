@@ -69,7 +69,13 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
       case RDFGPU_EX_LIT_BOOL: out = VK_BOOL; break;
       case RDFGPU_EX_ENC_TV: pop(VK_ID, "ENC_TV"); out = VK_TV; break;
       case RDFGPU_EX_GT: case RDFGPU_EX_LT: case RDFGPU_EX_GEQ: case RDFGPU_EX_LEQ: case RDFGPU_EX_EQ: case RDFGPU_EX_NEQ:
-      case RDFGPU_EX_ADD: case RDFGPU_EX_SUB: pop(VK_TV, "binary typed op"); pop(VK_TV, "binary typed op"); out = VK_TV; break;
+      case RDFGPU_EX_ADD: case RDFGPU_EX_SUB: case RDFGPU_EX_MUL: case RDFGPU_EX_DIV: pop(VK_TV, "binary typed op"); pop(VK_TV, "binary typed op"); out = VK_TV; break;
+      case RDFGPU_EX_NEG: case RDFGPU_EX_PLUS: case RDFGPU_EX_ABS: case RDFGPU_EX_ROUND: case RDFGPU_EX_CEIL: case RDFGPU_EX_FLOOR:
+        pop(VK_TV, "unary numeric op"); out = VK_TV; break;
+      case RDFGPU_EX_CAST:
+        if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
+          fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
+        pop(VK_TV, "CAST"); out = VK_TV; break;
       case RDFGPU_EX_EBV: pop(VK_TV, "EBV"); out = VK_BOOL; break;
       case RDFGPU_EX_REGEX: case RDFGPU_EX_CONTAINS: case RDFGPU_EX_STRSTARTS: case RDFGPU_EX_STRENDS:
         if (e.u >= n_regexes) fail(RDFGPU_ERR_INVALID, "expression: REGEX pattern %u out of range (%u patterns)", e.u, n_regexes);
@@ -356,10 +362,31 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
         if (r.table_cols && ((u64)r.table_slot + 2ull * r.table_cols > d->n_pool || !d->pool)) fail(RDFGPU_ERR_INVALID, "node %u: aggregate list outside the pool", i);
         for (u32 a = 0; a < r.table_cols; a++) {
           const u32 fn = d->pool[r.table_slot + 2 * a], in = d->pool[r.table_slot + 2 * a + 1];
+          const bool expr = fn != RDFGPU_AGG_COUNT_STAR && (in & RDFGPU_AGG_INPUT_EXPR) != 0;
           switch (fn) {
             case RDFGPU_AGG_COUNT_STAR: break;
-            case RDFGPU_AGG_COUNT: case RDFGPU_AGG_COUNT_DISTINCT: case RDFGPU_AGG_SUM: case RDFGPU_AGG_AVG:
-              if (in >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, in, c.width);
+            case RDFGPU_AGG_COUNT: case RDFGPU_AGG_COUNT_DISTINCT:
+              if (expr) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: COUNT / COUNT DISTINCT over an expression is not on the device (SUM and AVG are)", i, a);
+              [[fallthrough]];
+            case RDFGPU_AGG_SUM: case RDFGPU_AGG_AVG:
+              if (expr) {   // (expr_off, expr_len) in the pool: a program over the input's columns that leaves a typed value
+                const u32 at = in & ~RDFGPU_AGG_INPUT_EXPR;
+                if ((u64)at + 2 > d->n_pool) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression input at pool offset %u of %u", i, a, at, d->n_pool);
+                const u32 off = d->pool[at], len = d->pool[at + 1];
+                if (len == 0 || (u64)off + len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression outside the expression array", i, a);
+                for (u32 q = 0; q < len; q++) {   // the pattern ops get their per-node preparation in FilterExec and the joins only
+                  const u8 op = d->exprs[off + q].op;
+                  if (op == RDFGPU_EX_REGEX || op == RDFGPU_EX_REGEX_VAR || op == RDFGPU_EX_CONTAINS || op == RDFGPU_EX_STRSTARTS || op == RDFGPU_EX_STRENDS || op == RDFGPU_EX_LANG_IN)
+                    fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES in an aggregate's input expression are not on the device", i, a);
+                }
+                if (check_program(d->exprs + off, len, c.width, d->n_regexes) != VK_TV) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: the input expression does not yield a typed value", i, a);
+                ExprProgram pr{};
+                pr.n = len;
+                std::memcpy(pr.nodes, d->exprs + off, len * sizeof(rdfgpu_expr_node));
+                pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
+                nd.agg_prog[a] = (int)nd.agg_progs.size();
+                nd.agg_progs.push_back(pr);
+              } else if (in >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, in, c.width);
               break;
             case RDFGPU_AGG_MIN: case RDFGPU_AGG_MAX: case RDFGPU_AGG_SAMPLE: case RDFGPU_AGG_GROUP_CONCAT:
               fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: MIN / MAX / SAMPLE / GROUP_CONCAT are not on the device (MIN / MAX keep the first "
@@ -368,7 +395,7 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
               fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: SUM / AVG with DISTINCT and COUNT(DISTINCT *) are not on the device", i, a);
             default: fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: unknown function %u", i, a, fn);
           }
-          nd.agg_fn[a] = fn; nd.agg_col[a] = fn == RDFGPU_AGG_COUNT_STAR ? 0 : in;
+          nd.agg_fn[a] = fn; nd.agg_col[a] = fn == RDFGPU_AGG_COUNT_STAR || expr ? 0 : in;
         }
         nd.n_aggs = r.table_cols;
         if (nd.n_aggs && i != d->root) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: an AggregateExec with aggregates must be the plan's root (node %u)", i, d->root);
@@ -604,7 +631,8 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::oj_write_band_kernel(rdfgpu::OrderedJoinArgs, rdfgpu::OjBandFuse, rdfgpu::OjInPlace)", "void rdfgpu::semi_build_kernel",
       "void rdfgpu::semi_join_kernel<0, false", "void rdfgpu::semi_join_kernel<0, true", "void rdfgpu::semi_join_kernel<1, false",
       "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true",
-      "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel"};
+      "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel",
+      "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -832,6 +860,7 @@ void Plan::execute() {
   RDFGPU_HIP(hipGetLastError());
   if (const u32 rt = (u32)(ctx->counters_host[255] & 0xFFFFFFFFull)) {   // a row asked for something that is refused loudly, not answered differently
     if (rt & 1u) fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with \\d \\w \\s or \\b over a string with non-ASCII characters needs the regex crate's Unicode tables (not restated)");
+    if (rt & 8u) fail(RDFGPU_ERR_UNSUPPORTED, "a numeric CAST met a simple literal: the lexical forms of numbers are not parsed on the device");
     if (rt & 4u) fail(RDFGPU_ERR_UNSUPPORTED, "a string expression met what the device does not restate: UCASE / LCASE of a string with non-ASCII characters (Unicode case tables), "
                                                "a float / double / decimal SUBSTR position, or a comparison with a string that has no bytes on the device");
     fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with a per-row pattern: a row's pattern literal was not announced in the plan's pattern table");
@@ -1271,7 +1300,12 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
   bool distinct = false;
   for (u32 i = 0; i < a.n_aggs; i++) {
     const u32 fn = nd.agg_fn[i];
-    a.fn[i] = fn; a.in[i] = fn == RDFGPU_AGG_COUNT_STAR ? nullptr : in.cols[nd.agg_col[i]];
+    a.fn[i] = fn; a.in[i] = fn == RDFGPU_AGG_COUNT_STAR || nd.agg_prog[i] >= 0 ? nullptr : in.cols[nd.agg_col[i]];
+    if (nd.agg_prog[i] >= 0) {   // SUM / AVG over an expression: the VM form of the accumulate pass, over every input column
+      a.prog[i] = upload_program(nd.agg_progs[nd.agg_prog[i]]);
+      a.exprs = 1;
+      for (u32 c = 0; c < in.n_cols; c++) a.col[c] = in.cols[c];
+    }
     a.word0[i] = a.n_words;
     const u32 words = fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? kAggSumWords : 1;
     for (u32 w = 0; w < words; w++) a.word_op[a.n_words + w] = words == 1 ? kAggAdd : w == 0 ? kAggOr : w >= 9 ? kAggAddF64 : kAggAdd;
@@ -1314,7 +1348,7 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
       }
     }
     a.lds = !opt.on(RDFGPU_OPT_NO_AGG_LDS) && (u64)a.n_words * G * sizeof(unsigned long long) <= kAggLdsBytes;
-    timed(a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
+    timed(a.exprs ? (a.lds ? KC_AGG_ACCUM_EXPR_LDS : KC_AGG_ACCUM_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
   }
   timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
   return t;

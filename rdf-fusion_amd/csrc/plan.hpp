@@ -51,6 +51,8 @@ struct NodeInfo {
   bool transient_direct_failed = false;        // a build side that is not cached turned out not to be unique and dense: do not try the direct-address form again
   int parent = -1;                             // the one operator consuming this node (-1: the root, or several)
   u32 n_aggs = 0; u32 agg_fn[RDFGPU_MAX_AGGREGATES] = {}, agg_col[RDFGPU_MAX_AGGREGATES] = {};   // AggregateExec: (RDFGPU_AGG_*, input column)
+  int agg_prog[RDFGPU_MAX_AGGREGATES] = {-1, -1, -1, -1, -1, -1, -1, -1};                           // .. or the index in agg_progs of its input expression (RDFGPU_AGG_INPUT_EXPR)
+  std::vector<ExprProgram> agg_progs;
   BandHistory band;                            // the band join based on this node, if there was one
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
@@ -138,6 +140,7 @@ enum KernelClass {
   KC_SEMI_BUILD, KC_SEMI_JOIN0,      // 6 names: semi_join_kernel<form 0 / 1, anti>, semi_nested_kernel<anti> (semi_join_class)
   KC_SEMI_JOIN_END = KC_SEMI_JOIN0 + 6,
   KC_AGG_GROUPS = KC_SEMI_JOIN_END, KC_AGG_ACCUM_HBM, KC_AGG_ACCUM_LDS, KC_AGG_FINAL,
+  KC_AGG_ACCUM_EXPR_HBM, KC_AGG_ACCUM_EXPR_LDS,   // agg_accum_expr_kernel<LDS>: some SUM / AVG reads an expression
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };

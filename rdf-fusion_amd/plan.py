@@ -186,6 +186,31 @@ def SUB(a, b): return a._bin(b, abi.EX_SUB)
 def EBV(e): return e._un(abi.EX_EBV)
 
 
+# Numeric expressions (include/rdfgpu.h, ABI 4 addendum): scalar/numeric/{mul,div,unary_minus,unary_plus,abs,round,ceil,floor}.rs and the
+# XSD constructor functions scalar/conversion/cast_*.rs.
+def MUL(a, b): return a._bin(b, abi.EX_MUL)
+def DIV(a, b): return a._bin(b, abi.EX_DIV)
+def NEG(e): return e._un(abi.EX_NEG)
+def PLUS(e): return e._un(abi.EX_PLUS)
+def ABS(e): return e._un(abi.EX_ABS)
+def ROUND(e): return e._un(abi.EX_ROUND)
+def CEIL(e): return e._un(abi.EX_CEIL)
+def FLOOR(e): return e._un(abi.EX_FLOOR)
+
+
+def CAST(e, tag):
+    """xsd:<type>(e): `tag` = abi.TV_BOOLEAN / TV_INT / TV_INTEGER / TV_DECIMAL / TV_FLOAT / TV_DOUBLE (another tag is the library's to refuse)."""
+    return Expr(e.nodes + [(abi.EX_CAST, 0, 0, int(tag), 0, 0)])
+
+
+def xsd_boolean(e): return CAST(e, abi.TV_BOOLEAN)
+def xsd_int(e): return CAST(e, abi.TV_INT)
+def xsd_integer(e): return CAST(e, abi.TV_INTEGER)
+def xsd_decimal(e): return CAST(e, abi.TV_DECIMAL)
+def xsd_float(e): return CAST(e, abi.TV_FLOAT)
+def xsd_double(e): return CAST(e, abi.TV_DOUBLE)
+
+
 def REGEX(e, pattern, flags=""):
     """REGEX(value, "pattern"[, "flags"]) with constant pattern / flags (scalar/strings/regex.rs:47-141)."""
     enc = lambda x: x.encode("utf-8") if isinstance(x, str) else bytes(x)
@@ -467,20 +492,37 @@ class PlanBuilder:
 
     def aggregate(self, left, group_by, aggregates=()):
         """AggregateExec(mode=Single): GROUP BY the id columns `group_by` (0 to 4) with `aggregates` = [(abi.AGG_*, input column), ...]
-        (at most 8; AGG_COUNT_STAR takes no column: None).  Output: the keys in order, then the aggregates, named like DataFusion's
-        display (`COUNT(y)`).  Only the key columns are ids: a node with aggregates must be the plan's root."""
+        (at most 8; AGG_COUNT_STAR takes no column: None).  The input of AGG_SUM / AGG_AVG may be an `Expr` over the input's columns that
+        yields a typed value (`MUL(ENC_TV(col(1)), ENC_TV(col(2)))`): it goes into the pool as abi.AGG_INPUT_EXPR | offset of
+        (expr_off, expr_len).  Output: the keys in order, then the aggregates, named like DataFusion's display (`COUNT(y)`,
+        `SUM(MUL(ENC_TV(a), ENC_TV(b)))`).  Only the key columns are ids: a node with aggregates must be the plan's root."""
         group_by = [int(c) for c in group_by]
-        aggregates = [(int(fn), None if c is None else int(c)) for fn, c in aggregates]
+        aggregates = [(int(fn), c if c is None or isinstance(c, Expr) else int(c)) for fn, c in aggregates]
         names = self.names[left]
         n = abi.PlanNode(kind=abi.NODE_AGGREGATE, left=left, right=-1, n_keys=len(group_by), table_cols=len(aggregates),
                          table_slot=len(self.pool))
         for k, c in enumerate(group_by[:abi.MAX_KEYS]):
             n.left_keys[k] = c
         n.n_keys = len(group_by)           # (more than MAX_KEYS is the library's to refuse)
+        first = len(self.pool) + 2 * len(aggregates)   # the (expr_off, expr_len) pairs follow the aggregate list
+        n_expr = 0
         for fn, c in aggregates:
-            self.pool.extend([fn, 0 if c is None else c])
+            if isinstance(c, Expr):
+                self.pool.extend([fn, abi.AGG_INPUT_EXPR | (first + 2 * n_expr)])
+                n_expr += 1
+            else:
+                self.pool.extend([fn, 0 if c is None else c])
+        labels = []
+        for fn, c in aggregates:
+            if isinstance(c, Expr):
+                holder = abi.PlanNode()
+                self._expr(holder, c)
+                self.pool.extend([holder.expr_off, holder.expr_len])
+                labels.append(_agg_label(fn, format_expr(self.exprs[holder.expr_off:holder.expr_off + holder.expr_len], names, at=False)))
+            else:
+                labels.append(_agg_label(fn, None if c is None else names[c]))
         n.n_proj = abi.NO_PROJECTION
-        out = [names[c] for c in group_by] + [_agg_label(fn, None if c is None else names[c]) for fn, c in aggregates]
+        out = [names[c] for c in group_by] + labels
         return self._push(n, len(out), out)
 
     def build(self, root):
@@ -556,9 +598,13 @@ class PlanBuilder:
 # MemQuadPatternDataSource::fmt_as prints them, pattern_data_source.rs:80-105)
 # ----------------------------------------------------------------------------------------------
 _BIN = {abi.EX_GT: "GT", abi.EX_LT: "LT", abi.EX_GEQ: "GEQ", abi.EX_LEQ: "LEQ", abi.EX_EQ: "EQ", abi.EX_ADD: "ADD", abi.EX_SUB: "SUB",
-        abi.EX_IS_COMPATIBLE: "IS_COMPATIBLE"}
+        abi.EX_IS_COMPATIBLE: "IS_COMPATIBLE", abi.EX_MUL: "MUL", abi.EX_DIV: "DIV"}
 _JOIN_TYPE_NAMES = {abi.JOIN_INNER: "Inner", abi.JOIN_LEFT: "Left", abi.JOIN_LEFT_SEMI: "LeftSemi", abi.JOIN_LEFT_ANTI: "LeftAnti"}
-_UN = {abi.EX_ENC_TV: "ENC_TV", abi.EX_EBV: "EBV", abi.EX_BOUND: "BOUND", abi.EX_BOOL_AS_TV: "BOOLEAN_AS_TERM"}
+_UN = {abi.EX_ENC_TV: "ENC_TV", abi.EX_EBV: "EBV", abi.EX_BOUND: "BOUND", abi.EX_BOOL_AS_TV: "BOOLEAN_AS_TERM",
+       abi.EX_NEG: "MINUS", abi.EX_PLUS: "PLUS", abi.EX_ABS: "ABS", abi.EX_ROUND: "ROUND", abi.EX_CEIL: "CEIL", abi.EX_FLOOR: "FLOOR"}
+# BuiltinName::CastBoolean .. CastDouble as the reference's plans print them (`xsd:integer(..)`)
+_CAST = {abi.TV_BOOLEAN: "xsd:boolean", abi.TV_INT: "xsd:int", abi.TV_INTEGER: "xsd:integer", abi.TV_DECIMAL: "xsd:decimal",
+         abi.TV_FLOAT: "xsd:float", abi.TV_DOUBLE: "xsd:double"}
 
 
 def _agg_label(fn, column, at=None):
@@ -571,14 +617,15 @@ def _agg_label(fn, column, at=None):
     return f"{abi.AGG_NAMES.get(fn, f'AGG{fn}')}({arg})"
 
 
-def format_expr(nodes, names):
+def format_expr(nodes, names, at=True):
     """A postfix program as DataFusion prints the PhysicalExpr tree (`EBV(GT(ENC_TV(value1@1), 9:136))`,
-    `product@0 != <object id>`, `.. AND ..`); object-id literals print as the snapshots mask them (<c>)."""
+    `product@0 != <object id>`, `.. AND ..`); object-id literals print as the snapshots mask them (<c>).  `at=False`: columns by
+    name only, as in an output column's name (`SUM(MUL(ENC_TV(a), ENC_TV(b)))`)."""
     st = []
     for n in nodes:
         op, tag, u, lo = n.op, n.tag, n.u, n.lo
         if op == abi.EX_COLUMN:
-            st.append(f"{names[u]}@{u}")
+            st.append(f"{names[u]}@{u}" if at else f"{names[u]}")
         elif op == abi.EX_LIT_ID:
             st.append("<c>")
         elif op == abi.EX_LIT_TV:
@@ -587,6 +634,8 @@ def format_expr(nodes, names):
             st.append({0: "false", 1: "true", 2: "NULL"}[u])
         elif op in _UN:
             st.append(f"{_UN[op]}({st.pop()})")
+        elif op == abi.EX_CAST:
+            st.append(f"{_CAST.get(u, f'cast{u}')}({st.pop()})")
         elif op in _BIN:
             b, a = st.pop(), st.pop()
             st.append(f"{_BIN[op]}({a}, {b})")
@@ -670,6 +719,10 @@ def explain(pb, root, choose_index=None):
             aggs = []
             for a in range(n.table_cols):
                 fn, c = pb.pool[n.table_slot + 2 * a], pb.pool[n.table_slot + 2 * a + 1]
+                if fn != abi.AGG_COUNT_STAR and c & abi.AGG_INPUT_EXPR:
+                    off, ln = pb.pool[c & ~abi.AGG_INPUT_EXPR], pb.pool[(c & ~abi.AGG_INPUT_EXPR) + 1]
+                    aggs.append(_agg_label(fn, format_expr(pb.exprs[off:off + ln], full)))
+                    continue
                 aggs.append(_agg_label(fn, None if fn == abi.AGG_COUNT_STAR else full[c], c))
             lines.append(f"{pad}AggregateExec: mode=Single, gby=[{gby}], aggr=[{', '.join(aggs)}]")
             walk(n.left, depth + 1)
