@@ -69,6 +69,14 @@ def multiset(cols, n_rows=None):
     return m[order]
 
 
+def assert_same_sequence(got, exp, n, what=""):
+    """rows 0 .. n of two column lists are the same rows in the same order - for results whose order is stated (a TopK root)"""
+    assert len(got) == len(exp), (what, len(got), len(exp))
+    if len(got):
+        np.testing.assert_array_equal(np.stack([np.asarray(c, dtype=np.uint32)[:n] for c in got], 1),
+                                      np.stack([np.asarray(c, dtype=np.uint32)[:n] for c in exp], 1), err_msg=what)
+
+
 def kat_literal(v):
     """["int"|"integer"|"decimal"|"double"|"float", value] or ["string", rank, language id] of reference_kats.json -> a
     typed-value literal expression; "NaN" / "INF" / "-INF" / "MAX" / "MIN" name the IEEE specials of the kind"""

@@ -3,7 +3,7 @@ variables / graph variables, bound tables with nulls, FilterExecs over every exp
 with one or two keys, residual filters and projections, cross / nested-loop joins, UnionExec, KleenePlusClosureExec,
 DISTINCT + TopK) over a small random store with every typed-value kind.  Every plan runs three times (first run,
 speculative re-execution, fused chain) and a second time from a freshly compiled plan (store-level table caches); each
-result is compared multiset-equal with the oracle's.  The reference's own strategy for this layer is example-based
+result is compared multiset-equal with the oracle's, and row by row where the plan's root is a TopK.  The reference's own strategy for this layer is example-based
 (SURVEY §4); this adds the property-based side."""
 import numpy as np
 import pytest
@@ -261,6 +261,7 @@ def test_random_operator_trees(torch_cuda, seed, size):
             skipped += 1
             continue
         want = ku.multiset(exp, n_exp)
+        ordered = pb.nodes[root].kind == abi.NODE_TOPK                                  # a TopK root states the order of its rows
         try:
             gs.plan(desc).close()
         except rf.RdfGpuError as e:                                                     # documented limits (e.g. > 40 expression nodes): refused
@@ -275,6 +276,8 @@ def test_random_operator_trees(torch_cuda, seed, size):
                 got = plan.execute().fetch()
                 assert plan.result_info()[0] == n_exp, (seed, it, fresh, rep)
                 np.testing.assert_array_equal(ku.multiset(got, n_exp), want, err_msg=f"seed {seed} plan {it} fresh {fresh} rep {rep}")
+                if ordered:
+                    ku.assert_same_sequence(got, exp, n_exp, f"seed {seed} plan {it} fresh {fresh} rep {rep}")
             if fresh == 1 and it % 10 == 9:
                 # the store changes under a compiled plan (cached slice tables, located ranges, range indexes and verdict
                 # tables belong to a store version): the same plan object must answer for the new contents
@@ -293,6 +296,8 @@ def test_random_operator_trees(torch_cuda, seed, size):
                     got = plan.execute().fetch()
                     assert plan.result_info()[0] == n2, (seed, it, "after mutation")
                     np.testing.assert_array_equal(ku.multiset(got, n2), ku.multiset(exp2, n2), err_msg=f"seed {seed} plan {it} after store mutation")
+                    if ordered:
+                        ku.assert_same_sequence(got, exp2, n2, f"seed {seed} plan {it} after store mutation")
                 mutated += 1
             plan.close()
         ran += 1

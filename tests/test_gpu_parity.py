@@ -33,7 +33,8 @@ def both_stores(quads, batch=8192, typed=None, decimals=None):
     return gs, os_
 
 
-def run_both(gs, os_, desc, gpu_tables=None, cpu_tables=None):
+def run_both(gs, os_, desc, gpu_tables=None, cpu_tables=None, ordered=False):
+    """ordered: the plan's root is a TopK, whose rows come out in a stated order: the sequences are compared as well"""
     plan = gs.plan(desc)
     if gpu_tables:
         for slot, (ptrs, n) in enumerate(gpu_tables):
@@ -45,6 +46,8 @@ def run_both(gs, os_, desc, gpu_tables=None, cpu_tables=None):
     assert n_got == n_exp, (n_got, n_exp)
     assert len(got) == len(exp)
     np.testing.assert_array_equal(ku.multiset(got, n_got), ku.multiset(exp, n_exp))
+    if ordered:
+        ku.assert_same_sequence(got, exp, n_exp)
     return plan, got
 
 
@@ -1877,17 +1880,17 @@ def test_topk_distinct_matches_oracle(torch_cuda):
         for group, proj in ((0, None), (None, [1, 2]), (0, [2, 0, 1])):
             pb = PlanBuilder()
             desc = pb.build(pb.topk(pb.table(0, 3), keys=[(1, abi.SORT_BY_TERM), (2, abi.SORT_BY_ID)], limit=limit, group=group, projection=proj))
-            run_both(gs, os_, desc, gpu_tables=[(ptrs, n)], cpu_tables=[tab])
+            run_both(gs, os_, desc, gpu_tables=[(ptrs, n)], cpu_tables=[tab], ordered=True)
         pb = PlanBuilder()                                                 # three keys (Q4's ORDER BY label, product, propertyTextual)
         four = [g, lab, prod % 7 + 1, prod]
         keep4, ptrs4 = table_on_device(torch_cuda, four)
         for group, proj in ((None, [1, 2, 3]), (0, None)):
             pb = PlanBuilder()
             run_both(gs, os_, pb.build(pb.topk(pb.table(0, 4), keys=[(1, abi.SORT_BY_TERM), (2, abi.SORT_BY_ID), (3, abi.SORT_BY_ID)], limit=limit + 10,
-                                               group=group, projection=proj)), gpu_tables=[(ptrs4, n)], cpu_tables=[four])
+                                               group=group, projection=proj)), gpu_tables=[(ptrs4, n)], cpu_tables=[four], ordered=True)
         pb = PlanBuilder()                                                 # one key, by id
         run_both(gs, os_, pb.build(pb.topk(pb.table(0, 3), keys=[(2, abi.SORT_BY_ID)], limit=limit, group=0, projection=[0, 2])),
-                 gpu_tables=[(ptrs, n)], cpu_tables=[tab])
+                 gpu_tables=[(ptrs, n)], cpu_tables=[tab], ordered=True)
     # ORDER BY a numeric value (ENC_SORT of a numeric = Double::from(Numeric), total order; Q10's xsd:double(str(?price)))
     import test_oracle_pyarrow as tp
     tvn, decn, _ = tp.numeric_table(np.random.default_rng(6), 400)
@@ -1898,7 +1901,7 @@ def test_topk_distinct_matches_oracle(torch_cuda):
         for group in (None, 0):
             pb = PlanBuilder()
             run_both(gn, on_, pb.build(pb.topk(pb.table(0, 3), keys=[(2, abi.SORT_BY_DOUBLE), (1, abi.SORT_BY_ID), (2, abi.SORT_BY_ID)], limit=limit, group=group,
-                                               projection=[1, 2] if group is None else None)), gpu_tables=[(ptrs, n)], cpu_tables=[tab])
+                                               projection=[1, 2] if group is None else None)), gpu_tables=[(ptrs, n)], cpu_tables=[tab], ordered=True)
     # a numeric column cannot be ordered as a term here: refused loudly
     tv2 = tv.copy(); tv2["tag"][5] = abi.TV_INTEGER
     gs2, _ = both_stores((np.zeros(0, np.uint32),) * 4, typed=tv2)
@@ -1919,7 +1922,7 @@ def test_bsbm_q5_whole_query_on_device(bsbm_stores, torch_cuda):
     ds, gs, os_ = bsbm_stores
     rng = np.random.default_rng(21)
     for x in rng.choice(ds.n_products, 4, replace=False):
-        plan, got = run_both(gs, os_, bsbm.q5_plan(ds, ds.product(int(x)), topk=True))
+        plan, got = run_both(gs, os_, bsbm.q5_plan(ds, ds.product(int(x)), topk=True), ordered=True)
         assert plan.result_info()[0] <= 5
     desc = bsbm.q5_batch_plan(ds, topk=True)
     plan = gs.plan(desc)
@@ -1931,6 +1934,7 @@ def test_bsbm_q5_whole_query_on_device(bsbm_stores, torch_cuda):
         got = plan.execute().fetch()
         exp, n_exp, _ = os_.execute(desc, [params])
         np.testing.assert_array_equal(ku.multiset(got), ku.multiset(exp, n_exp))
+        ku.assert_same_sequence(got, exp, n_exp, f"batch of {batch}")      # instances ascending, each one's rows in ORDER BY order
         assert len(got[0]) <= 5 * batch
         # per instance the batch's rows are exactly the single-query plan's rows
         for i in (0, batch - 1):
@@ -1973,6 +1977,7 @@ def test_bsbm_10m_scale_configs(torch_cuda):
         got = plan.execute().fetch()
         exp, n_exp, _ = os_.execute(desc, [params])
         np.testing.assert_array_equal(ku.multiset(got), ku.multiset(exp, n_exp))
+        ku.assert_same_sequence(got, exp, n_exp)
 
 
 def test_bsbm_100m_timed_path_answers_to_the_oracle(torch_cuda):
@@ -2349,7 +2354,7 @@ def test_bsbm_q4_matches_oracle(bsbm_stores):
     assert total > 5
     # the whole query: + DISTINCT + ORDER BY label, product, propertyTextual + TopK(fetch = 15) (Q4 (Execution Plan).snap:7-8;
     # the OFFSET 5 above it, GlobalLimitExec, drops rows of a 15-row table on the host)
-    plan, got = run_both(gs, os_, bsbm.q4_plan(ds, ds.type_base + ds.n_types - 1, f1, f2, f3, 200, 300, topk=True))
+    plan, got = run_both(gs, os_, bsbm.q4_plan(ds, ds.type_base + ds.n_types - 1, f1, f2, f3, 200, 300, topk=True), ordered=True)
     assert 0 < plan.result_info()[0] <= 15
 
 
@@ -2396,7 +2401,7 @@ def test_bsbm_q10_matches_oracle(bsbm_stores):
     plan, got = run_both(gs, os_, bsbm.q10_plan(ds, ds.product(1), ds.country_base))      # the query's own constants
     # the whole query: + DISTINCT + ORDER BY xsd:double(str(?price)), ?offer, ?price LIMIT 10 (Q10 (Execution Plan).snap:6-8)
     for i in range(6):
-        plan, got = run_both(gs, os_, bsbm.q10_plan(ds, ds.product(i * 7), ds.country_base + i % ds.n_countries, max_days=21, after="2001-03-01T06:00:00", topk=True))
+        plan, got = run_both(gs, os_, bsbm.q10_plan(ds, ds.product(i * 7), ds.country_base + i % ds.n_countries, max_days=21, after="2001-03-01T06:00:00", topk=True), ordered=True)
         assert plan.result_info()[0] <= 10
     assert total > 10
 
