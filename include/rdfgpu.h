@@ -719,6 +719,7 @@ enum {
   RDFGPU_OPT_PARTITION_ROWS,            /* value: build rows per partition a partitioned join aims for (0 = automatic: 1024)   */
   RDFGPU_OPT_PARTITION_SLOTS,           /* value: slots of a partition's LDS table, a power of two from 1024 to 8192 (0 = automatic: 4096); a partition with more than slots / 2 build rows is joined chunk by chunk */
   RDFGPU_OPT_NO_SEMI_LDS,               /* flag: semi / anti joins never build their set of right rows in LDS (the HBM set, built per execution) */
+  RDFGPU_OPT_NO_BAND_ROW_CACHE,         /* flag: band join reading a slice's rows in place: the rows' decoded windows are not kept on the slice, every step gathers 16-byte records by key */
   RDFGPU_OPT_NO_AGG_LDS,                /* flag (ABI 4 addendum): AggregateExec never keeps per-workgroup partial accumulators in LDS (every row adds into the HBM accumulators) */
   RDFGPU_OPT__COUNT
 };
@@ -742,6 +743,14 @@ uint64_t rdfgpu_scan_score(const rdfgpu_scan_instruction instr[4]);
  * chosen permutation (ties prefer the first listed).
  */
 uint32_t rdfgpu_choose_index(const rdfgpu_scan_instruction gspo[4], uint32_t available);
+/*
+ * Band join reading a slice's rows in place: are the rows' decoded windows kept on the slice (1) or gathered by key every step (0)?
+ * operand_src / operand_keyed_by_join_key: per window w its two operands at [2w], [2w + 1] — where the ordered slice join below takes
+ * the operand from (0 = table row, 1 = slice row, 2 + t = stage t's row) and whether that stage's key column is the join's own key.
+ * option_set: RDFGPU_OPT_NO_BAND_ROW_CACHE.  A negative status on invalid arguments.
+ */
+int rdfgpu_band_row_cache_eligible(uint32_t in_place, uint32_t compact, uint32_t pack16, uint32_t option_set, uint32_t n_win,
+                                   const uint32_t operand_src[4], const uint32_t operand_keyed_by_join_key[4]);
 /*
  * MemIndexScanPredicate::try_and_with (scan_instructions.rs:170-210).  Predicates are given
  * as (pred, a, b) triples where IN sets are explicit arrays.  Writes the combined predicate;

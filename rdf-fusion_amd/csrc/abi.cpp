@@ -545,6 +545,19 @@ uint32_t rdfgpu_choose_index(const rdfgpu_scan_instruction gspo[4], uint32_t ava
     return choose_index(g, available);
   } catch (const std::exception& e) { set_last_error(e.what()); return 0xFFFFFFFFu; }
 }
+int rdfgpu_band_row_cache_eligible(uint32_t in_place, uint32_t compact, uint32_t pack16, uint32_t option_set, uint32_t n_win,
+                                   const uint32_t operand_src[4], const uint32_t operand_keyed_by_join_key[4]) {
+  try {
+    if (n_win > 2 || (n_win && (!operand_src || !operand_keyed_by_join_key))) fail(RDFGPU_ERR_INVALID, "band row cache: %u windows", n_win);
+    BandRowCacheShape s;
+    s.in_place = in_place != 0; s.compact = compact != 0; s.pack16 = pack16 != 0; s.option_off = option_set == 0; s.n_win = n_win;
+    for (u32 w = 0; w < n_win; w++) {
+      s.y0[w] = BandRowOperandShape{operand_src[2 * w], operand_keyed_by_join_key[2 * w] != 0};
+      s.y1[w] = BandRowOperandShape{operand_src[2 * w + 1], operand_keyed_by_join_key[2 * w + 1] != 0};
+    }
+    return band_row_cache_eligible(s) ? 1 : 0;
+  } catch (const Error& e) { set_last_error(e.what()); return e.status; }
+}
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;
   if (p->pred == RDFGPU_PRED_IN) { if (p->ids) r.ids.assign(p->ids, p->ids + p->n_ids); else r.ids = {p->from}; }

@@ -196,6 +196,12 @@ __global__ __launch_bounds__(256) void oj_band_records_kernel(const OrderedJoinA
   if (!linked) return;
   const u32* words = reinterpret_cast<const u32*>(a.trec) + r * 4ull * a.n_rec;
   auto word = [&](u8 slot) { return slot == 0xFFu ? 0u : words[slot]; };
+  if (f.key_val) {   // in place with the rows' windows cached on the slice (BandArgs::row_win): the row's output value is all that travels by key
+    const u32 v = word(f.row_slot[0]);
+    if (v == kNil) atomicAdd(b.slow_rows, 1u);   // (the value that says "no table row": the plan re-runs without the cached form, like any failed speculation)
+    f.key_val[key - a.kmin] = v;
+    return;
+  }
   u32 iy0[2], iy1[2];
 #pragma unroll
   for (u32 w = 0; w < 2; w++) { iy0[w] = word(f.y0_slot[w]); iy1[w] = word(f.y1_slot[w]); }
@@ -213,6 +219,54 @@ __global__ __launch_bounds__(256) void oj_band_records_kernel(const OrderedJoinA
 }
 void launch_oj_band_records(const OrderedJoinArgs& a, const BandArgs& b, const OjBandFuse& f, hipStream_t s) {
   if (a.n_probe_cap) hipLaunchKernelGGL(oj_band_records_kernel, grid256(a.n_probe_cap), dim3(256), 0, s, a, b, f);
+}
+
+// ---- the rows' windows as a table of the slice (BandArgs::row_win) ------------------------------------------------------------
+// In place, a row's windows are those of the table row that has its join key; when both operands of every window are reached from that
+// key alone (stages keyed by it), they are a function of the key, the store and the plan's literals: decoded once per store version.
+// Per key: the operand stages' look-ups, the operands' ids, band_row_record — what oj_band_records_kernel does per table row.  A key
+// without a stage row can have no linked table row: its record passes nothing.
+__global__ __launch_bounds__(256) void band_row_win_keys_kernel(const BandArgs b, const BandRowWinArgs w) {
+  const u32 d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= w.kn) return;
+  const u32 x = w.kmin + d;
+  auto fetch = [&](const BandRowOperand& op, u32& id) {
+    const u32 sd = x - op.kmin;
+    const u32 row = sd < op.kn ? op.direct[sd] : kNil;
+    if (row == kNil) return false;
+    id = op.val[row];
+    return true;
+  };
+  u32 iy0[2] = {0u, 0u}, iy1[2] = {0u, 0u};
+  bool has = x != 0;                                   // null keys never join
+#pragma unroll
+  for (u32 k = 0; k < 2; k++) if (k < b.n_win) { has = fetch(w.y0[k], iy0[k]) && has; has = fetch(w.y1[k], iy1[k]) && has; }
+  uint2 out = make_uint2(kBandPackedNone, 0u);
+  if (has) {
+    uint4 rec; u32 flags;
+    band_row_record(b, iy0, iy1, x, rec, flags);
+    if (flags & 1u) atomicAdd(w.slow_keys, 1u);
+    out = make_uint2(rec.x, rec.y);
+  }
+  w.by_key[d] = out;
+}
+// Per slice row (and the table's padding): its key's windows.
+__global__ __launch_bounds__(256) void band_row_win_rows_kernel(const BandRowWinArgs w) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= w.n_rows + 64) return;
+  uint2 out = make_uint2(kBandPackedNone, 0u);
+  if (i < w.n_rows) {
+    const u32 key = w.build_key[i];
+    const u32 d = key - w.kmin;
+    if (key != 0 && d < w.kn) out = w.by_key[d];
+  }
+  w.row_win[i] = out;
+}
+void launch_band_row_win_keys(const BandArgs& b, const BandRowWinArgs& w, hipStream_t s) {
+  if (w.kn) hipLaunchKernelGGL(band_row_win_keys_kernel, grid256(w.kn), dim3(256), 0, s, b, w);
+}
+void launch_band_row_win_rows(const BandRowWinArgs& w, hipStream_t s) {
+  hipLaunchKernelGGL(band_row_win_rows_kernel, grid256(w.n_rows + 64), dim3(256), 0, s, w);
 }
 
 // The records in sorted order: the one random access per probe row (32 contiguous bytes); everything downstream streams.
@@ -380,9 +434,10 @@ __global__ __launch_bounds__(256) void band_desc_kernel(const BandArgs b) {
 // kernel is NOT bound by those instructions (7 -> 6 per pair changed nothing; 200 k short waves with exposed scalar-load
 // latency are what it waits for; persistent waves made it slower, 240 -> 325 us).
 // NWIN = window stages (1..2; no window = one trivial window); NEQ = base filter: 0 none / 1 `!=` / 2 `=` / 3 `!=` by entry index (BandArgs::neq_self).
+// STATIC = the rows' windows come from the slice's cached table (BandArgs::row_win, row_val; NEQ = 3 and PACK): 12 bytes per row instead of 16.
 struct BandEntry8 { uint4 a[8]; };
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-template <int NWIN, int NEQ, bool PACK>
+template <int NWIN, int NEQ, bool PACK, bool STATIC = false>
 __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
   __shared__ uint4 ent[4][64];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -396,6 +451,10 @@ __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
   const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
   uint4 rec = PACK ? make_uint4(kBandPackedNone, 0u, 0u, 0u) : make_uint4(kBandInvalidLo, 0u, 1u, 0u);   // (nothing passes; PACK: the decode pass stored the packed form)
   u32 x = 0;
+  uint2 swin = make_uint2(kBandPackedNone, 0u); u32 sval = kNil;   // STATIC: the row's cached windows and this execution's value (kNil: its key has no table row)
+  if (STATIC) {
+    if (lane < nr) { swin = b.row_win[rb + lane]; sval = b.row_val[rb + lane]; x = rb + lane; }   // (the row's own entry is the row itself)
+  } else
   if (lane < nr) { rec = b.rec_s[rb + lane]; if (NEQ) x = b.compact ? rec.z : b.aux_s[rb + lane].x; }   // (compact: the 16-byte record carries the id operand itself)
   // The block's 64 entries go through LDS: lane e fetches entry e (one coalesced 1 KB load per block), every test then reads
   // ITS entry with a broadcast ds_read_b128 (all lanes one address).  Scalar loads (s_load_dwordx8 from the entry table) looked
@@ -404,6 +463,11 @@ __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
   u32 plo = 0, pw = 0;                                 // PACK: both windows' intervals as 2 x 16 bits
   {
     uint4 q = b.et[eb + lane];                          // the table is padded: reading past the group is harmless
+    if (STATIC) {   // windows, value and entry in ONE round trip: all three loads issued before the first wait (the compiler would wait for the value and load the windows under its verdict)
+      asm volatile("" :: "v"(swin.x), "v"(swin.y), "v"(sval), "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
+      const bool has = sval != kNil;
+      rec.x = has ? swin.x : rec.x; rec.y = has ? swin.y : rec.y;
+    }
     if (PACK) {
       q.x = (q.x & 0xFFFFu) | (q.y << 16);              // both windows' operands in one word
       plo = rec.x; pw = rec.y;
@@ -505,7 +569,8 @@ __global__ __launch_bounds__(256) void band_slow_kernel(const LdsJoinArgs* ap, c
 constexpr u32 kBandList = 1024;   // survivors listed at a time: a block with more is emitted 16 rows at a time (16 x 64 <= 1024)
 // NCOLS = output columns (1 .. 6): a template parameter so that only the live columns' pointers and selectors sit in SGPRs (the
 // six-column form kept 18 of them pinned and spilled scalars into vector lanes inside the loops)
-template <int NCOLS>
+// STATIC (BandArgs::row_win): the row's one output value is row_val[row] — 4 bytes per row, not the 16-byte record.
+template <int NCOLS, bool STATIC = false>
 __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
   __shared__ unsigned short list[4][kBandList];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -536,7 +601,10 @@ __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
   const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
   const u64 mask_all = lane < nr ? mask_raw : 0ull;
   u32 ev[kBandMaxSideCols], rv[kBandMaxRowCols];   // output values of the entry (lane = entry) / of the probe row (lane = row)
-  {
+  if (STATIC) {
+    rv[0] = 0u; rv[1] = 0u;
+    if (lane < nr) rv[0] = b.row_val[rb + lane];
+  } else {
     uint4 aux = make_uint4(0u, 0u, 0u, 0u);
     if (lane < nr) aux = b.compact ? b.rec_s[rb + lane] : b.aux_s[rb + lane];
     rv[0] = b.compact ? aux.w : aux.z; rv[1] = b.compact ? 0u : aux.w;
@@ -616,7 +684,13 @@ void launch_band_desc(const BandArgs& b, hipStream_t s) {
 }
 template <int NWIN, bool PACK> static void launch_band_mask_w(const BandArgs& b, dim3 g, hipStream_t s) {
   const int neq = b.has_neq ? (b.neq_is_eq ? 2 : b.neq_self ? 3 : 1) : 0;
-  if (neq == 3) { if constexpr (PACK) { hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true>), g, dim3(256), 0, s, b); return; } }
+  if (neq == 3) {
+    if constexpr (PACK) {
+      if (b.row_win) hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true>), g, dim3(256), 0, s, b);
+      else hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true>), g, dim3(256), 0, s, b);
+      return;
+    }
+  }
   if (neq == 0) hipLaunchKernelGGL((band_mask_kernel<NWIN, 0, PACK>), g, dim3(256), 0, s, b);
   else if (neq == 1) hipLaunchKernelGGL((band_mask_kernel<NWIN, 1, PACK>), g, dim3(256), 0, s, b);
   else hipLaunchKernelGGL((band_mask_kernel<NWIN, 2, PACK>), g, dim3(256), 0, s, b);
@@ -634,7 +708,15 @@ void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s
 void launch_band_emit(const BandArgs& b, hipStream_t s) {
   const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);
   static_assert(kBandMaxRowCols + kBandMaxSideCols == 6, "one instantiation per column count");
-  switch (b.n_out_cols) {
+  if (b.row_win) switch (b.n_out_cols) {
+    case 1: hipLaunchKernelGGL((band_emit_kernel<1, true>), g, dim3(256), 0, s, b); return;
+    case 2: hipLaunchKernelGGL((band_emit_kernel<2, true>), g, dim3(256), 0, s, b); return;
+    case 3: hipLaunchKernelGGL((band_emit_kernel<3, true>), g, dim3(256), 0, s, b); return;
+    case 4: hipLaunchKernelGGL((band_emit_kernel<4, true>), g, dim3(256), 0, s, b); return;
+    case 5: hipLaunchKernelGGL((band_emit_kernel<5, true>), g, dim3(256), 0, s, b); return;
+    case 6: hipLaunchKernelGGL((band_emit_kernel<6, true>), g, dim3(256), 0, s, b); return;
+  }
+  else switch (b.n_out_cols) {
     case 1: hipLaunchKernelGGL(band_emit_kernel<1>, g, dim3(256), 0, s, b); return;
     case 2: hipLaunchKernelGGL(band_emit_kernel<2>, g, dim3(256), 0, s, b); return;
     case 3: hipLaunchKernelGGL(band_emit_kernel<3>, g, dim3(256), 0, s, b); return;

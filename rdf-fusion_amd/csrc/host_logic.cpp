@@ -149,4 +149,12 @@ PrunePlan plan_pruning(const ScanInstructions& ix) {
   return p;
 }
 
+bool band_row_cache_eligible(const BandRowCacheShape& s) {
+  if (!s.in_place || !s.compact || !s.pack16 || !s.option_off || s.n_win > 2) return false;
+  for (u32 w = 0; w < s.n_win; w++)
+    for (const BandRowOperandShape* op : {&s.y0[w], &s.y1[w]})
+      if (op->src < 2 || !op->stage_keyed_by_join_key) return false;
+  return true;
+}
+
 }  // namespace rdfgpu

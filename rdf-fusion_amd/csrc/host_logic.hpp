@@ -50,4 +50,15 @@ struct PrunePlan {
 };
 PrunePlan plan_pruning(const ScanInstructions& ix);
 
+// Band join reading a store slice's rows in place (plan.cpp, exec_band_join): may the rows' decoded windows be kept on the slice
+// (SliceTable::BandRowWindows) instead of travelling by key every step?  Yes when the route is the in-place one with compact, packed
+// records, the option is off, and every window operand is a column the ordered slice join below reaches through a stage (src >= 2)
+// whose key column is that join's own key: the operand is then a function of the key alone, not of the batch.
+struct BandRowOperandShape { u32 src = 0; bool stage_keyed_by_join_key = false; };   // src: ColRef::src of the ordered join's output column holding the operand
+struct BandRowCacheShape {
+  bool in_place = false, compact = false, pack16 = false, option_off = false;
+  u32 n_win = 0; BandRowOperandShape y0[2], y1[2];
+};
+bool band_row_cache_eligible(const BandRowCacheShape& s);
+
 }  // namespace rdfgpu

@@ -346,6 +346,7 @@ struct OrderedJoinArgs {
   u32* row_head; unsigned char* row_cnt;                               // per slice row, from the count pass: first table row of its chain, chain length (capped at 255: longer chains are re-walked)
   u32* multi_rows;                                                     // table rows hung behind an existing chain head (null: not counted): a chain of 2+ rows rules out the in-place band records
   uint4* key_rec;                                                      // in place (OjInPlace): [kn] the band record of each key's table row, filled with one that passes nothing by the probe pass
+  u32* key_val;                                                        // .. with the rows' windows cached on the slice (BandArgs::row_win): [kn] the output value of each key's table row instead, filled with kNil (no table row)
 };
 struct BandArgs;
 // The ordered slice join feeding a band join (band_join.hip) writes the band join's ROW RECORDS itself: the windows, the id
@@ -362,6 +363,7 @@ struct OjBandFuse {
   u8 self_index;                     // the record's id-operand word holds the match's SLICE ROW instead (BandArgs::neq_self)
   u8 compact;                        // one 16-byte record per table row and match {lo pair, width pair, id operand, output value 0} instead of {record, aux} (BandArgs::compact)
   uint4* key_rec;                    // in place: the records by KEY (OrderedJoinArgs::key_rec) instead of by table row in brec — a slice row gathers its record in one step
+  u32* key_val; u32* row_val;        // in place, the rows' windows cached (BandArgs::row_win): the table rows' output values by KEY (OrderedJoinArgs::key_val); per slice row, its key's value (kNil: the key has no table row)
 };
 void launch_oj_band_records(const OrderedJoinArgs& a, const BandArgs& b, const OjBandFuse& f, hipStream_t s);
 void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, hipStream_t s);
@@ -482,7 +484,22 @@ struct BandArgs {
   ColRef entry_col[kBandMaxSideCols]; const u32* row_col[kBandMaxSideCols];
   u8 out_from_row[kMaxCols];  // per output column: 1 = next row column, 0 = next entry column
   u8 out_sel[kMaxCols];       // .. resolved: 0 / 1 = row column 0 / 1, 2 + u = entry column u
+  // in place, when a row's windows are a function of its join key alone (both operands reached through stages keyed by that key: host_logic.hpp,
+  // band_row_cache_eligible): row_win = the packed {lo pair, width pair} of every slice row, kept on the slice per store version beside the entries;
+  // row_val = this execution's output value per slice row (kNil: no table row has the row's key — its record passes nothing).  rec_s is not used.
+  const uint2* row_win; const u32* row_val;
 };
+// The build of BandArgs::row_win (band_join.hip): per join key d of [kmin, kmin + kn) the window operands are fetched through the operand stages' direct
+// tables and packed by band_row_record; then every slice row copies its key's 8 bytes.
+struct BandRowOperand { const u32* direct; u32 kmin, kn; const u32* val; };   // id of the operand = val[direct[key - kmin]] (no row: the key joins nothing)
+struct BandRowWinArgs {
+  BandRowOperand y0[2], y1[2];
+  u32 kmin, kn; uint2* by_key;       // the ordered slice join's key range; [kn] the packed windows by key
+  u32* slow_keys;                    // keys whose operands are not all xsd:integer (or overflow): counted — the cached form is declined when there is one
+  const u32* build_key; u64 n_rows; uint2* row_win;   // the slice's join-key column; row_win[n_rows + 64]
+};
+void launch_band_row_win_keys(const BandArgs& b, const BandRowWinArgs& w, hipStream_t s);
+void launch_band_row_win_rows(const BandRowWinArgs& w, hipStream_t s);
 void launch_band_pt(const BandArgs& b, hipStream_t s);
 void launch_band_entries(const BandArgs& b, hipStream_t s);
 void launch_band_rows(const BandArgs& b, hipStream_t s);      // records into sorted order

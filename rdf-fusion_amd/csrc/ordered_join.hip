@@ -26,6 +26,8 @@ __global__ __launch_bounds__(256) void oj_probe_kernel(const OrderedJoinArgs a) 
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (a.key_rec)   // (the records pass fills in the keys that have a table row)
     for (u64 z = r; z < a.kn; z += (u64)gridDim.x * blockDim.x) a.key_rec[z] = make_uint4(kBandPackedNone, 0u, 0u, 0u);
+  if (a.key_val)   // (the rows' windows are cached on the slice: only "this key has a table row, and its output value" is the execution's)
+    for (u64 z = r; z < a.kn; z += (u64)gridDim.x * blockDim.x) a.key_val[z] = kNil;
   const u64 n = live_rows(a.n_probe_dev, a.n_probe_cap);
   if (r >= n) return;
   const u32 key = a.probe_key[r];
@@ -261,6 +263,8 @@ __global__ __launch_bounds__(kOjBlock) void oj_write_band_kernel(const OrderedJo
 // records by key (4.6 MB at 285 K products; through head[] to a record by table row it took two dependent gathers), 16 bytes
 // written per row; kOjRounds rows per lane, every round's loads issued before the first is used.  A key with more rows is counted
 // by oj_probe_kernel (multi_rows): the plan then re-runs exactly and takes the counted route.
+// With the rows' windows cached on the slice (f.key_val, BandArgs::row_win) the pass carries the execution's part of a record alone: one
+// 4-byte gather per row from the values by key (1.1 MB at 285 K products: it stays in L2), 4 bytes written per row.
 __global__ __launch_bounds__(kOjBlock) void oj_write_band_kernel(const OrderedJoinArgs a, const OjBandFuse f, OjInPlace) {
   const u64 base = (u64)blockIdx.x * kOjTile + threadIdx.x;
   u32 dk[kOjRounds];
@@ -270,6 +274,17 @@ __global__ __launch_bounds__(kOjBlock) void oj_write_band_kernel(const OrderedJo
     const u32 key = row < a.n_build ? a.build_key[row] : 0u;
     const u32 d = key - a.kmin;
     dk[it] = key != 0 && d < a.kn ? d : kNil;
+  }
+  if (f.key_val) {   // (uniform)
+    u32 v[kOjRounds];
+#pragma unroll
+    for (int it = 0; it < kOjRounds; it++) v[it] = dk[it] != kNil ? f.key_val[dk[it]] : kNil;
+#pragma unroll
+    for (int it = 0; it < kOjRounds; it++) {
+      const u64 row = base + (u64)it * kOjBlock;
+      if (row < a.n_build) f.row_val[row] = v[it];
+    }
+    return;
   }
   uint4 rc[kOjRounds];
 #pragma unroll
@@ -289,7 +304,7 @@ void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& 
 }
 
 void launch_ordered_join_probe(const OrderedJoinArgs& a, hipStream_t s) {
-  const u64 n = a.key_rec && a.kn > a.n_probe_cap ? a.kn : a.n_probe_cap;   // (key_rec: one lane per key fills it, whatever the number of table rows)
+  const u64 n = (a.key_rec || a.key_val) && a.kn > a.n_probe_cap ? a.kn : a.n_probe_cap;   // (key_rec / key_val: one lane per key fills it, whatever the number of table rows)
   if (!n) return;
   hipLaunchKernelGGL(oj_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
 }

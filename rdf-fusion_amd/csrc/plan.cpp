@@ -632,7 +632,8 @@ const char* kernel_class_name(int kc) {
       "void rdfgpu::semi_join_kernel<0, false", "void rdfgpu::semi_join_kernel<0, true", "void rdfgpu::semi_join_kernel<1, false",
       "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true",
       "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel",
-      "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>"};
+      "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>",
+      "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -2193,7 +2194,9 @@ bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap)
   // (NO_BAND_COMPACT switches it off: the in-place records are the 16-byte ones)
   const bool in_place = held && nodes[consumer].band.in_place && nodes[consumer].band.multi_rows == 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT);
   if (held) o.multi_rows = reinterpret_cast<u32*>(new_counter());
-  if (in_place) o.key_rec = scratch<uint4>(a.direct_n);
+  // (.. and with the rows' windows cached on the slice last time, only the table rows' output values travel by key)
+  if (in_place && nodes[consumer].band.row_cache && !opt.on(RDFGPU_OPT_NO_BAND_ROW_CACHE)) o.key_val = scratch<u32>(a.direct_n);
+  else if (in_place) o.key_rec = scratch<uint4>(a.direct_n);
   timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
   if (!in_place) count_ordered_join(o);
   if (held) {
@@ -2340,7 +2343,12 @@ void Plan::exec_band_join(LdsJoin& j) {
   band_slice_tables(bj);
   hist.in_place = bj.lay.boff != nullptr;   // the layout exists: next time the ordered join below may leave its matches uncounted
   // In place: the ordered join below skipped its count pass, and the slice it streamed IS this join's build side.  Anything else counts the matches now and compacts them (the write-band pass).
-  bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place;
+  hist.row_cache = bj.row_win != nullptr;   // .. and its probe pass may prepare the values by key instead of the 16-byte records
+  // (the ordered join prepared what the last execution's flags said: values by key when the windows were cached, records by key otherwise — a step whose
+  // cached windows are gone, a non-integer operand having entered the store, counts and compacts once)
+  bj.row_static = bj.fused && bj.row_win && pending_oj.o.key_val;
+  bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place && (bj.row_static || pending_oj.o.key_rec);
+  bj.row_static = bj.row_static && bj.in_place;
   if (bj.fused && !bj.in_place) count_pending_oj();
   band_row_records(bj);
   band_blocks_and_emit(bj);
@@ -2411,6 +2419,7 @@ void Plan::band_slice_tables(BandJoin& bj) {
   if (bj.cache_entries) building.lock();
   band_entries(bj);
   if (const SliceTable::BandEntries* layout = band_layout(bj)) bj.lay = *layout;
+  band_row_windows(bj);
 }
 
 // The build side's decoded entries (the pair test's operands, the entries' output values), found on the slice's table (keys are unique there: an entry is
@@ -2465,11 +2474,58 @@ SliceTable::BandEntries* Plan::band_layout(BandJoin& bj) {
   return layout;
 }
 
+// In place, the ROW side of the pair test as a table of the slice: when both operands of every window are reached from the ordered join's key alone
+// (host_logic.hpp, band_row_cache_eligible) a slice row's windows are a function of the store and the plan's literals — decoded once per store version beside
+// the entries (same lock; built where the layout is, by the first execution that could take the route; fewer than 8 per slice), not gathered as 16-byte records
+// by key every step.  Its key = the entries' key + everything band_row_record reads.  A store in which some key's operands are not plain xsd:integers declines
+// the form: remembered as an entry without a table.  The caller holds the lock (the layout exists only when bj.cache_entries).
+void Plan::band_row_windows(BandJoin& bj) {
+  const BandArgs& b = bj.j.band; const OjBandFuse& fuse = bj.fuse; const OrderedJoinArgs& o = pending_oj.o; SliceTable* tab = bj.j.slice;
+  if (!bj.lay.boff) return;                              // the in-place route is closed
+  BandRowWinArgs w{}; BandRowCacheShape shape;
+  shape.in_place = true; shape.compact = fuse.compact != 0 && b.compact != 0; shape.pack16 = b.pack16 != 0;
+  shape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_ROW_CACHE); shape.n_win = b.n_win;
+  auto operand = [&](u8 slot, BandRowOperand& op, BandRowOperandShape& sh) {   // the ordered join's output column held in word `slot` of its packed record
+    for (u32 c = 0; c < o.n_out_cols; c++) {
+      if (slot == 0xFFu || o.out_slot[c] != slot) continue;
+      const ColRef ref = o.out_ref[c];
+      sh.src = ref.src;
+      if (ref.src >= 2 && ref.src - 2 < o.n_stages) {
+        const OrderedJoinStage& st = o.stage[ref.src - 2];
+        sh.stage_keyed_by_join_key = st.key_col == o.probe_key;
+        op = BandRowOperand{st.direct, st.kmin, st.kn, ref.ptr};
+      }
+      return;
+    }
+  };
+  for (u32 k = 0; k < b.n_win && k < 2; k++) { operand(fuse.y0_slot[k], w.y0[k], shape.y0[k]); operand(fuse.y1_slot[k], w.y1[k], shape.y1[k]); }
+  if (!band_row_cache_eligible(shape)) return;
+  std::string key = bj.ekey;
+  auto put = [&](const void* p, size_t n) { key.append(reinterpret_cast<const char*>(p), n); };
+  for (u32 k = 0; k < b.n_win; k++) {
+    put(&b.win[k].l0, sizeof(TvLiteral)); put(&b.win[k].l1, sizeof(TvLiteral)); put(&b.win[k].vbase, 8);
+    for (const BandRowOperand* op : {&w.y0[k], &w.y1[k]}) { put(&op->direct, sizeof(void*)); put(&op->kmin, 4); put(&op->kn, 4); put(&op->val, sizeof(void*)); }
+  }
+  put(&b.pack16, 4); put(&b.has_neq, 4); put(&b.tt.tv, sizeof(void*)); put(&b.tt.n_ids, sizeof b.tt.n_ids);
+  put(&o.build_key, sizeof(void*)); put(&o.kmin, 4); put(&o.kn, 4);
+  for (const auto& e : tab->band_row_windows) if (e.key == key) { bj.row_win = e.row_win; return; }
+  if (tab->band_row_windows.size() >= 8) return;
+  w.kmin = o.kmin; w.kn = o.kn; w.by_key = scratch<uint2>(o.kn); w.slow_keys = reinterpret_cast<u32*>(new_counter());
+  w.build_key = o.build_key; w.n_rows = bj.nb; w.row_win = store->table_alloc<uint2>(bj.nb + 64);
+  // per key: two look-ups, two ids and two typed values per window read, 8 B written; per slice row: its key read, 8 B gathered and written
+  timed(KC_BAND_ROW_WIN_KEYS, 0, o.kn, nullptr, 48ull * b.n_win + 8, nullptr, 0, 0, [&] { launch_band_row_win_keys(b, w, stream); });
+  timed(KC_BAND_ROW_WIN_ROWS, 0, bj.nb, nullptr, 4 + 8 + 8, nullptr, 0, 0, [&] { launch_band_row_win_rows(w, stream); });
+  const u32 slow = read_back<u32>(w.slow_keys);          // (the wait: published only when complete)
+  if (slow) { store->table_free(w.row_win); w.row_win = nullptr; } else metrics.tables_built++;
+  tab->band_row_windows.push_back(SliceTable::BandRowWindows{key, w.row_win});
+  bj.row_win = w.row_win;
+}
+
 // The probe rows' records in key order, with the rows per key (poff) and the blocks' counts zeroed: written by the ordered slice join below (fused; in place: one per slice row), else decoded from the probe columns.
 void Plan::band_row_records(BandJoin& bj) {
   const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band; OjBandFuse& fuse = bj.fuse;
   const u32 kn = bj.kn; const u64 np = bj.np, nb = bj.nb; const bool in_place = bj.in_place;
-  bj.nrows = in_place ? nb : np; b.rec_s = scratch<uint4>(bj.nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(bj.nrows);
+  bj.nrows = in_place ? nb : np; b.rec_s = bj.row_static ? nullptr : scratch<uint4>(bj.nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(bj.nrows);
   b.poff = in_place ? const_cast<u32*>(a.csr_off) : scratch<u32>((u64)kn + 2);
   // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
   bj.max_blocks = in_place ? bj.lay.n_blocks : bj.cmax * (np / 64 + 1) + nb / 64 + kn + 1;
@@ -2478,13 +2534,15 @@ void Plan::band_row_records(BandJoin& bj) {
   // decode, per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
   if (!bj.fused) return timed(KC_BAND_DECODE, 0, np, bj.j.P.n_dev, 4 + 4ull * (b.n_win + b.has_neq) + 9ull * b.n_win + 24 + 8, nullptr, 0, 0, [&] { launch_band_decode(b, stream); });
   const OrderedJoinArgs& o = pending_oj.o; pending_oj.active = false;
-  fuse.key_rec = in_place ? o.key_rec : nullptr;
+  fuse.key_rec = in_place && !bj.row_static ? o.key_rec : nullptr;
+  if (bj.row_static) { u32* row_val = scratch<u32>(nb); fuse.key_val = o.key_val; fuse.row_val = row_val; b.row_win = bj.row_win; b.row_val = row_val; }
   fuse.brec = in_place ? nullptr : scratch<uint4>((fuse.compact ? 1 : 2) * o.n_probe_cap);
   fuse.rec_s = b.rec_s; fuse.aux_s = b.aux_s; fuse.poff = b.poff; fuse.bcount = b.bcount; fuse.max_blocks = b.max_blocks; fuse.kmin = b.kmin; fuse.kn = b.kn;
   // per table row: its packed record read + two typed-value gathers + 32 B written; per slice row the count pass's 5 bytes + its key; per match a 32-byte record gathered and stored (in place: per slice row its key read, its key's 16-byte record gathered and stored)
+  // (the rows' windows cached: per table row its packed record read and 4 B written by key; per slice row its key read, 4 B gathered, 4 B written)
   const u64 rec_bytes = fuse.compact ? 16 : 32;
-  timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
-  if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
+  timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, bj.row_static ? 16ull * o.n_rec + 4 : 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
+  if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, bj.row_static ? 4 + 4 + 4 : 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
   else timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });
 }
 
@@ -2514,7 +2572,7 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
   if (!bj.presorted && !bj.counting) timed(KC_BAND_ROWS, 0, np, bj.j.P.n_dev, 4 + 32 + 32, nullptr, 0, 0, [&] { launch_band_rows(b, stream); });
   // pair test, per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count is not known on the host
   const u64* const nrows_dev = bj.in_place ? nullptr : bj.j.P.n_dev;
-  timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, bj.row_static ? 8 + 4 : b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
   if (!bj.skip_slow) {
     // the full-semantics pass needs the chain's literals and columns: the fused join kernel's argument block, by pointer
     static_assert(sizeof(LdsJoinArgs) <= ExecContext::kArgBytes, "argument staging slot too small");

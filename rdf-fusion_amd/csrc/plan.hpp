@@ -34,6 +34,7 @@ struct BandHistory {
   u64 multi_rows = 0;           // record_band_history: table rows the ordered slice join that wrote this join's records met behind another of the same key.  run_ordered_join: 0 = it may skip its count pass
   bool takes_records = false;   // exec_band_join: the probe side came presorted from an ordered slice join and no row needed the slow pass.  run_ordered_join / keeps_pending_oj: that join holds its write pass back
   bool in_place = false;        // exec_band_join: the slice's block layout is cached, the in-place route is available.  run_ordered_join reads it with multi_rows
+  bool row_cache = false;       // exec_band_join: the rows' decoded windows are cached on the slice too (SliceTable::BandRowWindows).  run_ordered_join: its probe pass prepares the values by key, not the 16-byte records
 };
 
 struct NodeInfo {
@@ -121,6 +122,8 @@ struct BandJoin {
   bool cache_entries = false;          // the build side is a store slice: its decoded entries and block layout are kept on its SliceTable
   OjBandFuse fuse{};                   // fused: where the ordered join's packed record holds what this join reads of a row
   std::string ekey; SliceTable::BandEntries lay{};   // what the decoded entries depend on, spelt out (SliceTable::BandEntries::key); a copy of the slice's in-place block layout (boff == nullptr: there is none, the route is closed)
+  const uint2* row_win = nullptr;      // the slice's cached row windows for this chain (band_row_windows; null: not eligible, declined, or the route is closed)
+  bool row_static = false;             // route: in place, the block kernels read row_win and this execution's values per row instead of 16-byte records
   u64 nrows = 0, max_blocks = 0;       // probe rows of the block kernels (in place: the slice's own rows); upper bound of the blocks (in place: exact)
   u32* skey = nullptr; u32* perm = nullptr; u32 sort_bits = 1; void* sort_temp = nullptr; size_t sort_temp_bytes = 0;   // the radix sort of the probe keys (its output pairs, key bits, temp): allocated by band_probe_side, run by band_blocks_and_emit
   BandJoin(LdsJoin& join) : j(join), kn(join.a.direct_n), np(join.P.cap), nb(join.B.cap), cmax((join.slice->csr_max_group + 63) / 64) {}
@@ -141,6 +144,7 @@ enum KernelClass {
   KC_SEMI_JOIN_END = KC_SEMI_JOIN0 + 6,
   KC_AGG_GROUPS = KC_SEMI_JOIN_END, KC_AGG_ACCUM_HBM, KC_AGG_ACCUM_LDS, KC_AGG_FINAL,
   KC_AGG_ACCUM_EXPR_HBM, KC_AGG_ACCUM_EXPR_LDS,   // agg_accum_expr_kernel<LDS>: some SUM / AVG reads an expression
+  KC_BAND_ROW_WIN_KEYS, KC_BAND_ROW_WIN_ROWS,     // the build of a slice's cached row windows (band_join.hip)
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
@@ -257,7 +261,7 @@ struct Plan {
   void prepare_partitions(const LdsJoinArgs& a, const DevTable& B, const DevTable& P, PartArgs& pa);
   void exec_band_join(LdsJoin& j);   // its steps, in order:
   bool take_pending_oj(BandJoin& bj); void band_probe_side(BandJoin& bj); void band_row_records(BandJoin& bj); void band_blocks_and_emit(BandJoin& bj);
-  void band_slice_tables(BandJoin& bj); void band_entries(BandJoin& bj); SliceTable::BandEntries* band_layout(BandJoin& bj);
+  void band_slice_tables(BandJoin& bj); void band_entries(BandJoin& bj); SliceTable::BandEntries* band_layout(BandJoin& bj); void band_row_windows(BandJoin& bj);
   bool choose_build_left(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf, bool lpost = false, bool rpost = false) const;
   void release_intermediates();
   template <class T> T* scratch(u64 n);

@@ -107,6 +107,12 @@ struct SliceTable {
   // itself: poff = csr_off), a function of the slice alone; built by the first such execution, n_blocks exact (null: not yet)
   struct BandEntries { std::string key; uint4* et; u32* eo[4]; u32* boff = nullptr; uint4* bdesc = nullptr; u32 n_blocks = 0; };
   std::vector<BandEntries> band_entries;
+  // the ROW side of the same test for a band join that reads the slice's rows in place, when a row's windows depend on its join key alone: per slice
+  // row the packed {lo pair, width pair} (padded like et).  `key` = the entries' key + the windows' literals, bias and packing, the operand stages' tables
+  // and value columns, the typed-value table.  row_win == nullptr: some key's operands are not plain xsd:integers — the form is declined for this key
+  // string (remembered, so that it is not built again every step).  Same lock, same rules as the entries.
+  struct BandRowWindows { std::string key; uint2* row_win; };
+  std::vector<BandRowWindows> band_row_windows;
   // the slice as the sorted input of a FILTER on its sort column (kernels.hip, run-copy form): lo[i] = first row whose id is >= first + i
   // (i = 0 .. span): where every distinct id's run starts — a function of the slice alone
   struct ValueStarts { u32 first; u64 span; u32* lo; };

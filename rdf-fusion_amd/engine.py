@@ -122,6 +122,7 @@ def load_library():
     lib.rdfgpu_scan_score.restype = C.c_uint64
     lib.rdfgpu_choose_index.argtypes = [C.POINTER(abi.ScanInstruction), C.c_uint32]
     lib.rdfgpu_choose_index.restype = C.c_uint32
+    lib.rdfgpu_band_row_cache_eligible.argtypes = [C.c_uint32] * 5 + [u32p, u32p]
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -160,6 +161,17 @@ def scan_score(instrs):
 def choose_index(gspo_instrs, available=0b111):
     """IndexPermutations::choose_index (permutations.rs:81-96)."""
     return int(load_library().rdfgpu_choose_index(_instr_array(gspo_instrs), available))
+
+
+def band_row_cache_eligible(operands, in_place=True, compact=True, pack16=True, option_set=False):
+    """Host decision of the band join that reads a slice's rows in place (host_logic.hpp): may the rows' decoded windows be kept on the
+    slice?  `operands`: per window its two operands as (src, keyed_by_join_key) pairs — where the ordered slice join below takes the
+    operand from (0 = table row, 1 = slice row, 2 + t = stage t's row) and whether that stage's key column is the join's own key."""
+    flat = [op for window in operands for op in window]
+    n = max(4, len(flat))
+    src = (C.c_uint32 * n)(*[int(s) for s, _ in flat])
+    keyed = (C.c_uint32 * n)(*[int(bool(k)) for _, k in flat])
+    return bool(_check(load_library().rdfgpu_band_row_cache_eligible(int(in_place), int(compact), int(pack16), int(option_set), len(operands), src, keyed)))
 
 
 def _pred_struct(p, keep):
