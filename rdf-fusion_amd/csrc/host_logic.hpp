@@ -50,7 +50,7 @@ struct PrunePlan {
 };
 PrunePlan plan_pruning(const ScanInstructions& ix);
 
-// Band join reading a store slice's rows in place (plan.cpp, exec_band_join): may the rows' decoded windows be kept on the slice
+// Band join reading a store slice's rows in place (plan_band.cpp, exec_band_join): may the rows' decoded windows be kept on the slice
 // (SliceTable::BandRowWindows) instead of travelling by key every step?  Yes when the route is the in-place one with compact, packed
 // records, the option is off, and every window operand is a column the ordered slice join below reaches through a stage (src >= 2)
 // whose key column is that join's own key: the operand is then a function of the key alone, not of the batch.

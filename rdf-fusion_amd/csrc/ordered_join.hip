@@ -1,6 +1,6 @@
 // ordered_join.hip — HashJoinExec of a small table against a store slice, emitted IN THE SLICE'S ORDER.
 //
-// The index join (plan.cpp: build on the slice's cached CSR table, probe with the table's rows) emits its matches in
+// The index join (plan_join.cpp: build on the slice's cached CSR table, probe with the table's rows) emits its matches in
 // probe-row order.  When the slice is sorted by a column that is NOT the join key — a GPOS slice (?s <p> ?o) joined on
 // ?s is sorted by ?o — and the next operator partitions this join's output by that very column (the key-partitioned band
 // join above it: BSBM Q5's candidates by product feature), walking the join the other way round saves that partition

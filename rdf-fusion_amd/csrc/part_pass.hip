@@ -118,7 +118,7 @@ __device__ __forceinline__ u32 wave_bin_add(u32* cnt, u32 bin, bool valid) {
   return rank;
 }
 
-constexpr u32 kPartDirMax = 4096;   // entries of the range directory (plan.cpp: n_coarse <= 4096)
+constexpr u32 kPartDirMax = 4096;   // entries of the range directory (plan_join.cpp: n_coarse <= 4096)
 // Histogram workgroups are small (256 lanes x 16 rows of a tile) and PERSISTENT: a tile is 4 - 48 KB of input, a workgroup per tile
 // lived for its launch and its two memory round trips (pass B, 1 byte per row: 276 us for 98 MB), and pass A's workgroups staged the
 // 32 KB range directory once per tile — as many bytes as the tile's keys (444 us against 209 us in hash mode).

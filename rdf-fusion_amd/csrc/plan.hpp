@@ -2,6 +2,7 @@
 // NestedLoopJoinExec / ProjectionExec over HBM-resident binding tables.
 #pragma once
 #include <memory>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -232,14 +233,27 @@ struct Plan {
   void ensure_host_copy();
 
  private:
+  void refresh_dynamic_sources(std::shared_lock<std::shared_mutex>& lock); void locate_sources();   // steps of execute
   DevTable exec_node(u32 idx);
+  DevTable exec_sub_plan(u32 idx);
   DevTable exec_source(NodeInfo& nd);
+  DevTable exec_projection(NodeInfo& nd);
+  DevTable exec_closure(NodeInfo& nd);
+  DevTable exec_union(NodeInfo& nd);
+  DevTable exec_table(NodeInfo& nd);
   DevTable exec_filter(NodeInfo& nd);
   DevTable exec_join(NodeInfo& nd);
   DevTable exec_topk(NodeInfo& nd);
   DevTable exec_semi_join(NodeInfo& nd);
   DevTable exec_aggregate(NodeInfo& nd);
-  DevTable apply_filter(NodeInfo& nd, const DevTable& in);
+  DevTable apply_filter(NodeInfo& nd, const DevTable& in);   // its routes:
+  bool filter_string_verdicts(const NodeInfo& nd, const DevTable& in, FilterArgs& a); bool filter_run_copy(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape);
+  void filter_streamed(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape); void filter_single_pass(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape);
+  // The inputs of a join as exec_join hands them to the join proper: lf / rf = the FilterExec above that input runs inside the probe; post = a build-side FilterExec kept as a conjunct of the join filter.
+  struct JoinInputs { DevTable L, R; bool lf = false, rf = false; const NodeInfo* post = nullptr; };
+  bool try_fused_chain(NodeInfo& nd, DevTable& fused); JoinInputs join_inputs(NodeInfo& nd);   // steps of exec_join
+  DevTable exec_cross_join(const NodeInfo& nd, const DevTable& L, const DevTable& R);
+  DevTable exec_generic_join(const NodeInfo& nd, const DevTable& L, const DevTable& R);
   bool keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const;
   DevTable exec_lds_join(NodeInfo& nd, const DevTable& L, const DevTable& R, bool build_left, const NodeInfo* probe_filter, const NodeInfo* post_filter = nullptr);
   void lds_join_args(LdsJoin& j);
