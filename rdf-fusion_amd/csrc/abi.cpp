@@ -558,6 +558,11 @@ int rdfgpu_band_row_cache_eligible(uint32_t in_place, uint32_t compact, uint32_t
     return band_row_cache_eligible(s) ? 1 : 0;
   } catch (const Error& e) { set_last_error(e.what()); return e.status; }
 }
+int rdfgpu_band_pair_cache_eligible(uint32_t row_windows, uint32_t neq_self, uint32_t pack16, uint32_t option_set, uint64_t n_blocks, uint64_t cap_blocks) {
+  BandPairCacheShape s;
+  s.row_windows = row_windows != 0; s.neq_self = neq_self != 0; s.pack16 = pack16 != 0; s.option_off = option_set == 0; s.n_blocks = n_blocks; s.cap = cap_blocks;
+  return band_pair_cache_eligible(s) ? 1 : 0;
+}
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;
   if (p->pred == RDFGPU_PRED_IN) { if (p->ids) r.ids.assign(p->ids, p->ids + p->n_ids); else r.ids = {p->from}; }

@@ -25,7 +25,8 @@
 //                       i64 -> biased u32 interval), id operand                                    -> rocPRIM radix sort
 //   band_bounds_kernel  poff[k] = first sorted position with key >= k (one pass, gaps filled)
 //   band_blocks_scan    blocks (64 entries x 64 rows) per key, computed inside the scan's input iterator: boff = first block of a key -> band_desc_kernel
-//   band_mask_kernel    per block: the pair tests, 1 bit per pair, count per block
+//   band_mask_kernel    per block: the pair tests, 1 bit per pair, count per block (CACHED: the bits are a table of the slice, built by
+//                       band_pair_bits_kernel once per store version; a step applies its rows to them and counts)
 //   band_slow_kernel    rows whose operands are not all xsd:integer: full semantics (exits at once if there are none)
 //   band_emit_kernel    per block: bits -> output rows at the block's scanned offset, coalesced
 #include <hip/hip_runtime.h>
@@ -437,8 +438,90 @@ __global__ __launch_bounds__(256) void band_desc_kernel(const BandArgs b) {
 // STATIC = the rows' windows come from the slice's cached table (BandArgs::row_win, row_val; NEQ = 3 and PACK): 12 bytes per row instead of 16.
 struct BandEntry8 { uint4 a[8]; };
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-template <int NWIN, int NEQ, bool PACK, bool STATIC = false>
+// The pair loop of one block, shared by the pair test of a step (band_mask_kernel) and the build of a slice's cached verdicts (band_pair_bits_kernel):
+// `ent` = the block's 64 entries staged in LDS by the calling wave (PACK: both windows' operands in word x), rec / plo / pw = this lane's row, x = its id
+// operand (NEQ = 3: its own entry's index).  Returns the lane's 64 verdict bits: entries past the group's end and the row's own entry cleared.
+template <int NWIN, int NEQ, bool PACK>
+__device__ __forceinline__ u64 band_pair_block(const uint4* ent, u32 eb, u32 ne, const uint4 rec, u32 plo, u32 pw, u32 x) {
+  u32 m[2] = {0u, 0u};
+#pragma unroll
+  for (u32 h = 0; h < 2; h++) {
+    if (h * 32 >= ne) continue;                       // wave-uniform
+    u32 acc = 0;
+    const u32 left = ne - h * 32;                      // entries of this half (wave-uniform): tested 8 at a time, not 32
+    const u32 g_end = left >= 32 ? 4u : (left + 7) >> 3;
+#pragma unroll 1
+    for (u32 g = 0; g < g_end; g++) {
+      uint4 q8[8];
+#pragma unroll
+      for (u32 e = 0; e < 8; e++) q8[e] = ent[h * 32 + g * 8 + e];
+#pragma unroll
+      for (u32 e = 0; e < 8; e++) {
+        const uint4 q = q8[e];
+        // the verdict of the 64 lanes IS the compares' lane mask (SGPR pairs, AND-ed on the scalar unit): shifting it into
+        // every lane's word is ONE add-with-carry (acc + acc + carry) instead of a select and an or per pair
+        u64 lanes;
+        if (PACK) {   // (x - lo) <= w in both 16-bit halves  <=>  min(x - lo, w) == x - lo as a 32-bit word: 3 instructions for two windows
+          const us2 d = __builtin_bit_cast(us2, q.x) - __builtin_bit_cast(us2, plo);
+          const us2 mn = __builtin_elementwise_min(d, __builtin_bit_cast(us2, pw));
+          lanes = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(u32, mn) == __builtin_bit_cast(u32, d));
+        } else {
+          lanes = __builtin_amdgcn_ballot_w64((q.x - rec.x) <= rec.y);
+          if (NWIN > 1) lanes &= __builtin_amdgcn_ballot_w64((q.y - rec.z) <= rec.w);
+        }
+        if (NEQ == 1) lanes &= __builtin_amdgcn_ballot_w64(q.z != x);
+        if (NEQ == 2) lanes &= __builtin_amdgcn_ballot_w64(q.z == x);
+        u64 carry_out;
+        asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(acc), "=s"(carry_out) : "v"(acc), "s"(lanes));
+      }
+    }
+    m[h] = __builtin_bitreverse32(g_end == 4 ? acc : acc << (32 - 8 * g_end));   // entry 0 was shifted in first: it belongs at bit 31
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the staging area is free for the wave's next block
+  // entries past the group's end belong to the next key: their bits do not count
+  const u64 live = ne >= 64 ? ~0ull : ((1ull << ne) - 1ull);
+  u64 mask = ((((u64)m[1]) << 32) | m[0]) & live;
+  if (NEQ == 3) { const u32 self = x - eb; if (self < 64u) mask &= ~(1ull << self); }   // the row's own entry, if it is in this chunk (x = its index)
+  return mask;
+}
+// CACHED (STATIC; BandArgs::masks = the slice's cached verdicts, SliceTable::BandRowWindows::pair_bits): no pair is tested — band_cached_blocks.
+constexpr u32 kBandCachedBlocks = 4;   // blocks per wave of the cached form: their loads are independent, all in flight before the first wait
+// The cached form of the pair test: the block's 64 words are already what the test would write for rows that all have a table row, so a step
+// applies this execution's rows and counts.  Per block: valid = the lanes whose row has a value (bvalid, read by the emit kernel), bcount = the
+// bits of the valid lanes.  A streaming pass, two round trips per wave: descriptors and bits of kBandCachedBlocks blocks, then their rows' values.
+__device__ __forceinline__ void band_cached_blocks(const BandArgs& b) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 n_blocks = b.max_blocks;                       // (in place: exact, known on the host)
+  const u32 blk0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4u + (threadIdx.x >> 6)) * kBandCachedBlocks);
+  if (blk0 >= n_blocks) return;
+  uint4 d[kBandCachedBlocks]; u64 bits[kBandCachedBlocks]; u32 val[kBandCachedBlocks];
+#pragma unroll
+  for (u32 k = 0; k < kBandCachedBlocks; k++) {
+    const u32 blk = blk0 + k < n_blocks ? blk0 + k : n_blocks - 1;   // (past the end: the last block again, nothing stored)
+    d[k] = b.bdesc[blk]; bits[k] = b.masks[(u64)blk * 64 + lane];
+  }
+#pragma unroll
+  for (u32 k = 0; k < kBandCachedBlocks; k++) asm volatile("" :: "v"(d[k].z), "v"(d[k].w), "v"(bits[k]));
+#pragma unroll
+  for (u32 k = 0; k < kBandCachedBlocks; k++) {
+    const u32 rb = __builtin_amdgcn_readfirstlane(d[k].z), nr = __builtin_amdgcn_readfirstlane(d[k].w);
+    val[k] = kNil;
+    if (lane < nr) val[k] = b.row_val[rb + lane];
+  }
+#pragma unroll
+  for (u32 k = 0; k < kBandCachedBlocks; k++) asm volatile("" :: "v"(val[k]));
+#pragma unroll
+  for (u32 k = 0; k < kBandCachedBlocks; k++) {
+    if (blk0 + k >= n_blocks) break;                       // wave-uniform
+    const bool valid = val[k] != kNil;                     // (lanes past the block's rows kept kNil)
+    const u64 rows = __builtin_amdgcn_ballot_w64(valid);
+    const u32 c = wave_incl_scan(valid ? (u32)__popcll(bits[k]) : 0u);
+    if (lane == 63) { b.bcount[blk0 + k] = c; b.bvalid[blk0 + k] = rows; }
+  }
+}
+template <int NWIN, int NEQ, bool PACK, bool STATIC = false, bool CACHED = false>
 __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
+  if constexpr (CACHED) { band_cached_blocks(b); return; } else {
   __shared__ uint4 ent[4][64];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // one wave per block; the grid is sized from the previous execution's block count, so a wave strides on in the rare case
@@ -475,49 +558,34 @@ __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
     ent[wave][lane] = q;
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  u32 m[2] = {0u, 0u};
-#pragma unroll
-  for (u32 h = 0; h < 2; h++) {
-    if (h * 32 >= ne) continue;                       // wave-uniform
-    u32 acc = 0;
-    const u32 left = ne - h * 32;                      // entries of this half (wave-uniform): tested 8 at a time, not 32
-    const u32 g_end = left >= 32 ? 4u : (left + 7) >> 3;
-#pragma unroll 1
-    for (u32 g = 0; g < g_end; g++) {
-      uint4 q8[8];
-#pragma unroll
-      for (u32 e = 0; e < 8; e++) q8[e] = ent[wave][h * 32 + g * 8 + e];
-#pragma unroll
-      for (u32 e = 0; e < 8; e++) {
-        const uint4 q = q8[e];
-        // the verdict of the 64 lanes IS the compares' lane mask (SGPR pairs, AND-ed on the scalar unit): shifting it into
-        // every lane's word is ONE add-with-carry (acc + acc + carry) instead of a select and an or per pair
-        u64 lanes;
-        if (PACK) {   // (x - lo) <= w in both 16-bit halves  <=>  min(x - lo, w) == x - lo as a 32-bit word: 3 instructions for two windows
-          const us2 d = __builtin_bit_cast(us2, q.x) - __builtin_bit_cast(us2, plo);
-          const us2 mn = __builtin_elementwise_min(d, __builtin_bit_cast(us2, pw));
-          lanes = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(u32, mn) == __builtin_bit_cast(u32, d));
-        } else {
-          lanes = __builtin_amdgcn_ballot_w64((q.x - rec.x) <= rec.y);
-          if (NWIN > 1) lanes &= __builtin_amdgcn_ballot_w64((q.y - rec.z) <= rec.w);
-        }
-        if (NEQ == 1) lanes &= __builtin_amdgcn_ballot_w64(q.z != x);
-        if (NEQ == 2) lanes &= __builtin_amdgcn_ballot_w64(q.z == x);
-        u64 carry_out;
-        asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(acc), "=s"(carry_out) : "v"(acc), "s"(lanes));
-      }
-    }
-    m[h] = __builtin_bitreverse32(g_end == 4 ? acc : acc << (32 - 8 * g_end));   // entry 0 was shifted in first: it belongs at bit 31
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the staging area is free for the wave's next block
-  // entries past the group's end belong to the next key: their bits do not count
-  const u64 live = ne >= 64 ? ~0ull : ((1ull << ne) - 1ull);
-  u64 mask = ((((u64)m[1]) << 32) | m[0]) & live;
-  if (NEQ == 3) { const u32 self = x - eb; if (self < 64u) mask &= ~(1ull << self); }   // the row's own entry, if it is in this chunk (x = its index)
+  const u64 mask = band_pair_block<NWIN, NEQ, PACK>(ent[wave], eb, ne, rec, plo, pw, x);
   b.masks[(u64)blk * 64 + lane] = mask;
   const u32 c = wave_incl_scan((u32)__popcll(mask));      // (DPP: lane 63 holds the block's count)
   if (lane == 63) b.bcount[blk] = c;
   }
+  }
+}
+
+// The build of a slice's cached verdicts (SliceTable::BandRowWindows::pair_bits; once per store version and literal set): one wave per block of the in-place
+// layout; exactly what band_mask_kernel<NWIN, 3, true, true> writes when every row has a table row — the live-entry mask, the row's own entry cleared, a
+// zero word for the lanes past the block's rows — and no counts.  b.masks = the table, b.max_blocks = the layout's blocks.
+template <int NWIN>
+__global__ __launch_bounds__(256) void band_pair_bits_kernel(const BandArgs b) {
+  __shared__ uint4 ent[4][64];
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + wave);
+  if (blk >= b.max_blocks) return;                         // wave-uniform
+  const uint4 d = b.bdesc[blk];
+  const u32 eb = __builtin_amdgcn_readfirstlane(d.x), ne = __builtin_amdgcn_readfirstlane(d.y);
+  const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
+  uint2 swin = make_uint2(kBandPackedNone, 0u); u32 x = 0;
+  if (lane < nr) { swin = b.row_win[rb + lane]; x = rb + lane; }
+  uint4 q = b.et[eb + lane];                               // (padded, like row_win)
+  q.x = (q.x & 0xFFFFu) | (q.y << 16);
+  ent[wave][lane] = q;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const u64 mask = band_pair_block<NWIN, 3, true>(ent[wave], eb, ne, make_uint4(swin.x, swin.y, 0u, 0u), swin.x, swin.y, x);
+  b.masks[(u64)blk * 64 + lane] = lane < nr ? mask : 0ull;
 }
 
 // Rare: probe rows whose window operands are not all xsd:integer (or overflow i64) take the full typed-value semantics,
@@ -570,7 +638,8 @@ constexpr u32 kBandList = 1024;   // survivors listed at a time: a block with mo
 // NCOLS = output columns (1 .. 6): a template parameter so that only the live columns' pointers and selectors sit in SGPRs (the
 // six-column form kept 18 of them pinned and spilled scalars into vector lanes inside the loops)
 // STATIC (BandArgs::row_win): the row's one output value is row_val[row] — 4 bytes per row, not the 16-byte record.
-template <int NCOLS, bool STATIC = false>
+// CACHED (STATIC; the bits are the slice's cached verdicts): bvalid[blk] says which rows of the block have a value in this execution.
+template <int NCOLS, bool STATIC = false, bool CACHED = false>
 __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
   __shared__ unsigned short list[4][kBandList];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -594,12 +663,17 @@ __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
   const uint4 d = b.bdesc[blk];
   u64 run = b.bofs[blk];
   const u64 mask_raw = b.masks[(u64)blk * 64 + lane];
+  u64 rows_valid = ~0ull;
+  if (CACHED) {
+    rows_valid = b.bvalid[blk];
+    asm volatile("" :: "v"(tot_v), "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w), "v"(run), "v"(mask_raw), "v"(rows_valid));
+  } else
   asm volatile("" :: "v"(tot_v), "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w), "v"(run), "v"(mask_raw));   // (all four loads issued before the first wait: the compiler would sink them below the branch)
   const u32 tot = __builtin_amdgcn_readfirstlane(tot_v);
   if (tot == 0) continue;
   const u32 eb = __builtin_amdgcn_readfirstlane(d.x), ne = __builtin_amdgcn_readfirstlane(d.y);
   const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
-  const u64 mask_all = lane < nr ? mask_raw : 0ull;
+  const u64 mask_all = (lane < nr && (!CACHED || ((rows_valid >> lane) & 1ull))) ? mask_raw : 0ull;
   u32 ev[kBandMaxSideCols], rv[kBandMaxRowCols];   // output values of the entry (lane = entry) / of the probe row (lane = row)
   if (STATIC) {
     rv[0] = 0u; rv[1] = 0u;
@@ -686,7 +760,10 @@ template <int NWIN, bool PACK> static void launch_band_mask_w(const BandArgs& b,
   const int neq = b.has_neq ? (b.neq_is_eq ? 2 : b.neq_self ? 3 : 1) : 0;
   if (neq == 3) {
     if constexpr (PACK) {
-      if (b.row_win) hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true>), g, dim3(256), 0, s, b);
+      if (b.row_win && b.bvalid) {   // the cached verdicts: a wave per kBandCachedBlocks blocks
+        const u32 waves = (b.max_blocks + kBandCachedBlocks - 1) / kBandCachedBlocks;
+        hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true, true>), dim3((waves + 3) / 4 ? (waves + 3) / 4 : 1), dim3(256), 0, s, b);
+      } else if (b.row_win) hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true>), g, dim3(256), 0, s, b);
       else hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true>), g, dim3(256), 0, s, b);
       return;
     }
@@ -701,6 +778,12 @@ void launch_band_mask(const BandArgs& b, hipStream_t s) {
   if (b.pack16) { if (b.n_win == 2) launch_band_mask_w<2, true>(b, g, s); else launch_band_mask_w<1, true>(b, g, s); }
   else if (b.n_win == 2) launch_band_mask_w<2, false>(b, g, s); else launch_band_mask_w<1, false>(b, g, s);   // no window = one trivial window
 }
+void launch_band_pair_bits(const BandArgs& b, hipStream_t s) {
+  if (!b.max_blocks) return;
+  const dim3 g((b.max_blocks + 3) / 4);
+  if (b.n_win == 2) hipLaunchKernelGGL(band_pair_bits_kernel<2>, g, dim3(256), 0, s, b);
+  else hipLaunchKernelGGL(band_pair_bits_kernel<1>, g, dim3(256), 0, s, b);
+}
 void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s) {
   const u32 g = (b.max_blocks + 3) / 4;
   hipLaunchKernelGGL(band_slow_kernel, dim3(g < 2048u ? (g ? g : 1u) : 2048u), dim3(256), 0, s, a_dev, b);
@@ -708,7 +791,15 @@ void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s
 void launch_band_emit(const BandArgs& b, hipStream_t s) {
   const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);
   static_assert(kBandMaxRowCols + kBandMaxSideCols == 6, "one instantiation per column count");
-  if (b.row_win) switch (b.n_out_cols) {
+  if (b.row_win && b.bvalid) switch (b.n_out_cols) {
+    case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true>), g, dim3(256), 0, s, b); return;
+    case 2: hipLaunchKernelGGL((band_emit_kernel<2, true, true>), g, dim3(256), 0, s, b); return;
+    case 3: hipLaunchKernelGGL((band_emit_kernel<3, true, true>), g, dim3(256), 0, s, b); return;
+    case 4: hipLaunchKernelGGL((band_emit_kernel<4, true, true>), g, dim3(256), 0, s, b); return;
+    case 5: hipLaunchKernelGGL((band_emit_kernel<5, true, true>), g, dim3(256), 0, s, b); return;
+    case 6: hipLaunchKernelGGL((band_emit_kernel<6, true, true>), g, dim3(256), 0, s, b); return;
+  }
+  else if (b.row_win) switch (b.n_out_cols) {
     case 1: hipLaunchKernelGGL((band_emit_kernel<1, true>), g, dim3(256), 0, s, b); return;
     case 2: hipLaunchKernelGGL((band_emit_kernel<2, true>), g, dim3(256), 0, s, b); return;
     case 3: hipLaunchKernelGGL((band_emit_kernel<3, true>), g, dim3(256), 0, s, b); return;

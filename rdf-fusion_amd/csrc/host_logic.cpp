@@ -157,4 +157,9 @@ bool band_row_cache_eligible(const BandRowCacheShape& s) {
   return true;
 }
 
+bool band_pair_cache_eligible(const BandPairCacheShape& s) {
+  if (!s.row_windows || !s.neq_self || !s.pack16 || !s.option_off) return false;
+  return s.n_blocks <= (s.cap ? s.cap : kBandPairCacheBlocks);
+}
+
 }  // namespace rdfgpu

@@ -60,5 +60,11 @@ struct BandRowCacheShape {
   u32 n_win = 0; BandRowOperandShape y0[2], y1[2];
 };
 bool band_row_cache_eligible(const BandRowCacheShape& s);
+// .. and may the pair test's verdicts be kept beside them (SliceTable::BandRowWindows::pair_bits: 512 bytes per block of the in-place layout)?  Yes when the
+// rows' windows are kept (eligible, and accepted for this store), the pair test is the packed form whose `!=` is by entry index (BandArgs::neq_self, pack16),
+// the option is off and the layout has at most `cap` blocks (RDFGPU_OPT_BAND_PAIR_CACHE_BLOCKS, inclusive; 0 = kBandPairCacheBlocks).
+constexpr u64 kBandPairCacheBlocks = 1ull << 21;   // 1 GiB of verdicts: ten times what BSBM Q5 at 285 k products needs, small against the device's memory
+struct BandPairCacheShape { bool row_windows = false, neq_self = false, pack16 = false, option_off = false; u64 n_blocks = 0, cap = 0; };
+bool band_pair_cache_eligible(const BandPairCacheShape& s);
 
 }  // namespace rdfgpu

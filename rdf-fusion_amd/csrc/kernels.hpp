@@ -488,6 +488,9 @@ struct BandArgs {
   // band_row_cache_eligible): row_win = the packed {lo pair, width pair} of every slice row, kept on the slice per store version beside the entries;
   // row_val = this execution's output value per slice row (kNil: no table row has the row's key — its record passes nothing).  rec_s is not used.
   const uint2* row_win; const u32* row_val;
+  // .. and the pair test's verdicts are cached too (masks = SliceTable::BandRowWindows::pair_bits, never written by a step): per block the rows that
+  // have a value in this execution, one bit per lane — written by the cached form of the mask pass, applied by the emit kernel.  Null: masks is this execution's own.
+  u64* bvalid;
 };
 // The build of BandArgs::row_win (band_join.hip): per join key d of [kmin, kmin + kn) the window operands are fetched through the operand stages' direct
 // tables and packed by band_row_record; then every slice row copies its key's 8 bytes.
@@ -500,6 +503,7 @@ struct BandRowWinArgs {
 };
 void launch_band_row_win_keys(const BandArgs& b, const BandRowWinArgs& w, hipStream_t s);
 void launch_band_row_win_rows(const BandRowWinArgs& w, hipStream_t s);
+void launch_band_pair_bits(const BandArgs& b, hipStream_t s);   // b.masks[64 * b.max_blocks] = the verdicts of the layout b.bdesc over b.et and b.row_win
 void launch_band_pt(const BandArgs& b, hipStream_t s);
 void launch_band_entries(const BandArgs& b, hipStream_t s);
 void launch_band_rows(const BandArgs& b, hipStream_t s);      // records into sorted order

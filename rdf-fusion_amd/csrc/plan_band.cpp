@@ -246,6 +246,7 @@ void Plan::exec_band_join(LdsJoin& j) {
   bj.row_static = bj.fused && bj.row_win && pending_oj.o.key_val;
   bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place && (bj.row_static || pending_oj.o.key_rec);
   bj.row_static = bj.row_static && bj.in_place;
+  bj.pair_cached = bj.row_static && bj.pair_bits != nullptr;   // (row_static implies skip_slow: the full-semantics pass, which patches the bits, never runs over the slice's)
   if (bj.fused && !bj.in_place) count_pending_oj();
   band_row_records(bj);
   band_blocks_and_emit(bj);
@@ -376,6 +377,8 @@ SliceTable::BandEntries* Plan::band_layout(BandJoin& bj) {
 // the entries (same lock; built where the layout is, by the first execution that could take the route; fewer than 8 per slice), not gathered as 16-byte records
 // by key every step.  Its key = the entries' key + everything band_row_record reads.  A store in which some key's operands are not plain xsd:integers declines
 // the form: remembered as an entry without a table.  The caller holds the lock (the layout exists only when bj.cache_entries).
+// With the windows, the pair test's verdicts (R12; SliceTable::BandRowWindows::pair_bits, host_logic.hpp: band_pair_cache_eligible): same key, same execution, same
+// lock, built behind the windows and waited for with them — the one read-back below.  A plan whose options decline them neither builds nor uses them.
 void Plan::band_row_windows(BandJoin& bj) {
   const BandArgs& b = bj.j.band; const OjBandFuse& fuse = bj.fuse; const OrderedJoinArgs& o = pending_oj.o; SliceTable* tab = bj.j.slice;
   if (!bj.lay.boff) return;                              // the in-place route is closed
@@ -405,17 +408,38 @@ void Plan::band_row_windows(BandJoin& bj) {
   }
   put(&b.pack16, 4); put(&b.has_neq, 4); put(&b.tt.tv, sizeof(void*)); put(&b.tt.n_ids, sizeof b.tt.n_ids);
   put(&o.build_key, sizeof(void*)); put(&o.kmin, 4); put(&o.kn, 4);
-  for (const auto& e : tab->band_row_windows) if (e.key == key) { bj.row_win = e.row_win; return; }
+  BandPairCacheShape pair;
+  pair.neq_self = b.neq_self != 0; pair.pack16 = b.pack16 != 0; pair.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_CACHE);
+  pair.n_blocks = bj.lay.n_blocks; pair.cap = opt.v[RDFGPU_OPT_BAND_PAIR_CACHE_BLOCKS];
+  auto build_pair_bits = [&](const uint2* row_win) {        // 512 B written per block; its descriptor, 64 entries and 64 rows' windows read
+    u64* bits = store->table_alloc<u64>(64ull * bj.lay.n_blocks);
+    BandArgs d = b; d.bdesc = bj.lay.bdesc; d.max_blocks = bj.lay.n_blocks; d.row_win = row_win; d.masks = bits;
+    timed(KC_BAND_PAIR_BITS, (512ull + 16) * bj.lay.n_blocks + 16ull * bj.nb, bj.nb, nullptr, 8, nullptr, 0, 0, [&] { launch_band_pair_bits(d, stream); });
+    return bits;
+  };
+  for (auto& e : tab->band_row_windows) if (e.key == key) {
+    bj.row_win = e.row_win; pair.row_windows = e.row_win != nullptr;
+    if (!band_pair_cache_eligible(pair)) return;
+    if (!e.pair_bits) {   // the windows were built by a plan whose options declined the verdicts: built now, published when complete
+      u64* bits = build_pair_bits(e.row_win);
+      RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++; metrics.tables_built++;
+      e.pair_bits = bits;
+    }
+    bj.pair_bits = e.pair_bits;
+    return;
+  }
   if (tab->band_row_windows.size() >= 8) return;
   w.kmin = o.kmin; w.kn = o.kn; w.by_key = scratch<uint2>(o.kn); w.slow_keys = reinterpret_cast<u32*>(new_counter());
   w.build_key = o.build_key; w.n_rows = bj.nb; w.row_win = store->table_alloc<uint2>(bj.nb + 64);
   // per key: two look-ups, two ids and two typed values per window read, 8 B written; per slice row: its key read, 8 B gathered and written
   timed(KC_BAND_ROW_WIN_KEYS, 0, o.kn, nullptr, 48ull * b.n_win + 8, nullptr, 0, 0, [&] { launch_band_row_win_keys(b, w, stream); });
   timed(KC_BAND_ROW_WIN_ROWS, 0, bj.nb, nullptr, 4 + 8 + 8, nullptr, 0, 0, [&] { launch_band_row_win_rows(w, stream); });
+  pair.row_windows = true;                               // (whether the store's operands accept the windows is known only after the wait: built behind them, freed if not)
+  u64* bits = band_pair_cache_eligible(pair) ? build_pair_bits(w.row_win) : nullptr;
   const u32 slow = read_back<u32>(w.slow_keys);          // (the wait: published only when complete)
-  if (slow) { store->table_free(w.row_win); w.row_win = nullptr; } else metrics.tables_built++;
-  tab->band_row_windows.push_back(SliceTable::BandRowWindows{key, w.row_win});
-  bj.row_win = w.row_win;
+  if (slow) { store->table_free(w.row_win); w.row_win = nullptr; if (bits) store->table_free(bits); bits = nullptr; } else metrics.tables_built += bits ? 2 : 1;
+  tab->band_row_windows.push_back(SliceTable::BandRowWindows{key, w.row_win, bits});
+  bj.row_win = w.row_win; bj.pair_bits = bits;
 }
 
 // The probe rows' records in key order, with the rows per key (poff) and the blocks' counts zeroed: written by the ordered slice join below (fused; in place: one per slice row), else decoded from the probe columns.
@@ -455,7 +479,9 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
   band_feedback.push_back({&bj.j.nd, (u32)(b.n_blocks_out - counters), (u32)(reinterpret_cast<u64*>(b.slow_rows) - counters), (u32)(reinterpret_cast<u64*>(b.run_stats) - counters),
                            bj.fused ? (int)(reinterpret_cast<u64*>(pending_oj.o.multi_rows) - counters) : -1, bj.skip_slow, bj.in_place, bj.in_place ? max_blocks : 0});
   const u64 hist = bj.j.nd.band.blocks; b.launch_blocks = (u32)(bj.in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
-  b.bdesc = bj.in_place ? bj.lay.bdesc : scratch<uint4>(max_blocks); b.masks = scratch<u64>(max_blocks * 64);
+  b.bdesc = bj.in_place ? bj.lay.bdesc : scratch<uint4>(max_blocks);
+  if (bj.pair_cached) { b.masks = bj.pair_bits; b.bvalid = scratch<u64>(max_blocks); }   // the slice's verdicts: read, never written
+  else b.masks = scratch<u64>(max_blocks * 64);
   const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn)); void* temp = scratch<unsigned char>(tb);
   if (bj.counting) {   // poff = exclusive scan of the rows per key (entry kn = the rows that join something); then the scatter
     timed(scan_class((u64)kn + 1), 0, (u64)kn + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.key_hist, b.poff, (u64)kn + 1, temp, tb, stream); });
@@ -469,8 +495,11 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
   if (!bj.presorted && !bj.counting) timed(KC_BAND_ROWS, 0, np, bj.j.P.n_dev, 4 + 32 + 32, nullptr, 0, 0, [&] { launch_band_rows(b, stream); });
   // pair test, per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count is not known on the host
   const u64* const nrows_dev = bj.in_place ? nullptr : bj.j.P.n_dev;
-  timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, bj.row_static ? 8 + 4 : b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  // (the verdicts cached: per block its 512 B of bits and its descriptor read, 4 + 8 B of count and valid rows written; per row its value read)
+  if (bj.pair_cached) timed(KC_BAND_MASK, (512ull + 16 + 4 + 8) * max_blocks, bj.nrows, nullptr, 4, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  else timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, bj.row_static ? 8 + 4 : b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
   if (!bj.skip_slow) {
+    if (bj.pair_cached) fail(RDFGPU_ERR_INVALID, "band join: the full-semantics pass over a slice's cached verdicts");
     // the full-semantics pass needs the chain's literals and columns: the fused join kernel's argument block, by pointer
     static_assert(sizeof(LdsJoinArgs) <= ExecContext::kArgBytes, "argument staging slot too small");
     const u32 slot = arg_slots_used++;

@@ -111,7 +111,10 @@ struct SliceTable {
   // row the packed {lo pair, width pair} (padded like et).  `key` = the entries' key + the windows' literals, bias and packing, the operand stages' tables
   // and value columns, the typed-value table.  row_win == nullptr: some key's operands are not plain xsd:integers — the form is declined for this key
   // string (remembered, so that it is not built again every step).  Same lock, same rules as the entries.
-  struct BandRowWindows { std::string key; uint2* row_win; };
+  // pair_bits: with the rows' windows and the entries both fixed, the pair test's verdicts themselves are a function of the store version and the literals: 64 words per
+  // block of the in-place layout (what the pair test writes when every row has a table row), 512 B per block, kept when the plan's options allow it
+  // (host_logic.hpp, band_pair_cache_eligible); null: not kept.  Freed with row_win.
+  struct BandRowWindows { std::string key; uint2* row_win; u64* pair_bits = nullptr; };
   std::vector<BandRowWindows> band_row_windows;
   // the slice as the sorted input of a FILTER on its sort column (kernels.hip, run-copy form): lo[i] = first row whose id is >= first + i
   // (i = 0 .. span): where every distinct id's run starts — a function of the slice alone

@@ -123,6 +123,7 @@ def load_library():
     lib.rdfgpu_choose_index.argtypes = [C.POINTER(abi.ScanInstruction), C.c_uint32]
     lib.rdfgpu_choose_index.restype = C.c_uint32
     lib.rdfgpu_band_row_cache_eligible.argtypes = [C.c_uint32] * 5 + [u32p, u32p]
+    lib.rdfgpu_band_pair_cache_eligible.argtypes = [C.c_uint32] * 4 + [C.c_uint64] * 2
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -172,6 +173,12 @@ def band_row_cache_eligible(operands, in_place=True, compact=True, pack16=True, 
     src = (C.c_uint32 * n)(*[int(s) for s, _ in flat])
     keyed = (C.c_uint32 * n)(*[int(bool(k)) for _, k in flat])
     return bool(_check(load_library().rdfgpu_band_row_cache_eligible(int(in_place), int(compact), int(pack16), int(option_set), len(operands), src, keyed)))
+
+
+def band_pair_cache_eligible(n_blocks, row_windows=True, neq_self=True, pack16=True, option_set=False, cap_blocks=0):
+    """.. and may the pair test's verdicts be kept beside the windows (host_logic.hpp)?  `n_blocks`: 64 x 64 blocks of the in-place layout;
+    `cap_blocks`: the BAND_PAIR_CACHE_BLOCKS option (inclusive; 0 = automatic, 2^21 blocks)."""
+    return bool(_check(load_library().rdfgpu_band_pair_cache_eligible(int(row_windows), int(neq_self), int(pack16), int(option_set), int(n_blocks), int(cap_blocks))))
 
 
 def _pred_struct(p, keep):
