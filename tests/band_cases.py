@@ -206,9 +206,10 @@ def window_expr(w, x, ya, yb):
     return AND(half(w.op0, w.sub0, w.lit0, ya), half(w.op1, w.sub1, w.lit1, yb if w.two else ya))
 
 
-def band_plan(windows, neq):
+def band_plan(windows, neq, probe=None):
+    """probe: builds the node that computes T(inst, X, f, ya, yb) in the plan (ordered_cases.py); None: T is the table bound at slot 0"""
     pb = PlanBuilder()
-    t = pb.table(0, 5)
+    t = probe(pb) if probe else pb.table(0, 5)
     scan = lambda p, v: pb.data_source(quad_pattern("product", p, v))
     node = pb.hash_join(t, scan(PF, "f"), on=[(2, 1)], filter=ID_NEQ(col(5), col(1)) if neq else None, projection=[0, 5, 3, 4])   # (inst, product, ya, yb)
     if len(windows) == 1:
