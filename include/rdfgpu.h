@@ -402,7 +402,24 @@ enum {
                                   aggregates must be the plan's root (their values are not object ids and cannot flow into another
                                   operator), anywhere else it is RDFGPU_ERR_UNSUPPORTED at compile.  An input of 2^32 rows or more fails
                                   the execute with RDFGPU_ERR_UNSUPPORTED.  The aggregate values leave through rdfgpu_plan_agg_*;
-                                  rdfgpu_plan_result_info / _device / _fetch report the key columns only.                              */
+                                  rdfgpu_plan_result_info / _device / _fetch report the key columns only.
+                                  With RDFGPU_PLAN_AGG_COLUMNS in rdfgpu_plan_desc.flags (opt-in per plan; without it all of the above holds
+                                  unchanged) a node with aggregates may sit ANYWHERE, the root included: its output has n_keys + table_cols
+                                  u32 columns, the keys and then one VALUE COLUMN per aggregate.  Row g of the node carries g + 1 in a value
+                                  column, or 0 where the aggregate is the error value: an error aggregate is an unbound binding everywhere
+                                  (BOUND is false, a LEFT join's padding looks the same, rdfgpu_plan_next exports a null).  The 24-byte
+                                  values stay in one device array per aggregate, which the entries index (rdfgpu_plan_result_values).
+                                  Value columns are typed at compile and carried through projections, filters and joins.  They may be
+                                  read by ENC_TV and BOUND in FILTER predicates and join filters (ENC_TV yields the aggregate's value:
+                                  the BI plans' HAVING, `FilterExec: EBV(GT(INT64_AS_TERM(count@1), 9:0))`, where INT64_AS_TERM is the
+                                  identity: counts are xsd:integer values already), projected, carried as payload of HASH_JOIN /
+                                  CROSS_JOIN / NESTED_LOOP_JOIN of every join type, consumed by two parents, and be the input of COUNT, SUM
+                                  and AVG (plain or inside an input expression) of a further AggregateExec.  Equal values have different
+                                  indexes, so whatever would compare the entries as ids is RDFGPU_ERR_UNSUPPORTED at compile (the text names
+                                  node and column): a join key, a group column, a COUNT_DISTINCT input, any TopK key / group / output, a
+                                  CLOSURE or UNION input; and so is rdfgpu_plan_decode_terms of a value column.  A value column under
+                                  ID_EQ / ID_NEQ / IS_COMPATIBLE / STR is RDFGPU_ERR_INVALID, like every operand of the wrong kind.  A
+                                  predicate that reads a value column runs in the generic VM.                                          */
 };
 /*
  * Aggregate functions of RDFGPU_NODE_AGGREGATE (ABI 4 addendum).  The reference plans SPARQL aggregates in
@@ -508,6 +525,7 @@ typedef struct rdfgpu_plan_desc {
   uint32_t reserved;
 } rdfgpu_plan_desc;
 #define RDFGPU_PLAN_ALLOW_OPAQUE 1u
+#define RDFGPU_PLAN_AGG_COLUMNS 2u        /* ABI 4 addendum: aggregate values are columns (RDFGPU_NODE_AGGREGATE) */
 
 /* ------------------------------------------------------------------------------------ */
 /* 4. Plans: compile, execute on device, stream result batches                           */
@@ -576,12 +594,23 @@ int rdfgpu_plan_agg_fetch(rdfgpu_plan* plan, uint32_t agg, rdfgpu_agg_value* hos
 /* Device pointer of aggregate `agg` (n_rows values; valid until the next execute / destroy of this plan; NULL when there are no rows). */
 int rdfgpu_plan_agg_device(rdfgpu_plan* plan, uint32_t agg, const rdfgpu_agg_value** values);
 /*
+ * ABI 4 addendum, plans compiled with RDFGPU_PLAN_AGG_COLUMNS: rdfgpu_plan_result_info / _device / _fetch count and deliver the value
+ * columns like any other column (u32 entries), and rdfgpu_plan_agg_count reports 0.
+ * rdfgpu_plan_result_values: the device array result column `col` indexes and its length — entry e of the column (1-based; 0 = unbound)
+ * is (*values)[e - 1].  An object-id column answers NULL and 0.  Valid until the next execute / destroy of this plan.
+ * rdfgpu_plan_result_values_fetch: one value per result row (n_rows of rdfgpu_plan_result_info), gathered on the host; tag 0
+ * (RDFGPU_TV_NULL) where the entry is 0.  RDFGPU_ERR_INVALID for an object-id column.
+ */
+int rdfgpu_plan_result_values(rdfgpu_plan* plan, uint32_t col, const rdfgpu_agg_value** values, uint64_t* n);
+int rdfgpu_plan_result_values_fetch(rdfgpu_plan* plan, uint32_t col, rdfgpu_agg_value* host);
+/*
  * SendableRecordBatchStream::poll_next (stream.rs:39-63): exports the next batch of at
  * most batch_size rows as an Arrow struct array of UInt32 children (format "+s" / "I");
  * id 0 becomes a null.  Never yields an empty batch (scan.rs:195-198).  Returns
  * RDFGPU_END once drained.  `schema` may be NULL.  ABI 4 addendum: after the key columns, each
  * aggregate of an RDFGPU_NODE_AGGREGATE root is one more child, a struct "+s" of
- * tag: uint8 "C", lo: int64 "l", hi: int64 "l" (rdfgpu_agg_value), null where the tag is 0.
+ * tag: uint8 "C", lo: int64 "l", hi: int64 "l" (rdfgpu_agg_value), null where the tag is 0.  With RDFGPU_PLAN_AGG_COLUMNS a value
+ * column is such a struct child in its own place among the columns, null where its entry is 0.
  */
 int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSchema* schema);
 /* Restarts the batch stream over the current result. */

@@ -50,6 +50,8 @@ JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
 MAX_KEYS = 4
 MAX_COLUMNS = 16
 NO_PROJECTION = 0xFFFFFFFF
+PLAN_ALLOW_OPAQUE = 1
+PLAN_AGG_COLUMNS = 2            # rdfgpu_plan_desc.flags: aggregate values are columns that flow into the operators above (RDFGPU_NODE_AGGREGATE)
 
 OP_EQ, OP_GT, OP_GTEQ, OP_LT, OP_LTEQ = range(5)
 
@@ -167,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "rdfgpu_plan_compile", "rdfgpu_plan_destroy", "rdfgpu_plan_bind_table", "rdfgpu_plan_execute",
     "rdfgpu_plan_result_info", "rdfgpu_plan_result_device", "rdfgpu_plan_fetch", "rdfgpu_plan_next",
     "rdfgpu_plan_agg_count", "rdfgpu_plan_agg_fetch", "rdfgpu_plan_agg_device",
+    "rdfgpu_plan_result_values", "rdfgpu_plan_result_values_fetch",
     "rdfgpu_plan_rewind", "rdfgpu_plan_decode_terms", "rdfgpu_ntriples_parse", "rdfgpu_ntriples_info", "rdfgpu_ntriples_terms", "rdfgpu_ntriples_decoded_info", "rdfgpu_ntriples_decoded", "rdfgpu_ntriples_columns", "rdfgpu_ntriples_destroy", "rdfgpu_plan_metrics", "rdfgpu_plan_selected_index", "rdfgpu_plan_stream",
     "rdfgpu_plan_enable_kernel_timing", "rdfgpu_plan_kernel_stats",
     "rdfgpu_plan_pushdown_filters", "rdfgpu_plan_set_dynamic_filters", "rdfgpu_plan_source_predicate",

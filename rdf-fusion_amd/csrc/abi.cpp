@@ -201,6 +201,28 @@ int rdfgpu_plan_agg_fetch(rdfgpu_plan* plan, uint32_t agg, rdfgpu_agg_value* hos
   RDFGPU_HIP(hipStreamSynchronize(p->stream));
   ABI_END
 }
+int rdfgpu_plan_result_values(rdfgpu_plan* plan, uint32_t col, const rdfgpu_agg_value** values, uint64_t* n) {
+  ABI_BEGIN
+  Plan* p = P(plan);
+  if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
+  if (!values) fail(RDFGPU_ERR_INVALID, "null out pointer");
+  *values = p->result_values(col, n);
+  ABI_END
+}
+int rdfgpu_plan_result_values_fetch(rdfgpu_plan* plan, uint32_t col, rdfgpu_agg_value* host) {
+  ABI_BEGIN
+  Plan* p = P(plan);
+  if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
+  if (!p->result_values(col, nullptr)) fail(RDFGPU_ERR_INVALID, "result column %u holds object ids, not aggregate values", col);
+  p->ensure_host_copy();
+  if (p->result_rows) {
+    if (!host) fail(RDFGPU_ERR_INVALID, "null host buffer");
+    std::memcpy(host, p->host_values[col].data(), p->result_rows * sizeof(rdfgpu_agg_value));
+  }
+  ABI_END
+}
 int rdfgpu_plan_agg_device(rdfgpu_plan* plan, uint32_t agg, const rdfgpu_agg_value** values) {
   ABI_BEGIN
   Plan* p = P(plan);
@@ -312,6 +334,10 @@ int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSche
     sp->buffers[0] = nullptr; sp->n = nc; sp->children = new ArrowArray*[nc ? nc : 1];
     for (u32 c = nk; c < nc; c++) sp->children[c] = export_agg(p->host_aggs[c - nk].data() + p->cursor, len);
     for (u32 c = 0; c < nk; c++) {
+      if (!p->host_values[c].empty() || p->result_values(c, nullptr)) {   // a value column: the values its entries stand for
+        sp->children[c] = export_agg(p->host_values[c].data() + p->cursor, len);
+        continue;
+      }
       ArrowArray* ch = new ArrowArray();
       std::memset(ch, 0, sizeof *ch);
       ChildPriv* cp = new ChildPriv();
@@ -341,7 +367,7 @@ int rdfgpu_plan_next(rdfgpu_plan* plan, struct ArrowArray* out, struct ArrowSche
       pr->n = nc; pr->children = new ArrowSchema*[nc ? nc : 1]; pr->names = new std::string[nc ? nc : 1];
       for (u32 c = 0; c < nc; c++) {
         pr->names[c] = "c" + std::to_string(c);
-        if (c >= nk) { pr->children[c] = agg_schema(pr->names[c].c_str()); continue; }
+        if (c >= nk || p->result_values(c, nullptr)) { pr->children[c] = agg_schema(pr->names[c].c_str()); continue; }
         ArrowSchema* cs = new ArrowSchema();
         std::memset(cs, 0, sizeof *cs);
         cs->format = "I"; cs->name = pr->names[c].c_str(); cs->flags = 2 /* ARROW_FLAG_NULLABLE */;
@@ -362,6 +388,8 @@ int rdfgpu_plan_decode_terms(rdfgpu_plan* plan, uint32_t col, uint64_t first_row
     if (!out) fail(RDFGPU_ERR_INVALID, "null out array");
     if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
     if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
+    if (const ValueOrigin& o = p->nodes[p->root].origin[col]; o.node >= 0)
+      fail(RDFGPU_ERR_UNSUPPORTED, "ENC_PT of result column %u: it is an aggregate value column (aggregate %u of node %d), its entries are not object ids (rdfgpu_plan_result_values)", col, o.agg, o.node);
     if (first_row > p->result_rows || n_rows > p->result_rows - first_row) fail(RDFGPU_ERR_INVALID, "rows %llu .. + %llu of a %llu-row result", (unsigned long long)first_row, (unsigned long long)n_rows, (unsigned long long)p->result_rows);
     Store* st = p->store;
     st->activate();

@@ -10,6 +10,7 @@
 //                      head lane issues the atomic (Guideline 12).  When every group's words fit in 64 KiB, each workgroup keeps
 //                      partials in LDS and merges them into HBM once; otherwise (or with NO_AGG_LDS) the atomics go to HBM directly.
 //   agg_final_kernel   one lane per group: the key ids from the group's first row, every aggregate's rdfgpu_agg_value.
+// When aggregate values are columns (RDFGPU_PLAN_AGG_COLUMNS) a fourth, agg_value_cols_kernel, writes each aggregate's value column.
 //
 // Accumulator words of one group (u64, structure of arrays: word w of group g at acc[w * groups + g]):
 //   word 0                  rows of the group (COUNT(*), AVG's count)
@@ -311,6 +312,15 @@ __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
   }
 }
 
+// ---- pass 4, aggregate values as columns (RDFGPU_PLAN_AGG_COLUMNS) only ------------------------------------------------------------
+// One lane per group: row g's entry of every aggregate's value column is g + 1, or 0 where the value is the error value (an unbound
+// binding).  A pass of its own, 4 bytes written per group and aggregate: agg_final_kernel stays what it is for the plans without the flag.
+__global__ __launch_bounds__(kAggBlock) void agg_value_cols_kernel(const AggArgs a) {
+  const u32 g = blockIdx.x * kAggBlock + threadIdx.x;
+  if (g >= a.n_groups) return;
+  for (u32 i = 0; i < a.n_aggs; i++) a.out_val[i][g] = a.out[i][g].tag == RDFGPU_TV_NULL ? 0u : g + 1u;
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
 void launch_agg_groups(const AggArgs& a, hipStream_t s) {
   u64 g = (a.cap + kAggTile - 1) / kAggTile;
@@ -338,6 +348,12 @@ void launch_agg_accum(const AggArgs& a, hipStream_t s) {
 void launch_agg_final(const AggArgs& a, hipStream_t s) {
   const u64 g = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
   hipLaunchKernelGGL(agg_final_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  RDFGPU_HIP(hipGetLastError());
+}
+
+void launch_agg_value_cols(const AggArgs& a, hipStream_t s) {
+  const u64 g = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
+  hipLaunchKernelGGL(agg_value_cols_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
   RDFGPU_HIP(hipGetLastError());
 }
 

@@ -48,8 +48,15 @@ struct TypedTable {
                                  // parsers are not restated)
 };
 
-// Value kinds on the evaluation stack.
-enum : uint32_t { VK_ID = 0, VK_TV = 1, VK_BOOL = 2 };
+// Value kinds on the evaluation stack.  VK_VALUE exists at compile only (check_program): COLUMN of an aggregate value column, whose u32 is
+// an index into its AggregateExec's value array and not an object id; on the device such a column is a VK_ID like any other.
+enum : uint32_t { VK_ID = 0, VK_TV = 1, VK_BOOL = 2, VK_VALUE = 3 };
+
+// Internal op (never accepted from a description: check_program knows RDFGPU_EX_* only).  plan_compile writes it in place of the ENC_TV of
+// an aggregate value column (RDFGPU_PLAN_AGG_COLUMNS): u = origin node << 8 | aggregate; Plan::bind_values fills in, per execution,
+// lo = the device address of that aggregate's rdfgpu_agg_value array and hi = its length.
+constexpr uint8_t kExAggValue = 250;
+static_assert(kExAggValue >= RDFGPU_EX__COUNT, "the internal op must lie outside the ABI's ops");
 
 struct Val {
   int64_t lo;     // ID: object id; TV: payload; BOOL: 0 false / 1 true / 2 null
@@ -96,6 +103,17 @@ __device__ __forceinline__ Val enc_tv(const TypedTable& t, uint32_t id) {
     const int64_t* d = t.dec + 2 * v.lo;
     v.lo = d[0]; v.hi = d[1];
   }
+  return v;
+}
+
+// kExAggValue: the value a value column's entry stands for.  `idx` is 1-based (row g of the AggregateExec carries g + 1); 0, the error
+// aggregate, and anything beyond the array are the null typed value.  An rdfgpu_agg_value is what enc_tv leaves after its side-table read:
+// integer lo; decimal (lo, hi) = the i128; float / double their bits in lo.
+__device__ __forceinline__ Val agg_value_load(const rdfgpu_expr_node& e, uint32_t idx) {
+  Val v = val_tv_null();
+  if (idx == 0 || (uint64_t)idx > (uint64_t)e.hi) return v;
+  const long long* p = reinterpret_cast<const long long*>(e.lo) + 3ull * (idx - 1u);
+  v.lo = p[0]; v.hi = p[1]; v.tag = (uint8_t)((uint64_t)p[2] & 0xff);
   return v;
 }
 
@@ -657,6 +675,7 @@ __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const Typed
       case RDFGPU_EX_LIT_TV: v = val_tv_null(); v.tag = e.tag; v.flags = e.flags; v.aux = e.u; v.lo = e.lo; v.hi = e.hi; break;
       case RDFGPU_EX_LIT_BOOL: v = val_bool(e.u > 2 ? 2 : e.u); break;
       case RDFGPU_EX_ENC_TV: v = enc_tv(tt, (uint32_t)st[--sp].lo); break;
+      case kExAggValue: v = agg_value_load(e, (uint32_t)st[--sp].lo); break;
       case RDFGPU_EX_GT: case RDFGPU_EX_LT: case RDFGPU_EX_GEQ: case RDFGPU_EX_LEQ: case RDFGPU_EX_EQ: case RDFGPU_EX_NEQ: {
         const Val b = st[--sp]; const Val a = st[--sp];
         const int o = (a.tag == RDFGPU_TV_STRING && b.tag == RDFGPU_TV_STRING && (str_is_view(a) || str_is_view(b))) ? tv_cmp_string_views(&prog, tt, a, b) : tv_partial_cmp(a, b);

@@ -316,10 +316,12 @@ struct AggArgs {
   u32 lds;                                       // pass 2: 1 = LDS partials per workgroup
   u32* out_key[RDFGPU_MAX_KEYS];
   rdfgpu_agg_value* out[RDFGPU_MAX_AGGREGATES];
+  u32* out_val[RDFGPU_MAX_AGGREGATES];           // RDFGPU_PLAN_AGG_COLUMNS: the aggregate's value column (row g: g + 1, or 0 for the error value); else null
 };
 void launch_agg_groups(const AggArgs& a, hipStream_t s);
 void launch_agg_accum(const AggArgs& a, hipStream_t s);
 void launch_agg_final(const AggArgs& a, hipStream_t s);
+void launch_agg_value_cols(const AggArgs& a, hipStream_t s);   // RDFGPU_PLAN_AGG_COLUMNS: every out_val[i] set
 void preload_tu_aggregate();
 
 void launch_lds_join(const LdsJoinArgs& a, hipStream_t s);

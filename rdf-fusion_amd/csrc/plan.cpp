@@ -146,7 +146,8 @@ const char* kernel_class_name(int kc) {
       "void rdfgpu::semi_join_kernel<1, true", "void rdfgpu::semi_nested_kernel<false", "void rdfgpu::semi_nested_kernel<true",
       "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel",
       "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>",
-      "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel", "void rdfgpu::band_pair_bits_kernel"};
+      "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel", "void rdfgpu::band_pair_bits_kernel",
+      "rdfgpu::agg_value_cols_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -197,8 +198,27 @@ const ExprProgram* Plan::upload_program(const ExprProgram& p) {
   if (progs_used >= ExecContext::kProgSlots) fail(RDFGPU_ERR_UNSUPPORTED, "plan needs more than %u device expression programs", ExecContext::kProgSlots);
   const u32 slot = progs_used++;
   ctx->progs_host[slot] = p;
+  bind_values(ctx->progs_host[slot]);
   RDFGPU_HIP(hipMemcpyAsync(ctx->progs_dev + slot, ctx->progs_host + slot, sizeof(ExprProgram), hipMemcpyHostToDevice, stream));
   return ctx->progs_dev + slot;
+}
+// A value load names its AggregateExec and aggregate; the arrays are scratch of the execution that wrote them, so every execution binds
+// its programs anew (the AggregateExec below has run by the time an operator above it prepares its launch).
+void Plan::bind_values(ExprProgram& p) const {
+  if (!agg_columns) return;
+  for (u32 i = 0; i < p.n; i++) {
+    rdfgpu_expr_node& e = p.nodes[i];
+    if (e.op != kExAggValue) continue;
+    const u32 node = e.u >> 8, agg = e.u & 0xffu;
+    if (node >= nodes.size() || nodes[node].values_run != run) fail(RDFGPU_ERR_INVALID, "a value column of node %u is read before the node ran", node);
+    e.lo = (int64_t)reinterpret_cast<uintptr_t>(nodes[node].values[agg]);
+    e.hi = (int64_t)nodes[node].n_values;
+  }
+}
+const rdfgpu_agg_value* Plan::result_values(u32 col, u64* n) const {
+  const ValueOrigin& o = nodes[root].origin[col];
+  if (n) *n = o.node < 0 ? 0 : nodes[o.node].n_values;
+  return o.node < 0 ? nullptr : nodes[o.node].values[o.agg];
 }
 u64* Plan::new_counter() {
   if (counters_used >= 255) fail(RDFGPU_ERR_UNSUPPORTED, "plan needs more than 255 cardinality counters");   // slot 255: run-time error flags
@@ -279,6 +299,7 @@ void Plan::execute() {
   metrics = rdfgpu_metrics{};
   const u64 mallocs0 = store->pool.mallocs() + store->table_pool.mallocs();
   const double malloc_ms0 = store->pool.malloc_ms() + store->table_pool.malloc_ms();
+  run++;
   counters_used = 0;
   progs_used = 0;
   arg_slots_used = 0;
@@ -638,10 +659,14 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
   }
   a.n_groups = (u32)G;
   DevTable t;
-  t.n_cols = a.n_keys; t.cap = G;
+  t.n_cols = nd.width; t.cap = G;   // the keys; with aggregate values as columns, one more per aggregate
   for (u32 k = 0; k < a.n_keys; k++) { a.out_key[k] = scratch<u32>(G); t.cols[k] = a.out_key[k]; }
-  for (u32 i = 0; i < a.n_aggs; i++) a.out[i] = scratch<rdfgpu_agg_value>(G);
-  if (&nd == &nodes[root]) agg_out.assign(a.out, a.out + a.n_aggs);
+  for (u32 i = 0; i < a.n_aggs; i++) {
+    a.out[i] = scratch<rdfgpu_agg_value>(G); nd.values[i] = a.out[i];
+    if (agg_columns) { a.out_val[i] = scratch<u32>(G); t.cols[a.n_keys + i] = a.out_val[i]; }
+  }
+  nd.n_values = G; nd.values_run = run;
+  if (&nd == &nodes[root] && !agg_columns) agg_out.assign(a.out, a.out + a.n_aggs);
   if (G == 0) return t;
   a.acc = scratch<unsigned long long>(a.n_words * G);
   RDFGPU_HIP(hipMemsetAsync(a.acc, 0, a.n_words * G * sizeof(unsigned long long), stream));
@@ -658,6 +683,8 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
     timed(a.exprs ? (a.lds ? KC_AGG_ACCUM_EXPR_LDS : KC_AGG_ACCUM_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
   }
   timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
+  // the value columns: per group and aggregate the tag read (the value was just written: cache) and 4 bytes written
+  if (agg_columns && a.n_aggs) timed(KC_AGG_VALUE_COLS, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_aggs, [&] { launch_agg_value_cols(a, stream); });
   return t;
 }
 
@@ -676,6 +703,28 @@ void Plan::ensure_host_copy() {
     if (result_rows) RDFGPU_HIP(hipMemcpyAsync(host_aggs[i].data(), agg_out[i], result_rows * sizeof(rdfgpu_agg_value), hipMemcpyDeviceToHost, stream));
   }
   RDFGPU_HIP(hipStreamSynchronize(stream));
+  // a value column's rows index their AggregateExec's array: one value per result row, tag 0 where the binding is unbound.  Each array comes
+  // over once, however many columns index it, and all of them behind one wait.
+  host_values.assign(result.n_cols, std::vector<rdfgpu_agg_value>());
+  std::vector<const rdfgpu_agg_value*> origins; std::vector<std::vector<rdfgpu_agg_value>> copies;
+  std::vector<int> copy_of(result.n_cols, -1);
+  for (u32 c = 0; c < result.n_cols; c++) {
+    u64 n = 0;
+    const rdfgpu_agg_value* dev = result_values(c, &n);
+    if (!dev) continue;
+    const size_t at = std::find(origins.begin(), origins.end(), dev) - origins.begin();
+    if (at == origins.size()) { origins.push_back(dev); copies.emplace_back(result_rows ? n : 0); }
+    copy_of[c] = (int)at;
+  }
+  for (size_t i = 0; i < origins.size(); i++)
+    if (!copies[i].empty()) RDFGPU_HIP(hipMemcpyAsync(copies[i].data(), origins[i], copies[i].size() * sizeof(rdfgpu_agg_value), hipMemcpyDeviceToHost, stream));
+  if (!origins.empty()) RDFGPU_HIP(hipStreamSynchronize(stream));
+  for (u32 c = 0; c < result.n_cols; c++) {
+    if (copy_of[c] < 0) continue;
+    const std::vector<rdfgpu_agg_value>& all = copies[copy_of[c]];
+    host_values[c].assign(result_rows, rdfgpu_agg_value{});
+    for (u64 r = 0; r < result_rows; r++) { const u32 id = host_cols[c][r]; if (id != 0 && id <= all.size()) host_values[c][r] = all[id - 1]; }
+  }
   host_valid = true;
 }
 

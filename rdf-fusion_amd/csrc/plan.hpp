@@ -38,9 +38,14 @@ struct BandHistory {
   bool row_cache = false;       // exec_band_join: the rows' decoded windows are cached on the slice too (SliceTable::BandRowWindows).  run_ordered_join: its probe pass prepares the values by key, not the 16-byte records
 };
 
+// Where an output column's aggregate values come from (RDFGPU_PLAN_AGG_COLUMNS): node < 0 = an object-id column; else the column holds
+// 1-based indexes into aggregate `agg` of AggregateExec `node` (0 = unbound).  Fixed at compile, carried through every operator above.
+struct ValueOrigin { int node = -1; u32 agg = 0; };
+
 struct NodeInfo {
   rdfgpu_plan_node d;
   u32 width = 0;                  // output columns
+  ValueOrigin origin[kMaxCols];   // per output column: the aggregate whose values it indexes, if it is a value column
   u32 n_proj = 0; u32 proj[kMaxCols] = {};
   ExprProgram prog{};             // filter / join filter
   int shape = 0;                  // filter kernel specialisation
@@ -55,6 +60,7 @@ struct NodeInfo {
   u32 n_aggs = 0; u32 agg_fn[RDFGPU_MAX_AGGREGATES] = {}, agg_col[RDFGPU_MAX_AGGREGATES] = {};   // AggregateExec: (RDFGPU_AGG_*, input column)
   int agg_prog[RDFGPU_MAX_AGGREGATES] = {-1, -1, -1, -1, -1, -1, -1, -1};                           // .. or the index in agg_progs of its input expression (RDFGPU_AGG_INPUT_EXPR)
   std::vector<ExprProgram> agg_progs;
+  rdfgpu_agg_value* values[RDFGPU_MAX_AGGREGATES] = {}; u64 n_values = 0, values_run = 0;   // AggregateExec: the value arrays (scratch) of execution `values_run` (Plan::run) and their length = its groups
   BandHistory band;                            // the band join based on this node, if there was one
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
@@ -149,6 +155,7 @@ enum KernelClass {
   KC_AGG_ACCUM_EXPR_HBM, KC_AGG_ACCUM_EXPR_LDS,   // agg_accum_expr_kernel<LDS>: some SUM / AVG reads an expression
   KC_BAND_ROW_WIN_KEYS, KC_BAND_ROW_WIN_ROWS,     // the build of a slice's cached row windows (band_join.hip)
   KC_BAND_PAIR_BITS,                              // .. and of its cached pair verdicts
+  KC_AGG_VALUE_COLS,                              // agg_value_cols_kernel: an AggregateExec's value columns (RDFGPU_PLAN_AGG_COLUMNS)
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
@@ -185,6 +192,8 @@ struct Plan {
   unsigned char* str_consts_dev = nullptr;   // bytes of the plan's string constants (RDFGPU_EX_LIT_STR)
   std::vector<std::string> regex_strings; std::vector<rdfgpu_regex> regex_text;   // their texts (pattern, flags per entry)
   u32 root = 0;
+  u64 run = 0;                    // counts the executions (a value array belongs to the one that wrote it)
+  bool agg_columns = false;       // RDFGPU_PLAN_AGG_COLUMNS: aggregate values are u32 columns that flow into the operators above
   ExecContext* ctx = nullptr;     // stream, events, counters (pooled per store)
   hipStream_t stream = nullptr;
   std::vector<BoundTable> tables;
@@ -224,6 +233,10 @@ struct Plan {
   std::vector<std::vector<u32>> host_cols; bool host_valid = false; u64 cursor = 0;
   // aggregate values of an AggregateExec root (result_rows each), on the device and their host copy
   std::vector<rdfgpu_agg_value*> agg_out; std::vector<std::vector<rdfgpu_agg_value>> host_aggs;
+  // .. and, per result column that is a value column, the value of every result row (gathered on the host; empty for an id column)
+  std::vector<std::vector<rdfgpu_agg_value>> host_values;
+  // the value array result column `col` indexes, of this execution (null / 0: an id column)
+  const rdfgpu_agg_value* result_values(u32 col, u64* n) const;
 
   ~Plan();
   // the store's typed-value table with this execution's run-time error word attached (the last counter slot)
@@ -284,6 +297,7 @@ struct Plan {
   template <class T> T* scratch(u64 n);
   u64* new_counter();
   const ExprProgram* upload_program(const ExprProgram& p);
+  void bind_values(ExprProgram& p) const;   // a program's value loads (kExAggValue) get this execution's arrays
   // one host round trip: `bytes` of device memory copied to `host`, then the stream waited for
   void read_back(void* host, const void* dev, size_t bytes);
   template <class T> T read_back(const void* dev) { T v{}; read_back(&v, dev, sizeof v); return v; }

@@ -14,18 +14,25 @@ bool is_cmp(u8 op) {
   return op == RDFGPU_EX_GT || op == RDFGPU_EX_LT || op == RDFGPU_EX_GEQ || op == RDFGPU_EX_LEQ || op == RDFGPU_EX_EQ || op == RDFGPU_EX_NEQ;
 }
 
-// Type-checks a postfix program against `n_cols` input columns; returns the kind it leaves.
-u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 0) {
+// Type-checks a postfix program against `n_cols` input columns; returns the kind it leaves.  `value_cols`: bit c = input column c is an
+// aggregate value column (RDFGPU_PLAN_AGG_COLUMNS) — COLUMN of it is a VK_VALUE, which only ENC_TV and BOUND take: its u32 is an index, so
+// whatever compares or prints ids (ID_EQ, ID_NEQ, IS_COMPATIBLE, STR) would answer about the index.
+u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 0, u32 value_cols = 0) {
   if (n > (u32)kMaxExpr) fail(RDFGPU_ERR_UNSUPPORTED, "expression has %u nodes (max %d)", n, kMaxExpr);
   u32 st[kMaxStack]; bool no_bytes[kMaxStack]; int sp = 0;
   bool views = false, rank_only_string = false;   // computed strings (views) / a string literal given by its rank in the dictionary only
   bool out_no_bytes = false;                      // the value being pushed is such a literal: it has no lexical form on the device
   auto pop = [&](u32 kind, const char* what) {
     if (sp < 1) fail(RDFGPU_ERR_INVALID, "expression: stack underflow at %s", what);
+    if (st[sp - 1] == VK_VALUE && kind == VK_ID) fail(RDFGPU_ERR_INVALID, "expression: %s got an aggregate value column, whose entries are not object ids (ENC_TV and BOUND read one)", what);
     if (st[--sp] != kind) fail(RDFGPU_ERR_INVALID, "expression: %s got an operand of the wrong kind", what);
   };
   // an operand whose BYTES the op reads (REGEX / CONTAINS / STRSTARTS / STRENDS / STRLEN / SUBSTR / UCASE / LCASE): a string literal
   // that came with its rank only would be the error value on every row — refused here, loudly, instead
+  auto pop_id_or_value = [&](const char* what) {   // ENC_TV / BOUND: an object id, or a value column's entry
+    if (sp >= 1 && st[sp - 1] == VK_VALUE) { --sp; return; }
+    pop(VK_ID, what);
+  };
   auto pop_bytes = [&](const char* what) {
     if (sp >= 1 && no_bytes[sp - 1]) fail(RDFGPU_ERR_UNSUPPORTED, "%s over a string literal given by its dictionary rank only: it has no lexical form on the device (pass it as RDFGPU_EX_LIT_STR)", what);
     pop(VK_TV, what);
@@ -35,13 +42,14 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
     u32 out;
     out_no_bytes = false;
     switch (e.op) {
-      case RDFGPU_EX_COLUMN: if (e.u >= n_cols) fail(RDFGPU_ERR_INVALID, "expression: column %u out of range (%u columns)", e.u, n_cols); out = VK_ID; break;
+      case RDFGPU_EX_COLUMN: if (e.u >= n_cols) fail(RDFGPU_ERR_INVALID, "expression: column %u out of range (%u columns)", e.u, n_cols);
+        out = e.u < 32 && ((value_cols >> e.u) & 1u) ? VK_VALUE : VK_ID; break;
       case RDFGPU_EX_LIT_ID: out = VK_ID; break;
       case RDFGPU_EX_LIT_TV: if (e.tag > RDFGPU_TV_OTHER) fail(RDFGPU_ERR_INVALID, "expression: bad literal tag %u", e.tag); out = VK_TV;
         out_no_bytes = e.tag == RDFGPU_TV_STRING && e.hi == 0;
         rank_only_string = rank_only_string || out_no_bytes; break;
       case RDFGPU_EX_LIT_BOOL: out = VK_BOOL; break;
-      case RDFGPU_EX_ENC_TV: pop(VK_ID, "ENC_TV"); out = VK_TV; break;
+      case RDFGPU_EX_ENC_TV: pop_id_or_value("ENC_TV"); out = VK_TV; break;
       case RDFGPU_EX_GT: case RDFGPU_EX_LT: case RDFGPU_EX_GEQ: case RDFGPU_EX_LEQ: case RDFGPU_EX_EQ: case RDFGPU_EX_NEQ:
       case RDFGPU_EX_ADD: case RDFGPU_EX_SUB: case RDFGPU_EX_MUL: case RDFGPU_EX_DIV: pop(VK_TV, "binary typed op"); pop(VK_TV, "binary typed op"); out = VK_TV; break;
       case RDFGPU_EX_NEG: case RDFGPU_EX_PLUS: case RDFGPU_EX_ABS: case RDFGPU_EX_ROUND: case RDFGPU_EX_CEIL: case RDFGPU_EX_FLOOR:
@@ -76,7 +84,7 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
       case RDFGPU_EX_ID_EQ: case RDFGPU_EX_ID_NEQ: case RDFGPU_EX_IS_COMPATIBLE: pop(VK_ID, "id comparison"); pop(VK_ID, "id comparison"); out = VK_BOOL; break;
       case RDFGPU_EX_AND: case RDFGPU_EX_OR: pop(VK_BOOL, "AND/OR"); pop(VK_BOOL, "AND/OR"); out = VK_BOOL; break;
       case RDFGPU_EX_NOT: pop(VK_BOOL, "NOT"); out = VK_BOOL; break;
-      case RDFGPU_EX_BOUND: pop(VK_ID, "BOUND"); out = VK_BOOL; break;
+      case RDFGPU_EX_BOUND: pop_id_or_value("BOUND"); out = VK_BOOL; break;
       case RDFGPU_EX_BOOL_AS_TV: pop(VK_BOOL, "BOOLEAN_AS_TERM"); out = VK_TV; break;
       default: fail(RDFGPU_ERR_INVALID, "expression: unknown op %u", e.op);
     }
@@ -90,8 +98,14 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
   return st[0];
 }
 
+// A program with a value load in it runs in the generic VM: the specialised forms gather from the typed-value table by object id.
+bool reads_values(const ExprProgram& pr) {
+  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue) return true;
+  return false;
+}
+
 int detect_shape(const ExprProgram& pr, bool force_vm) {
-  if (force_vm) return 0;
+  if (force_vm || reads_values(pr)) return 0;
   const rdfgpu_expr_node* e = pr.nodes;
   if (pr.n == 3 && e[0].op == RDFGPU_EX_COLUMN && e[1].op == RDFGPU_EX_LIT_ID && (e[2].op == RDFGPU_EX_ID_EQ || e[2].op == RDFGPU_EX_ID_NEQ)) return 1;
   if (pr.n == 5 && e[0].op == RDFGPU_EX_COLUMN && e[1].op == RDFGPU_EX_ENC_TV && e[2].op == RDFGPU_EX_LIT_TV && is_cmp(e[3].op) && e[4].op == RDFGPU_EX_EBV) return 2;
@@ -107,7 +121,7 @@ int detect_shape(const ExprProgram& pr, bool force_vm) {
 // (Q5 (Execution Plan).snap:10,12), 1 = generic VM, 0 = no filter.
 int detect_join_filter_shape(const ExprProgram& pr, bool force_vm) {
   if (pr.n == 0) return 0;
-  if (force_vm) return 1;
+  if (force_vm || reads_values(pr)) return 1;
   const rdfgpu_expr_node* e = pr.nodes;
   auto half = [&](u32 o) {
     return e[o].op == RDFGPU_EX_COLUMN && e[o + 1].op == RDFGPU_EX_ENC_TV && e[o + 2].op == RDFGPU_EX_COLUMN &&
@@ -120,20 +134,40 @@ int detect_join_filter_shape(const ExprProgram& pr, bool force_vm) {
   return 1;
 }
 
-void load_program(NodeInfo& nd, const rdfgpu_plan_desc* d, u32 n_cols, const char* what, const RegexProg* regex_dev, const unsigned char* str_consts = nullptr) {
+// The schema an operator's program and projection see: its input's columns (a join's: left, then right) with their value origins.
+struct InputSchema {
+  u32 n = 0; ValueOrigin origin[2 * kMaxCols];
+  void append(const NodeInfo& c) { for (u32 k = 0; k < c.width && n < 2u * kMaxCols; k++) origin[n++] = c.origin[k]; }
+  u32 value_cols() const { u32 m = 0; for (u32 k = 0; k < n; k++) if (origin[k].node >= 0) m |= 1u << k; return m; }
+};
+
+// ENC_TV of a value column becomes the value load of its origin.  (The operand of ENC_TV is a leaf, COLUMN or LIT_ID: the node before it.)
+void rewrite_value_loads(ExprProgram& pr, const InputSchema& in) {
+  for (u32 i = 1; i < pr.n; i++) {
+    rdfgpu_expr_node& e = pr.nodes[i];
+    const rdfgpu_expr_node& c = pr.nodes[i - 1];
+    if (e.op != RDFGPU_EX_ENC_TV || c.op != RDFGPU_EX_COLUMN || c.u >= in.n || in.origin[c.u].node < 0) continue;
+    e.op = kExAggValue; e.u = ((u32)in.origin[c.u].node << 8) | in.origin[c.u].agg;
+  }
+}
+
+void load_program(NodeInfo& nd, const rdfgpu_plan_desc* d, const InputSchema& in, const char* what, const RegexProg* regex_dev, const unsigned char* str_consts = nullptr) {
+  const u32 n_cols = in.n;
   const rdfgpu_plan_node& r = nd.d;
   nd.prog.n = 0;
   if (r.expr_len == 0) return;
   if ((u64)r.expr_off + r.expr_len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "%s: expression outside the expression array", what);
-  if (check_program(d->exprs + r.expr_off, r.expr_len, n_cols, d->n_regexes) != VK_BOOL) fail(RDFGPU_ERR_INVALID, "%s: predicate does not yield a boolean", what);
+  if (check_program(d->exprs + r.expr_off, r.expr_len, n_cols, d->n_regexes, in.value_cols()) != VK_BOOL) fail(RDFGPU_ERR_INVALID, "%s: predicate does not yield a boolean", what);
   nd.prog.n = r.expr_len;
   std::memcpy(nd.prog.nodes, d->exprs + r.expr_off, r.expr_len * sizeof(rdfgpu_expr_node));
   nd.prog.regex = regex_dev;
   nd.prog.str_consts = str_consts;
+  rewrite_value_loads(nd.prog, in);
 }
 
-void load_projection(NodeInfo& nd, const rdfgpu_plan_desc* d, u32 full, const char* what) {
+void load_projection(NodeInfo& nd, const rdfgpu_plan_desc* d, const InputSchema& in, const char* what) {
   const rdfgpu_plan_node& r = nd.d;
+  const u32 full = in.n;
   if (r.n_proj == RDFGPU_NO_PROJECTION) {
     if (full > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "%s: %u columns (max %d)", what, full, kMaxCols);
     nd.n_proj = full;
@@ -148,6 +182,13 @@ void load_projection(NodeInfo& nd, const rdfgpu_plan_desc* d, u32 full, const ch
     }
   }
   nd.width = nd.n_proj;
+  for (u32 i = 0; i < nd.n_proj; i++) nd.origin[i] = in.origin[nd.proj[i]];   // a projected value column keeps its origin
+}
+
+// The operators that compare, sort, chain or decode ids refuse a value column: equal values have different indexes.
+void refuse_value_column(const ValueOrigin& o, u32 node, const char* role, u32 column) {
+  if (o.node >= 0)
+    fail(RDFGPU_ERR_UNSUPPORTED, "node %u: %s column %u is an aggregate value column (aggregate %u of node %d): its entries index values, equal values have different indexes", node, role, column, o.agg, o.node);
 }
 
 // The plan's string table (REGEX patterns, needles, language sets, string constants): compiled by use, kept as texts, uploaded.
@@ -228,10 +269,10 @@ void check_string_functions(const Store* store, const rdfgpu_plan_desc* d) {
   }
 }
 
-// Input `c` of node `i`: an earlier node, and no AggregateExec that carries aggregate values.
+// Input `c` of node `i`: an earlier node, and — unless aggregate values are columns (RDFGPU_PLAN_AGG_COLUMNS) — no AggregateExec that carries them.
 const NodeInfo& child(const Plan* plan, u32 i, int32_t c, const char* what) {
   if (c < 0 || (u32)c >= i) fail(RDFGPU_ERR_INVALID, "node %u: %s child %d must precede the node", i, what, c);
-  if (plan->nodes[c].d.kind == RDFGPU_NODE_AGGREGATE && plan->nodes[c].n_aggs)   // aggregate values are not object ids
+  if (!plan->agg_columns && plan->nodes[c].d.kind == RDFGPU_NODE_AGGREGATE && plan->nodes[c].n_aggs)   // aggregate values are not object ids
     fail(RDFGPU_ERR_UNSUPPORTED, "node %u: input %d is an AggregateExec with aggregates, which must be the plan's root", i, c);
   return plan->nodes[c];
 }
@@ -246,14 +287,19 @@ void compile_join(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   if (r.join_type != RDFGPU_JOIN_INNER && r.join_type != RDFGPU_JOIN_LEFT && !semi) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: join type %u", i, r.join_type);
   if (r.kind == RDFGPU_NODE_HASH_JOIN) {
     if (r.n_keys == 0 || r.n_keys > RDFGPU_MAX_KEYS) fail(RDFGPU_ERR_INVALID, "node %u: HashJoinExec needs 1..%u keys", i, RDFGPU_MAX_KEYS);
-    for (u32 k = 0; k < r.n_keys; k++)
+    for (u32 k = 0; k < r.n_keys; k++) {
       if (r.left_keys[k] >= l.width || r.right_keys[k] >= rr.width) fail(RDFGPU_ERR_INVALID, "node %u: join key out of range", i);
+      refuse_value_column(l.origin[r.left_keys[k]], i, "left join key", r.left_keys[k]);
+      refuse_value_column(rr.origin[r.right_keys[k]], i, "right join key", r.right_keys[k]);
+    }
   }
   if (r.kind == RDFGPU_NODE_CROSS_JOIN && (r.expr_len || r.join_type != RDFGPU_JOIN_INNER)) fail(RDFGPU_ERR_INVALID, "node %u: CrossJoinExec takes no filter / join type", i);
   if (l.width + rr.width > 2u * kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
-  load_program(nd, d, l.width + rr.width, "join filter", plan->regex_dev, plan->str_consts_dev);
+  InputSchema both, left;
+  both.append(l); both.append(rr); left.append(l);
+  load_program(nd, d, both, "join filter", plan->regex_dev, plan->str_consts_dev);
   // a semi / anti join outputs the left columns only: its projection indexes them (the filter still sees both sides)
-  load_projection(nd, d, semi ? l.width : l.width + rr.width, "join");
+  load_projection(nd, d, semi ? left : both, "join");
   nd.shape = detect_join_filter_shape(nd.prog, plan->opt.on(RDFGPU_OPT_FORCE_GENERIC_VM));
   if (l.width > (u32)kMaxCols || rr.width > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
 }
@@ -268,9 +314,13 @@ void compile_topk(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   for (u32 k = 0; k < r.n_keys; k++) {
     if (r.left_keys[k] >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: sort key column %u out of range", i, r.left_keys[k]);
     if (r.right_keys[k] > RDFGPU_SORT_BY_DOUBLE) fail(RDFGPU_ERR_INVALID, "node %u: unknown sort mode %u", i, r.right_keys[k]);
+    refuse_value_column(c.origin[r.left_keys[k]], i, "TopK sort key", r.left_keys[k]);
   }
   if (r.table_slot > c.width) fail(RDFGPU_ERR_INVALID, "node %u: group column out of range", i);
-  load_projection(nd, d, c.width, "TopK");
+  if (r.table_slot != 0) refuse_value_column(c.origin[r.table_slot - 1], i, "TopK group", r.table_slot - 1);
+  InputSchema in; in.append(c);
+  load_projection(nd, d, in, "TopK");
+  for (u32 q = 0; q < nd.n_proj; q++) refuse_value_column(nd.origin[q], i, "TopK output", nd.proj[q]);
   for (u32 q = 0; q < nd.n_proj; q++) {   // DISTINCT is over (group, keys): the output may not carry anything else
     bool covered = r.table_slot != 0 && nd.proj[q] == r.table_slot - 1;
     for (u32 k = 0; k < r.n_keys; k++) covered = covered || (nd.proj[q] == r.left_keys[k] && r.right_keys[k] == RDFGPU_SORT_BY_ID);
@@ -288,12 +338,15 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   if (r.table_cols > RDFGPU_MAX_AGGREGATES) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u aggregates (at most %u)", i, r.table_cols, RDFGPU_MAX_AGGREGATES);
   if (r.n_proj != RDFGPU_NO_PROJECTION) fail(RDFGPU_ERR_INVALID, "node %u: AggregateExec takes no projection", i);
   if (r.n_keys + r.table_cols == 0) fail(RDFGPU_ERR_INVALID, "node %u: AggregateExec without group columns and aggregates", i);
-  for (u32 k = 0; k < r.n_keys; k++)
+  InputSchema in; in.append(c);
+  for (u32 k = 0; k < r.n_keys; k++) {
     if (r.left_keys[k] >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: group column %u out of range", i, r.left_keys[k]);
+    refuse_value_column(c.origin[r.left_keys[k]], i, "group", r.left_keys[k]);
+  }
   if (r.table_cols && ((u64)r.table_slot + 2ull * r.table_cols > d->n_pool || !d->pool)) fail(RDFGPU_ERR_INVALID, "node %u: aggregate list outside the pool", i);
   for (u32 a = 0; a < r.table_cols; a++) {
-    const u32 fn = d->pool[r.table_slot + 2 * a], in = d->pool[r.table_slot + 2 * a + 1];
-    const bool expr = fn != RDFGPU_AGG_COUNT_STAR && (in & RDFGPU_AGG_INPUT_EXPR) != 0;
+    const u32 fn = d->pool[r.table_slot + 2 * a], col = d->pool[r.table_slot + 2 * a + 1];
+    const bool expr = fn != RDFGPU_AGG_COUNT_STAR && (col & RDFGPU_AGG_INPUT_EXPR) != 0;
     switch (fn) {
       case RDFGPU_AGG_COUNT_STAR: break;
       case RDFGPU_AGG_COUNT: case RDFGPU_AGG_COUNT_DISTINCT:
@@ -301,7 +354,7 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
         [[fallthrough]];
       case RDFGPU_AGG_SUM: case RDFGPU_AGG_AVG:
         if (expr) {   // (expr_off, expr_len) in the pool: a program over the input's columns that leaves a typed value
-          const u32 at = in & ~RDFGPU_AGG_INPUT_EXPR;
+          const u32 at = col & ~RDFGPU_AGG_INPUT_EXPR;
           if ((u64)at + 2 > d->n_pool) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression input at pool offset %u of %u", i, a, at, d->n_pool);
           const u32 off = d->pool[at], len = d->pool[at + 1];
           if (len == 0 || (u64)off + len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression outside the expression array", i, a);
@@ -310,14 +363,28 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
             if (op == RDFGPU_EX_REGEX || op == RDFGPU_EX_REGEX_VAR || op == RDFGPU_EX_CONTAINS || op == RDFGPU_EX_STRSTARTS || op == RDFGPU_EX_STRENDS || op == RDFGPU_EX_LANG_IN)
               fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES in an aggregate's input expression are not on the device", i, a);
           }
-          if (check_program(d->exprs + off, len, c.width, d->n_regexes) != VK_TV) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: the input expression does not yield a typed value", i, a);
+          if (check_program(d->exprs + off, len, c.width, d->n_regexes, in.value_cols()) != VK_TV) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: the input expression does not yield a typed value", i, a);
           ExprProgram pr{};
           pr.n = len;
           std::memcpy(pr.nodes, d->exprs + off, len * sizeof(rdfgpu_expr_node));
           pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
+          rewrite_value_loads(pr, in);
           nd.agg_prog[a] = (int)nd.agg_progs.size();
           nd.agg_progs.push_back(pr);
-        } else if (in >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, in, c.width);
+        } else if (col >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, col, c.width);
+        else if (fn == RDFGPU_AGG_COUNT_DISTINCT) refuse_value_column(c.origin[col], i, "COUNT DISTINCT input", col);
+        else if (c.origin[col].node >= 0 && fn != RDFGPU_AGG_COUNT) {
+          // SUM / AVG of a value column: the two-node program [COLUMN, value load], so the EXPR form of the accumulate pass runs it.
+          // (COUNT needs nothing: an entry of 0 is "not counted" already.)
+          ExprProgram pr{};
+          pr.n = 2;
+          pr.nodes[0].op = RDFGPU_EX_COLUMN; pr.nodes[0].u = col;
+          pr.nodes[1].op = RDFGPU_EX_ENC_TV;
+          pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
+          rewrite_value_loads(pr, in);
+          nd.agg_prog[a] = (int)nd.agg_progs.size();
+          nd.agg_progs.push_back(pr);
+        }
         break;
       case RDFGPU_AGG_MIN: case RDFGPU_AGG_MAX: case RDFGPU_AGG_SAMPLE: case RDFGPU_AGG_GROUP_CONCAT:
         fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: MIN / MAX / SAMPLE / GROUP_CONCAT are not on the device (MIN / MAX keep the first "
@@ -326,11 +393,80 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
         fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: SUM / AVG with DISTINCT and COUNT(DISTINCT *) are not on the device", i, a);
       default: fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: unknown function %u", i, a, fn);
     }
-    nd.agg_fn[a] = fn; nd.agg_col[a] = fn == RDFGPU_AGG_COUNT_STAR || expr ? 0 : in;
+    nd.agg_fn[a] = fn; nd.agg_col[a] = fn == RDFGPU_AGG_COUNT_STAR || expr ? 0 : col;
   }
   nd.n_aggs = r.table_cols;
-  if (nd.n_aggs && i != d->root) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: an AggregateExec with aggregates must be the plan's root (node %u)", i, d->root);
-  nd.width = r.n_keys;   // the id columns; the aggregates leave through rdfgpu_plan_agg_*
+  if (!plan->agg_columns) {
+    if (nd.n_aggs && i != d->root) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: an AggregateExec with aggregates must be the plan's root (node %u)", i, d->root);
+    nd.width = r.n_keys;   // the id columns; the aggregates leave through rdfgpu_plan_agg_*
+    return;
+  }
+  // RDFGPU_PLAN_AGG_COLUMNS: the keys, then one value column per aggregate, each its own origin
+  nd.width = r.n_keys + nd.n_aggs;
+  if (nd.width > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u output columns (max %d)", i, nd.width, kMaxCols);
+  for (u32 a = 0; a < nd.n_aggs; a++) nd.origin[r.n_keys + a] = ValueOrigin{(int)i, a};
+}
+
+// Every node of the description, in order (an input precedes its consumer): checked, typed, its program and projection loaded.  Only a
+// DataSourceExec touches the store.
+void compile_nodes(Plan* plan, const rdfgpu_plan_desc* d) {
+  for (u32 i = 0; i < d->n_nodes; i++) {
+    NodeInfo& nd = plan->nodes[i];
+    nd.d = d->nodes[i];
+    const rdfgpu_plan_node& r = nd.d;
+    switch (r.kind) {
+      case RDFGPU_NODE_DATA_SOURCE: {
+        SourceInfo src;
+        src.node = i;
+        src.gspo = make_gspo(r.scan, d->pool, d->n_pool);
+        plan->derive_source(src, src.gspo);
+        nd.width = src.n_out;
+        nd.source = (int)plan->sources.size();
+        plan->sources.push_back(src);
+        break;
+      }
+      case RDFGPU_NODE_FILTER: {
+        InputSchema in; in.append(child(plan, i, r.left, "input"));
+        load_program(nd, d, in, "FilterExec", plan->regex_dev, plan->str_consts_dev);
+        load_projection(nd, d, in, "FilterExec");
+        nd.shape = detect_shape(nd.prog, plan->opt.on(RDFGPU_OPT_FORCE_GENERIC_VM));
+        break;
+      }
+      case RDFGPU_NODE_PROJECTION: {
+        InputSchema in; in.append(child(plan, i, r.left, "input"));
+        load_projection(nd, d, in, "ProjectionExec");
+        break;
+      }
+      case RDFGPU_NODE_HASH_JOIN: case RDFGPU_NODE_CROSS_JOIN: case RDFGPU_NODE_NESTED_LOOP_JOIN: compile_join(plan, d, i); break;
+      case RDFGPU_NODE_CLOSURE: {
+        const NodeInfo& c = child(plan, i, r.left, "inner paths");
+        if (c.width != 3) fail(RDFGPU_ERR_INVALID, "node %u: KleenePlusClosureExec input has %u columns, not (graph, start, end)", i, c.width);
+        if (r.join_type > 1) fail(RDFGPU_ERR_INVALID, "node %u: allow_cross_graph_paths is 0 or 1", i);
+        for (u32 k = 0; k < 3; k++) refuse_value_column(c.origin[k], i, "KleenePlusClosureExec input", k);
+        InputSchema in; in.append(c);
+        load_projection(nd, d, in, "KleenePlusClosureExec");
+        break;
+      }
+      case RDFGPU_NODE_UNION: {
+        const NodeInfo& l = child(plan, i, r.left, "left");
+        const NodeInfo& rr = child(plan, i, r.right, "right");
+        if (l.width != rr.width) fail(RDFGPU_ERR_INVALID, "node %u: UnionExec inputs have %u and %u columns", i, l.width, rr.width);
+        for (u32 k = 0; k < l.width; k++) { refuse_value_column(l.origin[k], i, "UnionExec left input", k); refuse_value_column(rr.origin[k], i, "UnionExec right input", k); }
+        InputSchema in; in.append(l);
+        load_projection(nd, d, in, "UnionExec");
+        break;
+      }
+      case RDFGPU_NODE_TABLE: {
+        if (r.table_cols > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: table with %u columns", i, r.table_cols);
+        nd.width = r.table_cols;
+        if (plan->tables.size() <= r.table_slot) plan->tables.resize(r.table_slot + 1);
+        break;
+      }
+      case RDFGPU_NODE_TOPK: compile_topk(plan, d, i); break;           // DISTINCT + TopK(fetch) per group, ..Q5 (Execution Plan).snap:5-9
+      case RDFGPU_NODE_AGGREGATE: compile_aggregate(plan, d, i); break;   // AggregateExec(mode=Single), ..Business Intelligence - Q8 (Execution Plan).snap
+      default: fail(RDFGPU_ERR_INVALID, "node %u: unknown kind %u", i, r.kind);
+    }
+  }
 }
 
 // Join reordering (physical rewrite, results unchanged): an inner HashJoinExec whose build child is a
@@ -368,7 +504,7 @@ void reorder_cross_joins(Plan* plan) {
     td.n_keys = nB;
     NodeInfo t;
     t.d = td; t.width = wB + wC; t.n_proj = wB + wC;
-    for (u32 k = 0; k < wB + wC; k++) t.proj[k] = k;
+    for (u32 k = 0; k < wB + wC; k++) { t.proj[k] = k; t.origin[k] = k < wB ? plan->nodes[bi].origin[k] : plan->nodes[cri].origin[k - wB]; }
     plan->nodes.push_back(t);
     NodeInfo& j = plan->nodes[i];
     j.d.left = (int32_t)ai; j.d.right = (int32_t)(plan->nodes.size() - 1);
@@ -426,62 +562,11 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
   plan->opt = store->opt;
   store->retain();
   plan->root = d->root;
+  plan->agg_columns = (d->flags & RDFGPU_PLAN_AGG_COLUMNS) != 0;
   plan->nodes.resize(d->n_nodes);
   if (d->n_regexes) compile_string_table(plan.get(), d);   // REGEX patterns are plan constants: compiled here, simulated per row on the device
   check_string_functions(store, d);
-  for (u32 i = 0; i < d->n_nodes; i++) {
-    NodeInfo& nd = plan->nodes[i];
-    nd.d = d->nodes[i];
-    const rdfgpu_plan_node& r = nd.d;
-    switch (r.kind) {
-      case RDFGPU_NODE_DATA_SOURCE: {
-        SourceInfo src;
-        src.node = i;
-        src.gspo = make_gspo(r.scan, d->pool, d->n_pool);
-        plan->derive_source(src, src.gspo);
-        nd.width = src.n_out;
-        nd.source = (int)plan->sources.size();
-        plan->sources.push_back(src);
-        break;
-      }
-      case RDFGPU_NODE_FILTER: {
-        const NodeInfo& c = child(plan.get(), i, r.left, "input");
-        load_program(nd, d, c.width, "FilterExec", plan->regex_dev, plan->str_consts_dev);
-        load_projection(nd, d, c.width, "FilterExec");
-        nd.shape = detect_shape(nd.prog, plan->opt.on(RDFGPU_OPT_FORCE_GENERIC_VM));
-        break;
-      }
-      case RDFGPU_NODE_PROJECTION: {
-        const NodeInfo& c = child(plan.get(), i, r.left, "input");
-        load_projection(nd, d, c.width, "ProjectionExec");
-        break;
-      }
-      case RDFGPU_NODE_HASH_JOIN: case RDFGPU_NODE_CROSS_JOIN: case RDFGPU_NODE_NESTED_LOOP_JOIN: compile_join(plan.get(), d, i); break;
-      case RDFGPU_NODE_CLOSURE: {
-        const NodeInfo& c = child(plan.get(), i, r.left, "inner paths");
-        if (c.width != 3) fail(RDFGPU_ERR_INVALID, "node %u: KleenePlusClosureExec input has %u columns, not (graph, start, end)", i, c.width);
-        if (r.join_type > 1) fail(RDFGPU_ERR_INVALID, "node %u: allow_cross_graph_paths is 0 or 1", i);
-        load_projection(nd, d, 3, "KleenePlusClosureExec");
-        break;
-      }
-      case RDFGPU_NODE_UNION: {
-        const NodeInfo& l = child(plan.get(), i, r.left, "left");
-        const NodeInfo& rr = child(plan.get(), i, r.right, "right");
-        if (l.width != rr.width) fail(RDFGPU_ERR_INVALID, "node %u: UnionExec inputs have %u and %u columns", i, l.width, rr.width);
-        load_projection(nd, d, l.width, "UnionExec");
-        break;
-      }
-      case RDFGPU_NODE_TABLE: {
-        if (r.table_cols > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: table with %u columns", i, r.table_cols);
-        nd.width = r.table_cols;
-        if (plan->tables.size() <= r.table_slot) plan->tables.resize(r.table_slot + 1);
-        break;
-      }
-      case RDFGPU_NODE_TOPK: compile_topk(plan.get(), d, i); break;           // DISTINCT + TopK(fetch) per group, ..Q5 (Execution Plan).snap:5-9
-      case RDFGPU_NODE_AGGREGATE: compile_aggregate(plan.get(), d, i); break;   // AggregateExec(mode=Single), ..Business Intelligence - Q8 (Execution Plan).snap
-      default: fail(RDFGPU_ERR_INVALID, "node %u: unknown kind %u", i, r.kind);
-    }
-  }
+  compile_nodes(plan.get(), d);
   if (!plan->opt.on(RDFGPU_OPT_NO_JOIN_REORDER)) reorder_cross_joins(plan.get());
   count_consumers(plan.get());
   account_columns_read(plan.get());

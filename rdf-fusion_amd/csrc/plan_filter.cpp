@@ -24,6 +24,7 @@ DevTable Plan::apply_filter(NodeInfo& nd, const DevTable& in) {
   a.n_out_dev = new_counter();
   a.tt = typed_table();
   a.prog = nd.prog;
+  bind_values(a.prog);
   int shape = nd.shape;
   if (shape == 3 && !filter_string_verdicts(nd, in, a)) shape = 0;
   if (!filter_run_copy(nd, in, a, shape)) {

@@ -164,6 +164,7 @@ DevTable Plan::exec_generic_join(const NodeInfo& nd, const DevTable& L, const De
   a.n_left_dev = L.n_dev; a.n_left_cap = L.cap; a.n_right_dev = R.n_dev; a.n_right_cap = R.cap;
   a.has_filter = nd.prog.n ? 1 : 0;
   a.prog = nd.prog;
+  bind_values(a.prog);
   a.tt = typed_table();
   if (L.cap >= 0xFFFFFFF0ull) fail(RDFGPU_ERR_UNSUPPORTED, "build side of %llu rows", (unsigned long long)L.cap);
   if (left_join) { a.visited = scratch<u8>(L.cap); if (!hash) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, L.cap, stream)); }

@@ -86,6 +86,8 @@ def load_library():
     lib.rdfgpu_plan_agg_count.argtypes = [vp, u32p]
     lib.rdfgpu_plan_agg_fetch.argtypes = [vp, C.c_uint32, vp]
     lib.rdfgpu_plan_agg_device.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    lib.rdfgpu_plan_result_values.argtypes = [vp, C.c_uint32, C.POINTER(vp), u64p]
+    lib.rdfgpu_plan_result_values_fetch.argtypes = [vp, C.c_uint32, vp]
     lib.rdfgpu_plan_rewind.argtypes = [vp]
     lib.rdfgpu_ntriples_parse.argtypes = [C.c_int32, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(vp)]
     lib.rdfgpu_ntriples_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -554,6 +556,29 @@ class GpuPlan:
         """Aggregate `agg` as Python values: int (xsd:integer), fractions.Fraction (xsd:decimal), float (xsd:float / xsd:double),
         None (the error value)."""
         return [agg_value(int(v["tag"]), int(v["lo"]), int(v["hi"])) for v in self.fetch_aggregate(agg)]
+
+    def result_values(self, col):
+        """(device pointer, length) of the rdfgpu_agg_value array result column `col` indexes (a plan built with agg_columns=True:
+        entry e of the column, 1-based, is element e - 1; 0 = unbound); (0, 0) for an object-id column."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib.rdfgpu_plan_result_values(self._h, col, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def value_columns(self):
+        """The result columns that are aggregate value columns (empty unless the plan was built with agg_columns=True)."""
+        return [c for c in range(self.result_info()[1]) if self.result_values(c)[0]]
+
+    def fetch_column_values(self, col):
+        """Value column `col`, one rdfgpu_agg_value per result row (numpy structured array; tag 0 where the entry is unbound)."""
+        n, _ = self.result_info()
+        out = np.zeros(n, AGG_DTYPE)
+        _check(self._lib.rdfgpu_plan_result_values_fetch(self._h, col, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def column_values(self, col):
+        """Value column `col` as Python values, one per result row, as aggregate_values gives them: int, fractions.Fraction, float,
+        None (unbound: the aggregate was the error value, or a LEFT join padded the row)."""
+        return [agg_value(int(v["tag"]), int(v["lo"]), int(v["hi"])) for v in self.fetch_column_values(col)]
 
     def batches(self):
         """Drains the Arrow batch stream; yields pyarrow StructArrays of UInt32 children."""

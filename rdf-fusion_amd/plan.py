@@ -315,15 +315,17 @@ def BOOLEAN_AS_TERM(e): return e._un(abi.EX_BOOL_AS_TV)
 class PlanDescription:
     """Owns the ctypes arrays behind one ``rdfgpu_plan_desc``."""
 
-    def __init__(self, nodes, exprs, pool, root, n_columns, regexes=()):
+    def __init__(self, nodes, exprs, pool, root, n_columns, regexes=(), flags=0, value_columns=()):
         self.n_columns = n_columns  # output width per node (host-side bookkeeping)
+        self.flags = int(flags)     # abi.PLAN_*
+        self.value_columns = list(value_columns)   # abi.PLAN_AGG_COLUMNS: which output columns of the root are aggregate value columns
         self._nodes = (abi.PlanNode * max(1, len(nodes)))(*nodes)
         self._exprs = (abi.ExprNode * max(1, len(exprs)))(*exprs)
         self._pool = (C.c_uint32 * max(1, len(pool)))(*pool)
         self._regex_bytes = [(bytes(r[0]), bytes(r[1]), int(r[2]) if len(r) > 2 else 0) for r in regexes]      # keeps the char buffers alive
         self._regexes = (abi.Regex * max(1, len(regexes)))(*[abi.Regex(p, f, len(p), len(f), pid, 0) for p, f, pid in self._regex_bytes])
         self.desc = abi.PlanDesc(self._nodes, len(nodes), root, self._exprs, len(exprs), self._pool,
-                                 len(pool), 0, self._regexes, len(regexes), 0)
+                                 len(pool), self.flags, self._regexes, len(regexes), 0)
         self.root = root
 
     @property
@@ -339,6 +341,7 @@ class PlanBuilder:
         self.regexes = []
         self._regex_keys = []
         self.vars = {}
+        self.values = []         # per node: which of its output columns are aggregate value columns (build(agg_columns=True))
 
     # -- helpers -------------------------------------------------------------------------------
     def _var(self, name):
@@ -396,8 +399,24 @@ class PlanBuilder:
         self.width.append(width)
         self.names.append(list(names) if names is not None else [f"c{i}" for i in range(width)])
         self.patterns.append(pattern)
+        self.values.append(self._value_columns(node, width))
         assert len(self.names[-1]) == width
         return len(self.nodes) - 1
+
+    def _value_columns(self, node, width):
+        """Which output columns of `node` carry aggregate values when they are columns: an AggregateExec's aggregates, and whatever a
+        projection, filter or join hands on of its inputs' (a semi / anti join: of its left input's)."""
+        if node.kind == abi.NODE_AGGREGATE:
+            return [False] * (width - node.table_cols) + [True] * node.table_cols
+        if node.kind in (abi.NODE_DATA_SOURCE, abi.NODE_TABLE) or node.left < 0:
+            return [False] * width
+        full = list(self.values[node.left])
+        binary = node.kind in (abi.NODE_HASH_JOIN, abi.NODE_CROSS_JOIN, abi.NODE_NESTED_LOOP_JOIN)
+        if binary and node.join_type not in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI):
+            full += self.values[node.right]
+        if node.n_proj == abi.NO_PROJECTION:
+            return full[:width] + [False] * (width - len(full))
+        return [full[self.pool[node.proj_off + q]] if self.pool[node.proj_off + q] < len(full) else False for q in range(node.n_proj)]
 
     def _projected(self, full_names, projection):
         return list(full_names) if projection is None else [full_names[int(c)] for c in projection]
@@ -495,7 +514,8 @@ class PlanBuilder:
         (at most 8; AGG_COUNT_STAR takes no column: None).  The input of AGG_SUM / AGG_AVG may be an `Expr` over the input's columns that
         yields a typed value (`MUL(ENC_TV(col(1)), ENC_TV(col(2)))`): it goes into the pool as abi.AGG_INPUT_EXPR | offset of
         (expr_off, expr_len).  Output: the keys in order, then the aggregates, named like DataFusion's display (`COUNT(y)`,
-        `SUM(MUL(ENC_TV(a), ENC_TV(b)))`).  Only the key columns are ids: a node with aggregates must be the plan's root."""
+        `SUM(MUL(ENC_TV(a), ENC_TV(b)))`).  Only the key columns are ids: a node with aggregates must be the plan's root — unless the
+        description is built with agg_columns=True, where the aggregates are value columns that the operators above read (build, sparql_having)."""
         group_by = [int(c) for c in group_by]
         aggregates = [(int(fn), c if c is None or isinstance(c, Expr) else int(c)) for fn, c in aggregates]
         names = self.names[left]
@@ -525,8 +545,21 @@ class PlanBuilder:
         out = [names[c] for c in group_by] + labels
         return self._push(n, len(out), out)
 
-    def build(self, root):
-        return PlanDescription(self.nodes, self.exprs, self.pool, root, list(self.width), list(self.regexes))
+    def build(self, root, agg_columns=False):
+        """agg_columns=True sets abi.PLAN_AGG_COLUMNS: an AggregateExec with aggregates may sit anywhere, its output is the keys and then
+        one value column per aggregate (n_columns counts them), and FilterExec / joins / further aggregates above read the values through
+        ENC_TV.  Without it the description is what it always was: aggregates at the root only, values through GpuPlan.aggregate_values."""
+        return PlanDescription(self.nodes, self.exprs, self.pool, root, list(self.width), list(self.regexes),
+                               flags=abi.PLAN_AGG_COLUMNS if agg_columns else 0,
+                               value_columns=[c for c, v in enumerate(self.values[root]) if v] if agg_columns else [])
+
+    def sparql_having(self, agg, predicate, projection=None):
+        """HAVING over an AggregateExec (or anything that carries its value columns): a FilterExec whose predicate reads the aggregates'
+        values through ENC_TV of their columns — BSBM Business Intelligence Q3 (Execution Plan).snap:17,
+        `FilterExec: EBV(GT(INT64_AS_TERM(count@1), 9:0))`, and Q6 (Execution Plan).snap:6, `FilterExec: EBV(GT(avg@1, MUL(avg@2, 1.5)))`.
+        INT64_AS_TERM(count) is the identity here: a COUNT's value already is an xsd:integer, so `ENC_TV(col(1))` stands for it.  The
+        description must be built with agg_columns=True."""
+        return self.filter(agg, predicate, projection)
 
 
     # -- SparqlJoinNode lowering ------------------------------------------------------------------
@@ -650,10 +683,11 @@ def format_expr(nodes, names, at=True):
     return st[0]
 
 
-def explain(pb, root, choose_index=None):
+def explain(pb, root, choose_index=None, agg_columns=False):
     """The operator tree under `root`, one line per operator, indented like DataFusion's `displayable(plan).indent()`.
     `choose_index(instructions) -> abi.GSPO | GPOS | GOSP` names the index of a DataSourceExec (the library's
-    rdfgpu_choose_index; default: engine.choose_index)."""
+    rdfgpu_choose_index; default: engine.choose_index).  `agg_columns=True` (the plan as build(root, agg_columns=True) describes it): an
+    AggregateExec line ends in `values=[COUNT(*)@1, ..]`, its aggregates as the value columns the operators above read."""
     if choose_index is None:
         from .engine import choose_index as _ci
         choose_index = lambda ins: _ci([PlanBuilder()._instr(i) for i in ins])
@@ -724,7 +758,10 @@ def explain(pb, root, choose_index=None):
                     aggs.append(_agg_label(fn, format_expr(pb.exprs[off:off + ln], full)))
                     continue
                 aggs.append(_agg_label(fn, None if fn == abi.AGG_COUNT_STAR else full[c], c))
-            lines.append(f"{pad}AggregateExec: mode=Single, gby=[{gby}], aggr=[{', '.join(aggs)}]")
+            values = ""
+            if agg_columns and n.table_cols:   # the aggregates' values as output columns, `name@index`
+                values = ", values=[" + ", ".join(f"{pb.names[i][n.n_keys + a]}@{n.n_keys + a}" for a in range(n.table_cols)) + "]"
+            lines.append(f"{pad}AggregateExec: mode=Single, gby=[{gby}], aggr=[{', '.join(aggs)}]{values}")
             walk(n.left, depth + 1)
             return
         name = {abi.NODE_PROJECTION: "ProjectionExec", abi.NODE_TOPK: "SortExec: TopK", abi.NODE_UNION: "UnionExec",
