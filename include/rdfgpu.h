@@ -385,7 +385,7 @@ enum {
                                   through the inner paths of any graph while keeping the first path's graph (join_type = 1 =
                                   allow_cross_graph_paths).  A null start / end is an execution error, as in the reference. */
   /* ABI 4 addendum (backward compatible: new enum values and functions, no struct changed) */
-  RDFGPU_NODE_AGGREGATE = 11   /* AggregateExec(mode=Single) over object-id group columns — what the BSBM Business Intelligence plans put
+  RDFGPU_NODE_AGGREGATE = 11,  /* AggregateExec(mode=Single) over object-id group columns — what the BSBM Business Intelligence plans put
                                   on top of their join trees (bench/tests/plans/snapshots/..Business Intelligence - Q1..Q8 (Execution
                                   Plan).snap).  Encoding: left = input; n_keys (0..RDFGPU_MAX_KEYS) group columns in left_keys[];
                                   table_cols = number of aggregates (0..RDFGPU_MAX_AGGREGATES); table_slot = offset into the u32 pool of
@@ -420,6 +420,35 @@ enum {
                                   CLOSURE or UNION input; and so is rdfgpu_plan_decode_terms of a value column.  A value column under
                                   ID_EQ / ID_NEQ / IS_COMPATIBLE / STR is RDFGPU_ERR_INVALID, like every operand of the wrong kind.  A
                                   predicate that reads a value column runs in the generic VM.                                          */
+  RDFGPU_NODE_EXTEND = 12      /* ProjectionExec whose `expr=[..]` holds expressions (SPARQL Extend: BIND, `SELECT (expr AS ?x)`) — what the
+                                  BSBM Business Intelligence plans put directly above their aggregates (..Business Intelligence - Q3 / Q4 /
+                                  Q8 (Execution Plan).snap: `DIV(xsd:float(monthCount@1), monthBeforeCount@2) as ratio`).  Encoding: left =
+                                  input, right = -1; proj_off / n_proj = the input columns kept, in order (RDFGPU_NO_PROJECTION keeps all);
+                                  table_cols = number k of computed columns (1..RDFGPU_MAX_AGGREGATES); table_slot = offset into the u32
+                                  pool of k pairs (expr_off, expr_len), each naming a program in `exprs`.  Output columns: the kept
+                                  columns, then the k computed columns, at most RDFGPU_MAX_COLUMNS together.
+                                  The node is accepted only in a plan compiled with RDFGPU_PLAN_AGG_COLUMNS; without the flag it is
+                                  RDFGPU_ERR_UNSUPPORTED at compile (its outputs are not object ids).
+                                  A program ranges over ALL input columns, not only the kept ones.  It may read id columns through ENC_TV /
+                                  BOUND, and value columns of aggregates and of other EXTEND nodes below.  It must leave a typed value: a
+                                  program that leaves a boolean verdict is RDFGPU_ERR_INVALID (wrap it in BOOLEAN_AS_TERM), one that leaves
+                                  an id is RDFGPU_ERR_INVALID (a plain column is a projection), and one with REGEX / CONTAINS / STRSTARTS /
+                                  STRENDS / LANG_IN or a string-view op (STR, LIT_STR, STRLEN, SUBSTR, UCASE, LCASE, STRBEFORE, STRAFTER)
+                                  in it is RDFGPU_ERR_UNSUPPORTED — the rule of an aggregate's input expression.
+                                  Row r of the node carries r + 1 in a computed column; its value is entry r of that column's
+                                  rdfgpu_agg_value array.  A row whose program yields the error value (DIV by an integer zero, an overflow,
+                                  an unbound or non-numeric operand) carries 0 and tag RDFGPU_TV_NULL: an unbound binding everywhere,
+                                  exactly like an error aggregate.  The 24-byte record carries INT, INTEGER, DECIMAL, FLOAT, DOUBLE and
+                                  BOOLEAN values, the payload laid out as a value load reads it back: lo, and (lo, hi) for a decimal.  A
+                                  row whose value is of any other kind (string, IRI, blank node, dateTime, date, time, duration) — the
+                                  record has no room for its `aux` — fails the execute with RDFGPU_ERR_UNSUPPORTED; such a row is never
+                                  answered differently, and the plan stays usable afterwards.  An input of 2^32 - 1 rows or more fails
+                                  the execute with RDFGPU_ERR_UNSUPPORTED.
+                                  A computed column is a value column everywhere above the node: everything the AGGREGATE entry says of
+                                  carriage (projections, filters, join payload of every join type, two parents, input of COUNT / SUM / AVG)
+                                  and of refusals (join key, group column, COUNT_DISTINCT input, TopK key / group / output, CLOSURE / UNION
+                                  input, rdfgpu_plan_decode_terms; the sharded path exchanges object ids only) applies, the texts naming
+                                  the node and the expression.  rdfgpu_plan_result_values / _fetch / rdfgpu_plan_next work unchanged.   */
 };
 /*
  * Aggregate functions of RDFGPU_NODE_AGGREGATE (ABI 4 addendum).  The reference plans SPARQL aggregates in
@@ -579,6 +608,8 @@ int rdfgpu_plan_fetch(rdfgpu_plan* plan, uint32_t* const* host_cols, uint32_t n_
  *   tag RDFGPU_TV_DECIMAL   (lo, hi) = the i128 value * 10^18
  *   tag RDFGPU_TV_FLOAT     lo = the IEEE-754 binary32 bits (zero-extended);  RDFGPU_TV_DOUBLE: lo = the binary64 bits
  *   tag RDFGPU_TV_NULL      the error value
+ * Below an RDFGPU_NODE_EXTEND, and only there, two more tags can appear in the array of a computed column:
+ *   tag RDFGPU_TV_INT       lo = the xsd:int value;  tag RDFGPU_TV_BOOLEAN: lo = 0 / 1
  * The host turns integers into xsd:integer terms (INT64_AS_TERM) and the rest into typed literals.
  */
 typedef struct rdfgpu_agg_value {

@@ -37,6 +37,7 @@ CAST_TARGETS = (TV_BOOLEAN, TV_INT, TV_INTEGER, TV_DECIMAL, TV_FLOAT, TV_DOUBLE)
 # plan nodes
 (NODE_DATA_SOURCE, NODE_FILTER, NODE_HASH_JOIN, NODE_CROSS_JOIN, NODE_NESTED_LOOP_JOIN,
  NODE_PROJECTION, NODE_TABLE, NODE_TOPK, NODE_UNION, NODE_CLOSURE, NODE_AGGREGATE) = range(1, 12)
+NODE_EXTEND = 12                # ProjectionExec with expressions (SPARQL Extend): the kept columns, then one value column per expression (PLAN_AGG_COLUMNS)
 # aggregate functions of NODE_AGGREGATE (ABI 4 addendum); MIN .. COUNT_DISTINCT_STAR are reserved and refused at compile
 (AGG_COUNT_STAR, AGG_COUNT, AGG_COUNT_DISTINCT, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_SAMPLE, AGG_GROUP_CONCAT,
  AGG_SUM_DISTINCT, AGG_AVG_DISTINCT, AGG_COUNT_DISTINCT_STAR) = range(1, 13)

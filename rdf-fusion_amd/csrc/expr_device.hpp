@@ -45,7 +45,8 @@ struct TypedTable {
                                  // class / word boundary met a non-ASCII subject, bit 1 a per-row REGEX pattern was not announced,
                                  // bit 2 a string expression met what the device does not restate (case mapping of a non-ASCII
                                  // string, a non-integer SUBSTR argument), bit 3 a numeric CAST met a simple literal (the lexical
-                                 // parsers are not restated)
+                                 // parsers are not restated), bit 4 a computed column (RDFGPU_NODE_EXTEND) met a value of a kind its
+                                 // 24-byte record cannot carry
 };
 
 // Value kinds on the evaluation stack.  VK_VALUE exists at compile only (check_program): COLUMN of an aggregate value column, whose u32 is
@@ -53,8 +54,9 @@ struct TypedTable {
 enum : uint32_t { VK_ID = 0, VK_TV = 1, VK_BOOL = 2, VK_VALUE = 3 };
 
 // Internal op (never accepted from a description: check_program knows RDFGPU_EX_* only).  plan_compile writes it in place of the ENC_TV of
-// an aggregate value column (RDFGPU_PLAN_AGG_COLUMNS): u = origin node << 8 | aggregate; Plan::bind_values fills in, per execution,
-// lo = the device address of that aggregate's rdfgpu_agg_value array and hi = its length.
+// an aggregate value column (RDFGPU_PLAN_AGG_COLUMNS): u = origin node << 8 | aggregate (of an AggregateExec) or expression (of a
+// ProjectionExec with expressions, RDFGPU_NODE_EXTEND); Plan::bind_values fills in, per execution, lo = the device address of that
+// rdfgpu_agg_value array and hi = its length.
 constexpr uint8_t kExAggValue = 250;
 static_assert(kExAggValue >= RDFGPU_EX__COUNT, "the internal op must lie outside the ABI's ops");
 
@@ -72,6 +74,7 @@ struct Val {
 constexpr uint8_t kStrUpper = 0x10, kStrLower = 0x20;
 constexpr uint32_t kRtStringUnsupported = 4u;
 constexpr uint32_t kRtCastFromString = 8u;
+constexpr uint32_t kRtExtendKind = 16u;
 
 typedef __int128 i128_t;
 typedef unsigned __int128 u128_t;

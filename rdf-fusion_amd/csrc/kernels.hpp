@@ -324,6 +324,20 @@ void launch_agg_final(const AggArgs& a, hipStream_t s);
 void launch_agg_value_cols(const AggArgs& a, hipStream_t s);   // RDFGPU_PLAN_AGG_COLUMNS: every out_val[i] set
 void preload_tu_aggregate();
 
+// ---- ProjectionExec with expressions (extend.hip, RDFGPU_NODE_EXTEND): one lane per input row evaluates the node's programs ----
+constexpr int kExtendBlock = 256;         // rows per workgroup
+struct ExtendArgs {
+  const u64* n_dev; u64 cap;                       // input rows: the device count when n_dev, else cap
+  const u32* col[kMaxCols];                        // the input's columns, which the programs read
+  u32 n_exprs;                                     // computed columns (1 .. RDFGPU_MAX_AGGREGATES)
+  const ExprProgram* prog[RDFGPU_MAX_AGGREGATES];  // their programs (device copies)
+  rdfgpu_agg_value* out[RDFGPU_MAX_AGGREGATES];    // per computed column: the value of every row (cap records)
+  u32* out_val[RDFGPU_MAX_AGGREGATES];             // .. and the value column (row r: r + 1, or 0 for the error value)
+  TypedTable tt;
+};
+void launch_extend(const ExtendArgs& a, hipStream_t s);
+void preload_tu_extend();
+
 void launch_lds_join(const LdsJoinArgs& a, hipStream_t s);
 // stream_join.hip: the same operator against a direct-address table as a streaming pass (launch_lds_join routes to it when a.stream_direct)
 bool direct_stream_join_ok(const LdsJoinArgs& a);

@@ -147,7 +147,7 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel",
       "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>",
       "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel", "void rdfgpu::band_pair_bits_kernel",
-      "rdfgpu::agg_value_cols_kernel"};
+      "rdfgpu::agg_value_cols_kernel", "rdfgpu::extend_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -330,6 +330,8 @@ void Plan::execute() {
   if (const u32 rt = (u32)(ctx->counters_host[255] & 0xFFFFFFFFull)) {   // a row asked for something that is refused loudly, not answered differently
     if (rt & 1u) fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with \\d \\w \\s or \\b over a string with non-ASCII characters needs the regex crate's Unicode tables (not restated)");
     if (rt & 8u) fail(RDFGPU_ERR_UNSUPPORTED, "a numeric CAST met a simple literal: the lexical forms of numbers are not parsed on the device");
+    if (rt & kRtExtendKind) fail(RDFGPU_ERR_UNSUPPORTED, "a computed column (ProjectionExec with expressions) met a value that is a string, IRI, blank node, dateTime, date, time or duration: "
+                                                         "its 24-byte value has no room for the language / datatype (numeric and boolean values are carried)");
     if (rt & 4u) fail(RDFGPU_ERR_UNSUPPORTED, "a string expression met what the device does not restate: UCASE / LCASE of a string with non-ASCII characters (Unicode case tables), "
                                                "a float / double / decimal SUBSTR position, or a comparison with a string that has no bytes on the device");
     fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with a per-row pattern: a row's pattern literal was not announced in the plan's pattern table");
@@ -351,6 +353,8 @@ void Plan::execute() {
   }
   result_rows = result.n_dev ? ctx->counters_host[result.n_dev - counters] : result.cap;
   if (result_rows > result.cap) result_rows = result.cap;
+  for (NodeInfo& nd : nodes)   // a computed column over rows counted on the device: its array holds that many values, not its capacity
+    if (nd.values_run == run && nd.n_values_dev) { nd.n_values = std::min<u64>(nd.n_values, ctx->counters_host[nd.n_values_dev - counters]); nd.n_values_dev = nullptr; }
   float ms = 0;
   RDFGPU_HIP(hipEventElapsedTime(&ms, ev_start, ev_stop));
   metrics.elapsed_compute_ms = ms;
@@ -431,6 +435,7 @@ DevTable Plan::exec_node(u32 idx) {
       break;
     case RDFGPU_NODE_TOPK: t = exec_topk(nd); break;
     case RDFGPU_NODE_AGGREGATE: t = exec_aggregate(nd); break;
+    case RDFGPU_NODE_EXTEND: t = exec_extend(nd); break;
     case RDFGPU_NODE_CLOSURE: t = exec_closure(nd); break;
     case RDFGPU_NODE_UNION: t = exec_union(nd); break;
     case RDFGPU_NODE_TABLE: t = exec_table(nd); break;
@@ -685,6 +690,38 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
   timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
   // the value columns: per group and aggregate the tag read (the value was just written: cache) and 4 bytes written
   if (agg_columns && a.n_aggs) timed(KC_AGG_VALUE_COLS, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_aggs, [&] { launch_agg_value_cols(a, stream); });
+  return t;
+}
+
+// ProjectionExec with expressions (extend.hip): one launch over the input's rows writes, per computed column, every row's 24-byte value
+// and its entry (row + 1, or 0).  The kept columns are the input's own buffers, handed on: nothing of them is copied.  The input's row
+// count may live on the device only: the arrays are sized by its capacity, the kernel stops at the live rows.  Behind the capacity of
+// every array lies one guard element, set before the launch, which a test can read (rdfgpu_plan_result_values' length is the capacity
+// when the row count is known on the host): a write past the input's rows would show there.
+// Compulsory bytes: per input row 4 per column a program reads, 16 per ENC_TV gather, 24 + 4 per computed column.
+constexpr int kExtendGuard = 0xA5;
+DevTable Plan::exec_extend(NodeInfo& nd) {
+  const DevTable in = exec_sub_plan((u32)nd.d.left);
+  flush_pending_oj();   // a held-back ordered-join write must have happened before the input is read
+  if (in.cap >= 0xFFFFFFFFull) fail(RDFGPU_ERR_UNSUPPORTED, "ProjectionExec with expressions over %llu rows (fewer than 2^32 - 1)", (unsigned long long)in.cap);
+  const u32 k = (u32)nd.agg_progs.size();
+  DevTable t = project(in, nd);
+  t.n_cols = nd.width;
+  ExtendArgs a{};
+  a.n_dev = in.n_dev; a.cap = in.cap;
+  for (u32 c = 0; c < in.n_cols; c++) a.col[c] = in.cols[c];
+  a.n_exprs = k;
+  a.tt = typed_table();
+  for (u32 q = 0; q < k; q++) {   // one guard record / word (bytes of kExtendGuard) behind each array: the kernel writes the live rows and nothing else
+    a.out[q] = scratch<rdfgpu_agg_value>(in.cap + 1); a.out_val[q] = scratch<u32>(in.cap + 1);
+    RDFGPU_HIP(hipMemsetAsync(a.out[q] + in.cap, kExtendGuard, sizeof(rdfgpu_agg_value), stream));
+    RDFGPU_HIP(hipMemsetAsync(a.out_val[q] + in.cap, kExtendGuard, sizeof(u32), stream));
+    nd.values[q] = a.out[q]; t.cols[nd.n_proj + q] = a.out_val[q];
+  }
+  nd.n_values = in.cap; nd.n_values_dev = in.cap ? in.n_dev : nullptr; nd.values_run = run;
+  if (in.cap == 0) return t;
+  for (u32 q = 0; q < k; q++) a.prog[q] = upload_program(nd.agg_progs[q]);
+  timed(KC_EXTEND, 0, in.cap, in.n_dev, 4ull * nd.n_cols_read + 16ull * nd.n_enc_tv + 28ull * k, nullptr, 0, 0, [&] { launch_extend(a, stream); });
   return t;
 }
 

@@ -38,9 +38,10 @@ struct BandHistory {
   bool row_cache = false;       // exec_band_join: the rows' decoded windows are cached on the slice too (SliceTable::BandRowWindows).  run_ordered_join: its probe pass prepares the values by key, not the 16-byte records
 };
 
-// Where an output column's aggregate values come from (RDFGPU_PLAN_AGG_COLUMNS): node < 0 = an object-id column; else the column holds
-// 1-based indexes into aggregate `agg` of AggregateExec `node` (0 = unbound).  Fixed at compile, carried through every operator above.
-struct ValueOrigin { int node = -1; u32 agg = 0; };
+// Where an output column's values come from (RDFGPU_PLAN_AGG_COLUMNS): node < 0 = an object-id column; else the column holds 1-based
+// indexes into value array `agg` of `node` (0 = unbound) — aggregate `agg` of an AggregateExec, or expression `agg` of a ProjectionExec
+// with expressions (RDFGPU_NODE_EXTEND).  Fixed at compile, carried through every operator above.
+struct ValueOrigin { int node = -1; u32 agg = 0; bool extend = false; };   // extend: `node` is an EXTEND (for the refusals' texts)
 
 struct NodeInfo {
   rdfgpu_plan_node d;
@@ -59,8 +60,9 @@ struct NodeInfo {
   int parent = -1;                             // the one operator consuming this node (-1: the root, or several)
   u32 n_aggs = 0; u32 agg_fn[RDFGPU_MAX_AGGREGATES] = {}, agg_col[RDFGPU_MAX_AGGREGATES] = {};   // AggregateExec: (RDFGPU_AGG_*, input column)
   int agg_prog[RDFGPU_MAX_AGGREGATES] = {-1, -1, -1, -1, -1, -1, -1, -1};                           // .. or the index in agg_progs of its input expression (RDFGPU_AGG_INPUT_EXPR)
-  std::vector<ExprProgram> agg_progs;
-  rdfgpu_agg_value* values[RDFGPU_MAX_AGGREGATES] = {}; u64 n_values = 0, values_run = 0;   // AggregateExec: the value arrays (scratch) of execution `values_run` (Plan::run) and their length = its groups
+  std::vector<ExprProgram> agg_progs;             // .. and, of a ProjectionExec with expressions (RDFGPU_NODE_EXTEND), the program of every computed column
+  rdfgpu_agg_value* values[RDFGPU_MAX_AGGREGATES] = {}; u64 n_values = 0, values_run = 0;   // AggregateExec / EXTEND: the value arrays (scratch) of execution `values_run` (Plan::run) and their length = its groups / rows
+  const u64* n_values_dev = nullptr;              // EXTEND over an input counted on the device only: n_values is the capacity while the plan runs (no entry exceeds the rows written) and becomes this count when it has come back
   BandHistory band;                            // the band join based on this node, if there was one
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
@@ -156,6 +158,7 @@ enum KernelClass {
   KC_BAND_ROW_WIN_KEYS, KC_BAND_ROW_WIN_ROWS,     // the build of a slice's cached row windows (band_join.hip)
   KC_BAND_PAIR_BITS,                              // .. and of its cached pair verdicts
   KC_AGG_VALUE_COLS,                              // agg_value_cols_kernel: an AggregateExec's value columns (RDFGPU_PLAN_AGG_COLUMNS)
+  KC_EXTEND,                                      // extend_kernel: the computed columns of a ProjectionExec with expressions (RDFGPU_NODE_EXTEND)
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
@@ -262,6 +265,7 @@ struct Plan {
   DevTable exec_topk(NodeInfo& nd);
   DevTable exec_semi_join(NodeInfo& nd);
   DevTable exec_aggregate(NodeInfo& nd);
+  DevTable exec_extend(NodeInfo& nd);
   DevTable apply_filter(NodeInfo& nd, const DevTable& in);   // its routes:
   bool filter_string_verdicts(const NodeInfo& nd, const DevTable& in, FilterArgs& a); bool filter_run_copy(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape);
   void filter_streamed(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape); void filter_single_pass(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape);

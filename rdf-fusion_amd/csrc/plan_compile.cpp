@@ -187,6 +187,8 @@ void load_projection(NodeInfo& nd, const rdfgpu_plan_desc* d, const InputSchema&
 
 // The operators that compare, sort, chain or decode ids refuse a value column: equal values have different indexes.
 void refuse_value_column(const ValueOrigin& o, u32 node, const char* role, u32 column) {
+  if (o.node >= 0 && o.extend)
+    fail(RDFGPU_ERR_UNSUPPORTED, "node %u: %s column %u is a computed value column (expression %u of the ProjectionExec with expressions, node %d): its entries index values, equal values have different indexes", node, role, column, o.agg, o.node);
   if (o.node >= 0)
     fail(RDFGPU_ERR_UNSUPPORTED, "node %u: %s column %u is an aggregate value column (aggregate %u of node %d): its entries index values, equal values have different indexes", node, role, column, o.agg, o.node);
 }
@@ -407,6 +409,43 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   for (u32 a = 0; a < nd.n_aggs; a++) nd.origin[r.n_keys + a] = ValueOrigin{(int)i, a};
 }
 
+// ProjectionExec with expressions (RDFGPU_NODE_EXTEND): the kept columns, then one value column per program — each checked like an
+// aggregate's input expression, over all of the input's columns.
+void compile_extend(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
+  NodeInfo& nd = plan->nodes[i];
+  const rdfgpu_plan_node& r = nd.d;
+  if (!plan->agg_columns) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: a ProjectionExec with expressions outputs value columns, which are not object ids: the plan must be compiled with RDFGPU_PLAN_AGG_COLUMNS", i);
+  const NodeInfo& c = child(plan, i, r.left, "input");
+  const u32 k = r.table_cols;
+  if (k < 1 || k > RDFGPU_MAX_AGGREGATES) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: ProjectionExec with %u expressions (1 to %u)", i, k, RDFGPU_MAX_AGGREGATES);
+  InputSchema in; in.append(c);
+  load_projection(nd, d, in, "ProjectionExec with expressions");
+  if (nd.n_proj + k > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: ProjectionExec with expressions: %u output columns (max %d)", i, nd.n_proj + k, kMaxCols);
+  if ((u64)r.table_slot + 2ull * k > d->n_pool || !d->pool) fail(RDFGPU_ERR_INVALID, "node %u: expression list outside the pool", i);
+  for (u32 q = 0; q < k; q++) {
+    const u32 off = d->pool[r.table_slot + 2 * q], len = d->pool[r.table_slot + 2 * q + 1];
+    if (len == 0 || (u64)off + len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "node %u: expression %u: program outside the expression array", i, q);
+    for (u32 e = 0; e < len; e++) {   // the pattern ops get their per-node preparation in FilterExec and the joins only; a string view has no 24-byte form
+      const u8 op = d->exprs[off + e].op;
+      if (op == RDFGPU_EX_REGEX || op == RDFGPU_EX_REGEX_VAR || op == RDFGPU_EX_CONTAINS || op == RDFGPU_EX_STRSTARTS || op == RDFGPU_EX_STRENDS || op == RDFGPU_EX_LANG_IN ||
+          op == RDFGPU_EX_STR || op == RDFGPU_EX_LIT_STR || op == RDFGPU_EX_STRLEN || op == RDFGPU_EX_SUBSTR || op == RDFGPU_EX_UCASE || op == RDFGPU_EX_LCASE ||
+          op == RDFGPU_EX_STRBEFORE || op == RDFGPU_EX_STRAFTER)
+        fail(RDFGPU_ERR_UNSUPPORTED, "node %u: expression %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES and the string functions in a computed column are not on the device", i, q);
+    }
+    const u32 kind = check_program(d->exprs + off, len, c.width, d->n_regexes, in.value_cols());
+    if (kind == VK_BOOL) fail(RDFGPU_ERR_INVALID, "node %u: expression %u leaves a boolean verdict, not a typed value: wrap it in BOOLEAN_AS_TERM", i, q);
+    if (kind != VK_TV) fail(RDFGPU_ERR_INVALID, "node %u: expression %u leaves an id, not a typed value: a plain column is a projection", i, q);
+    ExprProgram pr{};
+    pr.n = len;
+    std::memcpy(pr.nodes, d->exprs + off, len * sizeof(rdfgpu_expr_node));
+    pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
+    rewrite_value_loads(pr, in);
+    nd.agg_progs.push_back(pr);
+  }
+  nd.width = nd.n_proj + k;
+  for (u32 q = 0; q < k; q++) nd.origin[nd.n_proj + q] = ValueOrigin{(int)i, q, true};
+}
+
 // Every node of the description, in order (an input precedes its consumer): checked, typed, its program and projection loaded.  Only a
 // DataSourceExec touches the store.
 void compile_nodes(Plan* plan, const rdfgpu_plan_desc* d) {
@@ -464,6 +503,7 @@ void compile_nodes(Plan* plan, const rdfgpu_plan_desc* d) {
       }
       case RDFGPU_NODE_TOPK: compile_topk(plan, d, i); break;           // DISTINCT + TopK(fetch) per group, ..Q5 (Execution Plan).snap:5-9
       case RDFGPU_NODE_AGGREGATE: compile_aggregate(plan, d, i); break;   // AggregateExec(mode=Single), ..Business Intelligence - Q8 (Execution Plan).snap
+      case RDFGPU_NODE_EXTEND: compile_extend(plan, d, i); break;         // ProjectionExec: expr=[.., DIV(..) as ratio], ..Business Intelligence - Q3 (Execution Plan).snap
       default: fail(RDFGPU_ERR_INVALID, "node %u: unknown kind %u", i, r.kind);
     }
   }
@@ -547,6 +587,11 @@ void account_columns_read(Plan* plan) {
     u32 used = columns_read(nd.prog);
     for (u32 i = 0; i < nd.prog.n; i++) if (nd.prog.nodes[i].op == RDFGPU_EX_ENC_TV) nd.n_enc_tv++;
     if (nd.d.kind == RDFGPU_NODE_FILTER) for (u32 c = 0; c < nd.n_proj; c++) used |= 1u << nd.proj[c];
+    if (nd.d.kind == RDFGPU_NODE_EXTEND)   // the programs of the computed columns (the kept columns are handed on, not read)
+      for (const ExprProgram& pr : nd.agg_progs) {
+        used |= columns_read(pr);
+        for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_ENC_TV || pr.nodes[i].op == kExAggValue) nd.n_enc_tv++;
+      }
     nd.n_cols_read += (u32)__builtin_popcount(used);
   }
 }

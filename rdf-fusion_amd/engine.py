@@ -680,12 +680,14 @@ AGG_DTYPE = np.dtype([("lo", "<i8"), ("hi", "<i8"), ("tag", "u1"), ("reserved", 
 
 
 def agg_value(tag, lo, hi=0):
-    """One rdfgpu_agg_value as a Python value: int for xsd:integer, fractions.Fraction for xsd:decimal (the i128 / 10^18), float for
-    xsd:float / xsd:double, None for the error value."""
+    """One rdfgpu_agg_value as a Python value: int for xsd:integer / xsd:int, fractions.Fraction for xsd:decimal (the i128 / 10^18), float
+    for xsd:float / xsd:double, bool for xsd:boolean, None for the error value."""
     from fractions import Fraction
     lo &= (1 << 64) - 1
-    if tag == abi.TV_INTEGER:
+    if tag in (abi.TV_INTEGER, abi.TV_INT):        # (xsd:int, like xsd:boolean: in a computed column only, PlanBuilder.extend)
         return lo - (1 << 64) if lo >= 1 << 63 else lo
+    if tag == abi.TV_BOOLEAN:
+        return lo != 0
     if tag == abi.TV_DECIMAL:
         v = ((hi & ((1 << 64) - 1)) << 64) | lo
         return Fraction(v - (1 << 128) if v >= 1 << 127 else v, 10 ** 18)

@@ -410,6 +410,10 @@ class PlanBuilder:
             return [False] * (width - node.table_cols) + [True] * node.table_cols
         if node.kind in (abi.NODE_DATA_SOURCE, abi.NODE_TABLE) or node.left < 0:
             return [False] * width
+        if node.kind == abi.NODE_EXTEND:        # the kept columns as the input has them, then the computed ones
+            full = list(self.values[node.left])
+            kept = range(len(full)) if node.n_proj == abi.NO_PROJECTION else [self.pool[node.proj_off + q] for q in range(node.n_proj)]
+            return [full[c] for c in kept] + [True] * node.table_cols
         full = list(self.values[node.left])
         binary = node.kind in (abi.NODE_HASH_JOIN, abi.NODE_CROSS_JOIN, abi.NODE_NESTED_LOOP_JOIN)
         if binary and node.join_type not in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI):
@@ -439,9 +443,10 @@ class PlanBuilder:
         self._expr(n, predicate)
         return self._push(n, self._proj(n, projection, self.width[child]), self._projected(self.names[child], projection))
 
-    def projection(self, child, columns):
+    def projection(self, child, columns, names=None):
+        """ProjectionExec of plain columns; `names` renames them (`count(..)@1 as monthCount`: display only)."""
         n = abi.PlanNode(kind=abi.NODE_PROJECTION, left=child, right=-1)
-        return self._push(n, self._proj(n, columns, self.width[child]), self._projected(self.names[child], columns))
+        return self._push(n, self._proj(n, columns, self.width[child]), self._projected(self.names[child], columns) if names is None else names)
 
     def _join_output(self, left, right, join_type):
         """Columns a join outputs before its projection: [left, right], or the left ones only for LeftSemi / LeftAnti."""
@@ -544,6 +549,33 @@ class PlanBuilder:
         n.n_proj = abi.NO_PROJECTION
         out = [names[c] for c in group_by] + labels
         return self._push(n, len(out), out)
+
+    def extend(self, child, exprs, keep=None, names=None):
+        """ProjectionExec with expressions (SPARQL Extend; abi.NODE_EXTEND): the columns `keep` of `child` (None: all), then one computed
+        column per `Expr` of `exprs` (1 to 8) — a program over ALL of the child's columns that leaves a typed value, e.g. BSBM Business
+        Intelligence Q3's `DIV(xsd_float(ENC_TV(col(1))), ENC_TV(col(2)))`.  The computed columns are value columns (`value_columns`),
+        named `names` (default: the expression as DataFusion prints it).  In the pool: k pairs (expr_off, expr_len) at table_slot.  The
+        description must be built with agg_columns=True."""
+        exprs = list(exprs)
+        full = self.names[child]
+        n = abi.PlanNode(kind=abi.NODE_EXTEND, left=child, right=-1, table_cols=len(exprs))
+        kept = self._proj(n, None if keep is None else [int(c) for c in keep], self.width[child])
+        pairs = []
+        for e in exprs:
+            holder = abi.PlanNode()
+            self._expr(holder, e)
+            pairs += [holder.expr_off, holder.expr_len]
+        n.table_slot = len(self.pool)
+        self.pool.extend(pairs)
+        if names is None:
+            names = [format_expr(self.exprs[pairs[2 * q]:pairs[2 * q] + pairs[2 * q + 1]], full, at=False) for q in range(len(exprs))]
+        if len(names) != len(exprs):
+            raise ValueError("extend: one name per expression")
+        return self._push(n, kept + len(exprs), self._projected(full, keep) + list(names))
+
+    def sparql_bind(self, child, expr, name):
+        """BIND(expr AS ?name) / SELECT (expr AS ?name): every column of `child`, then the computed one."""
+        return self.extend(child, [expr], keep=None, names=[name])
 
     def build(self, root, agg_columns=False):
         """agg_columns=True sets abi.PLAN_AGG_COLUMNS: an AggregateExec with aggregates may sit anywhere, its output is the keys and then
@@ -762,6 +794,20 @@ def explain(pb, root, choose_index=None, agg_columns=False):
             if agg_columns and n.table_cols:   # the aggregates' values as output columns, `name@index`
                 values = ", values=[" + ", ".join(f"{pb.names[i][n.n_keys + a]}@{n.n_keys + a}" for a in range(n.table_cols)) + "]"
             lines.append(f"{pad}AggregateExec: mode=Single, gby=[{gby}], aggr=[{', '.join(aggs)}]{values}")
+            walk(n.left, depth + 1)
+            return
+        if n.kind == abi.NODE_EXTEND:       # `ProjectionExec: expr=[product@0 as product, .., DIV(..) as ratio]`
+            full = pb.names[n.left]
+            kept = range(len(full)) if n.n_proj == abi.NO_PROJECTION else [pb.pool[n.proj_off + q] for q in range(n.n_proj)]
+            items = [f"{full[c]}@{c} as {full[c]}" for c in kept]
+            for q in range(n.table_cols):
+                off, ln = pb.pool[n.table_slot + 2 * q], pb.pool[n.table_slot + 2 * q + 1]
+                ex = pb.exprs[off:off + ln]
+                # ENC_TV of a value column is the identity (its value is a typed value already): the reference prints the column
+                ex = [e for j, e in enumerate(ex) if not (e.op == abi.EX_ENC_TV and j and ex[j - 1].op == abi.EX_COLUMN
+                                                          and ex[j - 1].u < len(full) and pb.values[n.left][ex[j - 1].u])]
+                items.append(f"{format_expr(ex, full)} as {pb.names[i][len(kept) + q]}")
+            lines.append(f"{pad}ProjectionExec: expr=[{', '.join(items)}]")
             walk(n.left, depth + 1)
             return
         name = {abi.NODE_PROJECTION: "ProjectionExec", abi.NODE_TOPK: "SortExec: TopK", abi.NODE_UNION: "UnionExec",
