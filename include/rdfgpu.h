@@ -780,6 +780,7 @@ enum {
   RDFGPU_OPT_PARTITION_SLOTS,           /* value: slots of a partition's LDS table, a power of two from 1024 to 8192 (0 = automatic: 4096); a partition with more than slots / 2 build rows is joined chunk by chunk */
   RDFGPU_OPT_NO_SEMI_LDS,               /* flag: semi / anti joins never build their set of right rows in LDS (the HBM set, built per execution) */
   RDFGPU_OPT_NO_BAND_ROW_CACHE,         /* flag: band join reading a slice's rows in place: the rows' decoded windows are not kept on the slice, every step gathers 16-byte records by key */
+  RDFGPU_OPT_NO_BAND_PAIR_LIST,         /* flag: band join streaming a slice's cached pair verdicts: no list of the surviving pairs is kept beside them, every step expands the verdict bits into rows */
   RDFGPU_OPT_NO_BAND_PAIR_CACHE,        /* flag: band join reading a slice's rows in place with the rows' windows kept: the pair test's verdicts are not kept on the slice, every step tests every pair */
   RDFGPU_OPT_BAND_PAIR_CACHE_BLOCKS,    /* value: the largest number of 64 x 64 blocks whose verdicts are kept on a slice, 512 bytes each (0 = automatic: 2^21 blocks = 1 GiB) */
   RDFGPU_OPT_NO_AGG_LDS,                /* flag (ABI 4 addendum): AggregateExec never keeps per-workgroup partial accumulators in LDS (every row adds into the HBM accumulators) */
@@ -819,6 +820,13 @@ int rdfgpu_band_row_cache_eligible(uint32_t in_place, uint32_t compact, uint32_t
  * option_set: RDFGPU_OPT_NO_BAND_PAIR_CACHE; n_blocks: blocks of the in-place layout; cap_blocks: RDFGPU_OPT_BAND_PAIR_CACHE_BLOCKS (0 = 2^21; inclusive).
  */
 int rdfgpu_band_pair_cache_eligible(uint32_t row_windows, uint32_t neq_self, uint32_t pack16, uint32_t option_set, uint64_t n_blocks, uint64_t cap_blocks);
+/*
+ * .. and is a list of the surviving pairs kept beside the verdicts, 2 bytes per pair in the order the rows come out, for the emit pass to read instead of the bits (1),
+ * or does every step expand the bits (0)?  pair_cached: the step streams the slice's cached verdicts; option_set: RDFGPU_OPT_NO_BAND_PAIR_LIST; survivors: set bits of
+ * the verdicts; n_blocks: blocks of the in-place layout.  Kept when the list is no larger than the bits it stands in for, 2 * survivors <= 512 * n_blocks, and its
+ * 32-bit offsets cannot wrap (n_blocks < 2^20).
+ */
+int rdfgpu_band_pair_list_eligible(uint32_t pair_cached, uint32_t option_set, uint64_t survivors, uint64_t n_blocks);
 /*
  * MemIndexScanPredicate::try_and_with (scan_instructions.rs:170-210).  Predicates are given
  * as (pred, a, b) triples where IN sets are explicit arrays.  Writes the combined predicate;

@@ -591,6 +591,11 @@ int rdfgpu_band_pair_cache_eligible(uint32_t row_windows, uint32_t neq_self, uin
   s.row_windows = row_windows != 0; s.neq_self = neq_self != 0; s.pack16 = pack16 != 0; s.option_off = option_set == 0; s.n_blocks = n_blocks; s.cap = cap_blocks;
   return band_pair_cache_eligible(s) ? 1 : 0;
 }
+int rdfgpu_band_pair_list_eligible(uint32_t pair_cached, uint32_t option_set, uint64_t survivors, uint64_t n_blocks) {
+  BandPairListShape s;
+  s.pair_cached = pair_cached != 0; s.option_off = option_set == 0; s.survivors = survivors; s.n_blocks = n_blocks;
+  return band_pair_list_eligible(s) ? 1 : 0;
+}
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;
   if (p->pred == RDFGPU_PRED_IN) { if (p->ids) r.ids.assign(p->ids, p->ids + p->n_ids); else r.ids = {p->from}; }

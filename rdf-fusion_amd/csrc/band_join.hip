@@ -588,6 +588,33 @@ __global__ __launch_bounds__(256) void band_pair_bits_kernel(const BandArgs b) {
   b.masks[(u64)blk * 64 + lane] = lane < nr ? mask : 0ull;
 }
 
+// The build of a slice's pair list (SliceTable::BandRowWindows::pair_list; behind the verdicts, once per store version and literal set): the set bits of every block
+// as (row << 6) | entry, rows ascending and entries ascending within a row — the order in which band_emit_kernel lists a block's survivors, so the emit pass of a
+// steady step reads the list instead of expanding the bits.  One wave per block: the counts (one entry past the last block: 0, for the scan), then the lists at the
+// scanned offsets.  A list that would not fit `cap` items is not written (the host declines it); the total is left for the host either way.
+__global__ __launch_bounds__(256) void band_pair_list_count_kernel(const BandPairListArgs a) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+  if (blk > a.n_blocks) return;                            // wave-uniform
+  const u32 c = wave_incl_scan(blk < a.n_blocks ? (u32)__popcll(a.bits[(u64)blk * 64 + lane]) : 0u);
+  if (lane == 63) a.counts[blk] = c;
+}
+__global__ __launch_bounds__(256) void band_pair_list_write_kernel(const BandPairListArgs a) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+  const u32 total = a.off[a.n_blocks];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *a.total_out = total;
+  if (blk >= a.n_blocks || (u64)total > a.cap) return;     // wave-uniform
+  u64 mask = a.bits[(u64)blk * 64 + lane];
+  const u32 cnt = (u32)__popcll(mask);
+  u32 at = a.off[blk] + wave_incl_scan(cnt) - cnt;         // (< off[blk + 1] <= total <= cap for every item written below)
+  while (mask) {                                           // this lane's survivors, in entry order
+    const u32 e = (u32)__ffsll((long long)mask) - 1u;
+    mask &= mask - 1;
+    a.list[at++] = (unsigned short)((lane << 6) | e);
+  }
+}
+
 // Rare: probe rows whose window operands are not all xsd:integer (or overflow i64) take the full typed-value semantics,
 // pair by pair (stage_filter_slow), and patch their bits and their block's count.  Runs after the mask kernel; exits at
 // once when the decode pass met no such row.
@@ -639,8 +666,89 @@ constexpr u32 kBandList = 1024;   // survivors listed at a time: a block with mo
 // six-column form kept 18 of them pinned and spilled scalars into vector lanes inside the loops)
 // STATIC (BandArgs::row_win): the row's one output value is row_val[row] — 4 bytes per row, not the 16-byte record.
 // CACHED (STATIC; the bits are the slice's cached verdicts): bvalid[blk] says which rows of the block have a value in this execution.
-template <int NCOLS, bool STATIC = false, bool CACHED = false>
+// LIST (CACHED; BandArgs::pair_list): the block's survivors are read from the slice's list — band_emit_list.
+constexpr u32 kBandListAhead = 8;   // rounds of 64 list items a wave of the list form has in flight before its first round (whole rounds: the list is padded by one, Plan::band_row_windows)
+// The list form: the block's survivors, in output order, are a table of the slice; a step keeps the items whose row has a value in this execution.  Two round
+// trips per wave: everything indexed by the block number, then the rows' values, the entries' columns and the list's first kBandListAhead rounds (no load
+// inside the rounds: a wait there would wait for the round before's stores as well).  Per round of 64 items: row and entry unpacked, the columns fetched from the
+// owning lanes (ds_bpermute) — the row's value says whether the item counts —, the counting items compacted with a ballot and stored at scalar base + lane
+// offset.  No LDS, no per-lane loop; the block count is the layout's, known on the host.
+template <int NCOLS>
+__device__ __forceinline__ void band_emit_list(const BandArgs& b) {
+  const u32 lane = threadIdx.x & 63;
+  u32* outp[NCOLS]; u32 out_sel[NCOLS];
+#pragma unroll
+  for (u32 oc = 0; oc < (u32)NCOLS; oc++) { outp[oc] = b.out[oc]; out_sel[oc] = b.out_sel[oc]; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {   // the exact total, whether or not it fitted
+    const u64 total = b.bofs[b.max_blocks];
+    *b.n_out_dev = total;
+    if (total > b.out_cap) *b.overflow = 1u;
+  }
+  const u32 blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+  if (blk >= b.max_blocks) return;                         // wave-uniform (in place: exact)
+  const u32 tot_v = b.bcount[blk];
+  const uint4 d = b.bdesc[blk];
+  const u32 run_v = b.bofs[blk];
+  const u32 l0_v = b.pair_list_off[blk], l1_v = b.pair_list_off[blk + 1];
+  asm volatile("" :: "v"(tot_v), "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w), "v"(run_v), "v"(l0_v), "v"(l1_v));   // (one round trip: all issued before the first wait)
+  if (__builtin_amdgcn_readfirstlane(tot_v) == 0) return;
+  const u32 eb = __builtin_amdgcn_readfirstlane(d.x), ne = __builtin_amdgcn_readfirstlane(d.y);
+  const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
+  const u32 lb = __builtin_amdgcn_readfirstlane(l0_v), ln = (u32)__builtin_amdgcn_readfirstlane(l1_v) - lb;
+  const u64 run0 = (u64)(u32)__builtin_amdgcn_readfirstlane(run_v);
+  const unsigned short* items = b.pair_list + lb;
+  u32 rv = kNil;                                           // this execution's value of the row (lane = row; kNil: none)
+  if (lane < nr) rv = b.row_val[rb + lane];
+  u32 ev[kBandMaxSideCols];                                // output values of the entry (lane = entry)
+#pragma unroll
+  for (u32 u = 0; u < kBandMaxSideCols; u++) { ev[u] = 0; if (u < b.n_entry_cols && lane < ne) ev[u] = b.eo[u][eb + lane]; }
+  u32 pre[kBandListAhead];                                 // (lanes past the list's end read the next block's items or the padding: they never count)
+#pragma unroll
+  for (u32 k = 0; k < kBandListAhead; k++) { pre[k] = 0; if (k * 64u < ln) pre[k] = items[k * 64u + lane]; }
+#pragma unroll
+  for (u32 k = 0; k < kBandListAhead; k++) asm volatile("" :: "v"(pre[k]));
+  asm volatile("" :: "v"(rv), "v"(ev[0]), "v"(ev[1]), "v"(ev[2]), "v"(ev[3]));
+  // per output column, once per block: the entry register it comes from.  A row column is the row's value, rvp below: this form knows ONE row column
+  // (out_sel 0; the cached windows imply the compact record, which carries one — launch_band_emit keeps a plan with two on the bits form), and its
+  // slot here holds ev[0], permuted with the others and dropped for rvp: one permute per round more than needed, for rounds without a branch.
+  u32 srcv[NCOLS];
+#pragma unroll
+  for (u32 oc = 0; oc < (u32)NCOLS; oc++) {
+    u32 src = ev[0];
+#pragma unroll
+    for (u32 u = 1; u < kBandMaxSideCols; u++) src = out_sel[oc] == 2 + u ? ev[u] : src;
+    srcv[oc] = src;
+  }
+  // the block's output range starts at a wave-uniform offset: scalar base + 32-bit lane offset per store
+  const u64 room64 = b.out_cap > run0 ? b.out_cap - run0 : 0ull;           // rows that still fit (the count stays exact either way)
+  int room = room64 < 0x7FFFFFFFull ? (int)room64 : 0x7FFFFFFF;   // (signed, on the scalar unit: a block takes at most 4096 rows off it once it has run out)
+  u64 run_s = run0;
+  const u32 left = lane < ln ? ln - lane : 0u;             // items from this lane's first on: its item of the round at t0 is in the list iff t0 < left
+  auto round = [&](u32 item, u32 t0) {
+    u32 rvp = (u32)__builtin_amdgcn_ds_bpermute((int)((item >> 4) & 0xFCu), (int)rv);   // lane = the item's row
+    const int ea = (int)((item << 2) & 0xFCu);                                           // lane = the item's entry
+    u32 v[NCOLS];
+#pragma unroll
+    for (u32 oc = 0; oc < (u32)NCOLS; oc++) v[oc] = (u32)__builtin_amdgcn_ds_bpermute(ea, (int)srcv[oc]);
+    rvp = t0 < left ? rvp : kNil;                          // past the list's end
+    const u64 m = __builtin_amdgcn_ballot_w64(rvp != kNil);
+    const u32 pos = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+    const int lim = room < 64 ? (room > 0 ? room : 0) : 64;
+    if (rvp != kNil && pos < (u32)lim) {
+#pragma unroll
+      for (u32 oc = 0; oc < (u32)NCOLS; oc++)                // (scalar base + 32-bit lane offset)
+        *reinterpret_cast<u32*>(reinterpret_cast<char*>(outp[oc] + run_s) + (pos << 2)) = out_sel[oc] == 0 ? rvp : v[oc];
+    }
+    const int n = __popcll(m);
+    run_s += (u32)n; room -= n;
+  };
+#pragma unroll
+  for (u32 k = 0; k < kBandListAhead; k++) { if (k * 64u >= ln) return; round(pre[k], k * 64u); }
+  for (u32 t0 = kBandListAhead * 64u; t0 < ln; t0 += 64) round((u32)items[t0 + lane], t0);   // (longer lists: a round trip per round)
+}
+template <int NCOLS, bool STATIC = false, bool CACHED = false, bool LIST = false>
 __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
+  if constexpr (LIST) { band_emit_list<NCOLS>(b); return; } else {
   __shared__ unsigned short list[4][kBandList];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u32 n_all = b.boff[b.kn];
@@ -732,6 +840,7 @@ __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");              // the list is free again
   }
   }
+  }
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -784,6 +893,12 @@ void launch_band_pair_bits(const BandArgs& b, hipStream_t s) {
   if (b.n_win == 2) hipLaunchKernelGGL(band_pair_bits_kernel<2>, g, dim3(256), 0, s, b);
   else hipLaunchKernelGGL(band_pair_bits_kernel<1>, g, dim3(256), 0, s, b);
 }
+void launch_band_pair_list_count(const BandPairListArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(band_pair_list_count_kernel, dim3((a.n_blocks + 1 + 3) / 4), dim3(256), 0, s, a);   // (+ 1: the scan's closing zero)
+}
+void launch_band_pair_list_write(const BandPairListArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(band_pair_list_write_kernel, dim3((a.n_blocks + 3) / 4 ? (a.n_blocks + 3) / 4 : 1), dim3(256), 0, s, a);
+}
 void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s) {
   const u32 g = (b.max_blocks + 3) / 4;
   hipLaunchKernelGGL(band_slow_kernel, dim3(g < 2048u ? (g ? g : 1u) : 2048u), dim3(256), 0, s, a_dev, b);
@@ -791,7 +906,15 @@ void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s
 void launch_band_emit(const BandArgs& b, hipStream_t s) {
   const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);
   static_assert(kBandMaxRowCols + kBandMaxSideCols == 6, "one instantiation per column count");
-  if (b.row_win && b.bvalid) switch (b.n_out_cols) {
+  if (b.row_win && b.bvalid && b.pair_list && b.n_row_cols <= 1) switch (b.n_out_cols) {   // the slice's list of survivors (band_emit_list: one row column)
+    case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true>), g, dim3(256), 0, s, b); return;
+    case 2: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true>), g, dim3(256), 0, s, b); return;
+    case 3: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true>), g, dim3(256), 0, s, b); return;
+    case 4: hipLaunchKernelGGL((band_emit_kernel<4, true, true, true>), g, dim3(256), 0, s, b); return;
+    case 5: hipLaunchKernelGGL((band_emit_kernel<5, true, true, true>), g, dim3(256), 0, s, b); return;
+    case 6: hipLaunchKernelGGL((band_emit_kernel<6, true, true, true>), g, dim3(256), 0, s, b); return;
+  }
+  else if (b.row_win && b.bvalid) switch (b.n_out_cols) {
     case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true>), g, dim3(256), 0, s, b); return;
     case 2: hipLaunchKernelGGL((band_emit_kernel<2, true, true>), g, dim3(256), 0, s, b); return;
     case 3: hipLaunchKernelGGL((band_emit_kernel<3, true, true>), g, dim3(256), 0, s, b); return;

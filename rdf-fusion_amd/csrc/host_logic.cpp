@@ -162,4 +162,9 @@ bool band_pair_cache_eligible(const BandPairCacheShape& s) {
   return s.n_blocks <= (s.cap ? s.cap : kBandPairCacheBlocks);
 }
 
+bool band_pair_list_eligible(const BandPairListShape& s) {
+  if (!s.pair_cached || !s.option_off || s.n_blocks >= kBandPairListBlocks) return false;
+  return s.survivors <= 256 * s.n_blocks;
+}
+
 }  // namespace rdfgpu

@@ -66,5 +66,12 @@ bool band_row_cache_eligible(const BandRowCacheShape& s);
 constexpr u64 kBandPairCacheBlocks = 1ull << 21;   // 1 GiB of verdicts: ten times what BSBM Q5 at 285 k products needs, small against the device's memory
 struct BandPairCacheShape { bool row_windows = false, neq_self = false, pack16 = false, option_off = false; u64 n_blocks = 0, cap = 0; };
 bool band_pair_cache_eligible(const BandPairCacheShape& s);
+// .. and is a list of the surviving pairs kept beside the verdicts (SliceTable::BandRowWindows::pair_list: 2 bytes per set bit, in the order the emit pass writes the
+// rows)?  A condition, not a measurement: yes when the step streams the cached verdicts, the option is off, the list is no larger than the bits it stands in for
+// (2 * survivors <= 512 * n_blocks: at most 256 survivors per block on average) and the layout has fewer than kBandPairListBlocks blocks (4096 pairs per block:
+// the list's 32-bit offsets cannot wrap).  survivors = 0 asks before the build, when only the layout is known.
+constexpr u64 kBandPairListBlocks = 1ull << 20;
+struct BandPairListShape { bool pair_cached = false, option_off = false; u64 survivors = 0, n_blocks = 0; };
+bool band_pair_list_eligible(const BandPairListShape& s);
 
 }  // namespace rdfgpu

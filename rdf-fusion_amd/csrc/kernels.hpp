@@ -507,7 +507,15 @@ struct BandArgs {
   // .. and the pair test's verdicts are cached too (masks = SliceTable::BandRowWindows::pair_bits, never written by a step): per block the rows that
   // have a value in this execution, one bit per lane — written by the cached form of the mask pass, applied by the emit kernel.  Null: masks is this execution's own.
   u64* bvalid;
+  // .. and beside them the list of their set bits (SliceTable::BandRowWindows::pair_list; the list form of the emit kernel): block blk's surviving pairs are
+  // pair_list[pair_list_off[blk] .. pair_list_off[blk + 1]), (row << 6) | entry each, rows ascending and entries ascending within a row.  Null: the emit kernel expands the bits.
+  const unsigned short* pair_list; const u32* pair_list_off;
 };
+// The build of a slice's pair list from its cached verdicts (band_join.hip): the set bits of every block counted (counts[n_blocks] = 0), the counts scanned into `off`
+// by the caller, the lists written.  Nothing is written when the total, off[n_blocks], exceeds `cap` items; the total goes to *total_out either way.
+struct BandPairListArgs { const u64* bits; u32 n_blocks; u32* counts; const u32* off; unsigned short* list; u64 cap; u32* total_out; };
+void launch_band_pair_list_count(const BandPairListArgs& a, hipStream_t s);
+void launch_band_pair_list_write(const BandPairListArgs& a, hipStream_t s);
 // The build of BandArgs::row_win (band_join.hip): per join key d of [kmin, kmin + kn) the window operands are fetched through the operand stages' direct
 // tables and packed by band_row_record; then every slice row copies its key's 8 bytes.
 struct BandRowOperand { const u32* direct; u32 kmin, kn; const u32* val; };   // id of the operand = val[direct[key - kmin]] (no row: the key joins nothing)

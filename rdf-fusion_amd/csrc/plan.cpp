@@ -147,6 +147,7 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::agg_groups_kernel", "void rdfgpu::agg_accum_kernel<false>", "void rdfgpu::agg_accum_kernel<true>", "rdfgpu::agg_final_kernel",
       "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>",
       "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel", "void rdfgpu::band_pair_bits_kernel",
+      "rdfgpu::band_pair_list_count_kernel", "rdfgpu::band_pair_list_write_kernel",
       "rdfgpu::agg_value_cols_kernel", "rdfgpu::extend_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];

@@ -134,6 +134,7 @@ struct BandJoin {
   const uint2* row_win = nullptr;      // the slice's cached row windows for this chain (band_row_windows; null: not eligible, declined, or the route is closed)
   bool row_static = false;             // route: in place, the block kernels read row_win and this execution's values per row instead of 16-byte records
   u64* pair_bits = nullptr;            // the slice's cached pair verdicts for this chain (band_row_windows; null: not eligible, over the cap, or no row windows)
+  const unsigned short* pair_list = nullptr; const u32* pair_list_off = nullptr; u64 pair_survivors = 0;   // .. and the list of their set bits (band_row_windows; null: none kept, declined as larger than the bits, or the plan's options decline it)
   bool pair_cached = false;            // route: row_static, and the pair test is not run — its verdicts are pair_bits, a step applies its rows to them (band_mask_kernel's CACHED form)
   u64 nrows = 0, max_blocks = 0;       // probe rows of the block kernels (in place: the slice's own rows); upper bound of the blocks (in place: exact)
   u32* skey = nullptr; u32* perm = nullptr; u32 sort_bits = 1; void* sort_temp = nullptr; size_t sort_temp_bytes = 0;   // the radix sort of the probe keys (its output pairs, key bits, temp): allocated by band_probe_side, run by band_blocks_and_emit
@@ -157,6 +158,7 @@ enum KernelClass {
   KC_AGG_ACCUM_EXPR_HBM, KC_AGG_ACCUM_EXPR_LDS,   // agg_accum_expr_kernel<LDS>: some SUM / AVG reads an expression
   KC_BAND_ROW_WIN_KEYS, KC_BAND_ROW_WIN_ROWS,     // the build of a slice's cached row windows (band_join.hip)
   KC_BAND_PAIR_BITS,                              // .. and of its cached pair verdicts
+  KC_BAND_PAIR_LIST_COUNT, KC_BAND_PAIR_LIST_WRITE,   // .. and of the list of their set bits
   KC_AGG_VALUE_COLS,                              // agg_value_cols_kernel: an AggregateExec's value columns (RDFGPU_PLAN_AGG_COLUMNS)
   KC_EXTEND,                                      // extend_kernel: the computed columns of a ProjectionExec with expressions (RDFGPU_NODE_EXTEND)
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>

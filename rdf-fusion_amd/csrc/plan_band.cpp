@@ -417,15 +417,41 @@ void Plan::band_row_windows(BandJoin& bj) {
     timed(KC_BAND_PAIR_BITS, (512ull + 16) * bj.lay.n_blocks + 16ull * bj.nb, bj.nb, nullptr, 8, nullptr, 0, 0, [&] { launch_band_pair_bits(d, stream); });
     return bits;
   };
+  // .. and the list of the verdicts' set bits (R13; pair_list, host_logic.hpp: band_pair_list_eligible), launched behind the bits on the same stream.  Its size is the
+  // condition's bound, 256 items per block, not a read-back: the write pass leaves a longer list unwritten, and the total travels with the wait that is there anyway.
+  BandPairListShape lshape;
+  lshape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_LIST); lshape.n_blocks = bj.lay.n_blocks;
+  auto want_list = [&](const u64* bits) { lshape.pair_cached = bits != nullptr && bj.lay.n_blocks != 0; lshape.survivors = 0; return band_pair_list_eligible(lshape); };
+  BandPairListArgs la{};
+  auto build_pair_list = [&](const u64* bits, u32* total_out) {   // per block its 512 B of bits read twice, 4 B of count written and read, 4 B of offset written and read; 2 B per survivor written
+    const u64 nbk = bj.lay.n_blocks;
+    la.bits = bits; la.n_blocks = (u32)nbk; la.counts = scratch<u32>(nbk + 1); la.cap = 256ull * nbk; la.total_out = total_out;
+    u32* off = store->table_alloc<u32>(nbk + 1); la.off = off; la.list = store->table_alloc<unsigned short>(la.cap + 64);   // (padded: the emit pass reads whole rounds of 64 items)
+    const size_t tb = scan_temp_bytes(nbk + 1); void* temp = scratch<unsigned char>(tb);
+    timed(KC_BAND_PAIR_LIST_COUNT, 0, nbk, nullptr, 512 + 4, nullptr, 0, 0, [&] { launch_band_pair_list_count(la, stream); });
+    timed(scan_class(nbk + 1), 0, nbk + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(la.counts, off, nbk + 1, temp, tb, stream); });
+    timed(KC_BAND_PAIR_LIST_WRITE, 0, nbk, nullptr, 512 + 4 + 2 * 256, nullptr, 0, 0, [&] { launch_band_pair_list_write(la, stream); });
+  };
+  auto keep_pair_list = [&](SliceTable::BandRowWindows& e, u64 survivors) {   // after the wait: published when it meets the condition, else freed and remembered as declined
+    lshape.survivors = survivors;
+    if (band_pair_list_eligible(lshape)) { e.pair_list = la.list; e.pair_list_off = const_cast<u32*>(la.off); e.pair_survivors = survivors; metrics.tables_built++; }
+    else { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); e.list_declined = true; }
+  };
+  auto take_pair_list = [&](const SliceTable::BandRowWindows& e) {   // (a plan whose options decline the list does not use one another plan left)
+    if (e.pair_list && lshape.option_off) { bj.pair_list = e.pair_list; bj.pair_list_off = e.pair_list_off; bj.pair_survivors = e.pair_survivors; }
+  };
   for (auto& e : tab->band_row_windows) if (e.key == key) {
     bj.row_win = e.row_win; pair.row_windows = e.row_win != nullptr;
     if (!band_pair_cache_eligible(pair)) return;
-    if (!e.pair_bits) {   // the windows were built by a plan whose options declined the verdicts: built now, published when complete
-      u64* bits = build_pair_bits(e.row_win);
-      RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++; metrics.tables_built++;
-      e.pair_bits = bits;
-    }
-    bj.pair_bits = e.pair_bits;
+    // the windows were built by a plan whose options declined the verdicts, or the verdicts by one that declined the list: built now, published when complete
+    u64* bits = e.pair_bits ? nullptr : build_pair_bits(e.row_win);
+    const bool list = !e.pair_list && !e.list_declined && want_list(e.pair_bits ? e.pair_bits : bits);
+    u32 survivors = 0;
+    if (list) { u32* total = reinterpret_cast<u32*>(new_counter()); build_pair_list(e.pair_bits ? e.pair_bits : bits, total); survivors = read_back<u32>(total); }
+    else if (bits) { RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++; }
+    if (bits) { e.pair_bits = bits; metrics.tables_built++; }
+    if (list) keep_pair_list(e, survivors);
+    bj.pair_bits = e.pair_bits; take_pair_list(e);
     return;
   }
   if (tab->band_row_windows.size() >= 8) return;
@@ -436,10 +462,16 @@ void Plan::band_row_windows(BandJoin& bj) {
   timed(KC_BAND_ROW_WIN_ROWS, 0, bj.nb, nullptr, 4 + 8 + 8, nullptr, 0, 0, [&] { launch_band_row_win_rows(w, stream); });
   pair.row_windows = true;                               // (whether the store's operands accept the windows is known only after the wait: built behind them, freed if not)
   u64* bits = band_pair_cache_eligible(pair) ? build_pair_bits(w.row_win) : nullptr;
-  const u32 slow = read_back<u32>(w.slow_keys);          // (the wait: published only when complete)
+  const bool list = want_list(bits);
+  if (list) build_pair_list(bits, w.slow_keys + 1);      // (the total in the upper half of the counter the wait reads)
+  const uint2 got = read_back<uint2>(w.slow_keys);       // (the wait: published only when complete) {keys declined, survivors}
+  const u32 slow = got.x;
   if (slow) { store->table_free(w.row_win); w.row_win = nullptr; if (bits) store->table_free(bits); bits = nullptr; } else metrics.tables_built += bits ? 2 : 1;
   tab->band_row_windows.push_back(SliceTable::BandRowWindows{key, w.row_win, bits});
-  bj.row_win = w.row_win; bj.pair_bits = bits;
+  SliceTable::BandRowWindows& e = tab->band_row_windows.back();
+  if (list && slow) { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); }
+  else if (list) keep_pair_list(e, got.y);
+  bj.row_win = w.row_win; bj.pair_bits = bits; take_pair_list(e);
 }
 
 // The probe rows' records in key order, with the rows per key (poff) and the blocks' counts zeroed: written by the ordered slice join below (fused; in place: one per slice row), else decoded from the probe columns.
@@ -480,7 +512,7 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
                            bj.fused ? (int)(reinterpret_cast<u64*>(pending_oj.o.multi_rows) - counters) : -1, bj.skip_slow, bj.in_place, bj.in_place ? max_blocks : 0});
   const u64 hist = bj.j.nd.band.blocks; b.launch_blocks = (u32)(bj.in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
   b.bdesc = bj.in_place ? bj.lay.bdesc : scratch<uint4>(max_blocks);
-  if (bj.pair_cached) { b.masks = bj.pair_bits; b.bvalid = scratch<u64>(max_blocks); }   // the slice's verdicts: read, never written
+  if (bj.pair_cached) { b.masks = bj.pair_bits; b.bvalid = scratch<u64>(max_blocks); b.pair_list = bj.pair_list; b.pair_list_off = bj.pair_list_off; }   // the slice's verdicts (and their list, where kept): read, never written
   else b.masks = scratch<u64>(max_blocks * 64);
   const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn)); void* temp = scratch<unsigned char>(tb);
   if (bj.counting) {   // poff = exclusive scan of the rows per key (entry kn = the rows that join something); then the scatter
@@ -509,7 +541,9 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
     timed(KC_BAND_SLOW, 0, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_slow(a_dev, b, stream); });
   }
   timed(scan_class(max_blocks + 1), 0, max_blocks + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.bcount, b.bofs, max_blocks + 1, temp, tb, stream); });
-  timed(KC_BAND_EMIT, 4ull * b.n_entry_cols * nb, bj.nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
+  // (the list form: the slice's list and its offsets read as well, 2 B per survivor and 4 B per block + 4)
+  const u64 list_bytes = b.pair_list ? 2ull * bj.pair_survivors + 4ull * (max_blocks + 1) : 0;
+  timed(KC_BAND_EMIT, list_bytes + 4ull * b.n_entry_cols * nb, bj.nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
 }
 
 }  // namespace rdfgpu

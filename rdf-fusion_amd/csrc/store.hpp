@@ -114,7 +114,13 @@ struct SliceTable {
   // pair_bits: with the rows' windows and the entries both fixed, the pair test's verdicts themselves are a function of the store version and the literals: 64 words per
   // block of the in-place layout (what the pair test writes when every row has a table row), 512 B per block, kept when the plan's options allow it
   // (host_logic.hpp, band_pair_cache_eligible); null: not kept.  Freed with row_win.
-  struct BandRowWindows { std::string key; uint2* row_win; u64* pair_bits = nullptr; };
+  // pair_list / pair_list_off: the set bits of pair_bits as a list per block ((row << 6) | entry, rows ascending, entries ascending within a row; exclusive offsets,
+  // n_blocks + 1 of them), pair_survivors of them in all: what the emit pass reads instead of expanding the bits, kept when it is no larger than the bits
+  // (host_logic.hpp, band_pair_list_eligible); list_declined: it was built and turned out larger — not built again.  Key, lock and lifetime are pair_bits'.
+  struct BandRowWindows {
+    std::string key; uint2* row_win; u64* pair_bits = nullptr;
+    unsigned short* pair_list = nullptr; u32* pair_list_off = nullptr; u64 pair_survivors = 0; bool list_declined = false;
+  };
   std::vector<BandRowWindows> band_row_windows;
   // the slice as the sorted input of a FILTER on its sort column (kernels.hip, run-copy form): lo[i] = first row whose id is >= first + i
   // (i = 0 .. span): where every distinct id's run starts — a function of the slice alone

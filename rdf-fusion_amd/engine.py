@@ -126,6 +126,7 @@ def load_library():
     lib.rdfgpu_choose_index.restype = C.c_uint32
     lib.rdfgpu_band_row_cache_eligible.argtypes = [C.c_uint32] * 5 + [u32p, u32p]
     lib.rdfgpu_band_pair_cache_eligible.argtypes = [C.c_uint32] * 4 + [C.c_uint64] * 2
+    lib.rdfgpu_band_pair_list_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -181,6 +182,12 @@ def band_pair_cache_eligible(n_blocks, row_windows=True, neq_self=True, pack16=T
     """.. and may the pair test's verdicts be kept beside the windows (host_logic.hpp)?  `n_blocks`: 64 x 64 blocks of the in-place layout;
     `cap_blocks`: the BAND_PAIR_CACHE_BLOCKS option (inclusive; 0 = automatic, 2^21 blocks)."""
     return bool(_check(load_library().rdfgpu_band_pair_cache_eligible(int(row_windows), int(neq_self), int(pack16), int(option_set), int(n_blocks), int(cap_blocks))))
+
+
+def band_pair_list_eligible(survivors, n_blocks, pair_cached=True, option_set=False):
+    """.. and is a list of the surviving pairs kept beside the verdicts (host_logic.hpp)?  `survivors`: set bits of the verdicts; `n_blocks`:
+    64 x 64 blocks of the in-place layout.  Kept when it is no larger than the bits: 2 * survivors <= 512 * n_blocks."""
+    return bool(_check(load_library().rdfgpu_band_pair_list_eligible(int(pair_cached), int(option_set), int(survivors), int(n_blocks))))
 
 
 def _pred_struct(p, keep):
