@@ -420,7 +420,7 @@ enum {
                                   CLOSURE or UNION input; and so is rdfgpu_plan_decode_terms of a value column.  A value column under
                                   ID_EQ / ID_NEQ / IS_COMPATIBLE / STR is RDFGPU_ERR_INVALID, like every operand of the wrong kind.  A
                                   predicate that reads a value column runs in the generic VM.                                          */
-  RDFGPU_NODE_EXTEND = 12      /* ProjectionExec whose `expr=[..]` holds expressions (SPARQL Extend: BIND, `SELECT (expr AS ?x)`) — what the
+  RDFGPU_NODE_EXTEND = 12,     /* ProjectionExec whose `expr=[..]` holds expressions (SPARQL Extend: BIND, `SELECT (expr AS ?x)`) — what the
                                   BSBM Business Intelligence plans put directly above their aggregates (..Business Intelligence - Q3 / Q4 /
                                   Q8 (Execution Plan).snap: `DIV(xsd:float(monthCount@1), monthBeforeCount@2) as ratio`).  Encoding: left =
                                   input, right = -1; proj_off / n_proj = the input columns kept, in order (RDFGPU_NO_PROJECTION keeps all);
@@ -449,6 +449,29 @@ enum {
                                   and of refusals (join key, group column, COUNT_DISTINCT input, TopK key / group / output, CLOSURE / UNION
                                   input, rdfgpu_plan_decode_terms; the sharded path exchanges object ids only) applies, the texts naming
                                   the node and the expression.  rdfgpu_plan_result_values / _fetch / rdfgpu_plan_next work unchanged.   */
+  RDFGPU_NODE_SORT = 13        /* SortExec: ORDER BY over object-id and value columns, ascending or descending per key, with an optional
+                                  fetch — the operator that ends the BSBM Business Intelligence plans (..Business Intelligence - Q3
+                                  (Execution Plan).snap:6: `SortExec: TopK(fetch=10), expr=[ENC_SORT(DIV(xsd:float(monthCount@1),
+                                  monthBeforeCount@2)) DESC, ENC_SORT(ENC_PT(product@0)) ASC]`; Q1: `ENC_SORT(reviewCount@1) DESC`).
+                                  Encoding: left = input, right = -1; n_keys = 1..RDFGPU_MAX_KEYS; left_keys[i] = the column of key i;
+                                  right_keys[i] = how | RDFGPU_SORT_DESC (without the flag: ascending), `how` being RDFGPU_SORT_BY_ID,
+                                  _BY_TERM or _BY_DOUBLE over an object-id column — the keys RDFGPU_NODE_TOPK defines, BY_TERM's refusal of
+                                  a column of mixed kinds included (it fails the execute) — or RDFGPU_SORT_BY_VALUE over a value column;
+                                  table_cols = the fetch (0: none, every row); proj_off / n_proj = the output columns.
+                                  Rows: no de-duplication; the output is the input's rows, the first `fetch` of them in the order below.
+                                  Order: lexicographic over the keys; rows equal on every key come out in ascending input row order (the
+                                  reference leaves that order open; it is defined here so that results are reproducible).  DESC reverses
+                                  the whole key of that key (NULLs, which come first ascending, come last), never the final tie-break.
+                                  Columns: a value column of the input is a value column of the output, its origin carried like a
+                                  projection's and its entries unchanged (only the u32 entries of the columns are permuted, the 24-byte
+                                  values stay where they are): rdfgpu_plan_result_values / _fetch / rdfgpu_plan_next work unchanged.
+                                  Placement: anywhere a projection may sit.  The order is promised at the root and under plain PROJECTION
+                                  and EXTEND nodes above it; any other operator above may reorder.
+                                  RDFGPU_ERR_UNSUPPORTED / _INVALID at compile: n_keys outside 1..RDFGPU_MAX_KEYS; BY_VALUE over an
+                                  object-id column, an id form over a value column; BY_VALUE in a plan without RDFGPU_PLAN_AGG_COLUMNS (there
+                                  are no value columns without it); a key list whose record (below) exceeds 8 words.  The sharded path
+                                  exchanges rows between ranks and keeps no order: its stages refuse the node.  An input of 2^32 - 1 rows
+                                  or more fails the execute.  RDFGPU_NODE_TOPK (DISTINCT, ascending, per group) is unchanged.        */
 };
 /*
  * Aggregate functions of RDFGPU_NODE_AGGREGATE (ABI 4 addendum).  The reference plans SPARQL aggregates in
@@ -491,12 +514,28 @@ enum {
 #define RDFGPU_MAX_AGGREGATES 8u
 #define RDFGPU_AGG_INPUT_EXPR 0x80000000u   /* bit 31 of an aggregate's input: the low 31 bits are the pool offset of (expr_off, expr_len) */
 enum { RDFGPU_SORT_BY_ID = 0, RDFGPU_SORT_BY_TERM = 1,
-       RDFGPU_SORT_BY_DOUBLE = 2 /* ENC_SORT of a numeric value: the sortable encoding orders numerics by Double::from(Numeric)
+       RDFGPU_SORT_BY_DOUBLE = 2,/* ENC_SORT of a numeric value: the sortable encoding orders numerics by Double::from(Numeric)
                                     (lib/encoding/src/sortable_term/builder.rs:36-39, lib/model/src/xsd/double.rs:92-102) in IEEE
                                     total order (-0 < +0, NaN last); unbound and non-numeric values sort first (the `xsd:double(...)`
                                     cast of BSBM explore Q10's ORDER BY yields an error = null for them).  Exact for Q10, whose
                                     prices are xsd:double literals; a decimal's cast goes through its lexical form in the
-                                    reference and through the Decimal -> Double conversion here.                            */ };
+                                    reference and through the Decimal -> Double conversion here.                            */
+       /* ABI 4 addendum, RDFGPU_NODE_SORT only */
+       RDFGPU_SORT_BY_VALUE = 3  /* ENC_SORT of the typed value a value column's entry stands for: the reference's sortable encoding
+                                    (lib/encoding/src/sortable_term/builder.rs:24-39,113-140, term_type.rs:56-70, as
+                                    encoders/typed_value.rs:23-50 fills it; numeric.rs:52-60 for the bytes), the tuple (type, numeric,
+                                    bytes).  Entry 0 (unbound, the error value) has type 0 — the encoder appends a valid struct of type
+                                    Null, not an Arrow null — so unbound rows come first ascending and last descending.  A boolean has
+                                    type 3, numeric 0.0 / 1.0 and its one byte.  INT / INTEGER / DECIMAL / FLOAT / DOUBLE have type 4,
+                                    numeric = Double::from(Numeric) (a decimal through the Decimal -> Double routine, decimal.rs:445)
+                                    compared in IEEE total order (-0 < +0, NaN after +inf), then the value's own big-endian bytes compared
+                                    as byte strings (4 for INT and FLOAT, 8 for INTEGER and DOUBLE, 16 for DECIMAL; a string that is a
+                                    prefix of another sorts first).  The 24-byte value record carries no other kinds.
+                                    On the device a key is 64-bit words compared unsigned: one for an id form, 4 for BY_VALUE (type:3 |
+                                    numeric:64 | bytes:128 | length:5), plus one word for the row index; at most 8 words in all, so that
+                                    a tile of 1024 records fits 64 KB of LDS — (value, id, id, id) and (value, id) fit, two value keys
+                                    do not (RDFGPU_ERR_UNSUPPORTED at compile).                                                */ };
+#define RDFGPU_SORT_DESC 0x100u            /* RDFGPU_NODE_SORT, or-ed into right_keys[i]: key i descending                        */
 enum { RDFGPU_JOIN_INNER = 0, RDFGPU_JOIN_LEFT = 1,
        /* ABI 4: JoinType::LeftSemi / JoinType::LeftAnti of HashJoinExec and NestedLoopJoinExec (CROSS_JOIN stays inner-only) — what
           FILTER EXISTS / FILTER NOT EXISTS become (correlated subqueries, lib/logical/src/expr_builder_context.rs:197-300, decorrelated

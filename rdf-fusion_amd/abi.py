@@ -37,6 +37,7 @@ CAST_TARGETS = (TV_BOOLEAN, TV_INT, TV_INTEGER, TV_DECIMAL, TV_FLOAT, TV_DOUBLE)
 # plan nodes
 (NODE_DATA_SOURCE, NODE_FILTER, NODE_HASH_JOIN, NODE_CROSS_JOIN, NODE_NESTED_LOOP_JOIN,
  NODE_PROJECTION, NODE_TABLE, NODE_TOPK, NODE_UNION, NODE_CLOSURE, NODE_AGGREGATE) = range(1, 12)
+NODE_SORT = 13                  # SortExec: ORDER BY over id and value columns, ASC / DESC per key, optional fetch; no DISTINCT
 NODE_EXTEND = 12                # ProjectionExec with expressions (SPARQL Extend): the kept columns, then one value column per expression (PLAN_AGG_COLUMNS)
 # aggregate functions of NODE_AGGREGATE (ABI 4 addendum); MIN .. COUNT_DISTINCT_STAR are reserved and refused at compile
 (AGG_COUNT_STAR, AGG_COUNT, AGG_COUNT_DISTINCT, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_SAMPLE, AGG_GROUP_CONCAT,
@@ -47,6 +48,8 @@ AGG_NAMES = {AGG_COUNT_STAR: "COUNT(*)", AGG_COUNT: "COUNT", AGG_COUNT_DISTINCT:
 MAX_AGGREGATES = 8
 AGG_INPUT_EXPR = 0x80000000   # bit 31 of an aggregate's input: the low 31 bits are the pool offset of (expr_off, expr_len); SUM / AVG only
 SORT_BY_ID, SORT_BY_TERM, SORT_BY_DOUBLE = 0, 1, 2
+SORT_BY_VALUE = 3               # NODE_SORT only: ENC_SORT of the typed value a value column's entry stands for
+SORT_DESC = 0x100               # NODE_SORT, or-ed into a key's `how`: descending
 JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
 MAX_KEYS = 4
 MAX_COLUMNS = 16

@@ -46,7 +46,8 @@ struct TypedTable {
                                  // bit 2 a string expression met what the device does not restate (case mapping of a non-ASCII
                                  // string, a non-integer SUBSTR argument), bit 3 a numeric CAST met a simple literal (the lexical
                                  // parsers are not restated), bit 4 a computed column (RDFGPU_NODE_EXTEND) met a value of a kind its
-                                 // 24-byte record cannot carry
+                                 // 24-byte record cannot carry, bit 5 a SortExec key by term (RDFGPU_NODE_SORT, RDFGPU_SORT_BY_TERM) met a
+                                 // kind whose rank is not defined
 };
 
 // Value kinds on the evaluation stack.  VK_VALUE exists at compile only (check_program): COLUMN of an aggregate value column, whose u32 is
@@ -75,6 +76,7 @@ constexpr uint8_t kStrUpper = 0x10, kStrLower = 0x20;
 constexpr uint32_t kRtStringUnsupported = 4u;
 constexpr uint32_t kRtCastFromString = 8u;
 constexpr uint32_t kRtExtendKind = 16u;
+constexpr uint32_t kRtSortTerm = 32u;
 
 typedef __int128 i128_t;
 typedef unsigned __int128 u128_t;

@@ -585,6 +585,31 @@ void launch_topk_scatter(const TopkArgs& a, hipStream_t s);
 void launch_topk_select(const TopkArgs& a, hipStream_t s);
 void launch_topk_write(const TopkArgs& a, hipStream_t s);
 
+// ---- SortExec (sort.hip, RDFGPU_NODE_SORT): key records, a bitonic sort per tile in LDS, merge-path passes, a gather ----
+constexpr u32 kSortTile = 1024;          // rows one workgroup sorts in LDS
+constexpr u32 kSortMaxWords = 8;         // 64-bit words of a key record, the row index included: kSortTile of them fill 64 KB of LDS
+constexpr u32 kSortValueWords = 4;       // words of a key by value (an id key is one)
+constexpr u32 kSortMergeThreads = 256, kSortMergeItems = 4;   // a merge workgroup writes 1024 rows, every thread 4 of them
+struct SortArgs {
+  const u32* in[kMaxCols];
+  const u64* n_in_dev; u64 n_in_cap;
+  u32 n_keys, key_col[4], key_how[4], key_desc[4];   // RDFGPU_SORT_BY_*; 1 = descending
+  const rdfgpu_agg_value* key_values[4]; u64 key_n_values[4];   // a key by value: the array its column's entries index, and its length
+  u32 words;                  // words of a record = the keys' words + 1
+  u64 fetch;                  // rows kept (0: all)
+  TypedTable tt;
+  u64* rec;                   // [n_in_cap * words]: the records, row-major
+  u32* run[2];                // [n_in_cap] each: the sorted runs of row indices, alternating between the passes
+  u32* out[kMaxCols]; u32 n_out_cols; u32 proj[kMaxCols];
+  u64* n_out_dev;             // min(live rows, fetch) (null: known on the host)
+};
+u32 sort_merge_passes(u64 cap);   // ceil(log2(tiles)): 0 up to kSortTile rows
+void launch_sort_keys(const SortArgs& a, hipStream_t s);
+void launch_sort_tile(const SortArgs& a, hipStream_t s);
+void launch_sort_merge(const SortArgs& a, u32 pass, hipStream_t s);   // run[pass & 1] -> run[(pass + 1) & 1]
+void launch_sort_gather(const SortArgs& a, u32 final_run, u64 out_cap, hipStream_t s);
+void preload_tu_sort();
+
 // ---- utilities ----
 void launch_fill_u32(u32* p, u32 v, u64 n, hipStream_t s);
 void launch_mark_not_equal(const u32* col, u32 value, u32* keep, u64 n, hipStream_t s);   // keep[i] = col[i] != value

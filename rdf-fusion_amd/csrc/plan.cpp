@@ -1,5 +1,6 @@
 // plan.cpp — execution (device) of a compiled plan: the driver, timing, scans and the small operators.
-// Compilation: plan_compile.cpp; FilterExec: plan_filter.cpp; the joins: plan_join.cpp; chain fusion and the band join: plan_band.cpp.
+// Compilation: plan_compile.cpp; FilterExec: plan_filter.cpp; the joins: plan_join.cpp; chain fusion and the band join: plan_band.cpp;
+// SortExec: plan_sort.cpp.
 //
 // What replaces what (reference paths relative to the rdf-fusion tree):
 //   Plan::exec_source       DataSource::open + MemQuadIndexScanIterator::next  pattern_data_source.rs:42-58, scan.rs:104-212
@@ -148,7 +149,8 @@ const char* kernel_class_name(int kc) {
       "void rdfgpu::agg_accum_expr_kernel<false>", "void rdfgpu::agg_accum_expr_kernel<true>",
       "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel", "void rdfgpu::band_pair_bits_kernel",
       "rdfgpu::band_pair_list_count_kernel", "rdfgpu::band_pair_list_write_kernel",
-      "rdfgpu::agg_value_cols_kernel", "rdfgpu::extend_kernel"};
+      "rdfgpu::agg_value_cols_kernel", "rdfgpu::extend_kernel",
+      "rdfgpu::sort_keys_kernel", "rdfgpu::sort_tile_kernel", "rdfgpu::sort_merge_kernel", "rdfgpu::sort_gather_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -333,6 +335,7 @@ void Plan::execute() {
     if (rt & 8u) fail(RDFGPU_ERR_UNSUPPORTED, "a numeric CAST met a simple literal: the lexical forms of numbers are not parsed on the device");
     if (rt & kRtExtendKind) fail(RDFGPU_ERR_UNSUPPORTED, "a computed column (ProjectionExec with expressions) met a value that is a string, IRI, blank node, dateTime, date, time or duration: "
                                                          "its 24-byte value has no room for the language / datatype (numeric and boolean values are carried)");
+    if (rt & kRtSortTerm) fail(RDFGPU_ERR_UNSUPPORTED, "SortExec: SORT_BY_TERM over a column that is not all strings / IRIs / blank nodes");
     if (rt & 4u) fail(RDFGPU_ERR_UNSUPPORTED, "a string expression met what the device does not restate: UCASE / LCASE of a string with non-ASCII characters (Unicode case tables), "
                                                "a float / double / decimal SUBSTR position, or a comparison with a string that has no bytes on the device");
     fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with a per-row pattern: a row's pattern literal was not announced in the plan's pattern table");
@@ -437,6 +440,7 @@ DevTable Plan::exec_node(u32 idx) {
     case RDFGPU_NODE_TOPK: t = exec_topk(nd); break;
     case RDFGPU_NODE_AGGREGATE: t = exec_aggregate(nd); break;
     case RDFGPU_NODE_EXTEND: t = exec_extend(nd); break;
+    case RDFGPU_NODE_SORT: t = exec_sort(nd); break;
     case RDFGPU_NODE_CLOSURE: t = exec_closure(nd); break;
     case RDFGPU_NODE_UNION: t = exec_union(nd); break;
     case RDFGPU_NODE_TABLE: t = exec_table(nd); break;

@@ -64,6 +64,7 @@ struct NodeInfo {
   rdfgpu_agg_value* values[RDFGPU_MAX_AGGREGATES] = {}; u64 n_values = 0, values_run = 0;   // AggregateExec / EXTEND: the value arrays (scratch) of execution `values_run` (Plan::run) and their length = its groups / rows
   const u64* n_values_dev = nullptr;              // EXTEND over an input counted on the device only: n_values is the capacity while the plan runs (no entry exceeds the rows written) and becomes this count when it has come back
   BandHistory band;                            // the band join based on this node, if there was one
+  u32 sort_words = 0;                          // SortExec: 64-bit words of its key record, the row index included (compile_sort)
 };
 struct SpecCheck { NodeInfo* node; u32 counter; bool left_join; };   // counter = n_out slot, counter+1 = overflow flag
 
@@ -161,6 +162,7 @@ enum KernelClass {
   KC_BAND_PAIR_LIST_COUNT, KC_BAND_PAIR_LIST_WRITE,   // .. and of the list of their set bits
   KC_AGG_VALUE_COLS,                              // agg_value_cols_kernel: an AggregateExec's value columns (RDFGPU_PLAN_AGG_COLUMNS)
   KC_EXTEND,                                      // extend_kernel: the computed columns of a ProjectionExec with expressions (RDFGPU_NODE_EXTEND)
+  KC_SORT_KEYS, KC_SORT_TILE, KC_SORT_MERGE, KC_SORT_GATHER,   // SortExec (sort.hip, RDFGPU_NODE_SORT): records, tile sort, one launch per merge pass, gather
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
@@ -268,6 +270,7 @@ struct Plan {
   DevTable exec_semi_join(NodeInfo& nd);
   DevTable exec_aggregate(NodeInfo& nd);
   DevTable exec_extend(NodeInfo& nd);
+  DevTable exec_sort(NodeInfo& nd);
   DevTable apply_filter(NodeInfo& nd, const DevTable& in);   // its routes:
   bool filter_string_verdicts(const NodeInfo& nd, const DevTable& in, FilterArgs& a); bool filter_run_copy(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape);
   void filter_streamed(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape); void filter_single_pass(const NodeInfo& nd, const DevTable& in, FilterArgs& a, int shape);

@@ -446,6 +446,35 @@ void compile_extend(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   for (u32 q = 0; q < k; q++) nd.origin[nd.n_proj + q] = ValueOrigin{(int)i, q, true};
 }
 
+// SortExec (RDFGPU_NODE_SORT): the keys typed against the input's columns — an id form reads object ids, BY_VALUE a value column — the width
+// of the key record they make (sort.hip: one 64-bit word per id key, kSortValueWords per value key, one for the row index), the projection.
+void compile_sort(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
+  NodeInfo& nd = plan->nodes[i];
+  const rdfgpu_plan_node& r = nd.d;
+  const NodeInfo& c = child(plan, i, r.left, "input");
+  if (r.n_keys < 1 || r.n_keys > RDFGPU_MAX_KEYS) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: SortExec with %u sort keys (1 to %u)", i, r.n_keys, RDFGPU_MAX_KEYS);
+  u32 words = 1;
+  for (u32 k = 0; k < r.n_keys; k++) {
+    const u32 col = r.left_keys[k], how = r.right_keys[k] & ~RDFGPU_SORT_DESC;
+    if (col >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: sort key column %u out of range", i, col);
+    if (how > RDFGPU_SORT_BY_VALUE) fail(RDFGPU_ERR_INVALID, "node %u: unknown sort mode %u", i, r.right_keys[k]);
+    if (how == RDFGPU_SORT_BY_VALUE) {
+      if (!plan->agg_columns) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: SortExec key %u sorts a value column (RDFGPU_SORT_BY_VALUE): value columns exist only in a plan compiled with RDFGPU_PLAN_AGG_COLUMNS", i, k);
+      if (c.origin[col].node < 0) fail(RDFGPU_ERR_INVALID, "node %u: SortExec key %u: RDFGPU_SORT_BY_VALUE of column %u, which holds object ids (RDFGPU_SORT_BY_ID / _BY_TERM / _BY_DOUBLE sort those)", i, k, col);
+      words += kSortValueWords;
+    } else {
+      refuse_value_column(c.origin[col], i, "SortExec key by id / term / double", col);   // (RDFGPU_SORT_BY_VALUE sorts it)
+      words += 1;
+    }
+  }
+  if (words > kSortMaxWords)
+    fail(RDFGPU_ERR_UNSUPPORTED, "node %u: SortExec key record of %u 64-bit words (at most %u: a tile of %u records has to fit 64 KB of LDS; a key by value takes %u words, any other one, the row index one)",
+         i, words, kSortMaxWords, kSortTile, kSortValueWords);
+  nd.sort_words = words;
+  InputSchema in; in.append(c);
+  load_projection(nd, d, in, "SortExec");   // a projected value column keeps its origin: its entries leave unchanged
+}
+
 // Every node of the description, in order (an input precedes its consumer): checked, typed, its program and projection loaded.  Only a
 // DataSourceExec touches the store.
 void compile_nodes(Plan* plan, const rdfgpu_plan_desc* d) {
@@ -504,6 +533,7 @@ void compile_nodes(Plan* plan, const rdfgpu_plan_desc* d) {
       case RDFGPU_NODE_TOPK: compile_topk(plan, d, i); break;           // DISTINCT + TopK(fetch) per group, ..Q5 (Execution Plan).snap:5-9
       case RDFGPU_NODE_AGGREGATE: compile_aggregate(plan, d, i); break;   // AggregateExec(mode=Single), ..Business Intelligence - Q8 (Execution Plan).snap
       case RDFGPU_NODE_EXTEND: compile_extend(plan, d, i); break;         // ProjectionExec: expr=[.., DIV(..) as ratio], ..Business Intelligence - Q3 (Execution Plan).snap
+      case RDFGPU_NODE_SORT: compile_sort(plan, d, i); break;             // SortExec: TopK(fetch=10), expr=[.. DESC, .. ASC], ..Business Intelligence - Q3 (Execution Plan).snap:6
       default: fail(RDFGPU_ERR_INVALID, "node %u: unknown kind %u", i, r.kind);
     }
   }

@@ -181,6 +181,7 @@ void preload_code_objects() {
     preload_tu_semi_join();
     preload_tu_aggregate();
     preload_tu_extend();
+    preload_tu_sort();
     preload_tu_join_fs0();
     preload_tu_join_fs1();
     preload_tu_join_fs2();

@@ -405,7 +405,7 @@ class PlanBuilder:
 
     def _value_columns(self, node, width):
         """Which output columns of `node` carry aggregate values when they are columns: an AggregateExec's aggregates, and whatever a
-        projection, filter or join hands on of its inputs' (a semi / anti join: of its left input's)."""
+        projection, filter, sort or join hands on of its inputs' (a semi / anti join: of its left input's)."""
         if node.kind == abi.NODE_AGGREGATE:
             return [False] * (width - node.table_cols) + [True] * node.table_cols
         if node.kind in (abi.NODE_DATA_SOURCE, abi.NODE_TABLE) or node.left < 0:
@@ -499,6 +499,27 @@ class PlanBuilder:
         for i, (c, how) in enumerate(keys):
             n.left_keys[i], n.right_keys[i] = c, how
         return self._push(n, self._proj(n, projection, self.width[left]), self._projected(self.names[left], projection))
+
+    def sort(self, child, keys, fetch=None, projection=None):
+        """SortExec (abi.NODE_SORT): ORDER BY `keys` = [(column, how, descending), ...] (1 to 4), `how` = abi.SORT_BY_ID / SORT_BY_TERM /
+        SORT_BY_DOUBLE over an object-id column or abi.SORT_BY_VALUE over a value column; `fetch` keeps the first rows only
+        (`SortExec: TopK(fetch=10)`; None: all).  No DISTINCT; rows equal on every key keep their input order.  A value column stays a
+        value column of the output."""
+        keys = [(int(c), int(how), bool(desc)) for c, how, desc in keys]
+        n = abi.PlanNode(kind=abi.NODE_SORT, left=child, right=-1, n_keys=len(keys), table_cols=0 if fetch is None else int(fetch))
+        for i, (c, how, desc) in enumerate(keys[:abi.MAX_KEYS]):      # (more than MAX_KEYS is the library's to refuse)
+            n.left_keys[i], n.right_keys[i] = c, how | (abi.SORT_DESC if desc else 0)
+        return self._push(n, self._proj(n, projection, self.width[child]), self._projected(self.names[child], projection))
+
+    def sparql_order_by(self, child, keys, limit=None):
+        """ORDER BY .. [LIMIT limit] over `child`: keys = [(column, descending), ...] or [(column, descending, how), ...].  A value column
+        (an aggregate, a computed column) sorts BY_VALUE; an object-id column by `how` (default abi.SORT_BY_ID)."""
+        full = []
+        for key in keys:
+            c, desc = int(key[0]), bool(key[1])
+            how = abi.SORT_BY_VALUE if self.values[child][c] else (int(key[2]) if len(key) > 2 else abi.SORT_BY_ID)
+            full.append((c, how, desc))
+        return self.sort(child, full, fetch=limit)
 
     def union(self, left, right, projection=None):
         """UnionExec: bag union of two inputs with the same columns (SPARQL UNION; Q4 (Execution Plan).snap:11)."""
@@ -808,6 +829,12 @@ def explain(pb, root, choose_index=None, agg_columns=False):
                                                           and ex[j - 1].u < len(full) and pb.values[n.left][ex[j - 1].u])]
                 items.append(f"{format_expr(ex, full)} as {pb.names[i][len(kept) + q]}")
             lines.append(f"{pad}ProjectionExec: expr=[{', '.join(items)}]")
+            walk(n.left, depth + 1)
+            return
+        if n.kind == abi.NODE_SORT:         # `SortExec: TopK(fetch=10), expr=[ratio@3 DESC, product@0 ASC]`
+            full = pb.names[n.left]
+            keys = ", ".join(f"{full[n.left_keys[k]]}@{n.left_keys[k]} {'DESC' if n.right_keys[k] & abi.SORT_DESC else 'ASC'}" for k in range(min(n.n_keys, abi.MAX_KEYS)))
+            lines.append(f"{pad}SortExec: {f'TopK(fetch={n.table_cols}), ' if n.table_cols else ''}expr=[{keys}]{proj(i, full)}")
             walk(n.left, depth + 1)
             return
         name = {abi.NODE_PROJECTION: "ProjectionExec", abi.NODE_TOPK: "SortExec: TopK", abi.NODE_UNION: "UnionExec",

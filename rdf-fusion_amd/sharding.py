@@ -170,7 +170,9 @@ def run_stages(stages, execute, repartition):
     """Plans chained through hash repartitions (lubm.q9_sharded_stages): stage k's output, re-sharded by `key column`, is
     stage k + 1's bound table 0.  `repartition(table, key_col) -> table`."""
     table = None
-    for desc, key_col in stages:
+    for k, (desc, key_col) in enumerate(stages):
+        if any(n.kind == abi.NODE_SORT for n in desc._nodes[:desc.desc.n_nodes]):
+            raise ValueError(f"stage {k}: a SortExec (abi.NODE_SORT) in the sharded path: a rank sorts its own rows only, and the exchange keeps no order")
         table = execute(desc, [] if table is None else [table])
         if key_col is not None:
             table = repartition(table, key_col)
