@@ -340,6 +340,22 @@ enum {
                                  Named / blank nodes, language-tagged strings, dateTime / date / time, durations, other literals and null =>
                                  error.  A SIMPLE LITERAL would have to be parsed: such a row fails the execute with RDFGPU_ERR_UNSUPPORTED
                                  (the lexical parsers are not restated; never answered differently).                                  */
+  RDFGPU_EX_CAST_STRING = 46, /* ID -> TV(simple literal)  xsd:string(ENC_TV(id)), scalar/conversion/cast_string.rs:51-76.  Takes the object id,
+                                 as STR does (ENC_TV keeps the id for strings only); the host lowers xsd:string(ENC_TV(col)) to it.  A named
+                                 node, a simple literal, a language-tagged string and an other literal (`"12.5"^^bsbm:USD`) give their lexical
+                                 form without a language: a view of the store's heap, nothing is copied.  A blank node, null, id 0 and an id
+                                 beyond the table => error.  Booleans, numbers, dateTime / date / time and durations are FORMATTED by the
+                                 reference (format_value / to_string): such a row fails the execute with RDFGPU_ERR_UNSUPPORTED.  Needs
+                                 rdfgpu_store_set_strings; a value column or a computed typed value is a kind error.                      */
+  RDFGPU_EX_CAST_LEX = 47,    /* TV -> TV  RDFGPU_EX_CAST (same `u`, same targets) that PARSES a simple literal — a dictionary string, a window,
+                                 a case-mapped view or an RDFGPU_EX_LIT_STR constant, without a language — as the reference's FromStr impls do:
+                                 boolean exactly true / 1 / false / 0 (boolean.rs:108-115); int / integer i32::from_str / i64::from_str (an
+                                 optional sign, digits, checked range); decimal Decimal::from_str (decimal.rs:496-568); float / double
+                                 f32::from_str / f64::from_str: Rust's grammar (no whitespace; inf / infinity / nan in any case), correctly
+                                 rounded with ONE rounding to the target — Clinger's exact case, else Eisel-Lemire over the first 19
+                                 significant digits (w and w + 1 must agree when digits were dropped).  What does not parse => error.  A
+                                 literal Eisel-Lemire cannot decide (a half-way neighbourhood) and a signed NaN fail the execute with
+                                 RDFGPU_ERR_UNSUPPORTED; never answered differently.  Every other operand: exactly RDFGPU_EX_CAST.        */
   RDFGPU_EX__COUNT
 };
 

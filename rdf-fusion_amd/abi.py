@@ -31,7 +31,7 @@ NT_IRI, NT_BNODE, NT_SIMPLE, NT_LANG, NT_TYPED = 1, 2, 3, 4, 5   # rdfgpu_ntripl
  EX_EBV, EX_ID_EQ, EX_ID_NEQ, EX_AND, EX_OR, EX_NOT, EX_IS_COMPATIBLE, EX_BOUND, EX_BOOL_AS_TV,
  EX_LIT_BOOL, EX_NEQ, EX_REGEX, EX_CONTAINS, EX_STRSTARTS, EX_STRENDS, EX_LANG_IN, EX_REGEX_VAR,
  EX_STR, EX_LIT_STR, EX_STRLEN, EX_SUBSTR, EX_UCASE, EX_LCASE, EX_STRBEFORE, EX_STRAFTER,
- EX_MUL, EX_DIV, EX_NEG, EX_PLUS, EX_ABS, EX_ROUND, EX_CEIL, EX_FLOOR, EX_CAST) = range(1, 46)
+ EX_MUL, EX_DIV, EX_NEG, EX_PLUS, EX_ABS, EX_ROUND, EX_CEIL, EX_FLOOR, EX_CAST, EX_CAST_STRING, EX_CAST_LEX) = range(1, 48)
 CAST_TARGETS = (TV_BOOLEAN, TV_INT, TV_INTEGER, TV_DECIMAL, TV_FLOAT, TV_DOUBLE)   # EX_CAST's `u`; any other tag is refused at compile
 
 # plan nodes

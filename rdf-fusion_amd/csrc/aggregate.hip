@@ -151,7 +151,7 @@ __device__ __forceinline__ const u32* agg_col(const AggArgs& a, u32 c) {
 
 // EXPR: some SUM / AVG reads an expression (RDFGPU_AGG_INPUT_EXPR): that aggregate's value is its program's, evaluated by the VM.  A node
 // whose aggregates are all plain columns runs the instantiation without the VM in it.
-template <bool LDS, bool EXPR>
+template <bool LDS, bool EXPR, bool LEX = false>
 __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
   extern __shared__ unsigned long long lacc[];
   const u32 tid = threadIdx.x, lane = tid & 63;
@@ -184,7 +184,7 @@ __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
       if (fn == RDFGPU_AGG_COUNT_DISTINCT) { acc_add(acc, w, id != 0 && dset_insert(a.dset[i], a.dset_mask, g, id), r); continue; }
       // SUM / AVG: ENC_TV of the id, one 16-byte gather — or the value of the aggregate's program (the branch is uniform)
       Val v;
-      if constexpr (EXPR) v = a.prog[i] ? eval_program(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
+      if constexpr (EXPR) v = a.prog[i] ? eval_program<LEX>(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
       else v = enc_tv(a.tt, id);
       const int k = num_kind(v.tag);
       u32 kind = k == NK_NONE ? kKindOther : k == NK_DECIMAL ? kKindDec : k == NK_FLOAT ? kKindFloat : k == NK_DOUBLE ? kKindDouble : kKindInt;
@@ -220,6 +220,7 @@ __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
 
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) { agg_accum_rows<LDS, false>(a); }
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_expr_kernel(const AggArgs a) { agg_accum_rows<LDS, true>(a); }
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_lex_kernel(const AggArgs a) { agg_accum_rows<LDS, true, true>(a); }   // a.exprs == 2: a program holds RDFGPU_EX_CAST_LEX
 
 // ---- pass 3 ---------------------------------------------------------------------------------------------------------------------
 // 256-bit two's complement, enough for sum(limb_i * 2^(32 i)) over 2^32 rows and for the integer part scaled by 10^18.
@@ -335,11 +336,13 @@ void launch_agg_accum(const AggArgs& a, hipStream_t s) {
     const size_t lds = (size_t)a.n_words * a.n_groups * sizeof(unsigned long long);
     if (lds > kAggLdsBytes) fail(RDFGPU_ERR_INVALID, "aggregate: %zu bytes of LDS partials", lds);
     if (g > 512) g = 512;   // every workgroup zeroes and merges all partials: enough of them to fill the part, not one per tile
-    if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+    if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_lex_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+    else if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
     else hipLaunchKernelGGL(agg_accum_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
   } else {
     if (g > 16384) g = 16384;
-    if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+    if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_lex_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+    else if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
     else hipLaunchKernelGGL(agg_accum_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
   }
   RDFGPU_HIP(hipGetLastError());

@@ -11,6 +11,8 @@
 //   NEG/PLUS/ABS  unary_minus.rs, unary_plus.rs, abs.rs (lib/model/src/xsd/numeric.rs:20-38)
 //   ROUND/CEIL/FLOOR  round.rs:48-60, ceil.rs:48-60, floor.rs (decimal.rs:211-254; f32 / f64 round, ceil, floor)
 //   CAST     scalar/conversion/cast_{boolean,int,integer,decimal,float,double}.rs:48-62 and the From / TryFrom impls they call
+//   CAST_STRING  scalar/conversion/cast_string.rs:51-76 (the lexical form of a term that has one as written: a view, nothing copied)
+//   CAST_LEX     the same casts with the simple-literal arm: the FromStr impls of lib/model/src/xsd, restated in lex_parse.hpp
 //   EBV      lib/functions/src/builtin/native/effective_boolean_value.rs:99-119
 //   AND/OR   SQL three-valued logic on native booleans (lib/logical/src/expr_builder_context.rs:393-434)
 #pragma once
@@ -19,6 +21,7 @@
 
 #include "../../include/rdfgpu.h"
 #include "regex_prog.hpp"
+#include "lex_parse.hpp"
 
 namespace rdfgpu {
 
@@ -47,7 +50,8 @@ struct TypedTable {
                                  // string, a non-integer SUBSTR argument), bit 3 a numeric CAST met a simple literal (the lexical
                                  // parsers are not restated), bit 4 a computed column (RDFGPU_NODE_EXTEND) met a value of a kind its
                                  // 24-byte record cannot carry, bit 5 a SortExec key by term (RDFGPU_NODE_SORT, RDFGPU_SORT_BY_TERM) met a
-                                 // kind whose rank is not defined
+                                 // kind whose rank is not defined, bit 6 a lexical cast (RDFGPU_EX_CAST_LEX) met a literal the device
+                                 // cannot decide: a float / double at a rounding boundary that Eisel-Lemire declines, or a signed NaN
 };
 
 // Value kinds on the evaluation stack.  VK_VALUE exists at compile only (check_program): COLUMN of an aggregate value column, whose u32 is
@@ -77,6 +81,7 @@ constexpr uint32_t kRtStringUnsupported = 4u;
 constexpr uint32_t kRtCastFromString = 8u;
 constexpr uint32_t kRtExtendKind = 16u;
 constexpr uint32_t kRtSortTerm = 32u;
+constexpr uint32_t kRtLexParse = 64u;
 
 typedef __int128 i128_t;
 typedef unsigned __int128 u128_t;
@@ -500,20 +505,24 @@ __device__ __forceinline__ uint32_t tv_ebv(const Val& v) {
 constexpr uint32_t kRegexNeedsUnicode = 0xFFFFFFFFu;
 // The bytes of a string value: false when it has none on the device (not a string; an id without a lexical form in the heap).
 struct StrBytes { const uint8_t* p; uint64_t len; uint32_t xf; };   // xf: 0 as stored, 1 ASCII upper, 2 ASCII lower
-__device__ __forceinline__ bool str_bytes(const ExprProgram* prog, const TypedTable& t, const Val& v, StrBytes& s) {
+__device__ __forceinline__ bool str_bytes_of(const uint8_t* str_consts, const RegexProg* regex, const uint64_t* str_off, const uint8_t* heap, uint64_t n_str_ids, const Val& v, StrBytes& s) {
   if (v.tag != RDFGPU_TV_STRING) return false;
   s.xf = (v.flags & kStrUpper) ? 1u : (v.flags & kStrLower) ? 2u : 0u;
   if (v.pad == 2) {
-    if (prog == nullptr || prog->str_consts == nullptr) return false;
-    s.p = prog->str_consts + prog->regex[(uint32_t)v.hi].first + ((uint64_t)v.lo >> 32); s.len = (uint32_t)v.lo;
+    if (str_consts == nullptr) return false;
+    s.p = str_consts + regex[(uint32_t)v.hi].first + ((uint64_t)v.lo >> 32); s.len = (uint32_t)v.lo;
     return true;
   }
   const uint64_t id = (uint64_t)(uint32_t)v.hi;
-  if (t.str_off == nullptr || id == 0 || id >= t.n_str_ids) return false;   // (a string literal of the plan given by rank only has no bytes here)
-  const uint64_t b0 = t.str_off[id];
-  if (v.pad == 0) { s.p = t.heap + b0; s.len = t.str_off[id + 1] - b0; }
-  else { s.p = t.heap + b0 + ((uint64_t)v.lo >> 32); s.len = (uint32_t)v.lo; }
+  if (str_off == nullptr || id == 0 || id >= n_str_ids) return false;   // (a string literal of the plan given by rank only has no bytes here)
+  const uint64_t b0 = str_off[id];
+  if (v.pad == 0) { s.p = heap + b0; s.len = str_off[id + 1] - b0; }
+  else { s.p = heap + b0 + ((uint64_t)v.lo >> 32); s.len = (uint32_t)v.lo; }
   return true;
+}
+__device__ __forceinline__ bool str_bytes(const ExprProgram* prog, const TypedTable& t, const Val& v, StrBytes& s) {
+  if (prog == nullptr) return v.pad == 2 ? false : str_bytes_of(nullptr, nullptr, t.str_off, t.heap, t.n_str_ids, v, s);
+  return str_bytes_of(prog->str_consts, prog->regex, t.str_off, t.heap, t.n_str_ids, v, s);
 }
 __device__ __forceinline__ uint8_t str_at(const StrBytes& s, uint64_t i) {
   uint8_t b = s.p[i];
@@ -643,6 +652,77 @@ __device__ __forceinline__ Val tv_strpart(const ExprProgram* prog, const TypedTa
   return after ? val_str_view(kind, (uint32_t)a.hi, base + pos + y.len, x.len - pos - y.len, a.aux, cs)
                : val_str_view(kind, (uint32_t)a.hi, base, pos, a.aux, cs);
 }
+// CAST_STRING, cast_string.rs:51-76, over an object id (enc_tv keeps the id for strings only): a named node, a simple literal, a
+// language-tagged string and an other literal give their lexical form as a simple literal — a view of the heap; a blank node and null are
+// the error value; booleans, numbers, dateTime / date / time and durations are FORMATTED there (format_value / to_string), bytes a view
+// cannot express: the plan's run-time error.
+__device__ __forceinline__ Val tv_cast_string(const TypedTable& t, uint32_t id) {
+  if (id == 0 || (uint64_t)id >= t.n_ids) return val_tv_null();
+  const uint8_t tag = (uint8_t)(reinterpret_cast<const uint32_t*>(t.tv + id)[3] & 0xffu);
+  if (tag == RDFGPU_TV_NULL || tag == RDFGPU_TV_BLANK_NODE) return val_tv_null();
+  if (tag != RDFGPU_TV_NAMED_NODE && tag != RDFGPU_TV_STRING && tag != RDFGPU_TV_OTHER) {
+    if (t.rt_error) atomicOr(t.rt_error, kRtStringUnsupported);
+    return val_tv_null();
+  }
+  return tv_str_of_id(t, id);
+}
+struct LexAt {
+  const uint8_t* p;
+  __device__ __forceinline__ uint8_t operator()(uint32_t i) const { return p[i]; }
+};
+// The cast of a simple literal's bytes is two out-of-line leaves, and the calling kernel carries only the resolution of the bytes
+// (str_bytes) and the calls: what a hosting kernel pays is the registers a leaf writes and whatever is inlined around the call, so the
+// leaves are kept under what tv_unary_numeric writes and even the run-time flags are raised inside them.  They take the resolved bytes,
+// not the program or the typed table (an address of those handed to a call would pin the kernel's copy in scratch).
+// lex_words_bytes: the literals that are words — the case-sensitive boolean (of the bytes as a UCASE / LCASE view maps them) and inf /
+// infinity / nan of a float / double; p == nullptr: the operand has no lexical form on the device.  pad = LEX_NOT_SPECIAL: a number.
+// lex_number_bytes: int / integer / decimal and the numbers of float / double, from the bytes as stored: an ASCII case mapping cannot
+// change what those grammars answer (digits, signs, '.', 'e' / 'E').
+static __device__ __noinline__ Val lex_words_bytes(const uint8_t* p, uint32_t len, uint32_t xf, uint32_t target, uint32_t* rt_error) {
+  Val r = val_tv_null();
+  if (p == nullptr) { if (rt_error) atomicOr(rt_error, kRtStringUnsupported); return r; }   // refused loudly (check_program refuses a rank-only literal at compile)
+  if (len >= kLexMaxLen) { if (rt_error) atomicOr(rt_error, kRtLexParse); return r; }        // the parsers count in 32 bits: declined
+  int st = LEX_NOT_SPECIAL;
+  uint64_t bits = 0;
+  if (target == RDFGPU_TV_BOOLEAN) {
+    StrBytes s; s.p = p; s.len = len; s.xf = xf;
+    bool b = false;
+    st = lex_parse_boolean([&](uint32_t i) { return str_at(s, i); }, len, b);
+    bits = b;
+  } else if (target == RDFGPU_TV_FLOAT) st = lex_parse_float_special<true>(LexAt{p}, len, bits);
+  else if (target == RDFGPU_TV_DOUBLE) st = lex_parse_float_special<false>(LexAt{p}, len, bits);
+  if (st == LEX_DECLINED && rt_error) atomicOr(rt_error, kRtLexParse);
+  if (st == LEX_OK) { r.tag = (uint8_t)target; r.lo = (int64_t)bits; }
+  else if (st == LEX_NOT_SPECIAL) r.pad = LEX_NOT_SPECIAL;
+  return r;
+}
+static __device__ __noinline__ Val lex_number_bytes(const uint8_t* p, uint32_t len, uint32_t target, uint32_t* rt_error) {
+  const LexAt at{p};
+  Val r = val_tv_null();
+  int st = LEX_ERROR;
+  switch (target) {
+    case RDFGPU_TV_INT: { long long v = 0; st = lex_parse_i64(at, len, (long long)INT32_MIN, (long long)INT32_MAX, v); r.lo = v; break; }
+    case RDFGPU_TV_INTEGER: { long long v = 0; st = lex_parse_i64(at, len, INT64_MIN, INT64_MAX, v); r.lo = v; break; }
+    case RDFGPU_TV_DECIMAL: { uint64_t lo = 0, hi = 0; st = lex_parse_decimal(at, len, lo, hi); r.lo = (int64_t)lo; r.hi = (int64_t)hi; break; }
+    case RDFGPU_TV_FLOAT: { uint64_t bits = 0; st = lex_parse_float_number<true>(at, len, bits); r.lo = (int64_t)bits; break; }
+    case RDFGPU_TV_DOUBLE: { uint64_t bits = 0; st = lex_parse_float_number<false>(at, len, bits); r.lo = (int64_t)bits; break; }
+    default: break;
+  }
+  if (st == LEX_DECLINED && rt_error) atomicOr(rt_error, kRtLexParse);
+  if (st != LEX_OK) return val_tv_null();
+  r.tag = (uint8_t)target;
+  return r;
+}
+// CAST_LEX: RDFGPU_EX_CAST on every operand but a simple literal (a dictionary string, a window, a case-mapped view or a constant with
+// bytes, no language), whose bytes are parsed as the reference's FromStr impls do.  (eval_program sends every other operand to tv_cast.)
+__device__ __forceinline__ Val tv_cast_lex(const Val& a, uint32_t target, const ExprProgram* prog, const TypedTable& t) {
+  StrBytes s;
+  if (!str_bytes(prog, t, a, s)) { s.p = nullptr; s.len = 0; s.xf = 0; }
+  const uint32_t len = s.len < kLexMaxLen ? (uint32_t)s.len : kLexMaxLen;   // (kLexMaxLen: 256 MB or more, which the words leaf declines)
+  Val r = lex_words_bytes(s.p, len, s.xf, target, t.rt_error);
+  if (r.pad == LEX_NOT_SPECIAL) r = lex_number_bytes(s.p, len, target, t.rt_error);
+  return r;
+}
 // two strings of which at least one is a view: `str` order of their bytes (typed_value.rs:184-196 compares the values), same language only
 __device__ __forceinline__ bool str_is_view(const Val& v) { return v.tag == RDFGPU_TV_STRING && (v.pad != 0 || (v.flags & (kStrUpper | kStrLower))); }
 __device__ __forceinline__ int tv_cmp_string_views(const ExprProgram* prog, const TypedTable& t, const Val& a, const Val& b) {
@@ -667,7 +747,15 @@ __device__ __forceinline__ Val tv_regex_var(const RegexProg* progs, uint32_t fir
   return val_tv_null();
 }
 
-template <class ColFn>
+// A program that holds RDFGPU_EX_CAST_LEX: its host launches the instantiation of its kernel that compiles the case in (LEX = true).
+inline bool program_has_lex(const ExprProgram& pr) {
+  for (uint32_t i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_CAST_LEX) return true;
+  return false;
+}
+// LEX: whether `case RDFGPU_EX_CAST_LEX` is compiled in.  The case — the byte resolution and the calls around the leaves — costs a hosting
+// kernel one or two registers, which moved kernels that sit on an occupancy step; so every host exists twice, and the instantiation
+// without the case is, register for register, the kernel it was before the op existed.  Plans pick by program_has_lex / NodeInfo::lex.
+template <bool LEX = false, class ColFn>
 __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const TypedTable& tt, ColFn col) {
   Val st[kMaxStack];
   int sp = 0;
@@ -693,6 +781,11 @@ __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const Typed
       case RDFGPU_EX_NEG: case RDFGPU_EX_PLUS: case RDFGPU_EX_ABS: case RDFGPU_EX_ROUND: case RDFGPU_EX_CEIL: case RDFGPU_EX_FLOOR:
         v = tv_unary_numeric(st[--sp], e.op); break;
       case RDFGPU_EX_CAST: v = tv_cast(st[--sp], e.u, tt.rt_error); break;
+      case RDFGPU_EX_CAST_LEX:   // (a simple literal is parsed; every other operand is a CAST)
+        if constexpr (LEX) { const Val a = st[--sp]; v = a.tag == RDFGPU_TV_STRING && a.aux == 0 ? tv_cast_lex(a, e.u, &prog, tt) : tv_cast(a, e.u, tt.rt_error); }
+        else v = val_bool(2);     // (not reached: a program with the op runs in a LEX instantiation)
+        break;
+      case RDFGPU_EX_CAST_STRING: v = tv_cast_string(tt, (uint32_t)st[--sp].lo); break;
       case RDFGPU_EX_EBV: v = val_bool(tv_ebv(st[--sp])); break;
       case RDFGPU_EX_REGEX: v = tv_regex(prog.regex[e.u], tt, st[--sp], -1, &prog); break;
       case RDFGPU_EX_REGEX_VAR: { const Val pat = st[--sp]; const Val val = st[--sp]; v = tv_regex_var(prog.regex, e.u, (uint32_t)e.lo, tt, val, pat, &prog); break; }

@@ -31,7 +31,8 @@ __device__ __forceinline__ const u32* extend_col(const ExtendArgs& a, u32 c) {
   return p;
 }
 
-__global__ __launch_bounds__(kExtendBlock) void extend_kernel(const ExtendArgs a) {
+template <bool LEX>
+__device__ __forceinline__ void extend_rows(const ExtendArgs& a) {
   __shared__ __attribute__((aligned(16))) unsigned long long rec[(kExtendBlock / 64) * kWaveWords];   // 1536 B per wave
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const u64 n = live_rows(a.n_dev, a.cap);
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(kExtendBlock) void extend_kernel(const ExtendArgs a
   const u64 wave_live = wave_row < n ? (n - wave_row < 64 ? n - wave_row : 64) : 0;   // its live rows
   unsigned long long* const mine = rec + wave * kWaveWords;
   for (u32 q = 0; q < a.n_exprs; q++) {
-    Val v = eval_program(*a.prog[q], a.tt, [&](u32 c) { return valid ? extend_col(a, c)[row] : 0u; });
+    Val v = eval_program<LEX>(*a.prog[q], a.tt, [&](u32 c) { return valid ? extend_col(a, c)[row] : 0u; });
     const u8 t = v.tag;
     const bool carried = t == RDFGPU_TV_INT || t == RDFGPU_TV_INTEGER || t == RDFGPU_TV_DECIMAL || t == RDFGPU_TV_FLOAT ||
                          t == RDFGPU_TV_DOUBLE || t == RDFGPU_TV_BOOLEAN;
@@ -65,10 +66,13 @@ __global__ __launch_bounds__(kExtendBlock) void extend_kernel(const ExtendArgs a
     __syncthreads();                                             // the next column's records reuse `rec`
   }
 }
+__global__ __launch_bounds__(kExtendBlock) void extend_kernel(const ExtendArgs a) { extend_rows<false>(a); }
+__global__ __launch_bounds__(kExtendBlock) void extend_lex_kernel(const ExtendArgs a) { extend_rows<true>(a); }   // RDFGPU_EX_CAST_LEX compiled into the VM
 
-void launch_extend(const ExtendArgs& a, hipStream_t s) {
+void launch_extend(const ExtendArgs& a, bool lex, hipStream_t s) {
   const u64 g = (a.cap + kExtendBlock - 1) / kExtendBlock;       // (cap < 2^32 - 1: Plan::exec_extend)
-  hipLaunchKernelGGL(extend_kernel, dim3((unsigned)(g ? g : 1)), dim3(kExtendBlock), 0, s, a);
+  if (lex) hipLaunchKernelGGL(extend_lex_kernel, dim3((unsigned)(g ? g : 1)), dim3(kExtendBlock), 0, s, a);   // (a program holds RDFGPU_EX_CAST_LEX)
+  else hipLaunchKernelGGL(extend_kernel, dim3((unsigned)(g ? g : 1)), dim3(kExtendBlock), 0, s, a);
   RDFGPU_HIP(hipGetLastError());
 }
 

@@ -181,6 +181,7 @@ __device__ __forceinline__ bool filter_pred_value(const FilterArgs& a, u32 v) {
 // this chip, so per-1024-row reservations would cap a 5.5 M-row filter at ~60 us; pass 2 turns the masks
 // into wave ballots and writes each round's survivors contiguously.
 constexpr int kFilterMaxIters = 16;
+constexpr int kFilterVmLex = 5;
 template <int SHAPE>
 __global__ __launch_bounds__(kBlock) void filter_kernel(const FilterArgs a) {
   __shared__ u32 wave_tot[kBlock / 64];
@@ -192,14 +193,15 @@ __global__ __launch_bounds__(kBlock) void filter_kernel(const FilterArgs a) {
   const u64 base = (u64)blockIdx.x * chunk;
   if (base >= nv) return;                           // uniform per workgroup
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const u32* pcol = (SHAPE != 0) ? a.in[a.prog.nodes[0].u] : nullptr;
+  constexpr bool VM = SHAPE == 0 || SHAPE == kFilterVmLex;   // (kFilterVmLex: the generic VM with RDFGPU_EX_CAST_LEX compiled in)
+  const u32* pcol = !VM ? a.in[a.prog.nodes[0].u] : nullptr;
   unsigned long long bits = 0;
 #pragma unroll 2
   for (u32 it = 0; it < a.iters; it++) {
     const u64 v0 = base + (u64)it * kTile + (u64)threadIdx.x * 4;
     if (v0 >= nv) break;
     u32 val[4] = {0, 0, 0, 0};
-    if constexpr (SHAPE != 0) {
+    if constexpr (!VM) {
       if (a.vec_ok && v0 >= mis && v0 + 4 <= nv) {  // aligned 16-byte load, entirely inside the column
         const uint4 q = *reinterpret_cast<const uint4*>(pcol + (v0 - mis));
         val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
@@ -213,8 +215,8 @@ __global__ __launch_bounds__(kBlock) void filter_kernel(const FilterArgs a) {
       const u64 v = v0 + r;
       bool keep = v >= mis && v < nv;
       if (keep) {
-        if constexpr (SHAPE != 0) keep = filter_pred_value<SHAPE>(a, val[r]);
-        else if (a.prog.n) { const u64 row = v - mis; const Val res = eval_program(a.prog, a.tt, [&](u32 c) { return a.in[c][row]; }); keep = res.lo == 1; }
+        if constexpr (!VM) keep = filter_pred_value<SHAPE>(a, val[r]);
+        else if (a.prog.n) { const u64 row = v - mis; const Val res = eval_program<SHAPE == kFilterVmLex>(a.prog, a.tt, [&](u32 c) { return a.in[c][row]; }); keep = res.lo == 1; }
       }
       bits |= (unsigned long long)keep << (it * 4 + r);
     }
@@ -738,6 +740,7 @@ void launch_filter(const FilterArgs& a0, int shape, hipStream_t s) {
   if (shape == 3) hipLaunchKernelGGL(filter_kernel<3>, grid, dim3(kBlock), 0, s, a);
   else if (shape == 1) hipLaunchKernelGGL(filter_kernel<1>, grid, dim3(kBlock), 0, s, a);
   else if (shape == 2) hipLaunchKernelGGL(filter_kernel<2>, grid, dim3(kBlock), 0, s, a);
+  else if (program_has_lex(a.prog)) hipLaunchKernelGGL(filter_kernel<kFilterVmLex>, grid, dim3(kBlock), 0, s, a);
   else hipLaunchKernelGGL(filter_kernel<0>, grid, dim3(kBlock), 0, s, a);
 }
 
@@ -819,8 +822,8 @@ __global__ __launch_bounds__(kBlock) void join_build_kernel(const JoinArgs a) {
   }
 }
 
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void join_probe_kernel(const JoinArgs a) {
+template <bool WRITE, bool LEX>
+__device__ __forceinline__ void join_probe_rows(const JoinArgs a) {
   const u64 n = live_rows(a.n_right_dev, a.n_right_cap);
   const u64 base = (u64)blockIdx.x * kTile;
 #pragma unroll 1
@@ -839,7 +842,7 @@ __global__ __launch_bounds__(kBlock) void join_probe_kernel(const JoinArgs a) {
           for (u32 q = 0; q < a.n_keys; q++) eq = eq && a.left[a.left_keys[q]][i] == key[q];
           if (!eq) continue;
           if (a.has_filter) {
-            const Val r = eval_program(a.prog, a.tt, [&](u32 col) { return col < a.n_left_cols ? a.left[col][i] : a.right[col - a.n_left_cols][j]; });
+            const Val r = eval_program<LEX>(a.prog, a.tt, [&](u32 col) { return col < a.n_left_cols ? a.left[col][i] : a.right[col - a.n_left_cols][j]; });
             if (r.lo != 1) continue;
           }
           if (WRITE) {
@@ -858,9 +861,13 @@ __global__ __launch_bounds__(kBlock) void join_probe_kernel(const JoinArgs a) {
   }
 }
 
+// (.._lex_kernel: the same rows with RDFGPU_EX_CAST_LEX compiled into the filter's VM; launched for a program that holds the op)
+template <bool WRITE> __global__ __launch_bounds__(kBlock) void join_probe_kernel(const JoinArgs a) { join_probe_rows<WRITE, false>(a); }
+template <bool WRITE> __global__ __launch_bounds__(kBlock) void join_probe_lex_kernel(const JoinArgs a) { join_probe_rows<WRITE, true>(a); }
+
 // NestedLoopJoinExec: no equi keys; every probe row meets every build row (small inputs only).
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void nlj_kernel(const JoinArgs a) {
+template <bool WRITE, bool LEX>
+__device__ __forceinline__ void nlj_rows(const JoinArgs& a) {
   const u64 n = live_rows(a.n_right_dev, a.n_right_cap);
   const u64 nl = live_rows(a.n_left_dev, a.n_left_cap);
   const u64 base = (u64)blockIdx.x * kTile;
@@ -874,7 +881,7 @@ __global__ __launch_bounds__(kBlock) void nlj_kernel(const JoinArgs a) {
     if (j < n) {
       for (u64 i = 0; i < nl; i++) {
         if (a.has_filter) {
-          const Val r = eval_program(a.prog, a.tt, [&](u32 col) { return col < a.n_left_cols ? a.left[col][i] : a.right[col - a.n_left_cols][j]; });
+          const Val r = eval_program<LEX>(a.prog, a.tt, [&](u32 col) { return col < a.n_left_cols ? a.left[col][i] : a.right[col - a.n_left_cols][j]; });
           if (r.lo != 1) continue;
         }
         if (WRITE) {
@@ -891,6 +898,8 @@ __global__ __launch_bounds__(kBlock) void nlj_kernel(const JoinArgs a) {
     if (!WRITE) a.counts[j] = c;
   }
 }
+template <bool WRITE> __global__ __launch_bounds__(kBlock) void nlj_kernel(const JoinArgs a) { nlj_rows<WRITE, false>(a); }
+template <bool WRITE> __global__ __launch_bounds__(kBlock) void nlj_lex_kernel(const JoinArgs a) { nlj_rows<WRITE, true>(a); }
 
 // Left join tail: build rows that met no probe row are emitted once with nulls on the right
 // (join/logical.rs:262-277).  Block-aggregated append behind the matched rows.
@@ -1110,11 +1119,23 @@ void launch_csr_rel_keys(const u32* keys, u64 n, u32 kmin, u32 kn, u32* rel, u32
 }
 
 void launch_join_build(const JoinArgs& a, hipStream_t s) { hipLaunchKernelGGL(join_build_kernel, grid_for(a.n_left_cap), dim3(kBlock), 0, s, a); }
-void launch_join_count(const JoinArgs& a, hipStream_t s) { hipLaunchKernelGGL(join_probe_kernel<false>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a); }
-void launch_join_write(const JoinArgs& a, hipStream_t s) { hipLaunchKernelGGL(join_probe_kernel<true>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a); }
+void launch_join_count(const JoinArgs& a, hipStream_t s) {
+  if (a.has_filter && program_has_lex(a.prog)) hipLaunchKernelGGL(join_probe_lex_kernel<false>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL(join_probe_kernel<false>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+}
+void launch_join_write(const JoinArgs& a, hipStream_t s) {
+  if (a.has_filter && program_has_lex(a.prog)) hipLaunchKernelGGL(join_probe_lex_kernel<true>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL(join_probe_kernel<true>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+}
 void launch_join_left_unmatched(const JoinArgs& a, hipStream_t s) { hipLaunchKernelGGL(join_left_unmatched_kernel, grid_for(a.n_left_cap), dim3(kBlock), 0, s, a); }
-void launch_nlj_count(const JoinArgs& a, hipStream_t s) { hipLaunchKernelGGL(nlj_kernel<false>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a); }
-void launch_nlj_write(const JoinArgs& a, hipStream_t s) { hipLaunchKernelGGL(nlj_kernel<true>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a); }
+void launch_nlj_count(const JoinArgs& a, hipStream_t s) {
+  if (a.has_filter && program_has_lex(a.prog)) hipLaunchKernelGGL(nlj_lex_kernel<false>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL(nlj_kernel<false>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+}
+void launch_nlj_write(const JoinArgs& a, hipStream_t s) {
+  if (a.has_filter && program_has_lex(a.prog)) hipLaunchKernelGGL(nlj_lex_kernel<true>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL(nlj_kernel<true>, grid_for(a.n_right_cap), dim3(kBlock), 0, s, a);
+}
 
 // --------------------------------------------------------------------------------------------------
 // Load-path utilities (index build = radix sort of three permutations + dedupe)

@@ -335,6 +335,8 @@ void Plan::execute() {
     if (rt & 8u) fail(RDFGPU_ERR_UNSUPPORTED, "a numeric CAST met a simple literal: the lexical forms of numbers are not parsed on the device");
     if (rt & kRtExtendKind) fail(RDFGPU_ERR_UNSUPPORTED, "a computed column (ProjectionExec with expressions) met a value that is a string, IRI, blank node, dateTime, date, time or duration: "
                                                          "its 24-byte value has no room for the language / datatype (numeric and boolean values are carried)");
+    if (rt & kRtLexParse) fail(RDFGPU_ERR_UNSUPPORTED, "a lexical cast (RDFGPU_EX_CAST_LEX, xsd:float / xsd:double of a simple literal) met a literal the device cannot decide: "
+                                                       "its value lies at a rounding boundary where Eisel-Lemire declines (the big-decimal path is not restated), or it is a signed NaN");
     if (rt & kRtSortTerm) fail(RDFGPU_ERR_UNSUPPORTED, "SortExec: SORT_BY_TERM over a column that is not all strings / IRIs / blank nodes");
     if (rt & 4u) fail(RDFGPU_ERR_UNSUPPORTED, "a string expression met what the device does not restate: UCASE / LCASE of a string with non-ASCII characters (Unicode case tables), "
                                                "a float / double / decimal SUBSTR position, or a comparison with a string that has no bytes on the device");
@@ -641,7 +643,8 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
     a.fn[i] = fn; a.in[i] = fn == RDFGPU_AGG_COUNT_STAR || nd.agg_prog[i] >= 0 ? nullptr : in.cols[nd.agg_col[i]];
     if (nd.agg_prog[i] >= 0) {   // SUM / AVG over an expression: the VM form of the accumulate pass, over every input column
       a.prog[i] = upload_program(nd.agg_progs[nd.agg_prog[i]]);
-      a.exprs = 1;
+      if (a.exprs == 0) a.exprs = 1;
+      if (program_has_lex(nd.agg_progs[nd.agg_prog[i]])) a.exprs = 2;
       for (u32 c = 0; c < in.n_cols; c++) a.col[c] = in.cols[c];
     }
     a.word0[i] = a.n_words;
@@ -726,7 +729,7 @@ DevTable Plan::exec_extend(NodeInfo& nd) {
   nd.n_values = in.cap; nd.n_values_dev = in.cap ? in.n_dev : nullptr; nd.values_run = run;
   if (in.cap == 0) return t;
   for (u32 q = 0; q < k; q++) a.prog[q] = upload_program(nd.agg_progs[q]);
-  timed(KC_EXTEND, 0, in.cap, in.n_dev, 4ull * nd.n_cols_read + 16ull * nd.n_enc_tv + 28ull * k, nullptr, 0, 0, [&] { launch_extend(a, stream); });
+  timed(KC_EXTEND, 0, in.cap, in.n_dev, 4ull * nd.n_cols_read + 16ull * nd.n_enc_tv + 28ull * k, nullptr, 0, 0, [&] { launch_extend(a, nd.lex, stream); });
   return t;
 }
 

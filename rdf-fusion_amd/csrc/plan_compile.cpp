@@ -58,6 +58,11 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
         if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
           fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
         pop(VK_TV, "CAST"); out = VK_TV; break;
+      case RDFGPU_EX_CAST_STRING: pop(VK_ID, "CAST_STRING (xsd:string)"); out = VK_TV; views = true; break;
+      case RDFGPU_EX_CAST_LEX:
+        if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
+          fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST_LEX to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
+        pop_bytes("CAST_LEX"); out = VK_TV; break;
       case RDFGPU_EX_EBV: pop(VK_TV, "EBV"); out = VK_BOOL; break;
       case RDFGPU_EX_REGEX: case RDFGPU_EX_CONTAINS: case RDFGPU_EX_STRSTARTS: case RDFGPU_EX_STRENDS:
         if (e.u >= n_regexes) fail(RDFGPU_ERR_INVALID, "expression: REGEX pattern %u out of range (%u patterns)", e.u, n_regexes);
@@ -98,14 +103,15 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
   return st[0];
 }
 
-// A program with a value load in it runs in the generic VM: the specialised forms gather from the typed-value table by object id.
-bool reads_values(const ExprProgram& pr) {
-  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue) return true;
+// A program with a value load or a lexical cast in it runs in the generic VM: the specialised forms gather from the typed-value table by
+// object id and know the ops of their shape only.
+bool needs_generic_vm(const ExprProgram& pr) {
+  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue || pr.nodes[i].op == RDFGPU_EX_CAST_STRING || pr.nodes[i].op == RDFGPU_EX_CAST_LEX) return true;
   return false;
 }
 
 int detect_shape(const ExprProgram& pr, bool force_vm) {
-  if (force_vm || reads_values(pr)) return 0;
+  if (force_vm || needs_generic_vm(pr)) return 0;
   const rdfgpu_expr_node* e = pr.nodes;
   if (pr.n == 3 && e[0].op == RDFGPU_EX_COLUMN && e[1].op == RDFGPU_EX_LIT_ID && (e[2].op == RDFGPU_EX_ID_EQ || e[2].op == RDFGPU_EX_ID_NEQ)) return 1;
   if (pr.n == 5 && e[0].op == RDFGPU_EX_COLUMN && e[1].op == RDFGPU_EX_ENC_TV && e[2].op == RDFGPU_EX_LIT_TV && is_cmp(e[3].op) && e[4].op == RDFGPU_EX_EBV) return 2;
@@ -121,7 +127,7 @@ int detect_shape(const ExprProgram& pr, bool force_vm) {
 // (Q5 (Execution Plan).snap:10,12), 1 = generic VM, 0 = no filter.
 int detect_join_filter_shape(const ExprProgram& pr, bool force_vm) {
   if (pr.n == 0) return 0;
-  if (force_vm || reads_values(pr)) return 1;
+  if (force_vm || needs_generic_vm(pr)) return 1;
   const rdfgpu_expr_node* e = pr.nodes;
   auto half = [&](u32 o) {
     return e[o].op == RDFGPU_EX_COLUMN && e[o + 1].op == RDFGPU_EX_ENC_TV && e[o + 2].op == RDFGPU_EX_COLUMN &&
@@ -266,7 +272,8 @@ void compile_string_table(Plan* plan, const rdfgpu_plan_desc* d) {
 void check_string_functions(const Store* store, const rdfgpu_plan_desc* d) {
   for (u32 i = 0; i < d->n_exprs; i++) {
     const u8 op = d->exprs[i].op;
-    if ((op == RDFGPU_EX_STR || op == RDFGPU_EX_STRLEN || op == RDFGPU_EX_SUBSTR || op == RDFGPU_EX_UCASE || op == RDFGPU_EX_LCASE || op == RDFGPU_EX_STRBEFORE || op == RDFGPU_EX_STRAFTER) && !store->str_off)
+    if ((op == RDFGPU_EX_STR || op == RDFGPU_EX_STRLEN || op == RDFGPU_EX_SUBSTR || op == RDFGPU_EX_UCASE || op == RDFGPU_EX_LCASE || op == RDFGPU_EX_STRBEFORE || op == RDFGPU_EX_STRAFTER ||
+         op == RDFGPU_EX_CAST_STRING || op == RDFGPU_EX_CAST_LEX) && !store->str_off)
       fail(RDFGPU_ERR_INVALID, "plan uses string functions but the store has no strings (rdfgpu_store_set_strings)");
   }
 }
@@ -614,6 +621,8 @@ void count_consumers(Plan* plan) {
 // per-node byte accounting inputs: distinct columns read, typed gathers per row
 void account_columns_read(Plan* plan) {
   for (NodeInfo& nd : plan->nodes) {
+    nd.lex = program_has_lex(nd.prog);
+    for (const ExprProgram& pr : nd.agg_progs) nd.lex = nd.lex || program_has_lex(pr);
     u32 used = columns_read(nd.prog);
     for (u32 i = 0; i < nd.prog.n; i++) if (nd.prog.nodes[i].op == RDFGPU_EX_ENC_TV) nd.n_enc_tv++;
     if (nd.d.kind == RDFGPU_NODE_FILTER) for (u32 c = 0; c < nd.n_proj; c++) used |= 1u << nd.proj[c];

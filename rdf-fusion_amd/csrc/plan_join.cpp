@@ -15,7 +15,7 @@ u32 pow2_at_least(u64 v) { u64 p = 1024; while (p < v && p < (1ull << 31)) p <<=
 // the records last time (the sides as exec_join chooses them below).  exec_lds_join then hands it on to the band join or runs
 // it just before the probe side is read.
 bool Plan::keeps_pending_oj(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf) const {
-  if (!nd.band.takes_records || nd.d.kind != RDFGPU_NODE_HASH_JOIN || left_join || lf || rf || opt.on(RDFGPU_OPT_NO_LDS_JOIN)) return false;
+  if (!nd.band.takes_records || nd.d.kind != RDFGPU_NODE_HASH_JOIN || left_join || lf || rf || opt.on(RDFGPU_OPT_NO_LDS_JOIN) || nd.lex) return false;
   const bool build_left = choose_build_left(nd, L, R, false, false, false);
   const DevTable& B = build_left ? L : R; const DevTable& P = build_left ? R : L;
   return (B.cap <= kLdsJoinMaxBuild || !opt.on(RDFGPU_OPT_NO_GLOBAL_TABLE_JOIN)) && P.cols[0] == pending_oj.first_col && B.cols[0] != pending_oj.first_col;
@@ -60,7 +60,9 @@ DevTable Plan::exec_join(NodeInfo& nd) {
   DevTable t;
   t.n_cols = nd.n_proj;
   if (L.cap == 0 || (R.cap == 0 && !left_join)) { t.cap = 0; return t; }
-  if (nd.d.kind == RDFGPU_NODE_HASH_JOIN && !opt.on(RDFGPU_OPT_NO_LDS_JOIN)) {
+  // (a filter with RDFGPU_EX_CAST_LEX takes the generic join: the case is compiled into join_probe_lex_kernel / nlj_lex_kernel, not into
+  // the LDS / partitioned join forms, whose instantiations stay what they were)
+  if (nd.d.kind == RDFGPU_NODE_HASH_JOIN && !opt.on(RDFGPU_OPT_NO_LDS_JOIN) && !nd.lex) {
     const bool build_left = choose_build_left(nd, L, R, left_join, in.lf, in.rf);
     if ((build_left ? L.cap : R.cap) <= kLdsJoinMaxBuild || !opt.on(RDFGPU_OPT_NO_GLOBAL_TABLE_JOIN)) {
       const NodeInfo* pf = in.lf ? &nodes[nd.d.left] : in.rf ? &nodes[nd.d.right] : nullptr;
@@ -92,8 +94,9 @@ Plan::JoinInputs Plan::join_inputs(NodeInfo& nd) {
   // Pipeline fusion: a FilterExec child (identity projection, consumed by this join only) is not
   // materialised when it ends up on the probe side of the LDS join — its predicate runs inside the probe.
   auto fusable = [&](int32_t ci) {
-    if (nd.d.kind != RDFGPU_NODE_HASH_JOIN || opt.on(RDFGPU_OPT_NO_FILTER_FUSION) || opt.on(RDFGPU_OPT_NO_LDS_JOIN)) return false;
+    if (nd.d.kind != RDFGPU_NODE_HASH_JOIN || opt.on(RDFGPU_OPT_NO_FILTER_FUSION) || opt.on(RDFGPU_OPT_NO_LDS_JOIN) || nd.lex) return false;
     const NodeInfo& c = nodes[ci];
+    if (c.lex) return false;   // (its FilterExec runs filter_kernel<kFilterVmLex>; the probe filter of the LDS join has no such form)
     if (c.d.kind != RDFGPU_NODE_FILTER || c.prog.n == 0 || c.refs != 1 || c.n_proj != nodes[c.d.left].width) return false;
     for (u32 k = 0; k < c.n_proj; k++) if (c.proj[k] != k) return false;
     return true;
@@ -257,7 +260,7 @@ DevTable Plan::exec_semi_join(NodeInfo& nd) {
       filter = kSemiIdPair;
       a.idp = IdPairFilter{nd.prog.nodes[0].u, nd.prog.nodes[1].u, nd.prog.nodes[2].op == RDFGPU_EX_ID_EQ ? 1u : 0u};
     } else {
-      filter = kSemiVm;
+      filter = nd.lex ? kSemiVmLex : kSemiVm;
       a.prog = upload_program(nd.prog);
     }
   }

@@ -59,7 +59,7 @@ __device__ __forceinline__ bool semi_filter(const SemiJoinArgs& a, u64 j, Right 
     if (va == 0 || vb == 0) return false;   // null: not a match
     return (va == vb) == (a.idp.is_eq != 0);
   } else {
-    const Val v = eval_program(*a.prog, a.tt, [&](u32 c) { return c < a.n_left_cols ? a.cols[c][j] : right(c - a.n_left_cols); });
+    const Val v = eval_program<FK == kSemiVmLex>(*a.prog, a.tt, [&](u32 c) { return c < a.n_left_cols ? a.cols[c][j] : right(c - a.n_left_cols); });
     return v.lo == 1;
   }
 }
@@ -238,6 +238,7 @@ template <bool ANTI>
 static void launch_anti(const SemiJoinArgs& a, int form, int filter, hipStream_t s) {
   if (filter == kSemiNoFilter) launch_form<ANTI, kSemiNoFilter>(a, form, s);
   else if (filter == kSemiIdPair) launch_form<ANTI, kSemiIdPair>(a, form, s);
+  else if (filter == kSemiVmLex) launch_form<ANTI, kSemiVmLex>(a, form, s);
   else launch_form<ANTI, kSemiVm>(a, form, s);
 }
 

@@ -203,12 +203,30 @@ def CAST(e, tag):
     return Expr(e.nodes + [(abi.EX_CAST, 0, 0, int(tag), 0, 0)])
 
 
-def xsd_boolean(e): return CAST(e, abi.TV_BOOLEAN)
-def xsd_int(e): return CAST(e, abi.TV_INT)
-def xsd_integer(e): return CAST(e, abi.TV_INTEGER)
-def xsd_decimal(e): return CAST(e, abi.TV_DECIMAL)
-def xsd_float(e): return CAST(e, abi.TV_FLOAT)
-def xsd_double(e): return CAST(e, abi.TV_DOUBLE)
+def CAST_LEX(e, tag):
+    """xsd:<type>(e) that also PARSES a simple literal (RDFGPU_EX_CAST_LEX; the reference's FromStr impls: f32::from_str, Decimal::from_str,
+    ..): on every other operand exactly CAST.  `tag` as for CAST."""
+    return Expr(e.nodes + [(abi.EX_CAST_LEX, 0, 0, int(tag), 0, 0)])
+
+
+def xsd_string(e):
+    """xsd:string(ENC_TV(col(c))) (scalar/conversion/cast_string.rs), lowered to RDFGPU_EX_CAST_STRING over the column's object id: ENC_TV
+    keeps the id for strings only, and the cast needs the lexical form of IRIs and other literals (`"12.5"^^bsbm:USD`) too.  Anything but
+    ENC_TV of a column has no id to take the lexical form from: refused here."""
+    n = e.nodes
+    if len(n) != 2 or n[0][0] != abi.EX_COLUMN or n[1][0] != abi.EX_ENC_TV:
+        raise ValueError("xsd_string takes ENC_TV(col(c)): the cast reads the lexical form through the column's object id")
+    return Expr([n[0], (abi.EX_CAST_STRING, 0, 0, 0, 0, 0)])
+
+
+def _cast(e, tag, lexical): return CAST_LEX(e, tag) if lexical else CAST(e, tag)
+# lexical=True: the operand may be a simple literal (xsd:float(xsd:string(ENC_TV(price)))), parsed on the device (CAST_LEX)
+def xsd_boolean(e, lexical=False): return _cast(e, abi.TV_BOOLEAN, lexical)
+def xsd_int(e, lexical=False): return _cast(e, abi.TV_INT, lexical)
+def xsd_integer(e, lexical=False): return _cast(e, abi.TV_INTEGER, lexical)
+def xsd_decimal(e, lexical=False): return _cast(e, abi.TV_DECIMAL, lexical)
+def xsd_float(e, lexical=False): return _cast(e, abi.TV_FLOAT, lexical)
+def xsd_double(e, lexical=False): return _cast(e, abi.TV_DOUBLE, lexical)
 
 
 def REGEX(e, pattern, flags=""):
@@ -720,8 +738,10 @@ def format_expr(nodes, names, at=True):
             st.append({0: "false", 1: "true", 2: "NULL"}[u])
         elif op in _UN:
             st.append(f"{_UN[op]}({st.pop()})")
-        elif op == abi.EX_CAST:
+        elif op in (abi.EX_CAST, abi.EX_CAST_LEX):
             st.append(f"{_CAST.get(u, f'cast{u}')}({st.pop()})")
+        elif op == abi.EX_CAST_STRING:      # the id form of xsd:string(ENC_TV(c)), printed as the reference prints it
+            st.append(f"xsd:string(ENC_TV({st.pop()}))")
         elif op in _BIN:
             b, a = st.pop(), st.pop()
             st.append(f"{_BIN[op]}({a}, {b})")
