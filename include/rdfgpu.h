@@ -834,6 +834,8 @@ enum {
   RDFGPU_OPT_PARTITION_ROWS,            /* value: build rows per partition a partitioned join aims for (0 = automatic: 1024)   */
   RDFGPU_OPT_PARTITION_SLOTS,           /* value: slots of a partition's LDS table, a power of two from 1024 to 8192 (0 = automatic: 4096); a partition with more than slots / 2 build rows is joined chunk by chunk */
   RDFGPU_OPT_NO_SEMI_LDS,               /* flag: semi / anti joins never build their set of right rows in LDS (the HBM set, built per execution) */
+  RDFGPU_OPT_NO_BAND_PAIR_COUNTS,       /* flag: band join emitting from a slice's list of surviving pairs: no per-row counts of the verdicts are read, every step streams the verdict bits to count its blocks' rows */
+  RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS,    /* value: the smallest number of 64 x 64 blocks from which a step counts from the per-row counts, 64 bytes per block, instead of the bits (0 = automatic: 2^16 blocks = 32 MiB of verdicts) */
   RDFGPU_OPT_NO_BAND_ROW_CACHE,         /* flag: band join reading a slice's rows in place: the rows' decoded windows are not kept on the slice, every step gathers 16-byte records by key */
   RDFGPU_OPT_NO_BAND_PAIR_LIST,         /* flag: band join streaming a slice's cached pair verdicts: no list of the surviving pairs is kept beside them, every step expands the verdict bits into rows */
   RDFGPU_OPT_NO_BAND_PAIR_CACHE,        /* flag: band join reading a slice's rows in place with the rows' windows kept: the pair test's verdicts are not kept on the slice, every step tests every pair */
@@ -882,6 +884,12 @@ int rdfgpu_band_pair_cache_eligible(uint32_t row_windows, uint32_t neq_self, uin
  * 32-bit offsets cannot wrap (n_blocks < 2^20).
  */
 int rdfgpu_band_pair_list_eligible(uint32_t pair_cached, uint32_t option_set, uint64_t survivors, uint64_t n_blocks);
+/*
+ * .. and does a step that emits from the list count its blocks' rows from the per-row counts kept with the list, one byte per (block, row), without reading the
+ * verdict bits (1), or does it stream the bits (0)?  has_list: the step emits from the slice's list; option_set: RDFGPU_OPT_NO_BAND_PAIR_COUNTS; n_blocks: blocks of
+ * the in-place layout; min_blocks: RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS (inclusive; 0 = 2^16 blocks, whose 32 MiB of verdicts are the size of the L2).
+ */
+int rdfgpu_band_pair_count_eligible(uint32_t has_list, uint32_t option_set, uint64_t n_blocks, uint64_t min_blocks);
 /*
  * MemIndexScanPredicate::try_and_with (scan_instructions.rs:170-210).  Predicates are given
  * as (pred, a, b) triples where IN sets are explicit arrays.  Writes the combined predicate;

@@ -596,6 +596,11 @@ int rdfgpu_band_pair_list_eligible(uint32_t pair_cached, uint32_t option_set, ui
   s.pair_cached = pair_cached != 0; s.option_off = option_set == 0; s.survivors = survivors; s.n_blocks = n_blocks;
   return band_pair_list_eligible(s) ? 1 : 0;
 }
+int rdfgpu_band_pair_count_eligible(uint32_t has_list, uint32_t option_set, uint64_t n_blocks, uint64_t min_blocks) {
+  BandPairCountShape s;
+  s.has_list = has_list != 0; s.option_off = option_set == 0; s.n_blocks = n_blocks; s.min_blocks = min_blocks;
+  return band_pair_count_eligible(s) ? 1 : 0;
+}
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;
   if (p->pred == RDFGPU_PRED_IN) { if (p->ids) r.ids.assign(p->ids, p->ids + p->n_ids); else r.ids = {p->from}; }

@@ -519,8 +519,49 @@ __device__ __forceinline__ void band_cached_blocks(const BandArgs& b) {
     if (lane == 63) { b.bcount[blk0 + k] = c; b.bvalid[blk0 + k] = rows; }
   }
 }
-template <int NWIN, int NEQ, bool PACK, bool STATIC = false, bool CACHED = false>
+// COUNTS (CACHED; BandArgs::pair_cnt = SliceTable::BandRowWindows::pair_cnt, the set bits of every cached word as a byte): the bits are not read — band_count_blocks.
+constexpr u32 kBandCountGroups = 4;   // groups of 4 blocks per wave of the counts form: 16 blocks, their loads independent and all in flight before the first wait
+// The counts form of the cached pair test, for a step that emits from the slice's list (band_emit_list reads neither the bits nor bvalid): all the step needs of
+// the verdicts is bcount[blk] = the sum, over the rows that have a value in this execution, of the row's set bits — 64 bytes per block instead of 512.  A quarter
+// wave (one DPP row of 16 lanes) per block, 4 rows per lane: one dword of counts, the block's descriptor (one address per quarter wave), then the 4 rows' values,
+// each guarded by the block's row count (row_val has exactly the slice's rows: nothing is read past a block's last row).  No LDS, no atomics; bvalid and the bits untouched.
+__device__ __forceinline__ void band_count_blocks(const BandArgs& b) {
+  const u32 lane = threadIdx.x & 63, sub = lane & 15u;
+  const u32 n_blocks = b.max_blocks;                       // (in place: exact, known on the host)
+  const u32 blk0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * (4u * kBandCountGroups) + (lane >> 4);
+  uint4 d[kBandCountGroups]; u32 cnt[kBandCountGroups]; u32 val[kBandCountGroups][4];
+#pragma unroll
+  for (u32 g = 0; g < kBandCountGroups; g++) {
+    const u32 blk = blk0 + 4u * g;
+    d[g] = make_uint4(0u, 0u, 0u, 0u); cnt[g] = 0u;          // (past the end: no rows, nothing loaded, nothing stored)
+    if (blk < n_blocks) { d[g] = b.bdesc[blk]; cnt[g] = reinterpret_cast<const u32*>(b.pair_cnt)[(u64)blk * 16 + sub]; }
+  }
+#pragma unroll
+  for (u32 g = 0; g < kBandCountGroups; g++) asm volatile("" :: "v"(d[g].z), "v"(d[g].w), "v"(cnt[g]));
+#pragma unroll
+  for (u32 g = 0; g < kBandCountGroups; g++) {
+    const u32 rb = d[g].z, nr = d[g].w;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) { val[g][i] = kNil; if (4u * sub + i < nr) val[g][i] = b.row_val[rb + 4u * sub + i]; }
+  }
+#pragma unroll
+  for (u32 g = 0; g < kBandCountGroups; g++) asm volatile("" :: "v"(val[g][0]), "v"(val[g][1]), "v"(val[g][2]), "v"(val[g][3]));
+#pragma unroll
+  for (u32 g = 0; g < kBandCountGroups; g++) {
+    u32 c = 0;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) c += val[g][i] != kNil ? (cnt[g] >> (8u * i)) & 0xFFu : 0u;   // (rows past the block's kept kNil)
+    c += (u32)__builtin_amdgcn_update_dpp(0, (int)c, 0x111, 0xf, 0xf, false);   // row_shr:1 .. 8, as wave_incl_scan's first steps: lane 15 of every row holds its block's sum
+    c += (u32)__builtin_amdgcn_update_dpp(0, (int)c, 0x112, 0xf, 0xf, false);
+    c += (u32)__builtin_amdgcn_update_dpp(0, (int)c, 0x114, 0xf, 0xf, false);
+    c += (u32)__builtin_amdgcn_update_dpp(0, (int)c, 0x118, 0xf, 0xf, false);
+    const u32 blk = blk0 + 4u * g;
+    if (sub == 15u && blk < n_blocks) b.bcount[blk] = c;
+  }
+}
+template <int NWIN, int NEQ, bool PACK, bool STATIC = false, bool CACHED = false, bool COUNTS = false>
 __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
+  if constexpr (COUNTS) { band_count_blocks(b); return; } else
   if constexpr (CACHED) { band_cached_blocks(b); return; } else {
   __shared__ uint4 ent[4][64];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -591,12 +632,15 @@ __global__ __launch_bounds__(256) void band_pair_bits_kernel(const BandArgs b) {
 // The build of a slice's pair list (SliceTable::BandRowWindows::pair_list; behind the verdicts, once per store version and literal set): the set bits of every block
 // as (row << 6) | entry, rows ascending and entries ascending within a row — the order in which band_emit_kernel lists a block's survivors, so the emit pass of a
 // steady step reads the list instead of expanding the bits.  One wave per block: the counts (one entry past the last block: 0, for the scan), then the lists at the
-// scanned offsets.  A list that would not fit `cap` items is not written (the host declines it); the total is left for the host either way.
+// scanned offsets.  A list that would not fit `cap` items is not written (the host declines it); the total is left for the host either way.  The count pass also
+// keeps every lane's own count as a byte (pair_cnt, the list's companion: band_count_blocks).
 __global__ __launch_bounds__(256) void band_pair_list_count_kernel(const BandPairListArgs a) {
   const u32 lane = threadIdx.x & 63;
   const u32 blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
   if (blk > a.n_blocks) return;                            // wave-uniform
-  const u32 c = wave_incl_scan(blk < a.n_blocks ? (u32)__popcll(a.bits[(u64)blk * 64 + lane]) : 0u);
+  const u32 mine = blk < a.n_blocks ? (u32)__popcll(a.bits[(u64)blk * 64 + lane]) : 0u;
+  if (blk < a.n_blocks) a.pair_cnt[(u64)blk * 64 + lane] = (unsigned char)mine;   // (0 .. 64) the row's set bits, for the counts form of the cached pair test
+  const u32 c = wave_incl_scan(mine);
   if (lane == 63) a.counts[blk] = c;
 }
 __global__ __launch_bounds__(256) void band_pair_list_write_kernel(const BandPairListArgs a) {
@@ -869,7 +913,10 @@ template <int NWIN, bool PACK> static void launch_band_mask_w(const BandArgs& b,
   const int neq = b.has_neq ? (b.neq_is_eq ? 2 : b.neq_self ? 3 : 1) : 0;
   if (neq == 3) {
     if constexpr (PACK) {
-      if (b.row_win && b.bvalid) {   // the cached verdicts: a wave per kBandCachedBlocks blocks
+      if (b.row_win && b.pair_cnt) {   // the cached verdicts' per-row counts: a wave per 4 * kBandCountGroups blocks
+        const u32 waves = (b.max_blocks + 4 * kBandCountGroups - 1) / (4 * kBandCountGroups);
+        hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true, true, true>), dim3((waves + 3) / 4 ? (waves + 3) / 4 : 1), dim3(256), 0, s, b);
+      } else if (b.row_win && b.bvalid) {   // the cached verdicts: a wave per kBandCachedBlocks blocks
         const u32 waves = (b.max_blocks + kBandCachedBlocks - 1) / kBandCachedBlocks;
         hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true, true>), dim3((waves + 3) / 4 ? (waves + 3) / 4 : 1), dim3(256), 0, s, b);
       } else if (b.row_win) hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true>), g, dim3(256), 0, s, b);
@@ -906,7 +953,7 @@ void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s
 void launch_band_emit(const BandArgs& b, hipStream_t s) {
   const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);
   static_assert(kBandMaxRowCols + kBandMaxSideCols == 6, "one instantiation per column count");
-  if (b.row_win && b.bvalid && b.pair_list && b.n_row_cols <= 1) switch (b.n_out_cols) {   // the slice's list of survivors (band_emit_list: one row column)
+  if (b.row_win && (b.bvalid || b.pair_cnt) && b.pair_list && b.n_row_cols <= 1) switch (b.n_out_cols) {   // the slice's list of survivors (band_emit_list: one row column)
     case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true>), g, dim3(256), 0, s, b); return;
     case 2: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true>), g, dim3(256), 0, s, b); return;
     case 3: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true>), g, dim3(256), 0, s, b); return;

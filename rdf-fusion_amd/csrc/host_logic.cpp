@@ -167,4 +167,9 @@ bool band_pair_list_eligible(const BandPairListShape& s) {
   return s.survivors <= 256 * s.n_blocks;
 }
 
+bool band_pair_count_eligible(const BandPairCountShape& s) {
+  if (!s.has_list || !s.option_off) return false;
+  return s.n_blocks >= (s.min_blocks ? s.min_blocks : kBandPairCountBlocks);
+}
+
 }  // namespace rdfgpu

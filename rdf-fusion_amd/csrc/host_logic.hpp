@@ -73,5 +73,12 @@ bool band_pair_cache_eligible(const BandPairCacheShape& s);
 constexpr u64 kBandPairListBlocks = 1ull << 20;
 struct BandPairListShape { bool pair_cached = false, option_off = false; u64 survivors = 0, n_blocks = 0; };
 bool band_pair_list_eligible(const BandPairListShape& s);
+// .. and does a step that emits from the list count its blocks' rows from the per-row counts kept with it (SliceTable::BandRowWindows::pair_cnt: 64 bytes per
+// block, band_mask_kernel's COUNTS form) instead of streaming the 512 bytes of bits?  A condition, not a measurement: yes when the step emits from the list (nothing
+// else in it reads the bits), the option is off and the layout has at least `min_blocks` blocks (RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS, inclusive; 0 =
+// kBandPairCountBlocks: 32 MiB of verdicts, the size of the L2 — below it the bits stay in cache from step to step and the pass is bound by its launch either way).
+constexpr u64 kBandPairCountBlocks = 1ull << 16;
+struct BandPairCountShape { bool has_list = false, option_off = false; u64 n_blocks = 0, min_blocks = 0; };
+bool band_pair_count_eligible(const BandPairCountShape& s);
 
 }  // namespace rdfgpu

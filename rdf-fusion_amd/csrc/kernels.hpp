@@ -510,10 +510,13 @@ struct BandArgs {
   // .. and beside them the list of their set bits (SliceTable::BandRowWindows::pair_list; the list form of the emit kernel): block blk's surviving pairs are
   // pair_list[pair_list_off[blk] .. pair_list_off[blk + 1]), (row << 6) | entry each, rows ascending and entries ascending within a row.  Null: the emit kernel expands the bits.
   const unsigned short* pair_list; const u32* pair_list_off;
+  // .. and the set bits of every cached word as a byte (SliceTable::BandRowWindows::pair_cnt; the counts form of the mask pass, host_logic.hpp:
+  // band_pair_count_eligible): pair_cnt[blk * 64 + row] = popcount(masks[blk * 64 + row]).  Set: the step counts from these 64 B per block, masks and bvalid are null.
+  const unsigned char* pair_cnt;
 };
 // The build of a slice's pair list from its cached verdicts (band_join.hip): the set bits of every block counted (counts[n_blocks] = 0), the counts scanned into `off`
 // by the caller, the lists written.  Nothing is written when the total, off[n_blocks], exceeds `cap` items; the total goes to *total_out either way.
-struct BandPairListArgs { const u64* bits; u32 n_blocks; u32* counts; const u32* off; unsigned short* list; u64 cap; u32* total_out; };
+struct BandPairListArgs { const u64* bits; u32 n_blocks; u32* counts; const u32* off; unsigned short* list; u64 cap; u32* total_out; unsigned char* pair_cnt; };   // pair_cnt: [64 * n_blocks], every word's own count, written by the count pass
 void launch_band_pair_list_count(const BandPairListArgs& a, hipStream_t s);
 void launch_band_pair_list_write(const BandPairListArgs& a, hipStream_t s);
 // The build of BandArgs::row_win (band_join.hip): per join key d of [kmin, kmin + kn) the window operands are fetched through the operand stages' direct

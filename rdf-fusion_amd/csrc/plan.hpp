@@ -136,6 +136,7 @@ struct BandJoin {
   const uint2* row_win = nullptr;      // the slice's cached row windows for this chain (band_row_windows; null: not eligible, declined, or the route is closed)
   bool row_static = false;             // route: in place, the block kernels read row_win and this execution's values per row instead of 16-byte records
   u64* pair_bits = nullptr;            // the slice's cached pair verdicts for this chain (band_row_windows; null: not eligible, over the cap, or no row windows)
+  const u8* pair_cnt = nullptr;        // .. and the list's per-row counts (taken with the list; whether the step counts from them: band_pair_count_eligible, in band_blocks_and_emit)
   const unsigned short* pair_list = nullptr; const u32* pair_list_off = nullptr; u64 pair_survivors = 0;   // .. and the list of their set bits (band_row_windows; null: none kept, declined as larger than the bits, or the plan's options decline it)
   bool pair_cached = false;            // route: row_static, and the pair test is not run — its verdicts are pair_bits, a step applies its rows to them (band_mask_kernel's CACHED form)
   u64 nrows = 0, max_blocks = 0;       // probe rows of the block kernels (in place: the slice's own rows); upper bound of the blocks (in place: exact)

@@ -423,22 +423,23 @@ void Plan::band_row_windows(BandJoin& bj) {
   lshape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_LIST); lshape.n_blocks = bj.lay.n_blocks;
   auto want_list = [&](const u64* bits) { lshape.pair_cached = bits != nullptr && bj.lay.n_blocks != 0; lshape.survivors = 0; return band_pair_list_eligible(lshape); };
   BandPairListArgs la{};
-  auto build_pair_list = [&](const u64* bits, u32* total_out) {   // per block its 512 B of bits read twice, 4 B of count written and read, 4 B of offset written and read; 2 B per survivor written
+  auto build_pair_list = [&](const u64* bits, u32* total_out) {   // per block its 512 B of bits read twice, 64 B of per-row counts written, 4 B of count written and read, 4 B of offset written and read; 2 B per survivor written
     const u64 nbk = bj.lay.n_blocks;
     la.bits = bits; la.n_blocks = (u32)nbk; la.counts = scratch<u32>(nbk + 1); la.cap = 256ull * nbk; la.total_out = total_out;
     u32* off = store->table_alloc<u32>(nbk + 1); la.off = off; la.list = store->table_alloc<unsigned short>(la.cap + 64);   // (padded: the emit pass reads whole rounds of 64 items)
+    la.pair_cnt = store->table_alloc<u8>(64ull * nbk);       // (the list's companion: every word's own count, one more store of the count pass — no launch, no wait, no table of its own)
     const size_t tb = scan_temp_bytes(nbk + 1); void* temp = scratch<unsigned char>(tb);
-    timed(KC_BAND_PAIR_LIST_COUNT, 0, nbk, nullptr, 512 + 4, nullptr, 0, 0, [&] { launch_band_pair_list_count(la, stream); });
+    timed(KC_BAND_PAIR_LIST_COUNT, 0, nbk, nullptr, 512 + 4 + 64, nullptr, 0, 0, [&] { launch_band_pair_list_count(la, stream); });
     timed(scan_class(nbk + 1), 0, nbk + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(la.counts, off, nbk + 1, temp, tb, stream); });
     timed(KC_BAND_PAIR_LIST_WRITE, 0, nbk, nullptr, 512 + 4 + 2 * 256, nullptr, 0, 0, [&] { launch_band_pair_list_write(la, stream); });
   };
   auto keep_pair_list = [&](SliceTable::BandRowWindows& e, u64 survivors) {   // after the wait: published when it meets the condition, else freed and remembered as declined
     lshape.survivors = survivors;
-    if (band_pair_list_eligible(lshape)) { e.pair_list = la.list; e.pair_list_off = const_cast<u32*>(la.off); e.pair_survivors = survivors; metrics.tables_built++; }
-    else { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); e.list_declined = true; }
+    if (band_pair_list_eligible(lshape)) { e.pair_list = la.list; e.pair_list_off = const_cast<u32*>(la.off); e.pair_cnt = la.pair_cnt; e.pair_survivors = survivors; metrics.tables_built++; }
+    else { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); store->table_free(la.pair_cnt); e.list_declined = true; }
   };
   auto take_pair_list = [&](const SliceTable::BandRowWindows& e) {   // (a plan whose options decline the list does not use one another plan left)
-    if (e.pair_list && lshape.option_off) { bj.pair_list = e.pair_list; bj.pair_list_off = e.pair_list_off; bj.pair_survivors = e.pair_survivors; }
+    if (e.pair_list && lshape.option_off) { bj.pair_list = e.pair_list; bj.pair_list_off = e.pair_list_off; bj.pair_cnt = e.pair_cnt; bj.pair_survivors = e.pair_survivors; }
   };
   for (auto& e : tab->band_row_windows) if (e.key == key) {
     bj.row_win = e.row_win; pair.row_windows = e.row_win != nullptr;
@@ -469,7 +470,7 @@ void Plan::band_row_windows(BandJoin& bj) {
   if (slow) { store->table_free(w.row_win); w.row_win = nullptr; if (bits) store->table_free(bits); bits = nullptr; } else metrics.tables_built += bits ? 2 : 1;
   tab->band_row_windows.push_back(SliceTable::BandRowWindows{key, w.row_win, bits});
   SliceTable::BandRowWindows& e = tab->band_row_windows.back();
-  if (list && slow) { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); }
+  if (list && slow) { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); store->table_free(la.pair_cnt); }
   else if (list) keep_pair_list(e, got.y);
   bj.row_win = w.row_win; bj.pair_bits = bits; take_pair_list(e);
 }
@@ -512,7 +513,13 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
                            bj.fused ? (int)(reinterpret_cast<u64*>(pending_oj.o.multi_rows) - counters) : -1, bj.skip_slow, bj.in_place, bj.in_place ? max_blocks : 0});
   const u64 hist = bj.j.nd.band.blocks; b.launch_blocks = (u32)(bj.in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
   b.bdesc = bj.in_place ? bj.lay.bdesc : scratch<uint4>(max_blocks);
-  if (bj.pair_cached) { b.masks = bj.pair_bits; b.bvalid = scratch<u64>(max_blocks); b.pair_list = bj.pair_list; b.pair_list_off = bj.pair_list_off; }   // the slice's verdicts (and their list, where kept): read, never written
+  // a step that emits from the list needs the verdicts only to count: from the list's per-row counts where the layout is large enough (R14; host_logic.hpp)
+  BandPairCountShape cshape;
+  cshape.has_list = bj.pair_cached && bj.pair_list != nullptr && bj.pair_cnt != nullptr && b.n_row_cols <= 1;   // (the list form of the emit pass knows one row column: launch_band_emit)
+  cshape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_COUNTS); cshape.n_blocks = max_blocks; cshape.min_blocks = opt.v[RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS];
+  const bool counts = band_pair_count_eligible(cshape);
+  if (counts) { b.masks = nullptr; b.bvalid = nullptr; b.pair_cnt = bj.pair_cnt; b.pair_list = bj.pair_list; b.pair_list_off = bj.pair_list_off; }   // neither the bits nor the valid rows: the list form reads neither
+  else if (bj.pair_cached) { b.masks = bj.pair_bits; b.bvalid = scratch<u64>(max_blocks); b.pair_list = bj.pair_list; b.pair_list_off = bj.pair_list_off; }   // the slice's verdicts (and their list, where kept): read, never written
   else b.masks = scratch<u64>(max_blocks * 64);
   const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn)); void* temp = scratch<unsigned char>(tb);
   if (bj.counting) {   // poff = exclusive scan of the rows per key (entry kn = the rows that join something); then the scatter
@@ -528,7 +535,9 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
   // pair test, per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count is not known on the host
   const u64* const nrows_dev = bj.in_place ? nullptr : bj.j.P.n_dev;
   // (the verdicts cached: per block its 512 B of bits and its descriptor read, 4 + 8 B of count and valid rows written; per row its value read)
-  if (bj.pair_cached) timed(KC_BAND_MASK, (512ull + 16 + 4 + 8) * max_blocks, bj.nrows, nullptr, 4, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  // (.. counted from the per-row counts: per block its 64 B of counts and its descriptor read, 4 B of count written; per row its value read)
+  if (counts) timed(KC_BAND_MASK, (64ull + 16 + 4) * max_blocks, bj.nrows, nullptr, 4, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  else if (bj.pair_cached) timed(KC_BAND_MASK, (512ull + 16 + 4 + 8) * max_blocks, bj.nrows, nullptr, 4, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
   else timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, bj.row_static ? 8 + 4 : b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
   if (!bj.skip_slow) {
     if (bj.pair_cached) fail(RDFGPU_ERR_INVALID, "band join: the full-semantics pass over a slice's cached verdicts");

@@ -114,7 +114,7 @@ static const char* const kOptionNames[RDFGPU_OPT__COUNT] = {
     "NO_TABLE_CACHE", "NO_INDEX_JOIN", "NO_CHAIN_FUSION", "NO_VALUE_TABLES", "NO_RANGE_INDEX", "NO_FILTER_FUSION",
     "NO_LDS_JOIN", "NO_GLOBAL_TABLE_JOIN", "NO_DIRECT_TABLE", "NO_BAND_JOIN", "NO_PARTITIONED_JOIN", "NO_VALUE_VERDICTS", "NO_PRIMING", "NO_ORDERED_JOIN", "NO_BAND_PACK16", "NO_RUN_COPY", "NO_RANGE_PARTITION",
     "LDS_MAX_BUILD", "CSR_ROW_LANES_LOG2", "JOIN_WAVE_Q", "PARTITION_MIN_BUILD", "PARTITION_TWO_PASS_ROWS", "NO_OWN_PARTITION_PASS", "NO_BAND_COMPACT", "NO_PROBE_OUTER_JOIN", "NO_STREAM_JOIN", "PARTITION_ROWS", "PARTITION_SLOTS",
-    "NO_SEMI_LDS", "NO_BAND_ROW_CACHE", "NO_BAND_PAIR_LIST", "NO_BAND_PAIR_CACHE", "BAND_PAIR_CACHE_BLOCKS", "NO_AGG_LDS"};
+    "NO_SEMI_LDS", "NO_BAND_PAIR_COUNTS", "BAND_PAIR_COUNT_BLOCKS", "NO_BAND_ROW_CACHE", "NO_BAND_PAIR_LIST", "NO_BAND_PAIR_CACHE", "BAND_PAIR_CACHE_BLOCKS", "NO_AGG_LDS"};
 const char* engine_option_name(u32 option) { return option < RDFGPU_OPT__COUNT ? kOptionNames[option] : nullptr; }
 const EngineOptions& default_engine_options() {
   static const EngineOptions defaults = [] {
@@ -268,7 +268,7 @@ void Store::drop_slice_tables() {
     for (auto& v : t.values) table_free(v.val);
     for (auto& r : t.ranges) { table_free(r.rows); table_free(r.vals); table_free(r.link); }
     for (auto& e : t.band_entries) { table_free(e.et); for (u32* p : e.eo) table_free(p); table_free(e.boff); table_free(e.bdesc); }
-    for (auto& e : t.band_row_windows) { table_free(e.row_win); table_free(e.pair_bits); table_free(e.pair_list); table_free(e.pair_list_off); }
+    for (auto& e : t.band_row_windows) { table_free(e.row_win); table_free(e.pair_bits); table_free(e.pair_list); table_free(e.pair_list_off); table_free(e.pair_cnt); }
     for (auto& v : t.value_starts) table_free(v.lo);
   }
   slice_tables.clear();

@@ -117,9 +117,13 @@ struct SliceTable {
   // pair_list / pair_list_off: the set bits of pair_bits as a list per block ((row << 6) | entry, rows ascending, entries ascending within a row; exclusive offsets,
   // n_blocks + 1 of them), pair_survivors of them in all: what the emit pass reads instead of expanding the bits, kept when it is no larger than the bits
   // (host_logic.hpp, band_pair_list_eligible); list_declined: it was built and turned out larger — not built again.  Key, lock and lifetime are pair_bits'.
+  // pair_cnt: the list's companion, u8[64 * n_blocks] indexed like pair_bits: pair_cnt[blk * 64 + row] = popcount(pair_bits[blk * 64 + row]) (0 .. 64), what a step
+  // that emits from the list reads instead of the bits to count a block's rows (host_logic.hpp, band_pair_count_eligible).  Written by the list's count pass,
+  // published, declined and freed with the list.
   struct BandRowWindows {
     std::string key; uint2* row_win; u64* pair_bits = nullptr;
     unsigned short* pair_list = nullptr; u32* pair_list_off = nullptr; u64 pair_survivors = 0; bool list_declined = false;
+    u8* pair_cnt = nullptr;
   };
   std::vector<BandRowWindows> band_row_windows;
   // the slice as the sorted input of a FILTER on its sort column (kernels.hip, run-copy form): lo[i] = first row whose id is >= first + i

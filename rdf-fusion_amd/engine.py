@@ -127,6 +127,7 @@ def load_library():
     lib.rdfgpu_band_row_cache_eligible.argtypes = [C.c_uint32] * 5 + [u32p, u32p]
     lib.rdfgpu_band_pair_cache_eligible.argtypes = [C.c_uint32] * 4 + [C.c_uint64] * 2
     lib.rdfgpu_band_pair_list_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
+    lib.rdfgpu_band_pair_count_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -188,6 +189,12 @@ def band_pair_list_eligible(survivors, n_blocks, pair_cached=True, option_set=Fa
     """.. and is a list of the surviving pairs kept beside the verdicts (host_logic.hpp)?  `survivors`: set bits of the verdicts; `n_blocks`:
     64 x 64 blocks of the in-place layout.  Kept when it is no larger than the bits: 2 * survivors <= 512 * n_blocks."""
     return bool(_check(load_library().rdfgpu_band_pair_list_eligible(int(pair_cached), int(option_set), int(survivors), int(n_blocks))))
+
+
+def band_pair_count_eligible(n_blocks, has_list=True, option_set=False, min_blocks=0):
+    """.. and does a step that emits from the list count its blocks' rows from the per-row counts kept with it, 64 bytes per block, instead of
+    the 512 bytes of bits (host_logic.hpp)?  `min_blocks`: the BAND_PAIR_COUNT_BLOCKS option (inclusive; 0 = automatic, 2^16 blocks)."""
+    return bool(_check(load_library().rdfgpu_band_pair_count_eligible(int(has_list), int(option_set), int(n_blocks), int(min_blocks))))
 
 
 def _pred_struct(p, keep):
