@@ -710,89 +710,140 @@ constexpr u32 kBandList = 1024;   // survivors listed at a time: a block with mo
 // six-column form kept 18 of them pinned and spilled scalars into vector lanes inside the loops)
 // STATIC (BandArgs::row_win): the row's one output value is row_val[row] — 4 bytes per row, not the 16-byte record.
 // CACHED (STATIC; the bits are the slice's cached verdicts): bvalid[blk] says which rows of the block have a value in this execution.
-// LIST (CACHED; BandArgs::pair_list): the block's survivors are read from the slice's list — band_emit_list.
-constexpr u32 kBandListAhead = 8;   // rounds of 64 list items a wave of the list form has in flight before its first round (whole rounds: the list is padded by one, Plan::band_row_windows)
-// The list form: the block's survivors, in output order, are a table of the slice; a step keeps the items whose row has a value in this execution.  Two round
-// trips per wave: everything indexed by the block number, then the rows' values, the entries' columns and the list's first kBandListAhead rounds (no load
-// inside the rounds: a wait there would wait for the round before's stores as well).  Per round of 64 items: row and entry unpacked, the columns fetched from the
-// owning lanes (ds_bpermute) — the row's value says whether the item counts —, the counting items compacted with a ballot and stored at scalar base + lane
-// offset.  No LDS, no per-lane loop; the block count is the layout's, known on the host.
-template <int NCOLS>
-__device__ __forceinline__ void band_emit_list(const BandArgs& b) {
+// LIST (CACHED; BandArgs::pair_list): the blocks' survivors are read from the slice's list — band_emit_list; NSLOT = its value slots, the row's value and the live entry columns.
+constexpr u32 kBandEmitGroup = 2;   // consecutive blocks a wave of the list form owns: their lists are one range of pair_list, their rows one range of the output (both offset arrays are exclusive scans)
+constexpr u32 kBandEmitAhead = 12;  // rounds of 64 list items of its group's range a wave has in flight before its first round.  Whole rounds: a round is loaded when its FIRST item lies inside the
+                                    // range, so its lanes read at most 63 items past the range's end — the next group's items or, behind the last group, the one round the list is padded by
+                                    // (Plan::band_row_windows allocates 64 items past the bound that every total is checked against); such lanes never count
+constexpr u32 kBandEmitTail = 4;    // .. and per further round trip of a range that is longer than that
+// The list form: the survivors of every block, in output order, are a table of the slice; a step keeps the items whose row has a value in this execution.  One-shot waves, kBandEmitGroup
+// blocks each (the last group is partial: blocks at or past max_blocks do not exist for it), so that the two memory round trips of a wave are paid once per group of blocks' worth of
+// stores.  First round trip: lane i <= G the output offset and the list offset of block g0 + i (clamped to the arrays' last entry), lane i < G its descriptor; a block's count is the
+// difference of its output offsets, and a group whose output range or list range is empty leaves here.  Second, all issued before the one wait: for every block of the group that has
+// items and rows to emit the rows' values and the entries' live columns (lane = row / entry, guarded by the block's own counts), and the first kBandEmitAhead rounds of the group's list
+// range.  The values go once into a table of the wave in LDS, G x 64 dwords per slot (wave-scope fence, no barrier); a block that emits nothing leaves kNil for its rows.  The rounds
+// then run over the group's whole range and do not restart at block boundaries: the item at position p of the range belongs to block (number of inner offsets <= p), its row's value and
+// its entry's columns are one LDS read each at block * 64 + row / entry — the row's value says whether the item counts —, the counting items are compacted with a ballot and stored at
+// scalar base + lane offset.  Compaction keeps the list's order and the blocks' order, so every block still starts at bofs[blk].  Slot s feeds the one output column that selects it (the
+// schedule gives every row / entry column to exactly one output column), so a round reads and stores exactly the live columns.  No load inside a batch of rounds (its wait would wait
+// for the stores before it as well); a range longer than the prefetch takes one more round trip per further kBandEmitTail rounds.
+template <int NCOLS, int NSLOT>
+__device__ __forceinline__ void band_emit_list(const BandArgs& b, u32* tab) {   // tab: this wave's NSLOT x (G x 64) dwords of LDS
+  constexpr u32 G = kBandEmitGroup, A = kBandEmitAhead;
+  constexpr bool HAS_ROW = NSLOT == NCOLS;                 // the one row column is an output column (else NSLOT == NCOLS + 1: the row's value only says which items count)
+  static_assert(NSLOT == NCOLS || NSLOT == NCOLS + 1, "slots = the row's value + the entry columns");
   const u32 lane = threadIdx.x & 63;
-  u32* outp[NCOLS]; u32 out_sel[NCOLS];
+  u32* dst[NSLOT];                                         // per slot: the output column it feeds (slot 0 = out_sel 0, slot 1 + u = out_sel 2 + u)
+  static_assert(kMaxCols >= 8 && NCOLS <= 8, "the selectors of the live columns are read as one 8-byte word");
+  u64 sel8; __builtin_memcpy(&sel8, b.out_sel, 8);         // (one aligned scalar load: single bytes of the argument block at odd offsets would be a vector load and a wait of their own)
 #pragma unroll
-  for (u32 oc = 0; oc < (u32)NCOLS; oc++) { outp[oc] = b.out[oc]; out_sel[oc] = b.out_sel[oc]; }
+  for (u32 sl = 0; sl < (u32)NSLOT; sl++) {
+    dst[sl] = b.out[0];
+#pragma unroll
+    for (u32 oc = 1; oc < (u32)NCOLS; oc++) dst[sl] = ((u32)(sel8 >> (8 * oc)) & 0xFFu) == (sl ? sl + 1 : 0u) ? b.out[oc] : dst[sl];
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0) {   // the exact total, whether or not it fitted
     const u64 total = b.bofs[b.max_blocks];
     *b.n_out_dev = total;
     if (total > b.out_cap) *b.overflow = 1u;
   }
-  const u32 blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-  if (blk >= b.max_blocks) return;                         // wave-uniform (in place: exact)
-  const u32 tot_v = b.bcount[blk];
-  const uint4 d = b.bdesc[blk];
-  const u32 run_v = b.bofs[blk];
-  const u32 l0_v = b.pair_list_off[blk], l1_v = b.pair_list_off[blk + 1];
-  asm volatile("" :: "v"(tot_v), "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w), "v"(run_v), "v"(l0_v), "v"(l1_v));   // (one round trip: all issued before the first wait)
-  if (__builtin_amdgcn_readfirstlane(tot_v) == 0) return;
-  const u32 eb = __builtin_amdgcn_readfirstlane(d.x), ne = __builtin_amdgcn_readfirstlane(d.y);
-  const u32 rb = __builtin_amdgcn_readfirstlane(d.z), nr = __builtin_amdgcn_readfirstlane(d.w);
-  const u32 lb = __builtin_amdgcn_readfirstlane(l0_v), ln = (u32)__builtin_amdgcn_readfirstlane(l1_v) - lb;
-  const u64 run0 = (u64)(u32)__builtin_amdgcn_readfirstlane(run_v);
-  const unsigned short* items = b.pair_list + lb;
-  u32 rv = kNil;                                           // this execution's value of the row (lane = row; kNil: none)
-  if (lane < nr) rv = b.row_val[rb + lane];
-  u32 ev[kBandMaxSideCols];                                // output values of the entry (lane = entry)
-#pragma unroll
-  for (u32 u = 0; u < kBandMaxSideCols; u++) { ev[u] = 0; if (u < b.n_entry_cols && lane < ne) ev[u] = b.eo[u][eb + lane]; }
-  u32 pre[kBandListAhead];                                 // (lanes past the list's end read the next block's items or the padding: they never count)
-#pragma unroll
-  for (u32 k = 0; k < kBandListAhead; k++) { pre[k] = 0; if (k * 64u < ln) pre[k] = items[k * 64u + lane]; }
-#pragma unroll
-  for (u32 k = 0; k < kBandListAhead; k++) asm volatile("" :: "v"(pre[k]));
-  asm volatile("" :: "v"(rv), "v"(ev[0]), "v"(ev[1]), "v"(ev[2]), "v"(ev[3]));
-  // per output column, once per block: the entry register it comes from.  A row column is the row's value, rvp below: this form knows ONE row column
-  // (out_sel 0; the cached windows imply the compact record, which carries one — launch_band_emit keeps a plan with two on the bits form), and its
-  // slot here holds ev[0], permuted with the others and dropped for rvp: one permute per round more than needed, for rounds without a branch.
-  u32 srcv[NCOLS];
-#pragma unroll
-  for (u32 oc = 0; oc < (u32)NCOLS; oc++) {
-    u32 src = ev[0];
-#pragma unroll
-    for (u32 u = 1; u < kBandMaxSideCols; u++) src = out_sel[oc] == 2 + u ? ev[u] : src;
-    srcv[oc] = src;
+  const u32 g0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4u + (threadIdx.x >> 6)) * G);
+  if (g0 >= b.max_blocks) return;                          // wave-uniform (in place: exact)
+  u32 bo_v = 0, lo_v = 0; uint4 d = make_uint4(0u, 0u, 0u, 0u);
+  if (lane <= G) {
+    const u32 at = g0 + lane < b.max_blocks ? g0 + lane : b.max_blocks;
+    bo_v = b.bofs[at]; lo_v = b.pair_list_off[at];
   }
-  // the block's output range starts at a wave-uniform offset: scalar base + 32-bit lane offset per store
-  const u64 room64 = b.out_cap > run0 ? b.out_cap - run0 : 0ull;           // rows that still fit (the count stays exact either way)
-  int room = room64 < 0x7FFFFFFFull ? (int)room64 : 0x7FFFFFFF;   // (signed, on the scalar unit: a block takes at most 4096 rows off it once it has run out)
-  u64 run_s = run0;
-  const u32 left = lane < ln ? ln - lane : 0u;             // items from this lane's first on: its item of the round at t0 is in the list iff t0 < left
-  auto round = [&](u32 item, u32 t0) {
-    u32 rvp = (u32)__builtin_amdgcn_ds_bpermute((int)((item >> 4) & 0xFCu), (int)rv);   // lane = the item's row
-    const int ea = (int)((item << 2) & 0xFCu);                                           // lane = the item's entry
-    u32 v[NCOLS];
+  if (lane < G && g0 + lane < b.max_blocks) d = b.bdesc[g0 + lane];
+  asm volatile("" :: "v"(bo_v), "v"(lo_v), "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w));   // (one round trip: all issued before the first wait)
+  u32 ofs[G + 1], lof[G + 1];
 #pragma unroll
-    for (u32 oc = 0; oc < (u32)NCOLS; oc++) v[oc] = (u32)__builtin_amdgcn_ds_bpermute(ea, (int)srcv[oc]);
-    rvp = t0 < left ? rvp : kNil;                          // past the list's end
+  for (u32 i = 0; i <= G; i++) { ofs[i] = __builtin_amdgcn_readlane(bo_v, i); lof[i] = __builtin_amdgcn_readlane(lo_v, i); }
+  if (ofs[G] == ofs[0] || lof[G] == lof[0]) return;        // nothing to emit in the whole group
+  const u32 len = lof[G] - lof[0];
+  const unsigned short* items = b.pair_list + lof[0];
+  u32 pre[A];
+#pragma unroll
+  for (u32 k = 0; k < A; k++) { pre[k] = 0; if (k * 64u < len) pre[k] = items[k * 64u + lane]; }
+  u32 val[G][NSLOT];                                       // [block][0]: this execution's value of the row (lane = row; kNil: none); [block][1 + u]: entry column u (lane = entry)
+#pragma unroll
+  for (u32 i = 0; i < G; i++) {
+    val[i][0] = kNil;
+#pragma unroll
+    for (u32 u = 1; u < (u32)NSLOT; u++) val[i][u] = 0;
+    if (lof[i + 1] != lof[i] && ofs[i + 1] != ofs[i]) {    // wave-uniform: the block has items and rows that count
+      const u32 eb = __builtin_amdgcn_readlane(d.x, i), ne = __builtin_amdgcn_readlane(d.y, i);
+      const u32 rb = __builtin_amdgcn_readlane(d.z, i), nr = __builtin_amdgcn_readlane(d.w, i);
+      if (lane < nr) val[i][0] = b.row_val[rb + lane];
+#pragma unroll
+      for (u32 u = 1; u < (u32)NSLOT; u++) if (lane < ne) val[i][u] = b.eo[u - 1][eb + lane];
+    }
+  }
+#pragma unroll
+  for (u32 k = 0; k < A; k++) asm volatile("" :: "v"(pre[k]));
+#pragma unroll
+  for (u32 i = 0; i < G; i++) {
+#pragma unroll
+    for (u32 u = 0; u < (u32)NSLOT; u++) asm volatile("" :: "v"(val[i][u]));
+  }
+#pragma unroll
+  for (u32 i = 0; i < G; i++) {
+#pragma unroll
+    for (u32 u = 0; u < (u32)NSLOT; u++) tab[u * (G * 64u) + i * 64u + lane] = val[i][u];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  u32 inner[G];                                            // the later blocks' first positions in the range (inner[0] unused)
+#pragma unroll
+  for (u32 i = 1; i < G; i++) inner[i] = lof[i] - lof[0];
+  // the group's output range starts at a wave-uniform offset: scalar base + 32-bit lane offset per store
+  const u64 run0 = (u64)ofs[0];
+  const u64 room64 = b.out_cap > run0 ? b.out_cap - run0 : 0ull;           // rows that still fit (the count stays exact either way)
+  int room = room64 < 0x7FFFFFFFull ? (int)room64 : 0x7FFFFFFF;   // (signed, on the scalar unit: a group takes at most G * 4096 rows off it once it has run out)
+  u64 run_s = run0;
+  const char* const tabc = reinterpret_cast<const char*>(tab);
+  auto round = [&](u32 item, u32 p0) {                     // p0: the round's first position in the range
+    const u32 p = p0 + lane;
+    u32 at = 0;                                            // byte offset of the item's block in a slot: 256 x (inner offsets <= p)
+#pragma unroll
+    for (u32 i = 1; i < G; i++) at += p >= inner[i] ? 256u : 0u;
+    u32 rvp = *reinterpret_cast<const u32*>(tabc + (at + ((item >> 4) & 0xFCu)));            // the item's row
+    const char* const ea = tabc + (at + ((item << 2) & 0xFCu));                               // the item's entry
+    u32 v[NSLOT];
+#pragma unroll
+    for (u32 u = 1; u < (u32)NSLOT; u++) v[u] = *reinterpret_cast<const u32*>(ea + u * (G * 256u));
+#pragma unroll
+    for (u32 u = 1; u < (u32)NSLOT; u++) asm volatile("" :: "v"(v[u]));   // (every read of the round in flight, then one wait: the compiler would sink the columns' reads below the branch, a second LDS latency per round)
+    rvp = p < len ? rvp : kNil;                            // past the range's end
     const u64 m = __builtin_amdgcn_ballot_w64(rvp != kNil);
     const u32 pos = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
     const int lim = room < 64 ? (room > 0 ? room : 0) : 64;
-    if (rvp != kNil && pos < (u32)lim) {
+    if (rvp != kNil && pos < (u32)lim) {                   // (scalar base + 32-bit lane offset)
+      if (HAS_ROW) *reinterpret_cast<u32*>(reinterpret_cast<char*>(dst[0] + run_s) + (pos << 2)) = rvp;
 #pragma unroll
-      for (u32 oc = 0; oc < (u32)NCOLS; oc++)                // (scalar base + 32-bit lane offset)
-        *reinterpret_cast<u32*>(reinterpret_cast<char*>(outp[oc] + run_s) + (pos << 2)) = out_sel[oc] == 0 ? rvp : v[oc];
+      for (u32 u = 1; u < (u32)NSLOT; u++) *reinterpret_cast<u32*>(reinterpret_cast<char*>(dst[u] + run_s) + (pos << 2)) = v[u];
     }
     const int n = __popcll(m);
     run_s += (u32)n; room -= n;
   };
 #pragma unroll
-  for (u32 k = 0; k < kBandListAhead; k++) { if (k * 64u >= ln) return; round(pre[k], k * 64u); }
-  for (u32 t0 = kBandListAhead * 64u; t0 < ln; t0 += 64) round((u32)items[t0 + lane], t0);   // (longer lists: a round trip per round)
+  for (u32 k = 0; k < A; k++) { if (k * 64u >= len) return; round(pre[k], k * 64u); }
+  for (u32 base = A * 64u; base < len; base += kBandEmitTail * 64u) {   // (longer ranges: a round trip per kBandEmitTail further rounds)
+    u32 more[kBandEmitTail];
+#pragma unroll
+    for (u32 k = 0; k < kBandEmitTail; k++) { more[k] = 0; if (base + k * 64u < len) more[k] = items[base + k * 64u + lane]; }
+#pragma unroll
+    for (u32 k = 0; k < kBandEmitTail; k++) asm volatile("" :: "v"(more[k]));
+#pragma unroll
+    for (u32 k = 0; k < kBandEmitTail; k++) { if (base + k * 64u >= len) return; round(more[k], base + k * 64u); }
+  }
 }
-template <int NCOLS, bool STATIC = false, bool CACHED = false, bool LIST = false>
+template <int NCOLS, bool STATIC = false, bool CACHED = false, bool LIST = false, int NSLOT = 0>
 __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
-  if constexpr (LIST) { band_emit_list<NCOLS>(b); return; } else {
+  if constexpr (LIST) {
+    __shared__ u32 tab[4][NSLOT * kBandEmitGroup * 64];
+    band_emit_list<NCOLS, NSLOT>(b, tab[threadIdx.x >> 6]);
+    return;
+  } else {
   __shared__ unsigned short list[4][kBandList];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u32 n_all = b.boff[b.kn];
@@ -953,13 +1004,20 @@ void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s
 void launch_band_emit(const BandArgs& b, hipStream_t s) {
   const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);
   static_assert(kBandMaxRowCols + kBandMaxSideCols == 6, "one instantiation per column count");
-  if (b.row_win && (b.bvalid || b.pair_cnt) && b.pair_list && b.n_row_cols <= 1) switch (b.n_out_cols) {   // the slice's list of survivors (band_emit_list: one row column)
-    case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true>), g, dim3(256), 0, s, b); return;
-    case 2: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true>), g, dim3(256), 0, s, b); return;
-    case 3: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true>), g, dim3(256), 0, s, b); return;
-    case 4: hipLaunchKernelGGL((band_emit_kernel<4, true, true, true>), g, dim3(256), 0, s, b); return;
-    case 5: hipLaunchKernelGGL((band_emit_kernel<5, true, true, true>), g, dim3(256), 0, s, b); return;
-    case 6: hipLaunchKernelGGL((band_emit_kernel<6, true, true, true>), g, dim3(256), 0, s, b); return;
+  if (b.row_win && (b.bvalid || b.pair_cnt) && b.pair_list && b.n_row_cols <= 1) {   // the slice's list of survivors (band_emit_list: one row column), a wave per kBandEmitGroup blocks
+    const u32 waves = (b.max_blocks + kBandEmitGroup - 1) / kBandEmitGroup;
+    const dim3 gl((waves + 3) / 4 ? (waves + 3) / 4 : 1);
+    if (b.n_out_cols == b.n_row_cols + b.n_entry_cols) switch (b.n_out_cols * 2 + b.n_row_cols) {   // (slots: the row's value + the entry columns)
+      case 3: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true, 1>), gl, dim3(256), 0, s, b); return;
+      case 5: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true, 2>), gl, dim3(256), 0, s, b); return;
+      case 7: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true, 3>), gl, dim3(256), 0, s, b); return;
+      case 9: hipLaunchKernelGGL((band_emit_kernel<4, true, true, true, 4>), gl, dim3(256), 0, s, b); return;
+      case 11: hipLaunchKernelGGL((band_emit_kernel<5, true, true, true, 5>), gl, dim3(256), 0, s, b); return;
+      case 2: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true, 2>), gl, dim3(256), 0, s, b); return;
+      case 4: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true, 3>), gl, dim3(256), 0, s, b); return;
+      case 6: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true, 4>), gl, dim3(256), 0, s, b); return;
+      case 8: hipLaunchKernelGGL((band_emit_kernel<4, true, true, true, 5>), gl, dim3(256), 0, s, b); return;
+    }
   }
   else if (b.row_win && b.bvalid) switch (b.n_out_cols) {
     case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true>), g, dim3(256), 0, s, b); return;
