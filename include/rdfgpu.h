@@ -967,9 +967,16 @@ uint32_t rdfgpu_shard_of(uint32_t id, uint32_t world);
  * can observe the difference), and the s / p / o id columns in HBM, ready for rdfgpu_store_extend_device (graph column =
  * zeros = the default graph).  The distinct terms come back as written in the file (`<iri>`, `_:b1`, `"lex"`, `"lex"@en`,
  * `"lex"^^<dt>`: rdfgpu_ntriples_terms) and decoded + typed (rdfgpu_ntriples_decoded): the host builds its dictionary from them —
- * per distinct term, not per triple.  Text: UTF-8, one triple per line, blank lines and `#`
- * comment lines allowed.  A malformed line is RDFGPU_ERR_INVALID with its number; two different terms with one 64-bit
- * hash (probability ~ n_terms^2 / 2^65) is RDFGPU_ERR_UNSUPPORTED — loud, never a wrong id.
+ * per distinct term, not per triple.  Text: UTF-8, one triple per line (lines end at LF; one CR before it, or before the end of the
+ * text, belongs to the line end), blank lines and `#` comment lines allowed and not counted.  A malformed line is RDFGPU_ERR_INVALID
+ * with its number among the counted lines (the first one, if several are).  Malformed is what the terminals of the N-Triples grammar
+ * refuse: IRIREF (no byte up to 0x20 and none of < > " { } | ^ ` \ inside, but UCHAR escapes), BLANK_NODE_LABEL (a label ends at the
+ * first byte that cannot belong to it, and not in `.`), LANGTAG, STRING_LITERAL_QUOTE (no raw LF or CR; ECHAR and UCHAR escapes, a UCHAR
+ * names a Unicode scalar value), an IRI as predicate, `.` and an optional comment after the object; white space between tokens is
+ * optional.  Not checked, and accepted: what lies behind the terminals (relative IRIs, BCP 47 subtag lengths, a UCHAR that decodes
+ * to a character no IRI may hold) and whether a code point above U+007F in a blank-node label is one of PN_CHARS.  A lone CR between
+ * terms is taken as white space; CR-only line ends and a leading byte-order mark are refused like any malformed line.  Two different
+ * terms with one 64-bit hash (probability ~ n_terms^2 / 2^65) is RDFGPU_ERR_UNSUPPORTED — loud, never a wrong id.
  */
 typedef struct rdfgpu_ntriples rdfgpu_ntriples;
 int rdfgpu_ntriples_parse(int32_t device, const char* text, uint64_t text_bytes, uint32_t first_id, rdfgpu_ntriples** out);

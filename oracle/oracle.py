@@ -116,7 +116,9 @@ def ntriples_encode(text):
     """The per-triple half of the reference's bulk load, restated (Store::load_from_reader, lib/rdf-fusion/src/store.rs:477-493
     -> MemObjectIdMapping::encode_quad, object_id_mapping.rs:106-116): every term of every triple line is interned, ids in
     insertion order from 1.  Returns (terms: list of bytes, id t + 1 = terms[t]; s, p, o id lists).  Terms are kept as
-    written (`<iri>`, `_:b`, `"lex"`, `"lex"@en`, `"lex"^^<dt>`).  Raises ValueError(line number) on a malformed line."""
+    written (`<iri>`, `_:b`, `"lex"`, `"lex"@en`, `"lex"^^<dt>`).  Raises ValueError(line number) on a malformed line: one that the
+    terminals of the N-Triples grammar refuse (IRIREF, BLANK_NODE_LABEL, LANGTAG, STRING_LITERAL_QUOTE, an IRI as predicate), scanned
+    byte by byte as nt_terms_kernel does; tests/nt_cases.py holds both to a reference written from the productions."""
     data = text.encode("utf-8") if isinstance(text, str) else bytes(text)
     ids, terms, cols = {}, [], ([], [], [])
     n_line = 0
@@ -132,31 +134,40 @@ def ntriples_encode(text):
             b = p
             c = line[p:p + 1]
             if c == b"<":
-                e = line.find(b">", p)
-                if e < 0:
-                    raise ValueError(n_line)
-                p = e + 1
+                p = _nt_iri_end(line, p + 1, n_line)
             elif line[p:p + 2] == b"_:":
-                while p < len(line) and line[p:p + 1] not in b" \t\r":
+                if k == 1:
+                    raise ValueError(n_line)                  # a blank node is no predicate
+                p += 2
+                if p >= len(line) or not (line[p:p + 1].isalnum() or line[p] in b"_:" or line[p] >= 0x80):
+                    raise ValueError(n_line)                  # an empty label, or a first character no label begins with
+                while p < len(line) and (line[p:p + 1].isalnum() or line[p] in b"_:-." or line[p] >= 0x80):
                     p += 1
-                if k == 2 and p > b + 2 and line[p - 1:p] == b".":
+                while line[p - 1:p] == b".":                  # a label does not end in `.`
                     p -= 1
             elif c == b'"' and k == 2:
                 p += 1
-                while p < len(line) and line[p:p + 1] != b'"':
+                while p < len(line) and line[p:p + 1] not in (b'"', b"\r"):
                     p += 2 if line[p:p + 1] == b"\\" else 1
-                if p >= len(line):
+                if p >= len(line) or line[p:p + 1] == b"\r":
                     raise ValueError(n_line)
                 p += 1
-                if line[p:p + 1] == b"@":
+                if line[p:p + 1] == b"@":                      # LANGTAG ::= '@' [a-zA-Z]+ ('-' [a-zA-Z0-9]+)*
                     p += 1
-                    while p < len(line) and (line[p:p + 1].isalnum() or line[p:p + 1] == b"-"):
-                        p += 1
-                elif line[p:p + 3] == b"^^<":
-                    e = line.find(b">", p)
-                    if e < 0:
+                    e = p
+                    while line[e:e + 1].isalpha():
+                        e += 1
+                    ok = e > p
+                    while ok and line[e:e + 1] == b"-":
+                        p = e = e + 1
+                        while line[e:e + 1].isalnum():
+                            e += 1
+                        ok = e > p
+                    if not ok:
                         raise ValueError(n_line)
-                    p = e + 1
+                    p = e
+                elif line[p:p + 3] == b"^^<":
+                    p = _nt_iri_end(line, p + 3, n_line)
             else:
                 raise ValueError(n_line)
             got.append(line[b:p])
@@ -173,6 +184,18 @@ def ntriples_encode(text):
                 terms.append(t)
             cols[k].append(ids[key])
     return terms, cols[0], cols[1], cols[2]
+
+
+def _nt_iri_end(line, p, n_line):
+    """IRIREF from the byte after `<`: the index behind the closing `>`; no byte up to 0x20 and none of < " { } | ^ ` inside
+    (a backslash is let through: _nt_unescape refuses one that opens no UCHAR)."""
+    while p < len(line) and line[p:p + 1] != b">":
+        if line[p] <= 0x20 or line[p] in b'<"{}|^`':
+            raise ValueError(n_line)
+        p += 1
+    if p >= len(line):
+        raise ValueError(n_line)
+    return p + 1
 
 
 _NT_ECHAR = {b"t": b"\t", b"b": b"\b", b"n": b"\n", b"r": b"\r", b"f": b"\f", b'"': b'"', b"'": b"'", b"\\": b"\\"}

@@ -5,11 +5,12 @@
 // lib/storage/src/memory/object_id_mapping.rs:106-116: three hash-map probes per triple, an insertion per new term).
 // Here the per-TRIPLE work runs on the device:
 //   nt_line_flags     which bytes start a triple line (not blank, not a `#` comment)           -> rocPRIM select = line starts
-//   nt_terms          one lane per line: the three term spans (`<iri>`, `_:b1`, `"lex"`, `"lex"@en`, `"lex"^^<dt>`), the closing
-//                     `.`, and a 64-bit hash of each term's CANONICAL bytes: kind, the lexical form with its escapes decoded
-//                     (ECHAR \t \b \n \r \f \" \' \\ and UCHAR \uXXXX / \UXXXXXXXX -> UTF-8, in literals and IRIs), the language
-//                     tag in lower case or the datatype IRI (`^^xsd:string` = a simple literal) — what the reference's parser
-//                     hands its interner (oxttl + oxrdf), so two spellings of one term get one id
+//   nt_terms          one lane per line: the three term spans (`<iri>`, `_:b1`, `"lex"`, `"lex"@en`, `"lex"^^<dt>`) scanned by the grammar's
+//                     terminals (a line that breaks one fails the call with its number), the closing `.`, and a 64-bit hash of each
+//                     term's CANONICAL bytes: kind, the lexical form with its escapes decoded (ECHAR \t \b \n \r \f \" \' \\ and UCHAR
+//                     \uXXXX / \UXXXXXXXX -> UTF-8, in literals and IRIs), the language tag in lower case or the decoded datatype IRI
+//                     (one that decodes to xsd:string = a simple literal) — what the reference's parser hands its interner (oxttl +
+//                     oxrdf), so two spellings of one term get one id
 //   radix sort        (hash, term occurrence) pairs                                              -> equal terms adjacent
 //   nt_unique         first occurrence of every distinct term; neighbours with one hash must be the same bytes (two
 //                     different terms with one 64-bit hash fail the call loudly — it is not papered over)
@@ -62,27 +63,6 @@ __device__ __forceinline__ void nt_fail(u64* err, u64 line, u32 code) {
 // A term span as written -> kind + the sub-spans of its lexical part and its suffix (language tag / datatype IRI, without delimiters)
 enum : u32 { NT_IRI = 1, NT_BNODE = 2, NT_SIMPLE = 3, NT_LANG = 4, NT_TYPED = 5 };
 struct NtSplit { u32 kind; u64 lb, le, sb, se; };
-__device__ __forceinline__ bool nt_eq_str(const unsigned char* t, u64 b, u64 e, const char* lit) {
-  u64 k = 0;
-  for (; lit[k]; k++) if (b + k >= e || t[b + k] != (unsigned char)lit[k]) return false;
-  return b + k == e;
-}
-__device__ __forceinline__ NtSplit nt_split(const unsigned char* t, u64 b, u64 e) {
-  NtSplit s{NT_IRI, b, e, e, e};
-  if (t[b] == '<') { s.kind = NT_IRI; s.lb = b + 1; s.le = e - 1; return s; }
-  if (t[b] == '_') { s.kind = NT_BNODE; s.lb = b + 2; s.le = e; return s; }
-  u64 q = b + 1;                                              // a literal: the closing quote is the first unescaped one
-  while (q < e && t[q] != '"') q += t[q] == '\\' ? 2 : 1;
-  s.lb = b + 1; s.le = q;
-  s.kind = NT_SIMPLE;
-  if (q + 1 < e && t[q + 1] == '@') { s.kind = NT_LANG; s.sb = q + 2; s.se = e; }
-  else if (q + 3 < e && t[q + 1] == '^') {
-    s.sb = q + 4; s.se = e - 1;                               // ^^< ... >
-    if (!nt_eq_str(t, s.sb, s.se, "http://www.w3.org/2001/XMLSchema#string")) s.kind = NT_TYPED;
-    else { s.sb = s.se = e; }                                 // "x"^^xsd:string IS the simple literal "x" (RDF 1.1; oxrdf normalises alike)
-  }
-  return s;
-}
 // Decodes [b, e) — ECHAR / UCHAR escapes -> bytes — feeding every byte to `emit`; false on a malformed escape.
 template <class F>
 __device__ __forceinline__ bool nt_decode(const unsigned char* t, u64 b, u64 e, bool echar_ok, F&& emit) {
@@ -120,6 +100,36 @@ __device__ __forceinline__ bool nt_decode(const unsigned char* t, u64 b, u64 e, 
   }
   return true;
 }
+// Is the datatype IRI [b, e) xsd:string once its UCHAR escapes are decoded?  Bytes as written are compared up to the first backslash; only from
+// there on is the rest decoded, so an IRI without escapes costs one pass over at most the constant's length.
+__device__ __forceinline__ bool nt_is_xsd_string(const unsigned char* t, u64 b, u64 e) {
+  const char* lit = "http://www.w3.org/2001/XMLSchema#string";
+  u64 k = 0;
+  for (; lit[k]; k++) {
+    if (b + k >= e) return false;
+    if (t[b + k] != (unsigned char)lit[k]) { if (t[b + k] != '\\') return false; break; }
+  }
+  if (!lit[k]) return b + k == e;
+  bool eq = true;
+  const bool ok = nt_decode(t, b + k, e, false, [&](unsigned char ch) { if (eq && lit[k] && ch == (unsigned char)lit[k]) k++; else eq = false; });
+  return ok && eq && !lit[k];
+}
+__device__ __forceinline__ NtSplit nt_split(const unsigned char* t, u64 b, u64 e) {
+  NtSplit s{NT_IRI, b, e, e, e};
+  if (t[b] == '<') { s.kind = NT_IRI; s.lb = b + 1; s.le = e - 1; return s; }
+  if (t[b] == '_') { s.kind = NT_BNODE; s.lb = b + 2; s.le = e; return s; }
+  u64 q = b + 1;                                              // a literal: the closing quote is the first unescaped one
+  while (q < e && t[q] != '"') q += t[q] == '\\' ? 2 : 1;
+  s.lb = b + 1; s.le = q;
+  s.kind = NT_SIMPLE;
+  if (q + 1 < e && t[q + 1] == '@') { s.kind = NT_LANG; s.sb = q + 2; s.se = e; }
+  else if (q + 3 < e && t[q + 1] == '^') {
+    s.sb = q + 4; s.se = e - 1;                               // ^^< ... >
+    if (!nt_is_xsd_string(t, s.sb, s.se)) s.kind = NT_TYPED;
+    else { s.sb = s.se = e; }                                 // "x"^^xsd:string IS the simple literal "x" (RDF 1.1; oxrdf normalises alike)
+  }
+  return s;
+}
 // every byte of the canonical form, in order: kind, decoded lexical form, 0xFF, suffix (language tag lower-cased / decoded datatype IRI)
 template <class F>
 __device__ __forceinline__ bool nt_canonical(const unsigned char* t, u64 b, u64 e, F&& emit) {
@@ -132,6 +142,24 @@ __device__ __forceinline__ bool nt_canonical(const unsigned char* t, u64 b, u64 
   return true;
 }
 
+// The grammar's terminals, on bytes.  IRIREF ::= '<' ([^#x00-#x20<>"{}|^`\] | UCHAR)* '>': from the byte after `<`, p is left behind the
+// closing `>`; false with p at the offending byte (a `\` is let through here: nt_decode refuses one that opens no UCHAR).
+__device__ __forceinline__ bool nt_scan_iri(const unsigned char* text, u64 n, u64& p) {
+  for (; p < n && text[p] != '>'; p++) {
+    const unsigned char c = text[p];
+    if (c <= 0x20 || c == '<' || c == '"' || c == '{' || c == '}' || c == '|' || c == '^' || c == '`') return false;
+  }
+  if (p >= n) return false;
+  p++;
+  return true;
+}
+__device__ __forceinline__ bool nt_alpha(unsigned char c) { return (unsigned char)((c | 32) - 'a') < 26; }
+__device__ __forceinline__ bool nt_digit(unsigned char c) { return (unsigned char)(c - '0') < 10; }
+// BLANK_NODE_LABEL ::= '_:' (PN_CHARS_U | [0-9]) ((PN_CHARS | '.')* PN_CHARS)?  A byte >= 0x80 (part of a code point above U+007F) counts as
+// a label character: the ranges of PN_CHARS above ASCII are not checked.
+__device__ __forceinline__ bool nt_label_start(unsigned char c) { return nt_alpha(c) || nt_digit(c) || c == '_' || c == ':' || c >= 0x80; }
+__device__ __forceinline__ bool nt_label_char(unsigned char c) { return nt_label_start(c) || c == '-' || c == '.'; }
+
 __global__ __launch_bounds__(256) void nt_terms_kernel(const unsigned char* text, u64 n, const u64* line_start, u64 n_lines,
                                                         u64* span_off, u32* span_len, u64* hash, u32* occ, u64* err) {
   const u64 l = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -143,22 +171,30 @@ __global__ __launch_bounds__(256) void nt_terms_kernel(const unsigned char* text
     if (p >= n) { nt_fail(err, l, 1); return; }
     const unsigned char c = text[p];
     if (c == '<') {
-      while (p < n && text[p] != '>' && text[p] != '\n') p++;
-      if (p >= n || text[p] != '>') { nt_fail(err, l, 2); return; }
       p++;
+      if (!nt_scan_iri(text, n, p)) { nt_fail(err, l, p < n && text[p] != '\n' ? 10 : 2); return; }
     } else if (c == '_' && p + 1 < n && text[p + 1] == ':') {
-      while (p < n && !nt_space(text[p]) && text[p] != '\n') p++;
-      if (k == 2 && p > b + 2 && text[p - 1] == '.') p--;                     // `_:b1.` without a space before the dot
+      if (k == 1) { nt_fail(err, l, 12); return; }
+      p += 2;
+      if (!nt_label_start(text[p])) { nt_fail(err, l, 11); return; }        // an empty label, or a first character no label begins with
+      while (nt_label_char(text[p])) p++;                                       // (the text ends in '\n' padding: no label runs past it)
+      while (text[p - 1] == '.') p--;                                           // a label does not end in `.`: `_:b1.` closes the triple, `_:a.b` is one label
     } else if (c == '"' && k == 2) {
       p++;
-      while (p < n && text[p] != '"' && text[p] != '\n') p += text[p] == '\\' ? 2 : 1;
+      while (p < n && text[p] != '"' && text[p] != '\n' && text[p] != '\r') p += text[p] == '\\' ? 2 : 1;
+      if (p < n && text[p] == '\r') { nt_fail(err, l, 14); return; }
       if (p >= n || text[p] != '"') { nt_fail(err, l, 3); return; }
       p++;
-      if (p < n && text[p] == '@') { p++; while (p < n && (((text[p] | 32) >= 'a' && (text[p] | 32) <= 'z') || (text[p] >= '0' && text[p] <= '9') || text[p] == '-')) p++; }
-      else if (p + 2 < n && text[p] == '^' && text[p + 1] == '^' && text[p + 2] == '<') {
-        while (p < n && text[p] != '>' && text[p] != '\n') p++;
-        if (p >= n || text[p] != '>') { nt_fail(err, l, 2); return; }
+      if (p < n && text[p] == '@') {                                            // LANGTAG ::= '@' [a-zA-Z]+ ('-' [a-zA-Z0-9]+)*
         p++;
+        const u64 t0 = p;
+        while (nt_alpha(text[p])) p++;
+        bool ok = p > t0;
+        while (ok && text[p] == '-') { p++; const u64 t1 = p; while (nt_alpha(text[p]) || nt_digit(text[p])) p++; ok = p > t1; }
+        if (!ok) { nt_fail(err, l, 13); return; }
+      } else if (p + 2 < n && text[p] == '^' && text[p + 1] == '^' && text[p + 2] == '<') {
+        p += 3;
+        if (!nt_scan_iri(text, n, p)) { nt_fail(err, l, p < n && text[p] != '\n' ? 10 : 2); return; }
       }
     } else { nt_fail(err, l, k == 2 ? 4 : 5); return; }                       // subject / predicate must be an IRI or a blank node
     unsigned long long h = 0xcbf29ce484222325ull;                             // FNV-1a over the term's CANONICAL bytes, then a finaliser
@@ -377,7 +413,9 @@ struct DevBuf {   // frees what a failed parse has allocated so far
 inline dim3 g256(u64 n) { return dim3((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1)); }
 const char* const kNtErrors[] = {"", "line ends inside a term", "unterminated IRI", "unterminated string literal", "object is not an IRI, a blank node or a literal",
                                  "subject / predicate is not an IRI or a blank node", "missing `.` after the object", "text after the closing `.`",
-                                 "two different terms share one 64-bit hash", "malformed escape sequence (ECHAR / UCHAR)"};
+                                 "two different terms share one 64-bit hash", "malformed escape sequence (ECHAR / UCHAR)",
+                                 "a character no IRI may hold (a space or control character, or one of < \" { } | ^ `)", "malformed blank-node label",
+                                 "a blank node as predicate", "malformed language tag", "carriage return inside a string literal"};
 }  // namespace
 
 NTriples::~NTriples() {
@@ -434,7 +472,7 @@ NTriples* ntriples_parse(int device, const char* text, u64 n, u32 first_id) {
     RDFGPU_HIP(hipStreamSynchronize(st));
     if (h_err != ~0ull) {
       const u32 code = (u32)(h_err & 0xFF);
-      fail(code == 8 ? RDFGPU_ERR_UNSUPPORTED : RDFGPU_ERR_INVALID, "N-Triples, triple line %llu: %s", (unsigned long long)(h_err >> 8) + 1, kNtErrors[code < 10 ? code : 0]);
+      fail(code == 8 ? RDFGPU_ERR_UNSUPPORTED : RDFGPU_ERR_INVALID, "N-Triples, triple line %llu: %s", (unsigned long long)(h_err >> 8) + 1, kNtErrors[code < sizeof(kNtErrors) / sizeof(kNtErrors[0]) ? code : 0]);
     }
   };
   check();
