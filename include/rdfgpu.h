@@ -891,6 +891,16 @@ int rdfgpu_band_pair_list_eligible(uint32_t pair_cached, uint32_t option_set, ui
  */
 int rdfgpu_band_pair_count_eligible(uint32_t has_list, uint32_t option_set, uint64_t n_blocks, uint64_t min_blocks);
 /*
+ * The form one band-join step runs in, the one decision the four above feed: 0 RECORDS (row records by key, every route that does not read the slice's rows through
+ * their cached windows), 1 ROW_WINDOWS (the pair test over the cached windows), 2 VERDICTS (the cached verdicts, bits expanded by the emit pass), 3 VERDICTS_LIST (..
+ * emitted from the slice's list), 4 COUNTS_LIST (.. and counted from the list's per-row counts).  row_static: the step reads the slice's rows in place through their
+ * cached windows; has_verdicts, has_list: the slice keeps the verdicts / the list with its counts for this chain; list_option_set, counts_option_set:
+ * RDFGPU_OPT_NO_BAND_PAIR_LIST and RDFGPU_OPT_NO_BAND_PAIR_COUNTS; n_row_cols: output columns taken from the row (the list serves at most one); n_blocks, min_blocks: as for
+ * rdfgpu_band_pair_count_eligible.
+ */
+int rdfgpu_band_step_form(uint32_t row_static, uint32_t has_verdicts, uint32_t has_list, uint32_t list_option_set, uint32_t counts_option_set,
+                          uint32_t n_row_cols, uint64_t n_blocks, uint64_t min_blocks);
+/*
  * MemIndexScanPredicate::try_and_with (scan_instructions.rs:170-210).  Predicates are given
  * as (pred, a, b) triples where IN sets are explicit arrays.  Writes the combined predicate;
  * `out_ids` needs room for min(na, nb) ids.  Returns 1 if combinable, 0 if not (EqualTo).

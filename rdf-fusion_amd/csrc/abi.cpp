@@ -601,6 +601,13 @@ int rdfgpu_band_pair_count_eligible(uint32_t has_list, uint32_t option_set, uint
   s.has_list = has_list != 0; s.option_off = option_set == 0; s.n_blocks = n_blocks; s.min_blocks = min_blocks;
   return band_pair_count_eligible(s) ? 1 : 0;
 }
+int rdfgpu_band_step_form(uint32_t row_static, uint32_t has_verdicts, uint32_t has_list, uint32_t list_option_set, uint32_t counts_option_set,
+                          uint32_t n_row_cols, uint64_t n_blocks, uint64_t min_blocks) {
+  BandStepShape s;
+  s.row_static = row_static != 0; s.has_verdicts = has_verdicts != 0; s.has_list = has_list != 0; s.list_option_off = list_option_set == 0;
+  s.counts_option_off = counts_option_set == 0; s.n_row_cols = n_row_cols; s.n_blocks = n_blocks; s.min_blocks = min_blocks;
+  return (int)band_step_form(s);
+}
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;
   if (p->pred == RDFGPU_PRED_IN) { if (p->ids) r.ids.assign(p->ids, p->ids + p->n_ids); else r.ids = {p->from}; }

@@ -25,10 +25,23 @@
 //                       i64 -> biased u32 interval), id operand                                    -> rocPRIM radix sort
 //   band_bounds_kernel  poff[k] = first sorted position with key >= k (one pass, gaps filled)
 //   band_blocks_scan    blocks (64 entries x 64 rows) per key, computed inside the scan's input iterator: boff = first block of a key -> band_desc_kernel
-//   band_mask_kernel    per block: the pair tests, 1 bit per pair, count per block (CACHED: the bits are a table of the slice, built by
-//                       band_pair_bits_kernel once per store version; a step applies its rows to them and counts)
+//   band_mask_kernel    per block: the pair tests, 1 bit per pair, count per block
 //   band_slow_kernel    rows whose operands are not all xsd:integer: full semantics (exits at once if there are none)
 //   band_emit_kernel    per block: bits -> output rows at the block's scanned offset, coalesced
+//
+// The two block passes run in one of five FORMS (BandForm, host_logic.hpp), decided once per step by band_step_form.  Plan sets the pointers of BandArgs from the form
+// (Plan::band_form_args), the launchers below are told it and pick the kernel by it; a form whose preconditions the arguments do not meet is refused before any launch.
+//
+//   form           mask pass                           emit pass      a step reads
+//   RECORDS        pair test over rec_s / aux_s        from records   every route that is not row_static: the rows' records, partitioned or written by key
+//   ROW_WINDOWS    pair test, STATIC                   STATIC         row_win (the slice's cached windows), row_val (this execution's values); its own masks
+//   VERDICTS       cached bits (band_cached_blocks)    CACHED         masks = the slice's pair_bits, built once per store version by band_pair_bits_kernel; bvalid
+//   VERDICTS_LIST  cached bits                         list           the above plus pair_list, pair_list_off (band_emit_list)
+//   COUNTS_LIST    per-row counts (band_count_blocks)  list           pair_cnt, pair_list, pair_list_off; masks and bvalid null
+//
+// Every form but RECORDS reads the slice's rows in place and needs the packed pair test with `!=` by entry index (neq_self, pack16) and at most one row column; the list
+// forms need every row and entry column to be exactly one output column.  The kernels take the form as a template parameter; a pass that does the same in two forms is
+// instantiated once (the mask pass for VERDICTS / VERDICTS_LIST, the emit pass for VERDICTS_LIST / COUNTS_LIST), and the forms that test no pair ignore NWIN, NEQ and PACK.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -435,7 +448,7 @@ __global__ __launch_bounds__(256) void band_desc_kernel(const BandArgs b) {
 // kernel is NOT bound by those instructions (7 -> 6 per pair changed nothing; 200 k short waves with exposed scalar-load
 // latency are what it waits for; persistent waves made it slower, 240 -> 325 us).
 // NWIN = window stages (1..2; no window = one trivial window); NEQ = base filter: 0 none / 1 `!=` / 2 `=` / 3 `!=` by entry index (BandArgs::neq_self).
-// STATIC = the rows' windows come from the slice's cached table (BandArgs::row_win, row_val; NEQ = 3 and PACK): 12 bytes per row instead of 16.
+// STATIC (the ROW_WINDOWS form) = the rows' windows come from the slice's cached table: 12 bytes per row instead of 16.
 struct BandEntry8 { uint4 a[8]; };
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 // The pair loop of one block, shared by the pair test of a step (band_mask_kernel) and the build of a slice's cached verdicts (band_pair_bits_kernel):
@@ -484,9 +497,8 @@ __device__ __forceinline__ u64 band_pair_block(const uint4* ent, u32 eb, u32 ne,
   if (NEQ == 3) { const u32 self = x - eb; if (self < 64u) mask &= ~(1ull << self); }   // the row's own entry, if it is in this chunk (x = its index)
   return mask;
 }
-// CACHED (STATIC; BandArgs::masks = the slice's cached verdicts, SliceTable::BandRowWindows::pair_bits): no pair is tested — band_cached_blocks.
 constexpr u32 kBandCachedBlocks = 4;   // blocks per wave of the cached form: their loads are independent, all in flight before the first wait
-// The cached form of the pair test: the block's 64 words are already what the test would write for rows that all have a table row, so a step
+// The mask pass of the VERDICTS forms, no pair tested: the block's 64 words (BandArgs::masks = the slice's pair_bits) are already what the test would write for rows that all have a table row, so a step
 // applies this execution's rows and counts.  Per block: valid = the lanes whose row has a value (bvalid, read by the emit kernel), bcount = the
 // bits of the valid lanes.  A streaming pass, two round trips per wave: descriptors and bits of kBandCachedBlocks blocks, then their rows' values.
 __device__ __forceinline__ void band_cached_blocks(const BandArgs& b) {
@@ -519,9 +531,8 @@ __device__ __forceinline__ void band_cached_blocks(const BandArgs& b) {
     if (lane == 63) { b.bcount[blk0 + k] = c; b.bvalid[blk0 + k] = rows; }
   }
 }
-// COUNTS (CACHED; BandArgs::pair_cnt = SliceTable::BandRowWindows::pair_cnt, the set bits of every cached word as a byte): the bits are not read — band_count_blocks.
 constexpr u32 kBandCountGroups = 4;   // groups of 4 blocks per wave of the counts form: 16 blocks, their loads independent and all in flight before the first wait
-// The counts form of the cached pair test, for a step that emits from the slice's list (band_emit_list reads neither the bits nor bvalid): all the step needs of
+// The mask pass of the COUNTS_LIST form, whose step emits from the slice's list (band_emit_list reads neither the bits nor bvalid): all the step needs of
 // the verdicts is bcount[blk] = the sum, over the rows that have a value in this execution, of the row's set bits — 64 bytes per block instead of 512.  A quarter
 // wave (one DPP row of 16 lanes) per block, 4 rows per lane: one dword of counts, the block's descriptor (one address per quarter wave), then the 4 rows' values,
 // each guarded by the block's row count (row_val has exactly the slice's rows: nothing is read past a block's last row).  No LDS, no atomics; bvalid and the bits untouched.
@@ -559,10 +570,13 @@ __device__ __forceinline__ void band_count_blocks(const BandArgs& b) {
     if (sub == 15u && blk < n_blocks) b.bcount[blk] = c;
   }
 }
-template <int NWIN, int NEQ, bool PACK, bool STATIC = false, bool CACHED = false, bool COUNTS = false>
+template <BandForm FORM, int NWIN = 0, int NEQ = 0, bool PACK = false>
 __global__ __launch_bounds__(256) void band_mask_kernel(const BandArgs b) {
-  if constexpr (COUNTS) { band_count_blocks(b); return; } else
-  if constexpr (CACHED) { band_cached_blocks(b); return; } else {
+  static_assert(FORM != BandForm::VERDICTS_LIST && (FORM == BandForm::RECORDS || FORM == BandForm::ROW_WINDOWS) == (NWIN != 0), "one instantiation per variant of the pass");
+  static_assert(FORM != BandForm::ROW_WINDOWS || (NEQ == 3 && PACK), "the cached windows are the packed form, `!=` by entry index");
+  constexpr bool STATIC = FORM == BandForm::ROW_WINDOWS;
+  if constexpr (FORM == BandForm::COUNTS_LIST) { band_count_blocks(b); return; } else
+  if constexpr (FORM == BandForm::VERDICTS) { band_cached_blocks(b); return; } else {
   __shared__ uint4 ent[4][64];
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // one wave per block; the grid is sized from the previous execution's block count, so a wave strides on in the rare case
@@ -708,9 +722,9 @@ __global__ __launch_bounds__(256) void band_slow_kernel(const LdsJoinArgs* ap, c
 constexpr u32 kBandList = 1024;   // survivors listed at a time: a block with more is emitted 16 rows at a time (16 x 64 <= 1024)
 // NCOLS = output columns (1 .. 6): a template parameter so that only the live columns' pointers and selectors sit in SGPRs (the
 // six-column form kept 18 of them pinned and spilled scalars into vector lanes inside the loops)
-// STATIC (BandArgs::row_win): the row's one output value is row_val[row] — 4 bytes per row, not the 16-byte record.
-// CACHED (STATIC; the bits are the slice's cached verdicts): bvalid[blk] says which rows of the block have a value in this execution.
-// LIST (CACHED; BandArgs::pair_list): the blocks' survivors are read from the slice's list — band_emit_list; NSLOT = its value slots, the row's value and the live entry columns.
+// STATIC (every form but RECORDS): the row's one output value is row_val[row] — 4 bytes per row, not the 16-byte record.
+// CACHED (the VERDICTS form): bvalid[blk] says which rows of the block have a value in this execution.
+// The list forms: the blocks' survivors are read from the slice's list — band_emit_list; NSLOT = its value slots, the row's value and the live entry columns.
 constexpr u32 kBandEmitGroup = 2;   // consecutive blocks a wave of the list form owns: their lists are one range of pair_list, their rows one range of the output (both offset arrays are exclusive scans)
 constexpr u32 kBandEmitAhead = 12;  // rounds of 64 list items of its group's range a wave has in flight before its first round.  Whole rounds: a round is loaded when its FIRST item lies inside the
                                     // range, so its lanes read at most 63 items past the range's end — the next group's items or, behind the last group, the one round the list is padded by
@@ -837,9 +851,11 @@ __device__ __forceinline__ void band_emit_list(const BandArgs& b, u32* tab) {   
     for (u32 k = 0; k < kBandEmitTail; k++) { if (base + k * 64u >= len) return; round(more[k], base + k * 64u); }
   }
 }
-template <int NCOLS, bool STATIC = false, bool CACHED = false, bool LIST = false, int NSLOT = 0>
+template <BandForm FORM, int NCOLS, int NSLOT = 0>
 __global__ __launch_bounds__(256) void band_emit_kernel(const BandArgs b) {
-  if constexpr (LIST) {
+  static_assert(FORM != BandForm::COUNTS_LIST && (FORM == BandForm::VERDICTS_LIST) == (NSLOT != 0), "one instantiation per variant of the pass");
+  constexpr bool STATIC = FORM != BandForm::RECORDS, CACHED = FORM == BandForm::VERDICTS;
+  if constexpr (FORM == BandForm::VERDICTS_LIST) {
     __shared__ u32 tab[4][NSLOT * kBandEmitGroup * 64];
     band_emit_list<NCOLS, NSLOT>(b, tab[threadIdx.x >> 6]);
     return;
@@ -960,30 +976,45 @@ void launch_band_entries(const BandArgs& b, hipStream_t s) {
 void launch_band_desc(const BandArgs& b, hipStream_t s) {
   hipLaunchKernelGGL(band_desc_kernel, grid256(b.kn), dim3(256), 0, s, b);
 }
-template <int NWIN, bool PACK> static void launch_band_mask_w(const BandArgs& b, dim3 g, hipStream_t s) {
-  const int neq = b.has_neq ? (b.neq_is_eq ? 2 : b.neq_self ? 3 : 1) : 0;
-  if (neq == 3) {
-    if constexpr (PACK) {
-      if (b.row_win && b.pair_cnt) {   // the cached verdicts' per-row counts: a wave per 4 * kBandCountGroups blocks
-        const u32 waves = (b.max_blocks + 4 * kBandCountGroups - 1) / (4 * kBandCountGroups);
-        hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true, true, true>), dim3((waves + 3) / 4 ? (waves + 3) / 4 : 1), dim3(256), 0, s, b);
-      } else if (b.row_win && b.bvalid) {   // the cached verdicts: a wave per kBandCachedBlocks blocks
-        const u32 waves = (b.max_blocks + kBandCachedBlocks - 1) / kBandCachedBlocks;
-        hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true, true>), dim3((waves + 3) / 4 ? (waves + 3) / 4 : 1), dim3(256), 0, s, b);
-      } else if (b.row_win) hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true, true>), g, dim3(256), 0, s, b);
-      else hipLaunchKernelGGL((band_mask_kernel<NWIN, 3, true>), g, dim3(256), 0, s, b);
-      return;
-    }
-  }
-  if (neq == 0) hipLaunchKernelGGL((band_mask_kernel<NWIN, 0, PACK>), g, dim3(256), 0, s, b);
-  else if (neq == 1) hipLaunchKernelGGL((band_mask_kernel<NWIN, 1, PACK>), g, dim3(256), 0, s, b);
-  else hipLaunchKernelGGL((band_mask_kernel<NWIN, 2, PACK>), g, dim3(256), 0, s, b);
+// What a form needs of the arguments, checked before either block pass launches anything: a form is never swapped for another one.
+static void band_form_check(const BandArgs& b, BandForm form) {
+  const char* const name = band_form_name(form);
+  if (b.neq_self && (!b.has_neq || b.neq_is_eq || !b.pack16)) fail(RDFGPU_ERR_INVALID, "band join: form %s, `!=` by entry index without the packed `!=` pair test", name);
+  if (form == BandForm::RECORDS) return;
+  if (!b.neq_self || b.n_row_cols > 1)
+    fail(RDFGPU_ERR_INVALID, "band join: form %s needs the packed pair test with `!=` by entry index and at most one row column (neq_self %u, pack16 %u, %u row columns)", name, b.neq_self, b.pack16, b.n_row_cols);
+  if ((form == BandForm::VERDICTS_LIST || form == BandForm::COUNTS_LIST) && b.n_out_cols != b.n_row_cols + b.n_entry_cols)
+    fail(RDFGPU_ERR_INVALID, "band join: form %s needs every row and entry column to be one output column (%u output, %u row, %u entry columns)", name, b.n_out_cols, b.n_row_cols, b.n_entry_cols);
 }
-void launch_band_mask(const BandArgs& b, hipStream_t s) {
-  const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);   // the number of blocks lives on the device: surplus waves leave at once, missing ones are made up by striding
+static inline dim3 grid_waves(u32 waves) { return dim3((waves + 3) / 4 ? (waves + 3) / 4 : 1); }   // four waves per workgroup
+template <int NWIN, bool PACK> static void launch_band_pairs(const BandArgs& b, dim3 g, hipStream_t s) {   // the RECORDS form's pair test
+  const int neq = b.has_neq ? (b.neq_is_eq ? 2 : b.neq_self ? 3 : 1) : 0;
+  if (neq == 0) hipLaunchKernelGGL((band_mask_kernel<BandForm::RECORDS, NWIN, 0, PACK>), g, dim3(256), 0, s, b);
+  else if (neq == 2) hipLaunchKernelGGL((band_mask_kernel<BandForm::RECORDS, NWIN, 2, PACK>), g, dim3(256), 0, s, b);
+  else if (neq == 3) { if constexpr (PACK) hipLaunchKernelGGL((band_mask_kernel<BandForm::RECORDS, NWIN, 3, true>), g, dim3(256), 0, s, b); }   // (packed only: band_form_check)
+  else hipLaunchKernelGGL((band_mask_kernel<BandForm::RECORDS, NWIN, 1, PACK>), g, dim3(256), 0, s, b);
+}
+void launch_band_mask(const BandArgs& b, BandForm form, hipStream_t s) {
+  band_form_check(b, form);
+  const dim3 g = grid_waves(b.launch_blocks);   // the number of blocks lives on the device: surplus waves leave at once, missing ones are made up by striding
   // (one wave per block beats persistent waves here: 2048 / 4096 / 8192 workgroups striding over the blocks took 223 / 211 / 202 us against 187)
-  if (b.pack16) { if (b.n_win == 2) launch_band_mask_w<2, true>(b, g, s); else launch_band_mask_w<1, true>(b, g, s); }
-  else if (b.n_win == 2) launch_band_mask_w<2, false>(b, g, s); else launch_band_mask_w<1, false>(b, g, s);   // no window = one trivial window
+  switch (form) {
+    case BandForm::RECORDS:   // no window = one trivial window
+      if (b.pack16) { if (b.n_win == 2) launch_band_pairs<2, true>(b, g, s); else launch_band_pairs<1, true>(b, g, s); }
+      else if (b.n_win == 2) launch_band_pairs<2, false>(b, g, s); else launch_band_pairs<1, false>(b, g, s);
+      return;
+    case BandForm::ROW_WINDOWS:
+      if (b.n_win == 2) hipLaunchKernelGGL((band_mask_kernel<BandForm::ROW_WINDOWS, 2, 3, true>), g, dim3(256), 0, s, b);
+      else hipLaunchKernelGGL((band_mask_kernel<BandForm::ROW_WINDOWS, 1, 3, true>), g, dim3(256), 0, s, b);
+      return;
+    case BandForm::VERDICTS: case BandForm::VERDICTS_LIST:   // a wave per kBandCachedBlocks blocks
+      hipLaunchKernelGGL(band_mask_kernel<BandForm::VERDICTS>, grid_waves((b.max_blocks + kBandCachedBlocks - 1) / kBandCachedBlocks), dim3(256), 0, s, b);
+      return;
+    case BandForm::COUNTS_LIST:   // a wave per 4 * kBandCountGroups blocks
+      hipLaunchKernelGGL(band_mask_kernel<BandForm::COUNTS_LIST>, grid_waves((b.max_blocks + 4 * kBandCountGroups - 1) / (4 * kBandCountGroups)), dim3(256), 0, s, b);
+      return;
+  }
+  fail(RDFGPU_ERR_INVALID, "band join: form %u", (u32)form);
 }
 void launch_band_pair_bits(const BandArgs& b, hipStream_t s) {
   if (!b.max_blocks) return;
@@ -1001,49 +1032,46 @@ void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s
   const u32 g = (b.max_blocks + 3) / 4;
   hipLaunchKernelGGL(band_slow_kernel, dim3(g < 2048u ? (g ? g : 1u) : 2048u), dim3(256), 0, s, a_dev, b);
 }
-void launch_band_emit(const BandArgs& b, hipStream_t s) {
-  const dim3 g((b.launch_blocks + 3) / 4 ? (b.launch_blocks + 3) / 4 : 1);
+template <BandForm FORM> static bool launch_band_emit_cols(const BandArgs& b, dim3 g, hipStream_t s) {   // one instantiation per column count; false: none for b.n_out_cols
   static_assert(kBandMaxRowCols + kBandMaxSideCols == 6, "one instantiation per column count");
-  if (b.row_win && (b.bvalid || b.pair_cnt) && b.pair_list && b.n_row_cols <= 1) {   // the slice's list of survivors (band_emit_list: one row column), a wave per kBandEmitGroup blocks
-    const u32 waves = (b.max_blocks + kBandEmitGroup - 1) / kBandEmitGroup;
-    const dim3 gl((waves + 3) / 4 ? (waves + 3) / 4 : 1);
-    if (b.n_out_cols == b.n_row_cols + b.n_entry_cols) switch (b.n_out_cols * 2 + b.n_row_cols) {   // (slots: the row's value + the entry columns)
-      case 3: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true, 1>), gl, dim3(256), 0, s, b); return;
-      case 5: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true, 2>), gl, dim3(256), 0, s, b); return;
-      case 7: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true, 3>), gl, dim3(256), 0, s, b); return;
-      case 9: hipLaunchKernelGGL((band_emit_kernel<4, true, true, true, 4>), gl, dim3(256), 0, s, b); return;
-      case 11: hipLaunchKernelGGL((band_emit_kernel<5, true, true, true, 5>), gl, dim3(256), 0, s, b); return;
-      case 2: hipLaunchKernelGGL((band_emit_kernel<1, true, true, true, 2>), gl, dim3(256), 0, s, b); return;
-      case 4: hipLaunchKernelGGL((band_emit_kernel<2, true, true, true, 3>), gl, dim3(256), 0, s, b); return;
-      case 6: hipLaunchKernelGGL((band_emit_kernel<3, true, true, true, 4>), gl, dim3(256), 0, s, b); return;
-      case 8: hipLaunchKernelGGL((band_emit_kernel<4, true, true, true, 5>), gl, dim3(256), 0, s, b); return;
-    }
+  switch (b.n_out_cols) {
+    case 1: hipLaunchKernelGGL((band_emit_kernel<FORM, 1>), g, dim3(256), 0, s, b); return true;
+    case 2: hipLaunchKernelGGL((band_emit_kernel<FORM, 2>), g, dim3(256), 0, s, b); return true;
+    case 3: hipLaunchKernelGGL((band_emit_kernel<FORM, 3>), g, dim3(256), 0, s, b); return true;
+    case 4: hipLaunchKernelGGL((band_emit_kernel<FORM, 4>), g, dim3(256), 0, s, b); return true;
+    case 5: hipLaunchKernelGGL((band_emit_kernel<FORM, 5>), g, dim3(256), 0, s, b); return true;
+    case 6: hipLaunchKernelGGL((band_emit_kernel<FORM, 6>), g, dim3(256), 0, s, b); return true;
   }
-  else if (b.row_win && b.bvalid) switch (b.n_out_cols) {
-    case 1: hipLaunchKernelGGL((band_emit_kernel<1, true, true>), g, dim3(256), 0, s, b); return;
-    case 2: hipLaunchKernelGGL((band_emit_kernel<2, true, true>), g, dim3(256), 0, s, b); return;
-    case 3: hipLaunchKernelGGL((band_emit_kernel<3, true, true>), g, dim3(256), 0, s, b); return;
-    case 4: hipLaunchKernelGGL((band_emit_kernel<4, true, true>), g, dim3(256), 0, s, b); return;
-    case 5: hipLaunchKernelGGL((band_emit_kernel<5, true, true>), g, dim3(256), 0, s, b); return;
-    case 6: hipLaunchKernelGGL((band_emit_kernel<6, true, true>), g, dim3(256), 0, s, b); return;
+  return false;
+}
+// The list form (band_emit_list): NSLOT value slots = the row's value + the entry columns; the row's value is an output column (NSLOT == NCOLS) or only says which items count.
+static bool launch_band_emit_list(const BandArgs& b, dim3 g, hipStream_t s) {
+  constexpr BandForm L = BandForm::VERDICTS_LIST;
+  switch (b.n_out_cols * 2 + b.n_row_cols) {
+    case 3: hipLaunchKernelGGL((band_emit_kernel<L, 1, 1>), g, dim3(256), 0, s, b); return true;
+    case 5: hipLaunchKernelGGL((band_emit_kernel<L, 2, 2>), g, dim3(256), 0, s, b); return true;
+    case 7: hipLaunchKernelGGL((band_emit_kernel<L, 3, 3>), g, dim3(256), 0, s, b); return true;
+    case 9: hipLaunchKernelGGL((band_emit_kernel<L, 4, 4>), g, dim3(256), 0, s, b); return true;
+    case 11: hipLaunchKernelGGL((band_emit_kernel<L, 5, 5>), g, dim3(256), 0, s, b); return true;
+    case 2: hipLaunchKernelGGL((band_emit_kernel<L, 1, 2>), g, dim3(256), 0, s, b); return true;
+    case 4: hipLaunchKernelGGL((band_emit_kernel<L, 2, 3>), g, dim3(256), 0, s, b); return true;
+    case 6: hipLaunchKernelGGL((band_emit_kernel<L, 3, 4>), g, dim3(256), 0, s, b); return true;
+    case 8: hipLaunchKernelGGL((band_emit_kernel<L, 4, 5>), g, dim3(256), 0, s, b); return true;
   }
-  else if (b.row_win) switch (b.n_out_cols) {
-    case 1: hipLaunchKernelGGL((band_emit_kernel<1, true>), g, dim3(256), 0, s, b); return;
-    case 2: hipLaunchKernelGGL((band_emit_kernel<2, true>), g, dim3(256), 0, s, b); return;
-    case 3: hipLaunchKernelGGL((band_emit_kernel<3, true>), g, dim3(256), 0, s, b); return;
-    case 4: hipLaunchKernelGGL((band_emit_kernel<4, true>), g, dim3(256), 0, s, b); return;
-    case 5: hipLaunchKernelGGL((band_emit_kernel<5, true>), g, dim3(256), 0, s, b); return;
-    case 6: hipLaunchKernelGGL((band_emit_kernel<6, true>), g, dim3(256), 0, s, b); return;
+  return false;
+}
+void launch_band_emit(const BandArgs& b, BandForm form, hipStream_t s) {
+  band_form_check(b, form);
+  const dim3 g = grid_waves(b.launch_blocks);
+  bool launched = false;
+  switch (form) {
+    case BandForm::RECORDS: launched = launch_band_emit_cols<BandForm::RECORDS>(b, g, s); break;
+    case BandForm::ROW_WINDOWS: launched = launch_band_emit_cols<BandForm::ROW_WINDOWS>(b, g, s); break;
+    case BandForm::VERDICTS: launched = launch_band_emit_cols<BandForm::VERDICTS>(b, g, s); break;
+    case BandForm::VERDICTS_LIST: case BandForm::COUNTS_LIST:   // a wave per kBandEmitGroup blocks
+      launched = launch_band_emit_list(b, grid_waves((b.max_blocks + kBandEmitGroup - 1) / kBandEmitGroup), s); break;
   }
-  else switch (b.n_out_cols) {
-    case 1: hipLaunchKernelGGL(band_emit_kernel<1>, g, dim3(256), 0, s, b); return;
-    case 2: hipLaunchKernelGGL(band_emit_kernel<2>, g, dim3(256), 0, s, b); return;
-    case 3: hipLaunchKernelGGL(band_emit_kernel<3>, g, dim3(256), 0, s, b); return;
-    case 4: hipLaunchKernelGGL(band_emit_kernel<4>, g, dim3(256), 0, s, b); return;
-    case 5: hipLaunchKernelGGL(band_emit_kernel<5>, g, dim3(256), 0, s, b); return;
-    case 6: hipLaunchKernelGGL(band_emit_kernel<6>, g, dim3(256), 0, s, b); return;
-  }
-  fail(RDFGPU_ERR_INVALID, "band join with %u output columns", b.n_out_cols);
+  if (!launched) fail(RDFGPU_ERR_INVALID, "band join: form %s with %u output columns (%u from the row)", band_form_name(form), b.n_out_cols, b.n_row_cols);
 }
 
 // blocks (64 entries x 64 rows) per key, scanned in one go: boff[k] = first block of key k, boff[kn] = all blocks.  The per-key

@@ -172,4 +172,13 @@ bool band_pair_count_eligible(const BandPairCountShape& s) {
   return s.n_blocks >= (s.min_blocks ? s.min_blocks : kBandPairCountBlocks);
 }
 
+BandForm band_step_form(const BandStepShape& s) {
+  if (!s.row_static) return BandForm::RECORDS;
+  if (!s.has_verdicts) return BandForm::ROW_WINDOWS;
+  if (!s.has_list || !s.list_option_off || s.n_row_cols > 1) return BandForm::VERDICTS;
+  BandPairCountShape c;
+  c.has_list = true; c.option_off = s.counts_option_off; c.n_blocks = s.n_blocks; c.min_blocks = s.min_blocks;
+  return band_pair_count_eligible(c) ? BandForm::COUNTS_LIST : BandForm::VERDICTS_LIST;
+}
+
 }  // namespace rdfgpu

@@ -81,4 +81,20 @@ constexpr u64 kBandPairCountBlocks = 1ull << 16;
 struct BandPairCountShape { bool has_list = false, option_off = false; u64 n_blocks = 0, min_blocks = 0; };
 bool band_pair_count_eligible(const BandPairCountShape& s);
 
+// The way one band-join step runs (band_join.hip's header has the table: what the mask pass and the emit pass do in each form, and what the step reads).  Decided
+// here, once per step; Plan sets the kernel arguments from it and the launchers pick their kernels by it.
+enum class BandForm : u32 { RECORDS, ROW_WINDOWS, VERDICTS, VERDICTS_LIST, COUNTS_LIST };
+constexpr const char* band_form_name(BandForm f) {
+  return f == BandForm::RECORDS ? "RECORDS" : f == BandForm::ROW_WINDOWS ? "ROW_WINDOWS" : f == BandForm::VERDICTS ? "VERDICTS" : f == BandForm::VERDICTS_LIST ? "VERDICTS_LIST" : "COUNTS_LIST";
+}
+// row_static: the step reads the slice's rows in place, through their cached windows and this execution's values by key (else: RECORDS, whatever the slice keeps).
+// has_verdicts / has_list: the slice keeps the pair test's verdicts / their list and per-row counts for this chain, built under options like this plan's.  The list
+// serves a step that streams the verdicts, has at most one row column (the list form of the emit pass knows one) and whose RDFGPU_OPT_NO_BAND_PAIR_LIST is off;
+// such a step counts from the per-row counts when band_pair_count_eligible says so for the layout's n_blocks.
+struct BandStepShape {
+  bool row_static = false, has_verdicts = false, has_list = false, list_option_off = false, counts_option_off = false;
+  u32 n_row_cols = 0; u64 n_blocks = 0, min_blocks = 0;
+};
+BandForm band_step_form(const BandStepShape& s);
+
 }  // namespace rdfgpu

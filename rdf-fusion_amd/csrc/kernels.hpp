@@ -3,6 +3,7 @@
 #include <functional>
 #include "common.hpp"
 #include "expr_device.hpp"
+#include "host_logic.hpp"
 
 namespace rdfgpu {
 
@@ -362,7 +363,7 @@ struct OrderedJoinArgs {
   u32* row_head; unsigned char* row_cnt;                               // per slice row, from the count pass: first table row of its chain, chain length (capped at 255: longer chains are re-walked)
   u32* multi_rows;                                                     // table rows hung behind an existing chain head (null: not counted): a chain of 2+ rows rules out the in-place band records
   uint4* key_rec;                                                      // in place (OjInPlace): [kn] the band record of each key's table row, filled with one that passes nothing by the probe pass
-  u32* key_val;                                                        // .. with the rows' windows cached on the slice (BandArgs::row_win): [kn] the output value of each key's table row instead, filled with kNil (no table row)
+  u32* key_val;                                                        // .. with the rows' windows cached on the slice (every BandForm but RECORDS): [kn] the output value of each key's table row instead, filled with kNil (no table row)
 };
 struct BandArgs;
 // The ordered slice join feeding a band join (band_join.hip) writes the band join's ROW RECORDS itself: the windows, the id
@@ -500,18 +501,18 @@ struct BandArgs {
   ColRef entry_col[kBandMaxSideCols]; const u32* row_col[kBandMaxSideCols];
   u8 out_from_row[kMaxCols];  // per output column: 1 = next row column, 0 = next entry column
   u8 out_sel[kMaxCols];       // .. resolved: 0 / 1 = row column 0 / 1, 2 + u = entry column u
-  // in place, when a row's windows are a function of its join key alone (both operands reached through stages keyed by that key: host_logic.hpp,
-  // band_row_cache_eligible): row_win = the packed {lo pair, width pair} of every slice row, kept on the slice per store version beside the entries;
-  // row_val = this execution's output value per slice row (kNil: no table row has the row's key — its record passes nothing).  rec_s is not used.
+  // What the step's form adds (BandForm; the table of the forms heads band_join.hip).  Plan::band_form_args sets these from the form and nothing else does; the
+  // launchers are told the form and do not look at them; a form that does not read a field leaves it null.
+  // row_win, row_val (every form but RECORDS, which streams rec_s): the packed {lo pair, width pair} of every slice row, kept on the slice per store version beside the
+  // entries; this execution's output value per slice row (kNil: no table row has the row's key — the row passes nothing).
   const uint2* row_win; const u32* row_val;
-  // .. and the pair test's verdicts are cached too (masks = SliceTable::BandRowWindows::pair_bits, never written by a step): per block the rows that
-  // have a value in this execution, one bit per lane — written by the cached form of the mask pass, applied by the emit kernel.  Null: masks is this execution's own.
+  // bvalid (VERDICTS, VERDICTS_LIST: masks is the slice's SliceTable::BandRowWindows::pair_bits, read and never written): per block the rows that have a value in this
+  // execution, one bit per lane — written by the mask pass, applied by the emit pass.
   u64* bvalid;
-  // .. and beside them the list of their set bits (SliceTable::BandRowWindows::pair_list; the list form of the emit kernel): block blk's surviving pairs are
-  // pair_list[pair_list_off[blk] .. pair_list_off[blk + 1]), (row << 6) | entry each, rows ascending and entries ascending within a row.  Null: the emit kernel expands the bits.
+  // pair_list, pair_list_off (VERDICTS_LIST, COUNTS_LIST): block blk's surviving pairs are pair_list[pair_list_off[blk] .. pair_list_off[blk + 1]), (row << 6) | entry
+  // each, rows ascending and entries ascending within a row.
   const unsigned short* pair_list; const u32* pair_list_off;
-  // .. and the set bits of every cached word as a byte (SliceTable::BandRowWindows::pair_cnt; the counts form of the mask pass, host_logic.hpp:
-  // band_pair_count_eligible): pair_cnt[blk * 64 + row] = popcount(masks[blk * 64 + row]).  Set: the step counts from these 64 B per block, masks and bvalid are null.
+  // pair_cnt (COUNTS_LIST: masks and bvalid are null): pair_cnt[blk * 64 + row] = the set bits of the slice's verdict word of (blk, row), one byte each.
   const unsigned char* pair_cnt;
 };
 // The build of a slice's pair list from its cached verdicts (band_join.hip): the set bits of every block counted (counts[n_blocks] = 0), the counts scanned into `off`
@@ -540,9 +541,9 @@ void launch_band_decode(const BandArgs& b, hipStream_t s);   // + sort keys
 void launch_band_bounds(const u32* skey_sorted, u64 n, u32 kn, u32* poff, hipStream_t s);
 size_t band_blocks_scan_temp_bytes(u32 kn);
 void band_blocks_scan(const u32* csr_off, const u32* poff, u32 kn, u32* boff, void* temp, size_t temp_bytes, hipStream_t s);   // blocks per key computed inside the scan's input iterator
-void launch_band_mask(const BandArgs& b, hipStream_t s);
+void launch_band_mask(const BandArgs& b, BandForm form, hipStream_t s);   // (both block passes: a form whose preconditions b does not meet is RDFGPU_ERR_INVALID before any launch)
 void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s);   // patches masks / counts of the rare slow rows
-void launch_band_emit(const BandArgs& b, hipStream_t s);
+void launch_band_emit(const BandArgs& b, BandForm form, hipStream_t s);
 size_t sort_u32_temp_bytes(u64 n, u32 bits);
 void sort_pairs_u32_u32(const u32* kin, u32* kout, const u32* vin, u32* vout, u64 n, u32 bits, void* temp, size_t temp_bytes, hipStream_t s);
 void launch_val_minmax(const long long* val, u64 n, long long* out_minmax /* preset {INT64_MAX, INT64_MIN + 1} */, hipStream_t s);

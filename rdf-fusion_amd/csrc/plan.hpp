@@ -133,16 +133,18 @@ struct BandJoin {
   bool cache_entries = false;          // the build side is a store slice: its decoded entries and block layout are kept on its SliceTable
   OjBandFuse fuse{};                   // fused: where the ordered join's packed record holds what this join reads of a row
   std::string ekey; SliceTable::BandEntries lay{};   // what the decoded entries depend on, spelt out (SliceTable::BandEntries::key); a copy of the slice's in-place block layout (boff == nullptr: there is none, the route is closed)
-  const uint2* row_win = nullptr;      // the slice's cached row windows for this chain (band_row_windows; null: not eligible, declined, or the route is closed)
-  bool row_static = false;             // route: in place, the block kernels read row_win and this execution's values per row instead of 16-byte records
-  u64* pair_bits = nullptr;            // the slice's cached pair verdicts for this chain (band_row_windows; null: not eligible, over the cap, or no row windows)
-  const u8* pair_cnt = nullptr;        // .. and the list's per-row counts (taken with the list; whether the step counts from them: band_pair_count_eligible, in band_blocks_and_emit)
-  const unsigned short* pair_list = nullptr; const u32* pair_list_off = nullptr; u64 pair_survivors = 0;   // .. and the list of their set bits (band_row_windows; null: none kept, declined as larger than the bits, or the plan's options decline it)
-  bool pair_cached = false;            // route: row_static, and the pair test is not run — its verdicts are pair_bits, a step applies its rows to them (band_mask_kernel's CACHED form)
+  SliceTable::BandRowWindows rw{};     // what the slice keeps of the row side for this chain and this plan's options accept (band_row_windows; a copy without the key, as `lay` is of the
+                                       // layout): row_win (null: not eligible, declined, or the route is closed), and behind it pair_bits, and behind them the list with its counts
+  BandForm form = BandForm::RECORDS;   // route: which way the block passes run and what they read (host_logic.hpp, band_step_form; the table: band_join.hip).  Every form but RECORDS is in_place
+  bool row_static() const { return form != BandForm::RECORDS; }   // .. the rows come as the slice's cached windows and this execution's values by key, not as 16-byte records
   u64 nrows = 0, max_blocks = 0;       // probe rows of the block kernels (in place: the slice's own rows); upper bound of the blocks (in place: exact)
   u32* skey = nullptr; u32* perm = nullptr; u32 sort_bits = 1; void* sort_temp = nullptr; size_t sort_temp_bytes = 0;   // the radix sort of the probe keys (its output pairs, key bits, temp): allocated by band_probe_side, run by band_blocks_and_emit
   BandJoin(LdsJoin& join) : j(join), kn(join.a.direct_n), np(join.P.cap), nb(join.B.cap), cmax((join.slice->csr_max_group + 63) / 64) {}
 };
+
+// The tiers of a slice's BandRowWindows entry as one step meets them (Plan::band_row_windows): use_* = this plan's options accept the tier (the windows are used wherever
+// the entry has them); build_* = accepted and missing — launched behind one another before the step's one wait.
+struct BandRowTiers { bool build_windows = false, build_verdicts = false, build_list = false, use_verdicts = false, use_list = false; };
 
 // Kernel classes for per-kernel timing; names are what rocprofv3 --kernel-trace prints.
 enum KernelClass {
@@ -302,7 +304,10 @@ struct Plan {
   void prepare_partitions(const LdsJoinArgs& a, const DevTable& B, const DevTable& P, PartArgs& pa);
   void exec_band_join(LdsJoin& j);   // its steps, in order:
   bool take_pending_oj(BandJoin& bj); void band_probe_side(BandJoin& bj); void band_row_records(BandJoin& bj); void band_blocks_and_emit(BandJoin& bj);
-  void band_slice_tables(BandJoin& bj); void band_entries(BandJoin& bj); SliceTable::BandEntries* band_layout(BandJoin& bj); void band_row_windows(BandJoin& bj);
+  void band_slice_tables(BandJoin& bj); void band_entries(BandJoin& bj); SliceTable::BandEntries* band_layout(BandJoin& bj); void band_row_windows(BandJoin& bj);   // .. and its steps:
+  bool band_row_operands(const BandJoin& bj, BandRowWinArgs& w); std::string band_row_win_key(const BandJoin& bj, const BandRowWinArgs& w); BandRowTiers band_row_tiers(const BandJoin& bj, const SliceTable::BandRowWindows& e, bool fresh);
+  uint2* build_row_win(const BandJoin& bj, BandRowWinArgs& w, u32* declined); u64* build_pair_bits(const BandJoin& bj, const uint2* row_win); BandPairListArgs build_pair_list(const BandJoin& bj, const u64* bits, u32* total_out);
+  void band_form_args(BandJoin& bj);
   bool choose_build_left(const NodeInfo& nd, const DevTable& L, const DevTable& R, bool left_join, bool lf, bool rf, bool lpost = false, bool rpost = false) const;
   void release_intermediates();
   template <class T> T* scratch(u64 n);

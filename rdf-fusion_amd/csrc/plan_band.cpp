@@ -223,7 +223,7 @@ void Plan::chain_range_index(LdsJoin& j, const ChainStage& s0) {
 
 // The fused chain as a key-partitioned band join (band_join.hip).  j.a is complete (chain, output columns, out_cap, counters), j.band holds what apply_chain
 // resolved; everything allocated here is scratch of this execution.  Bytes recorded per kernel = what that kernel has to move once (compulsory).  The route flags
-// (BandJoin says what each means) are all set here, before the first launch; in_place alone has to wait for band_slice_tables, which finds or builds the layout it needs.
+// (BandJoin says what each means) and the step's form are all set here, before the first launch; in_place alone has to wait for band_slice_tables, which finds or builds the layout it needs.
 void Plan::exec_band_join(LdsJoin& j) {
   BandJoin bj(j);
   BandHistory& hist = j.nd.band; const DevTable& P = j.P; const bool ordered = !opt.on(RDFGPU_OPT_NO_ORDERED_JOIN);
@@ -240,13 +240,16 @@ void Plan::exec_band_join(LdsJoin& j) {
   band_slice_tables(bj);
   hist.in_place = bj.lay.boff != nullptr;   // the layout exists: next time the ordered join below may leave its matches uncounted
   // In place: the ordered join below skipped its count pass, and the slice it streamed IS this join's build side.  Anything else counts the matches now and compacts them (the write-band pass).
-  hist.row_cache = bj.row_win != nullptr;   // .. and its probe pass may prepare the values by key instead of the 16-byte records
+  hist.row_cache = bj.rw.row_win != nullptr;   // .. and its probe pass may prepare the values by key instead of the 16-byte records
   // (the ordered join prepared what the last execution's flags said: values by key when the windows were cached, records by key otherwise — a step whose
   // cached windows are gone, a non-integer operand having entered the store, counts and compacts once)
-  bj.row_static = bj.fused && bj.row_win && pending_oj.o.key_val;
-  bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place && (bj.row_static || pending_oj.o.key_rec);
-  bj.row_static = bj.row_static && bj.in_place;
-  bj.pair_cached = bj.row_static && bj.pair_bits != nullptr;   // (row_static implies skip_slow: the full-semantics pass, which patches the bits, never runs over the slice's)
+  BandStepShape step;
+  step.row_static = bj.fused && bj.rw.row_win && pending_oj.o.key_val;
+  bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place && (step.row_static || pending_oj.o.key_rec);
+  step.row_static = step.row_static && bj.in_place;   // (implies skip_slow: the full-semantics pass, which patches the bits, never runs over the slice's)
+  step.has_verdicts = bj.rw.pair_bits != nullptr; step.has_list = bj.rw.pair_list != nullptr; step.n_row_cols = j.band.n_row_cols; step.n_blocks = bj.lay.n_blocks;
+  step.list_option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_LIST); step.counts_option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_COUNTS); step.min_blocks = opt.v[RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS];
+  bj.form = band_step_form(step);
   if (bj.fused && !bj.in_place) count_pending_oj();
   band_row_records(bj);
   band_blocks_and_emit(bj);
@@ -372,17 +375,53 @@ SliceTable::BandEntries* Plan::band_layout(BandJoin& bj) {
   return layout;
 }
 
-// In place, the ROW side of the pair test as a table of the slice: when both operands of every window are reached from the ordered join's key alone
-// (host_logic.hpp, band_row_cache_eligible) a slice row's windows are a function of the store and the plan's literals — decoded once per store version beside
-// the entries (same lock; built where the layout is, by the first execution that could take the route; fewer than 8 per slice), not gathered as 16-byte records
-// by key every step.  Its key = the entries' key + everything band_row_record reads.  A store in which some key's operands are not plain xsd:integers declines
-// the form: remembered as an entry without a table.  The caller holds the lock (the layout exists only when bj.cache_entries).
-// With the windows, the pair test's verdicts (R12; SliceTable::BandRowWindows::pair_bits, host_logic.hpp: band_pair_cache_eligible): same key, same execution, same
-// lock, built behind the windows and waited for with them — the one read-back below.  A plan whose options decline them neither builds nor uses them.
+// In place, the ROW side of the pair test as tables of the slice (SliceTable::BandRowWindows; at most 8 entries per slice, beside the entries: same lock, which the caller holds —
+// the layout exists only when bj.cache_entries).  Three tiers, each behind the one before: the rows' WINDOWS, when both operands of every window are reached from the ordered
+// join's key alone (band_row_operands); the pair test's VERDICTS over them (host_logic.hpp: band_pair_cache_eligible); the LIST of the verdicts' set bits with its per-row
+// counts (band_pair_list_eligible).  One path: the entry is found or started, the tiers it lacks and this plan's options want are launched behind one another, waited for
+// once — no wait when nothing is built — and published only then; a fresh entry is one that lacks all three.  A store in which some key's operands are not plain xsd:integers
+// declines the windows: remembered as an entry without tables, everything built behind them freed.  The step is handed what this plan's options accept (bj.rw).
 void Plan::band_row_windows(BandJoin& bj) {
-  const BandArgs& b = bj.j.band; const OjBandFuse& fuse = bj.fuse; const OrderedJoinArgs& o = pending_oj.o; SliceTable* tab = bj.j.slice;
+  std::vector<SliceTable::BandRowWindows>& kept = bj.j.slice->band_row_windows;
   if (!bj.lay.boff) return;                              // the in-place route is closed
-  BandRowWinArgs w{}; BandRowCacheShape shape;
+  BandRowWinArgs w{};
+  if (!band_row_operands(bj, w)) return;
+  std::string key = band_row_win_key(bj, w);
+  SliceTable::BandRowWindows fresh, *e = &fresh;
+  for (auto& x : kept) if (x.key == key) e = &x;
+  if (e == &fresh && kept.size() >= 8) return;
+  const BandRowTiers t = band_row_tiers(bj, *e, e == &fresh);
+  // one counter pair for the one wait: {keys declined, survivors} (the windows exist: the first half stays 0)
+  u32* const count = t.build_windows || t.build_list ? reinterpret_cast<u32*>(new_counter()) : nullptr;
+  uint2* const row_win = t.build_windows ? build_row_win(bj, w, count) : e->row_win;
+  u64* const bits = t.build_verdicts ? build_pair_bits(bj, row_win) : e->pair_bits;
+  BandPairListArgs la{};
+  if (t.build_list) la = build_pair_list(bj, bits, count + 1);
+  uint2 got = make_uint2(0u, 0u);
+  if (count) got = read_back<uint2>(count);
+  else if (t.build_verdicts) { RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++; }
+  const bool declined = got.x != 0;                      // (only a fresh entry's windows can be: whatever was built, was built behind them)
+  if (declined) { store->table_free(row_win); store->table_free(bits); }
+  else {
+    if (t.build_windows) { e->row_win = row_win; metrics.tables_built++; }
+    if (t.build_verdicts) { e->pair_bits = bits; metrics.tables_built++; }
+  }
+  if (t.build_list && !declined && band_pair_list_eligible(BandPairListShape{true, true, got.y, bj.lay.n_blocks})) {   // kept when it meets the condition (the counts are no table of their own)
+    e->pair_list = la.list; e->pair_list_off = const_cast<u32*>(la.off); e->pair_cnt = la.pair_cnt; e->pair_survivors = got.y; metrics.tables_built++;
+  } else if (t.build_list) {                             // larger than its bound: freed, and not built again
+    store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); store->table_free(la.pair_cnt); e->list_declined = !declined;
+  }
+  if (e == &fresh) { fresh.key = std::move(key); kept.push_back(fresh); e = &kept.back(); }
+  bj.rw.row_win = e->row_win;                            // (a plan whose options decline a tier does not use one another plan left)
+  if (t.use_verdicts) bj.rw.pair_bits = e->pair_bits;
+  if (t.use_list && e->pair_list) { bj.rw.pair_list = e->pair_list; bj.rw.pair_list_off = e->pair_list_off; bj.rw.pair_cnt = e->pair_cnt; bj.rw.pair_survivors = e->pair_survivors; }
+}
+
+// The window operands as the ordered join below reaches them (w.y0, w.y1: the stage's direct table and the column), and whether their shape lets the rows' windows be
+// a table of the slice (host_logic.hpp, band_row_cache_eligible).
+bool Plan::band_row_operands(const BandJoin& bj, BandRowWinArgs& w) {
+  const BandArgs& b = bj.j.band; const OjBandFuse& fuse = bj.fuse; const OrderedJoinArgs& o = pending_oj.o;
+  BandRowCacheShape shape;
   shape.in_place = true; shape.compact = fuse.compact != 0 && b.compact != 0; shape.pack16 = b.pack16 != 0;
   shape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_ROW_CACHE); shape.n_win = b.n_win;
   auto operand = [&](u8 slot, BandRowOperand& op, BandRowOperandShape& sh) {   // the ordered join's output column held in word `slot` of its packed record
@@ -399,7 +438,12 @@ void Plan::band_row_windows(BandJoin& bj) {
     }
   };
   for (u32 k = 0; k < b.n_win && k < 2; k++) { operand(fuse.y0_slot[k], w.y0[k], shape.y0[k]); operand(fuse.y1_slot[k], w.y1[k], shape.y1[k]); }
-  if (!band_row_cache_eligible(shape)) return;
+  return band_row_cache_eligible(shape);
+}
+
+// The key of a slice's BandRowWindows entry: the entries' key + everything band_row_record reads.
+std::string Plan::band_row_win_key(const BandJoin& bj, const BandRowWinArgs& w) {
+  const BandArgs& b = bj.j.band; const OrderedJoinArgs& o = pending_oj.o;
   std::string key = bj.ekey;
   auto put = [&](const void* p, size_t n) { key.append(reinterpret_cast<const char*>(p), n); };
   for (u32 k = 0; k < b.n_win; k++) {
@@ -408,95 +452,111 @@ void Plan::band_row_windows(BandJoin& bj) {
   }
   put(&b.pack16, 4); put(&b.has_neq, 4); put(&b.tt.tv, sizeof(void*)); put(&b.tt.n_ids, sizeof b.tt.n_ids);
   put(&o.build_key, sizeof(void*)); put(&o.kmin, 4); put(&o.kn, 4);
+  return key;
+}
+
+// Which tiers of entry `e` this plan's options accept, and which of those it lacks.  A plan that wants a tier an earlier plan declined to build, builds it then.
+BandRowTiers Plan::band_row_tiers(const BandJoin& bj, const SliceTable::BandRowWindows& e, bool fresh) {
+  const BandArgs& b = bj.j.band; BandRowTiers t;
   BandPairCacheShape pair;
+  pair.row_windows = fresh || e.row_win != nullptr;      // (fresh: whether the store's operands accept the windows is known only after the wait — built behind them, freed if not)
   pair.neq_self = b.neq_self != 0; pair.pack16 = b.pack16 != 0; pair.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_CACHE);
   pair.n_blocks = bj.lay.n_blocks; pair.cap = opt.v[RDFGPU_OPT_BAND_PAIR_CACHE_BLOCKS];
-  auto build_pair_bits = [&](const uint2* row_win) {        // 512 B written per block; its descriptor, 64 entries and 64 rows' windows read
-    u64* bits = store->table_alloc<u64>(64ull * bj.lay.n_blocks);
-    BandArgs d = b; d.bdesc = bj.lay.bdesc; d.max_blocks = bj.lay.n_blocks; d.row_win = row_win; d.masks = bits;
-    timed(KC_BAND_PAIR_BITS, (512ull + 16) * bj.lay.n_blocks + 16ull * bj.nb, bj.nb, nullptr, 8, nullptr, 0, 0, [&] { launch_band_pair_bits(d, stream); });
-    return bits;
-  };
-  // .. and the list of the verdicts' set bits (R13; pair_list, host_logic.hpp: band_pair_list_eligible), launched behind the bits on the same stream.  Its size is the
-  // condition's bound, 256 items per block, not a read-back: the write pass leaves a longer list unwritten, and the total travels with the wait that is there anyway.
-  BandPairListShape lshape;
-  lshape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_LIST); lshape.n_blocks = bj.lay.n_blocks;
-  auto want_list = [&](const u64* bits) { lshape.pair_cached = bits != nullptr && bj.lay.n_blocks != 0; lshape.survivors = 0; return band_pair_list_eligible(lshape); };
-  BandPairListArgs la{};
-  auto build_pair_list = [&](const u64* bits, u32* total_out) {   // per block its 512 B of bits read twice, 64 B of per-row counts written, 4 B of count written and read, 4 B of offset written and read; 2 B per survivor written
-    const u64 nbk = bj.lay.n_blocks;
-    la.bits = bits; la.n_blocks = (u32)nbk; la.counts = scratch<u32>(nbk + 1); la.cap = 256ull * nbk; la.total_out = total_out;
-    u32* off = store->table_alloc<u32>(nbk + 1); la.off = off; la.list = store->table_alloc<unsigned short>(la.cap + 64);   // (padded: the emit pass reads whole rounds of 64 items)
-    la.pair_cnt = store->table_alloc<u8>(64ull * nbk);       // (the list's companion: every word's own count, one more store of the count pass — no launch, no wait, no table of its own)
-    const size_t tb = scan_temp_bytes(nbk + 1); void* temp = scratch<unsigned char>(tb);
-    timed(KC_BAND_PAIR_LIST_COUNT, 0, nbk, nullptr, 512 + 4 + 64, nullptr, 0, 0, [&] { launch_band_pair_list_count(la, stream); });
-    timed(scan_class(nbk + 1), 0, nbk + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(la.counts, off, nbk + 1, temp, tb, stream); });
-    timed(KC_BAND_PAIR_LIST_WRITE, 0, nbk, nullptr, 512 + 4 + 2 * 256, nullptr, 0, 0, [&] { launch_band_pair_list_write(la, stream); });
-  };
-  auto keep_pair_list = [&](SliceTable::BandRowWindows& e, u64 survivors) {   // after the wait: published when it meets the condition, else freed and remembered as declined
-    lshape.survivors = survivors;
-    if (band_pair_list_eligible(lshape)) { e.pair_list = la.list; e.pair_list_off = const_cast<u32*>(la.off); e.pair_cnt = la.pair_cnt; e.pair_survivors = survivors; metrics.tables_built++; }
-    else { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); store->table_free(la.pair_cnt); e.list_declined = true; }
-  };
-  auto take_pair_list = [&](const SliceTable::BandRowWindows& e) {   // (a plan whose options decline the list does not use one another plan left)
-    if (e.pair_list && lshape.option_off) { bj.pair_list = e.pair_list; bj.pair_list_off = e.pair_list_off; bj.pair_cnt = e.pair_cnt; bj.pair_survivors = e.pair_survivors; }
-  };
-  for (auto& e : tab->band_row_windows) if (e.key == key) {
-    bj.row_win = e.row_win; pair.row_windows = e.row_win != nullptr;
-    if (!band_pair_cache_eligible(pair)) return;
-    // the windows were built by a plan whose options declined the verdicts, or the verdicts by one that declined the list: built now, published when complete
-    u64* bits = e.pair_bits ? nullptr : build_pair_bits(e.row_win);
-    const bool list = !e.pair_list && !e.list_declined && want_list(e.pair_bits ? e.pair_bits : bits);
-    u32 survivors = 0;
-    if (list) { u32* total = reinterpret_cast<u32*>(new_counter()); build_pair_list(e.pair_bits ? e.pair_bits : bits, total); survivors = read_back<u32>(total); }
-    else if (bits) { RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++; }
-    if (bits) { e.pair_bits = bits; metrics.tables_built++; }
-    if (list) keep_pair_list(e, survivors);
-    bj.pair_bits = e.pair_bits; take_pair_list(e);
-    return;
-  }
-  if (tab->band_row_windows.size() >= 8) return;
-  w.kmin = o.kmin; w.kn = o.kn; w.by_key = scratch<uint2>(o.kn); w.slow_keys = reinterpret_cast<u32*>(new_counter());
+  t.use_verdicts = band_pair_cache_eligible(pair);
+  BandPairListShape list;                                // (survivors = 0: asked before the build, when only the layout is known)
+  list.pair_cached = t.use_verdicts && bj.lay.n_blocks != 0; list.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_LIST); list.n_blocks = bj.lay.n_blocks;
+  t.use_list = band_pair_list_eligible(list);
+  t.build_windows = fresh; t.build_verdicts = t.use_verdicts && !e.pair_bits; t.build_list = t.use_list && !e.pair_list && !e.list_declined;
+  return t;
+}
+
+// The windows: per key two look-ups, two ids and two typed values per window read, 8 B written; per slice row its key read, 8 B gathered and written.  *declined = keys whose operands decline the form.
+uint2* Plan::build_row_win(const BandJoin& bj, BandRowWinArgs& w, u32* declined) {
+  const BandArgs& b = bj.j.band; const OrderedJoinArgs& o = pending_oj.o;
+  w.kmin = o.kmin; w.kn = o.kn; w.by_key = scratch<uint2>(o.kn); w.slow_keys = declined;
   w.build_key = o.build_key; w.n_rows = bj.nb; w.row_win = store->table_alloc<uint2>(bj.nb + 64);
-  // per key: two look-ups, two ids and two typed values per window read, 8 B written; per slice row: its key read, 8 B gathered and written
   timed(KC_BAND_ROW_WIN_KEYS, 0, o.kn, nullptr, 48ull * b.n_win + 8, nullptr, 0, 0, [&] { launch_band_row_win_keys(b, w, stream); });
   timed(KC_BAND_ROW_WIN_ROWS, 0, bj.nb, nullptr, 4 + 8 + 8, nullptr, 0, 0, [&] { launch_band_row_win_rows(w, stream); });
-  pair.row_windows = true;                               // (whether the store's operands accept the windows is known only after the wait: built behind them, freed if not)
-  u64* bits = band_pair_cache_eligible(pair) ? build_pair_bits(w.row_win) : nullptr;
-  const bool list = want_list(bits);
-  if (list) build_pair_list(bits, w.slow_keys + 1);      // (the total in the upper half of the counter the wait reads)
-  const uint2 got = read_back<uint2>(w.slow_keys);       // (the wait: published only when complete) {keys declined, survivors}
-  const u32 slow = got.x;
-  if (slow) { store->table_free(w.row_win); w.row_win = nullptr; if (bits) store->table_free(bits); bits = nullptr; } else metrics.tables_built += bits ? 2 : 1;
-  tab->band_row_windows.push_back(SliceTable::BandRowWindows{key, w.row_win, bits});
-  SliceTable::BandRowWindows& e = tab->band_row_windows.back();
-  if (list && slow) { store->table_free(la.list); store->table_free(const_cast<u32*>(la.off)); store->table_free(la.pair_cnt); }
-  else if (list) keep_pair_list(e, got.y);
-  bj.row_win = w.row_win; bj.pair_bits = bits; take_pair_list(e);
+  return w.row_win;
+}
+
+// The verdicts: 512 B written per block; its descriptor, 64 entries and 64 rows' windows read.
+u64* Plan::build_pair_bits(const BandJoin& bj, const uint2* row_win) {
+  u64* bits = store->table_alloc<u64>(64ull * bj.lay.n_blocks);
+  BandArgs d = bj.j.band; d.bdesc = bj.lay.bdesc; d.max_blocks = bj.lay.n_blocks; d.row_win = row_win; d.masks = bits;
+  timed(KC_BAND_PAIR_BITS, (512ull + 16) * bj.lay.n_blocks + 16ull * bj.nb, bj.nb, nullptr, 8, nullptr, 0, 0, [&] { launch_band_pair_bits(d, stream); });
+  return bits;
+}
+
+// The list of the verdicts' set bits: per block its 512 B of bits read twice, 64 B of per-row counts written, 4 B of count written and read, 4 B of offset written and read; 2 B per
+// survivor written.  Its size is the condition's bound, 256 items per block, not a read-back: the write pass leaves a longer list unwritten, and the total (*total_out) travels with
+// the wait that is there anyway.  pair_cnt is the list's companion: every word's own count, one more store of the count pass — no launch, no wait, no table of its own.
+BandPairListArgs Plan::build_pair_list(const BandJoin& bj, const u64* bits, u32* total_out) {
+  const u64 nbk = bj.lay.n_blocks; BandPairListArgs la{};
+  la.bits = bits; la.n_blocks = (u32)nbk; la.counts = scratch<u32>(nbk + 1); la.cap = 256ull * nbk; la.total_out = total_out;
+  u32* off = store->table_alloc<u32>(nbk + 1); la.off = off; la.list = store->table_alloc<unsigned short>(la.cap + 64);   // (padded: the emit pass reads whole rounds of 64 items)
+  la.pair_cnt = store->table_alloc<u8>(64ull * nbk);
+  const size_t tb = scan_temp_bytes(nbk + 1); void* temp = scratch<unsigned char>(tb);
+  timed(KC_BAND_PAIR_LIST_COUNT, 0, nbk, nullptr, 512 + 4 + 64, nullptr, 0, 0, [&] { launch_band_pair_list_count(la, stream); });
+  timed(scan_class(nbk + 1), 0, nbk + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(la.counts, off, nbk + 1, temp, tb, stream); });
+  timed(KC_BAND_PAIR_LIST_WRITE, 0, nbk, nullptr, 512 + 4 + 2 * 256, nullptr, 0, 0, [&] { launch_band_pair_list_write(la, stream); });
+  return la;
+}
+
+// What the step's form reads (the table: band_join.hip), set here and nowhere else; a form leaves what it does not read null.  Everything is scratch of this
+// execution but the slice's own tables, which a step reads and never writes.
+void Plan::band_form_args(BandJoin& bj) {
+  BandArgs& b = bj.j.band; const SliceTable::BandRowWindows& rw = bj.rw;
+  b.row_win = nullptr; b.row_val = nullptr; b.masks = nullptr; b.bvalid = nullptr; b.pair_list = nullptr; b.pair_list_off = nullptr; b.pair_cnt = nullptr;
+  if (bj.row_static()) { bj.fuse.key_val = pending_oj.o.key_val; bj.fuse.row_val = scratch<u32>(bj.nb); b.row_win = rw.row_win; b.row_val = bj.fuse.row_val; }
+  switch (bj.form) {
+    case BandForm::RECORDS: case BandForm::ROW_WINDOWS: b.masks = scratch<u64>(bj.max_blocks * 64); break;
+    case BandForm::VERDICTS: b.masks = rw.pair_bits; b.bvalid = scratch<u64>(bj.max_blocks); break;
+    case BandForm::VERDICTS_LIST: b.masks = rw.pair_bits; b.bvalid = scratch<u64>(bj.max_blocks); b.pair_list = rw.pair_list; b.pair_list_off = rw.pair_list_off; break;
+    case BandForm::COUNTS_LIST: b.pair_cnt = rw.pair_cnt; b.pair_list = rw.pair_list; b.pair_list_off = rw.pair_list_off; break;
+  }
+}
+
+// The bytes the two block passes have to move once in the step's form: the mask pass's fixed and per-row bytes, the emit pass's fixed bytes (per row and per output row it is the same in every form).
+struct BandPassBytes { u64 mask_fixed, mask_row, emit_fixed; };
+static BandPassBytes band_pass_bytes(const BandJoin& bj) {
+  const BandArgs& b = bj.j.band; const u64 blocks = bj.max_blocks, entries = 4ull * b.n_entry_cols * bj.nb;
+  const u64 list = 2ull * bj.rw.pair_survivors + 4ull * (blocks + 1);   // the list forms' emit pass: 2 B per survivor of the slice's list, 4 B per block + 4 of its offsets
+  switch (bj.form) {
+    // the pair test, per entry 16 B read, per pair one bit written (the pair count is not known on the host); per probe row 4 (sorted position) + 24 (record) read, compact: its 16 bytes
+    case BandForm::RECORDS: return {16ull * bj.nb, b.compact ? 16ull : 4ull + 24, entries};
+    case BandForm::ROW_WINDOWS: return {16ull * bj.nb, 8 + 4, entries};   // .. per row its cached windows and its value
+    // the verdicts cached: per block its 512 B of bits and its descriptor read, 4 + 8 B of count and valid rows written; per row its value read
+    case BandForm::VERDICTS: return {(512ull + 16 + 4 + 8) * blocks, 4, entries};
+    case BandForm::VERDICTS_LIST: return {(512ull + 16 + 4 + 8) * blocks, 4, list + entries};
+    // .. counted from the per-row counts: per block its 64 B of counts and its descriptor read, 4 B of count written; per row its value read
+    case BandForm::COUNTS_LIST: return {(64ull + 16 + 4) * blocks, 4, list + entries};
+  }
+  fail(RDFGPU_ERR_INVALID, "band join: form %u", (u32)bj.form);
 }
 
 // The probe rows' records in key order, with the rows per key (poff) and the blocks' counts zeroed: written by the ordered slice join below (fused; in place: one per slice row), else decoded from the probe columns.
 void Plan::band_row_records(BandJoin& bj) {
   const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band; OjBandFuse& fuse = bj.fuse;
-  const u32 kn = bj.kn; const u64 np = bj.np, nb = bj.nb; const bool in_place = bj.in_place;
-  bj.nrows = in_place ? nb : np; b.rec_s = bj.row_static ? nullptr : scratch<uint4>(bj.nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(bj.nrows);
+  const u32 kn = bj.kn; const u64 np = bj.np, nb = bj.nb; const bool in_place = bj.in_place, row_static = bj.row_static();
+  bj.nrows = in_place ? nb : np; b.rec_s = row_static ? nullptr : scratch<uint4>(bj.nrows); b.aux_s = b.compact ? nullptr : scratch<uint4>(bj.nrows);
   b.poff = in_place ? const_cast<u32*>(a.csr_off) : scratch<u32>((u64)kn + 2);
   // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
   bj.max_blocks = in_place ? bj.lay.n_blocks : bj.cmax * (np / 64 + 1) + nb / 64 + kn + 1;
   if (bj.max_blocks >= (1ull << 31)) fail(RDFGPU_ERR_UNSUPPORTED, "band join of %llu blocks", (unsigned long long)bj.max_blocks);
   b.max_blocks = (u32)bj.max_blocks; b.bcount = scratch<u32>(bj.max_blocks + 1); b.bofs = scratch<u32>(bj.max_blocks + 1);   // (bcount is zeroed by the decode pass: a memset is two more launches, ~10 us of launch gap each on this part)
+  band_form_args(bj);
   // decode, per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
   if (!bj.fused) return timed(KC_BAND_DECODE, 0, np, bj.j.P.n_dev, 4 + 4ull * (b.n_win + b.has_neq) + 9ull * b.n_win + 24 + 8, nullptr, 0, 0, [&] { launch_band_decode(b, stream); });
   const OrderedJoinArgs& o = pending_oj.o; pending_oj.active = false;
-  fuse.key_rec = in_place && !bj.row_static ? o.key_rec : nullptr;
-  if (bj.row_static) { u32* row_val = scratch<u32>(nb); fuse.key_val = o.key_val; fuse.row_val = row_val; b.row_win = bj.row_win; b.row_val = row_val; }
+  fuse.key_rec = in_place && !row_static ? o.key_rec : nullptr;
   fuse.brec = in_place ? nullptr : scratch<uint4>((fuse.compact ? 1 : 2) * o.n_probe_cap);
   fuse.rec_s = b.rec_s; fuse.aux_s = b.aux_s; fuse.poff = b.poff; fuse.bcount = b.bcount; fuse.max_blocks = b.max_blocks; fuse.kmin = b.kmin; fuse.kn = b.kn;
   // per table row: its packed record read + two typed-value gathers + 32 B written; per slice row the count pass's 5 bytes + its key; per match a 32-byte record gathered and stored (in place: per slice row its key read, its key's 16-byte record gathered and stored)
   // (the rows' windows cached: per table row its packed record read and 4 B written by key; per slice row its key read, 4 B gathered, 4 B written)
   const u64 rec_bytes = fuse.compact ? 16 : 32;
-  timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, bj.row_static ? 16ull * o.n_rec + 4 : 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
-  if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, bj.row_static ? 4 + 4 + 4 : 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
+  timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, row_static ? 16ull * o.n_rec + 4 : 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
+  if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, row_static ? 4 + 4 + 4 : 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
   else timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });
 }
 
@@ -505,7 +565,7 @@ void Plan::band_row_records(BandJoin& bj) {
 // leaves its own counts, the rows per key and the blocks of every key laid out; then the pair test, the full-semantics pass where rows may need it, the scan of the blocks' counts, the output rows.
 void Plan::band_blocks_and_emit(BandJoin& bj) {
   const LdsJoinArgs& a = bj.j.a; BandArgs& b = bj.j.band;
-  const u32 kn = bj.kn; const u64 np = bj.np, nb = bj.nb, max_blocks = bj.max_blocks;
+  const u32 kn = bj.kn; const u64 np = bj.np, max_blocks = bj.max_blocks;
   if (!bj.presorted && !bj.counting) timed(KC_RADIX_SORT, 0, np, nullptr, 0, nullptr, 0, 0, [&] { sort_pairs_u32_u32(b.skey_in, bj.skey, b.sval_in, bj.perm, np, bj.sort_bits, bj.sort_temp, bj.sort_temp_bytes, stream); });
   b.boff = bj.in_place ? bj.lay.boff : scratch<u32>((u64)kn + 1); b.n_blocks_out = new_counter();
   // the multi-row count is the ordered join's (pending_oj.o stays as it was when that join was taken over); a band join that was not fused has none
@@ -513,14 +573,6 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
                            bj.fused ? (int)(reinterpret_cast<u64*>(pending_oj.o.multi_rows) - counters) : -1, bj.skip_slow, bj.in_place, bj.in_place ? max_blocks : 0});
   const u64 hist = bj.j.nd.band.blocks; b.launch_blocks = (u32)(bj.in_place ? max_blocks : std::min<u64>(max_blocks, hist ? hist + hist / 4 + 1024 : max_blocks));
   b.bdesc = bj.in_place ? bj.lay.bdesc : scratch<uint4>(max_blocks);
-  // a step that emits from the list needs the verdicts only to count: from the list's per-row counts where the layout is large enough (R14; host_logic.hpp)
-  BandPairCountShape cshape;
-  cshape.has_list = bj.pair_cached && bj.pair_list != nullptr && bj.pair_cnt != nullptr && b.n_row_cols <= 1;   // (the list form of the emit pass knows one row column: launch_band_emit)
-  cshape.option_off = !opt.on(RDFGPU_OPT_NO_BAND_PAIR_COUNTS); cshape.n_blocks = max_blocks; cshape.min_blocks = opt.v[RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS];
-  const bool counts = band_pair_count_eligible(cshape);
-  if (counts) { b.masks = nullptr; b.bvalid = nullptr; b.pair_cnt = bj.pair_cnt; b.pair_list = bj.pair_list; b.pair_list_off = bj.pair_list_off; }   // neither the bits nor the valid rows: the list form reads neither
-  else if (bj.pair_cached) { b.masks = bj.pair_bits; b.bvalid = scratch<u64>(max_blocks); b.pair_list = bj.pair_list; b.pair_list_off = bj.pair_list_off; }   // the slice's verdicts (and their list, where kept): read, never written
-  else b.masks = scratch<u64>(max_blocks * 64);
   const size_t tb = std::max(scan_temp_bytes(std::max<u64>((u64)kn + 1, max_blocks + 1)), band_blocks_scan_temp_bytes(kn)); void* temp = scratch<unsigned char>(tb);
   if (bj.counting) {   // poff = exclusive scan of the rows per key (entry kn = the rows that join something); then the scatter
     timed(scan_class((u64)kn + 1), 0, (u64)kn + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.key_hist, b.poff, (u64)kn + 1, temp, tb, stream); });
@@ -532,15 +584,11 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
     timed(KC_BAND_DESC, 12ull * kn, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_desc(b, stream); });
   }
   if (!bj.presorted && !bj.counting) timed(KC_BAND_ROWS, 0, np, bj.j.P.n_dev, 4 + 32 + 32, nullptr, 0, 0, [&] { launch_band_rows(b, stream); });
-  // pair test, per probe row 4 (sorted position) + 24 (record) read, per entry 16 B read, per pair one bit written; the pair count is not known on the host
   const u64* const nrows_dev = bj.in_place ? nullptr : bj.j.P.n_dev;
-  // (the verdicts cached: per block its 512 B of bits and its descriptor read, 4 + 8 B of count and valid rows written; per row its value read)
-  // (.. counted from the per-row counts: per block its 64 B of counts and its descriptor read, 4 B of count written; per row its value read)
-  if (counts) timed(KC_BAND_MASK, (64ull + 16 + 4) * max_blocks, bj.nrows, nullptr, 4, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
-  else if (bj.pair_cached) timed(KC_BAND_MASK, (512ull + 16 + 4 + 8) * max_blocks, bj.nrows, nullptr, 4, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
-  else timed(KC_BAND_MASK, 16ull * nb, bj.nrows, nrows_dev, bj.row_static ? 8 + 4 : b.compact ? 16 : 4 + 24, nullptr, 0, 0, [&] { launch_band_mask(b, stream); });
+  const BandPassBytes bytes = band_pass_bytes(bj);
+  timed(KC_BAND_MASK, bytes.mask_fixed, bj.nrows, nrows_dev, bytes.mask_row, nullptr, 0, 0, [&] { launch_band_mask(b, bj.form, stream); });
   if (!bj.skip_slow) {
-    if (bj.pair_cached) fail(RDFGPU_ERR_INVALID, "band join: the full-semantics pass over a slice's cached verdicts");
+    if (bj.row_static()) fail(RDFGPU_ERR_INVALID, "band join: the full-semantics pass over a step of form %s", band_form_name(bj.form));
     // the full-semantics pass needs the chain's literals and columns: the fused join kernel's argument block, by pointer
     static_assert(sizeof(LdsJoinArgs) <= ExecContext::kArgBytes, "argument staging slot too small");
     const u32 slot = arg_slots_used++;
@@ -550,9 +598,7 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
     timed(KC_BAND_SLOW, 0, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_slow(a_dev, b, stream); });
   }
   timed(scan_class(max_blocks + 1), 0, max_blocks + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.bcount, b.bofs, max_blocks + 1, temp, tb, stream); });
-  // (the list form: the slice's list and its offsets read as well, 2 B per survivor and 4 B per block + 4)
-  const u64 list_bytes = b.pair_list ? 2ull * bj.pair_survivors + 4ull * (max_blocks + 1) : 0;
-  timed(KC_BAND_EMIT, list_bytes + 4ull * b.n_entry_cols * nb, bj.nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, stream); });
+  timed(KC_BAND_EMIT, bytes.emit_fixed, bj.nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, bj.form, stream); });
 }
 
 }  // namespace rdfgpu

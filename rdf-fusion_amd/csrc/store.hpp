@@ -111,6 +111,8 @@ struct SliceTable {
   // row the packed {lo pair, width pair} (padded like et).  `key` = the entries' key + the windows' literals, bias and packing, the operand stages' tables
   // and value columns, the typed-value table.  row_win == nullptr: some key's operands are not plain xsd:integers — the form is declined for this key
   // string (remembered, so that it is not built again every step).  Same lock, same rules as the entries.
+  // An entry has three tiers, each kept only behind the one before — the windows, the verdicts, the list with its counts; a plan whose options decline a tier leaves
+  // it missing, the next plan that wants it builds it (Plan::band_row_windows), and which tiers an entry has is what the forms of a step (BandForm) are chosen from.
   // pair_bits: with the rows' windows and the entries both fixed, the pair test's verdicts themselves are a function of the store version and the literals: 64 words per
   // block of the in-place layout (what the pair test writes when every row has a table row), 512 B per block, kept when the plan's options allow it
   // (host_logic.hpp, band_pair_cache_eligible); null: not kept.  Freed with row_win.
@@ -121,7 +123,7 @@ struct SliceTable {
   // that emits from the list reads instead of the bits to count a block's rows (host_logic.hpp, band_pair_count_eligible).  Written by the list's count pass,
   // published, declined and freed with the list.
   struct BandRowWindows {
-    std::string key; uint2* row_win; u64* pair_bits = nullptr;
+    std::string key; uint2* row_win = nullptr; u64* pair_bits = nullptr;
     unsigned short* pair_list = nullptr; u32* pair_list_off = nullptr; u64 pair_survivors = 0; bool list_declined = false;
     u8* pair_cnt = nullptr;
   };

@@ -128,6 +128,7 @@ def load_library():
     lib.rdfgpu_band_pair_cache_eligible.argtypes = [C.c_uint32] * 4 + [C.c_uint64] * 2
     lib.rdfgpu_band_pair_list_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
     lib.rdfgpu_band_pair_count_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
+    lib.rdfgpu_band_step_form.argtypes = [C.c_uint32] * 6 + [C.c_uint64] * 2
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -195,6 +196,17 @@ def band_pair_count_eligible(n_blocks, has_list=True, option_set=False, min_bloc
     """.. and does a step that emits from the list count its blocks' rows from the per-row counts kept with it, 64 bytes per block, instead of
     the 512 bytes of bits (host_logic.hpp)?  `min_blocks`: the BAND_PAIR_COUNT_BLOCKS option (inclusive; 0 = automatic, 2^16 blocks)."""
     return bool(_check(load_library().rdfgpu_band_pair_count_eligible(int(has_list), int(option_set), int(n_blocks), int(min_blocks))))
+
+
+BAND_FORMS = ("RECORDS", "ROW_WINDOWS", "VERDICTS", "VERDICTS_LIST", "COUNTS_LIST")   # host_logic.hpp, BandForm
+
+
+def band_step_form(n_blocks, row_static=True, has_verdicts=True, has_list=True, list_option_set=False, counts_option_set=False, n_row_cols=1, min_blocks=0):
+    """The form one band-join step runs in (host_logic.hpp, band_step_form; the table of the forms: band_join.hip), as its name in BAND_FORMS.
+    `row_static`: the step reads the slice's rows in place through their cached windows; `has_verdicts`, `has_list`: the slice keeps the pair
+    test's verdicts / their list with its per-row counts; `min_blocks`: the BAND_PAIR_COUNT_BLOCKS option, as for band_pair_count_eligible."""
+    return BAND_FORMS[_check(load_library().rdfgpu_band_step_form(int(row_static), int(has_verdicts), int(has_list), int(list_option_set), int(counts_option_set),
+                                                                   int(n_row_cols), int(n_blocks), int(min_blocks)))]
 
 
 def _pred_struct(p, keep):
