@@ -406,7 +406,7 @@ enum {
                                   Plan).snap).  Encoding: left = input; n_keys (0..RDFGPU_MAX_KEYS) group columns in left_keys[];
                                   table_cols = number of aggregates (0..RDFGPU_MAX_AGGREGATES); table_slot = offset into the u32 pool of
                                   table_cols pairs (RDFGPU_AGG_*, input); n_proj must be RDFGPU_NO_PROJECTION.  The input is a column of
-                                  `left`, or — SUM and AVG only — RDFGPU_AGG_INPUT_EXPR | the pool offset of two words (expr_off, expr_len)
+                                  `left`, or — SUM, AVG, MIN and MAX only — RDFGPU_AGG_INPUT_EXPR | the pool offset of two words (expr_off, expr_len)
                                   naming a program in `exprs` over the input's columns that leaves a typed value (`SUM(?price * ?qty)`);
                                   such an input of COUNT / COUNT_DISTINCT, and a program with REGEX / CONTAINS / STRSTARTS / STRENDS /
                                   LANG_IN in it, is RDFGPU_ERR_UNSUPPORTED at compile.  Output columns: the
@@ -429,8 +429,8 @@ enum {
                                   read by ENC_TV and BOUND in FILTER predicates and join filters (ENC_TV yields the aggregate's value:
                                   the BI plans' HAVING, `FilterExec: EBV(GT(INT64_AS_TERM(count@1), 9:0))`, where INT64_AS_TERM is the
                                   identity: counts are xsd:integer values already), projected, carried as payload of HASH_JOIN /
-                                  CROSS_JOIN / NESTED_LOOP_JOIN of every join type, consumed by two parents, and be the input of COUNT, SUM
-                                  and AVG (plain or inside an input expression) of a further AggregateExec.  Equal values have different
+                                  CROSS_JOIN / NESTED_LOOP_JOIN of every join type, consumed by two parents, and be the input of COUNT, SUM,
+                                  AVG, MIN and MAX (plain or inside an input expression) of a further AggregateExec.  Equal values have different
                                   indexes, so whatever would compare the entries as ids is RDFGPU_ERR_UNSUPPORTED at compile (the text names
                                   node and column): a join key, a group column, a COUNT_DISTINCT input, any TopK key / group / output, a
                                   CLOSURE or UNION input; and so is rdfgpu_plan_decode_terms of a value column.  A value column under
@@ -510,6 +510,34 @@ enum {
  *                   restated bit-exactly: the dividend is scaled by 10 while it stays inside i128, the divisor's trailing zeros are
  *                   stripped, two truncating divisions, and a scale beyond 10^38 is the error value.  Float results divide by
  *                   f32(count), double results by f64(count).
+ *   MIN / MAX       aggregates/min.rs:42-53, max.rs:43-54.  Accepted only in a plan compiled with RDFGPU_PLAN_AGG_COLUMNS (like
+ *                   RDFGPU_NODE_EXTEND and RDFGPU_SORT_BY_VALUE; without the flag they are RDFGPU_ERR_UNSUPPORTED at compile, as they
+ *                   always were).  The input is SUM's: an object-id column read through ENC_TV, a value column of an aggregate or
+ *                   EXTEND below, or an expression program (RDFGPU_AGG_INPUT_EXPR, the same refusals).  The reference's accumulator
+ *                   keeps its first row's value — its error state and its NaN included — and replaces it only by a value that is
+ *                   strictly less (greater), so its answer depends on row order.  The device's answer is fixed, independent of row
+ *                   order, and always one the reference gives for SOME order of the same rows.  For one group:
+ *                     1. no rows (the zero-key node over an empty input): the error value, RDFGPU_TV_NULL (`min: ThinError::expected()`);
+ *                     2. any error value in the group — an unbound id, a value-column entry of 0, a program that yields the error
+ *                        value — : the error value (the reference's answer when such a row comes first; AVG's rule here);
+ *                     3. a bound value that is not numeric (string, IRI, blank node, boolean, dateTime, date, time, duration) fails the
+ *                        EXECUTE with RDFGPU_ERR_UNSUPPORTED, the text naming MIN / MAX; the plan stays usable.  Such a row is never
+ *                        answered differently (the 24-byte record has no room for such values, and the reference's order between
+ *                        kinds is partial: its own order dependence);
+ *                     4. otherwise every value is int, integer, decimal, float or double.  Each kind present gives a candidate: its
+ *                        exact minimum (maximum) among that kind's values that are not NaN — int and integer compared as i64, decimal
+ *                        as i128, float and double in IEEE order with the bit pattern deciding between the zeros (MIN prefers -0, MAX
+ *                        +0); a kind whose values are all NaN gives a NaN candidate, and NaN candidates take part only if every
+ *                        candidate is NaN.  A candidate is beaten if another is strictly less (greater) under Numeric::partial_cmp
+ *                        (numeric.rs:90-99, with NumericPair::with_casts_from) — the comparison LT / GT use.  The result is the
+ *                        unbeaten candidate of the lowest kind in the order int, integer, decimal, float, double, with its own tag and
+ *                        payload (so RDFGPU_TV_INT can appear in an aggregate's array).  Of an all-NaN group only the tag and the
+ *                        NaN-ness are promised, not the payload.
+ *                   Why that is an answer of the reference: the casts of with_casts_from are monotone, so a value that is
+ *                   reference-less than a candidate m is exactly less than m, and then its kind's candidate is reference-less than m
+ *                   too; an unbeaten candidate is therefore not reference-greater than any value of the group, and put first in row
+ *                   order it is never replaced.  (tests/test_minmax_cpu.py proves it by enumerating the orders.)
+ *                   The result is a value column like any other aggregate's, under the same carriage and refusal rules.
  * Exactness.  Counts and every integer / decimal sum are exact and independent of row order (each value's i128 is added as 32-bit limbs
  * into u64 counters, carried and range-checked once per group: exact up to 2^32 rows per group).  The reference adds float and double
  * values one after the other in row order, so its result depends on that order; here the order is the device's, and the result satisfies
@@ -517,14 +545,15 @@ enum {
  * where x_i is each value as the reference casts it (to f32 for a float result, to f64 for a double one), n the group's numeric values and
  * eta the spacing of the subnormals (a rounding near zero is absolute, not relative).  AVG divides that sum once more, correctly rounded.
  * The reference's integer / decimal overflow can depend on order too (a prefix overflows, the total does not); here the TOTAL decides.
- * Not on the device — refused with RDFGPU_ERR_UNSUPPORTED at compile, never answered differently: MIN, MAX, SAMPLE, GROUP_CONCAT (MIN / MAX
- * keep the first value's error state, so their result depends on row order when a group holds unbound values, min.rs:42-53), SUM / AVG
- * with DISTINCT, COUNT(DISTINCT *), more than RDFGPU_MAX_KEYS keys or RDFGPU_MAX_AGGREGATES aggregates.
+ * Not on the device — refused with RDFGPU_ERR_UNSUPPORTED at compile, never answered differently: SAMPLE, GROUP_CONCAT, SUM / AVG
+ * with DISTINCT, COUNT(DISTINCT *), more than RDFGPU_MAX_KEYS keys or RDFGPU_MAX_AGGREGATES aggregates; and, in a plan without
+ * RDFGPU_PLAN_AGG_COLUMNS, the two functions above that need the flag.
  */
 enum {
   RDFGPU_AGG_COUNT_STAR = 1, RDFGPU_AGG_COUNT = 2, RDFGPU_AGG_COUNT_DISTINCT = 3, RDFGPU_AGG_SUM = 4, RDFGPU_AGG_AVG = 5,
+  RDFGPU_AGG_MIN = 6, RDFGPU_AGG_MAX = 7,   /* in plans compiled with RDFGPU_PLAN_AGG_COLUMNS; RDFGPU_ERR_UNSUPPORTED at compile without */
   /* reserved, RDFGPU_ERR_UNSUPPORTED at compile */
-  RDFGPU_AGG_MIN = 6, RDFGPU_AGG_MAX = 7, RDFGPU_AGG_SAMPLE = 8, RDFGPU_AGG_GROUP_CONCAT = 9,
+  RDFGPU_AGG_SAMPLE = 8, RDFGPU_AGG_GROUP_CONCAT = 9,
   RDFGPU_AGG_SUM_DISTINCT = 10, RDFGPU_AGG_AVG_DISTINCT = 11, RDFGPU_AGG_COUNT_DISTINCT_STAR = 12
 };
 #define RDFGPU_MAX_AGGREGATES 8u
@@ -663,7 +692,8 @@ int rdfgpu_plan_fetch(rdfgpu_plan* plan, uint32_t* const* host_cols, uint32_t n_
  *   tag RDFGPU_TV_DECIMAL   (lo, hi) = the i128 value * 10^18
  *   tag RDFGPU_TV_FLOAT     lo = the IEEE-754 binary32 bits (zero-extended);  RDFGPU_TV_DOUBLE: lo = the binary64 bits
  *   tag RDFGPU_TV_NULL      the error value
- * Below an RDFGPU_NODE_EXTEND, and only there, two more tags can appear in the array of a computed column:
+ * A MIN / MAX keeps the tag of the value it picked, so RDFGPU_TV_INT (lo = the xsd:int value) can appear in its array.  In the array of
+ * an RDFGPU_NODE_EXTEND's computed column two more tags can appear:
  *   tag RDFGPU_TV_INT       lo = the xsd:int value;  tag RDFGPU_TV_BOOLEAN: lo = 0 / 1
  * The host turns integers into xsd:integer terms (INT64_AS_TERM) and the rest into typed literals.
  */

@@ -46,7 +46,7 @@ AGG_NAMES = {AGG_COUNT_STAR: "COUNT(*)", AGG_COUNT: "COUNT", AGG_COUNT_DISTINCT:
              AGG_MIN: "MIN", AGG_MAX: "MAX", AGG_SAMPLE: "SAMPLE", AGG_GROUP_CONCAT: "GROUP_CONCAT", AGG_SUM_DISTINCT: "SUM(DISTINCT)",
              AGG_AVG_DISTINCT: "AVG(DISTINCT)", AGG_COUNT_DISTINCT_STAR: "COUNT(DISTINCT *)"}
 MAX_AGGREGATES = 8
-AGG_INPUT_EXPR = 0x80000000   # bit 31 of an aggregate's input: the low 31 bits are the pool offset of (expr_off, expr_len); SUM / AVG only
+AGG_INPUT_EXPR = 0x80000000   # bit 31 of an aggregate's input: the low 31 bits are the pool offset of (expr_off, expr_len); SUM / AVG / MIN / MAX only
 SORT_BY_ID, SORT_BY_TERM, SORT_BY_DOUBLE = 0, 1, 2
 SORT_BY_VALUE = 3               # NODE_SORT only: ENC_SORT of the typed value a value column's entry stands for
 SORT_DESC = 0x100               # NODE_SORT, or-ed into a key's `how`: descending

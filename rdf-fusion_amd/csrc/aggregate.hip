@@ -11,6 +11,8 @@
 //                      partials in LDS and merges them into HBM once; otherwise (or with NO_AGG_LDS) the atomics go to HBM directly.
 //   agg_final_kernel   one lane per group: the key ids from the group's first row, every aggregate's rdfgpu_agg_value.
 // When aggregate values are columns (RDFGPU_PLAN_AGG_COLUMNS) a fourth, agg_value_cols_kernel, writes each aggregate's value column.
+// A node with a MIN / MAX (RDFGPU_PLAN_AGG_COLUMNS only) runs the MINMAX instantiation of the accumulate pass (agg_accum_minmax_kernel),
+// then agg_minmax_refine_kernel (the low word of decimal candidates) and, beside agg_final_kernel, agg_minmax_final_kernel.
 //
 // Accumulator words of one group (u64, structure of arrays: word w of group g at acc[w * groups + g]):
 //   word 0                  rows of the group (COUNT(*), AVG's count)
@@ -19,6 +21,7 @@
 //                           values as sums of their two 32-bit limbs + the number of negative ones; the decimal values (i128 x 10^18) as
 //                           sums of their four 32-bit limbs + the number of negative ones; the sum of the values cast to f64; the sum of the
 //                           values cast to f32, kept in f64.
+//   MIN / MAX               7 words (kAggMinMaxWords): flags, one key per numeric kind, the decimal's low word ("MIN / MAX" below).
 // A limb sum of up to 2^32 rows fits a u64, and two's complement makes the exact total sum(limb_i * 2^(32 i)) - negatives * 2^64 (2^128):
 // integer and decimal results are exact and do not depend on row order.  Float and double results are the f64 sums, in the device's
 // order (the header states the bound).
@@ -122,6 +125,45 @@ __device__ __forceinline__ void acc_add_f64(unsigned long long* acc, u64 at, dou
   v = run_reduce(v, r, [](double x, double y) { return __dadd_rn(x, y); });
   if (r.head && v != 0.0) unsafeAtomicAdd(reinterpret_cast<double*>(acc + at), v);
 }
+// MIN / MAX: the largest key of the run.  0 is the identity (zeroed memory), so a wave none of whose lanes holds a key for this word —
+// every word but one, over a column of one kind — leaves before the shuffles.
+__device__ __forceinline__ void acc_max(unsigned long long* acc, u64 at, unsigned long long v, const AggRun& r) {
+  if (!__any(v != 0ull)) return;
+  v = run_reduce(v, r, [](unsigned long long x, unsigned long long y) { return x > y ? x : y; });
+  // The word only grows, so a key that is not above what is there changes nothing: read first, and most rows of a group that has met
+  // its extremum issue no atomic (every row of one group on one word ran at the contended-atomic rate).  A stale read costs only the
+  // atomic it would have saved.
+  if (r.head && v && v > __hip_atomic_load(acc + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(acc + at, v);
+}
+
+// ---- MIN / MAX (min.rs / max.rs; the rule is in include/rdfgpu.h) ----------------------------------------------------------------
+// Words of one MIN / MAX (kAggMinMaxWords): word 0 the flags below (kAggOr); words 1 .. 5 one key per kind in the order int, integer,
+// decimal (its high word), float, double; word 6 the decimal's low word, which the refinement settles.  A key is an order-preserving u64
+// of the value, complemented for MIN: the largest key is the candidate for both functions and 0 is the identity of both, so the memset
+// and the merge that skips zero partials stay what they are.  A kind's `seen` bit tells a legitimate key of 0 from "no value".
+enum : u32 { kMmSeen0 = 1, kMmNanFloat = 32, kMmNanDouble = 64, kMmError = 128, kMmOther = 256 };
+constexpr u32 kMmDecKind = 2, kMmDecHi = 3, kMmDecLo = 6;   // the decimal's kind index, and its two words
+__device__ __forceinline__ u64 mm_key_i64(long long v) { return (u64)v ^ (1ull << 63); }
+__device__ __forceinline__ u64 mm_key_f32(u32 b) { return (b & 0x80000000u) ? (u32)~b : (b | 0x80000000u); }   // IEEE order, -0 below +0
+__device__ __forceinline__ u64 mm_key_f64(u64 b) { return (b >> 63) ? ~b : (b | (1ull << 63)); }
+__device__ __forceinline__ u32 mm_unkey_f32(u64 k) { const u32 b = (u32)k; return (b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b; }
+__device__ __forceinline__ u64 mm_unkey_f64(u64 k) { return (k >> 63) ? (k & ~(1ull << 63)) : ~k; }
+
+// One row's contribution: which flag it sets and, for a numeric value that is not NaN, its kind (0 .. 4) and key (before MIN's complement).
+struct MmRow { u32 flags; u32 kind; u64 key; bool has; };
+__device__ __forceinline__ MmRow mm_row(const Val& v) {
+  MmRow m{0, 0, 0, false};
+  switch (num_kind(v.tag)) {
+    case NK_INT: m.kind = 0; m.key = mm_key_i64(v.lo); m.has = true; break;
+    case NK_INTEGER: m.kind = 1; m.key = mm_key_i64(v.lo); m.has = true; break;
+    case NK_DECIMAL: m.kind = kMmDecKind; m.key = mm_key_i64(v.hi); m.has = true; break;
+    case NK_FLOAT: { const u32 b = (u32)v.lo; if ((b & 0x7FFFFFFFu) > 0x7F800000u) m.flags = kMmNanFloat; else { m.kind = 3; m.key = mm_key_f32(b); m.has = true; } break; }
+    case NK_DOUBLE: { const u64 b = (u64)v.lo; if ((b & ~(1ull << 63)) > 0x7FF0000000000000ull) m.flags = kMmNanDouble; else { m.kind = 4; m.key = mm_key_f64(b); m.has = true; } break; }
+    default: m.flags = v.tag == RDFGPU_TV_NULL ? kMmError : kMmOther;
+  }
+  if (m.has) m.flags = kMmSeen0 << m.kind;
+  return m;
+}
 
 // First insertion of (g, id) into the COUNT DISTINCT set.
 __device__ __forceinline__ bool dset_insert(unsigned long long* set, u32 mask, u32 g, u32 id) {
@@ -151,10 +193,12 @@ __device__ __forceinline__ const u32* agg_col(const AggArgs& a, u32 c) {
 
 // EXPR: some SUM / AVG reads an expression (RDFGPU_AGG_INPUT_EXPR): that aggregate's value is its program's, evaluated by the VM.  A node
 // whose aggregates are all plain columns runs the instantiation without the VM in it.
-template <bool LDS, bool EXPR, bool LEX = false>
+// MINMAX: some aggregate is a MIN / MAX.  The instantiations without it are the code they were before MIN / MAX existed.
+template <bool LDS, bool EXPR, bool LEX = false, bool MINMAX = false>
 __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
   extern __shared__ unsigned long long lacc[];
   const u32 tid = threadIdx.x, lane = tid & 63;
+  [[maybe_unused]] bool dec_seen = false;
   const u64 n = live_rows(a.n_dev, a.cap);
   const u32 G = a.n_groups;
   unsigned long long* acc = a.acc;
@@ -186,6 +230,18 @@ __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
       Val v;
       if constexpr (EXPR) v = a.prog[i] ? eval_program<LEX>(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
       else v = enc_tv(a.tt, id);
+      if constexpr (MINMAX) {
+        if (fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX) {   // (uniform)
+          MmRow m = mm_row(v);
+          if (!valid) m = MmRow{0, 0, 0, false};
+          if (fn == RDFGPU_AGG_MIN) m.key = ~m.key;
+          dec_seen = dec_seen || (m.has && m.kind == kMmDecKind);
+          acc_or(acc, w, m.flags, r);
+#pragma unroll
+          for (u32 q = 0; q < 5; q++) acc_max(acc, w + (u64)(1 + q) * G, m.has && m.kind == q ? m.key : 0ull, r);
+          continue;
+        }
+      }
       const int k = num_kind(v.tag);
       u32 kind = k == NK_NONE ? kKindOther : k == NK_DECIMAL ? kKindDec : k == NK_FLOAT ? kKindFloat : k == NK_DOUBLE ? kKindDouble : kKindInt;
       if (!valid) kind = 0;
@@ -212,15 +268,61 @@ __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
       if (v == 0ull) continue;
       const u8 op = a.word_op[i / G];
       if (op == kAggOr) atomicOr(a.acc + i, v);
+      else if (MINMAX && op == kAggMax) atomicMax(a.acc + i, v);
       else if (op == kAggAddF64) unsafeAtomicAdd(reinterpret_cast<double*>(a.acc + i), __longlong_as_double((long long)v));
       else atomicAdd(a.acc + i, v);
     }
+  }
+  if constexpr (MINMAX) {   // at most one atomic per wave: a decimal was met, the refinement has work
+    if (__any(dec_seen) && lane == 0) atomicOr(reinterpret_cast<unsigned long long*>(a.mm_dec_seen), 1ull);
   }
 }
 
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) { agg_accum_rows<LDS, false>(a); }
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_expr_kernel(const AggArgs a) { agg_accum_rows<LDS, true>(a); }
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_lex_kernel(const AggArgs a) { agg_accum_rows<LDS, true, true>(a); }   // a.exprs == 2: a program holds RDFGPU_EX_CAST_LEX
+
+// .. and with a MIN / MAX among the aggregates (a.minmax): kernels of their own, so that a node without one launches what it always did
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_minmax_kernel(const AggArgs a) { agg_accum_rows<LDS, false, false, true>(a); }
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_minmax_expr_kernel(const AggArgs a) { agg_accum_rows<LDS, true, false, true>(a); }
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_minmax_lex_kernel(const AggArgs a) { agg_accum_rows<LDS, true, true, true>(a); }
+
+// The refinement of MIN / MAX over decimals: pass 2 settled the high word of every group's decimal candidate; among the rows whose high
+// word is that one, the largest low-word key is the candidate's low word.  HBM atomics after the same run merging.  A node whose MIN /
+// MAX inputs held no decimal leaves on the device word pass 2 would have set.
+template <bool EXPR, bool LEX>
+__global__ __launch_bounds__(kAggBlock) void agg_minmax_refine_kernel(const AggArgs a) {
+  if (*a.mm_dec_seen == 0) return;
+  const u32 tid = threadIdx.x, lane = tid & 63;
+  const u64 n = live_rows(a.n_dev, a.cap);
+  const u32 G = a.n_groups;
+  for (u64 base = (u64)blockIdx.x * kAggBlock; base < n; base += (u64)gridDim.x * kAggBlock) {
+    const u64 row = base + tid;
+    const bool valid = row < n;
+    const u32 g = !valid ? kGroupNone : a.n_keys ? a.slot_gid[a.row_slot[row]] : 0u;
+    const u32 prev = __shfl_up(g, 1);
+    const bool head = lane == 0 || prev != g;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long after = heads & ~((2ull << lane) - 1ull);
+    AggRun r{lane, after ? (u32)__ffsll((long long)after) - 1u : 64u, head && valid, heads != ~0ull};
+    for (u32 i = 0; i < a.n_aggs; i++) {
+      const u32 fn = a.fn[i];
+      if (fn != RDFGPU_AGG_MIN && fn != RDFGPU_AGG_MAX) continue;
+      const u64 w = (u64)a.word0[i] * G + (valid ? g : 0u);
+      u32 id;
+      if constexpr (EXPR) id = valid && a.in[i] ? a.in[i][row] : 0u;
+      else id = valid ? a.in[i][row] : 0u;
+      Val v;
+      if constexpr (EXPR) v = a.prog[i] ? eval_program<LEX>(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
+      else v = enc_tv(a.tt, id);
+      const bool mn = fn == RDFGPU_AGG_MIN;
+      const bool dec = valid && v.tag == RDFGPU_TV_DECIMAL;
+      const u64 hi = mn ? ~mm_key_i64(v.hi) : mm_key_i64(v.hi);
+      const bool won = dec && a.acc[w + (u64)kMmDecHi * G] == hi;
+      acc_max(a.acc, w + (u64)kMmDecLo * G, won ? (mn ? ~(u64)v.lo : (u64)v.lo) : 0ull, r);
+    }
+  }
+}
 
 // ---- pass 3 ---------------------------------------------------------------------------------------------------------------------
 // 256-bit two's complement, enough for sum(limb_i * 2^(32 i)) over 2^32 rows and for the integer part scaled by 10^18.
@@ -259,6 +361,46 @@ __device__ __forceinline__ void put(rdfgpu_agg_value* o, u32 g, u8 tag, long lon
   p[0] = lo; p[1] = hi; p[2] = (long long)tag;   // (tag, reserved bytes = 0)
 }
 
+// MIN / MAX of one group (rule 4 of include/rdfgpu.h): the up-to-five candidates are rebuilt from the key words; a candidate is beaten
+// if another is strictly less (MIN) / greater (MAX) under tv_partial_cmp, the comparison of the FILTER VM's LT / GT; the result is the
+// unbeaten candidate of the lowest kind.  NaN candidates (a kind whose values were all NaN) take part only if there is no other.
+__device__ __noinline__ int mm_cmp(const Val& x, const Val& y) { return tv_partial_cmp(x, y); }
+__device__ __forceinline__ void minmax_final(const AggArgs& a, u32 i, u32 g, u64 rows) {
+  const u32 G = a.n_groups;
+  const bool mn = a.fn[i] == RDFGPU_AGG_MIN;
+  rdfgpu_agg_value* o = a.out[i];
+  const unsigned long long* w = a.acc + (u64)a.word0[i] * G + g;
+  const u32 flags = (u32)w[0];
+  if (flags & kMmOther) { if (a.tt.rt_error) atomicOr(a.tt.rt_error, kRtMinMaxKind); put(o, g, RDFGPU_TV_NULL, 0, 0); return; }   // rule 3: the execute fails
+  if (rows == 0 || (flags & kMmError)) { put(o, g, RDFGPU_TV_NULL, 0, 0); return; }                                                // rules 1 and 2
+  const u8 tags[5] = {RDFGPU_TV_INT, RDFGPU_TV_INTEGER, RDFGPU_TV_DECIMAL, RDFGPU_TV_FLOAT, RDFGPU_TV_DOUBLE};
+  Val c[5];
+  u32 have = flags & 31u;
+  for (u32 q = 0; q < 5; q++) {
+    c[q] = val_tv_null();
+    if (!(have >> q & 1u)) continue;
+    u64 k = w[(u64)(1 + q) * G];
+    if (mn) k = ~k;
+    c[q].tag = tags[q];
+    if (q == 3) c[q].lo = (int64_t)(u64)mm_unkey_f32(k);
+    else if (q == 4) c[q].lo = (int64_t)mm_unkey_f64(k);
+    else if (q == kMmDecKind) { const u64 lo = w[(u64)kMmDecLo * G]; c[q].hi = (int64_t)(k ^ (1ull << 63)); c[q].lo = (int64_t)(mn ? ~lo : lo); }
+    else c[q].lo = (int64_t)(k ^ (1ull << 63));
+  }
+  if (have == 0) {   // every value a NaN: the lowest kind's
+    if (flags & kMmNanFloat) put(o, g, RDFGPU_TV_FLOAT, 0x7FC00000ll, 0); else put(o, g, RDFGPU_TV_DOUBLE, 0x7FF8000000000000ll, 0);
+    return;
+  }
+  const int beats = mn ? -1 : 1;
+  for (u32 q = 0; q < 5; q++) {
+    if (!(have >> q & 1u)) continue;
+    bool beaten = false;
+    for (u32 p = 0; p < 5; p++) if (p != q && (have >> p & 1u) && mm_cmp(c[p], c[q]) == beats) beaten = true;
+    if (!beaten) { put(o, g, c[q].tag, c[q].lo, c[q].hi); return; }
+  }
+  put(o, g, RDFGPU_TV_NULL, 0, 0);   // (unreachable: the exact extremum's candidate is unbeaten)
+}
+
 __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
   const u32 G = a.n_groups;
   const u32 g = blockIdx.x * kAggBlock + threadIdx.x;
@@ -274,6 +416,7 @@ __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
     if (fn == RDFGPU_AGG_COUNT_STAR) { put(o, g, RDFGPU_TV_INTEGER, (long long)rows, 0); continue; }
     const unsigned long long* w = a.acc + (u64)a.word0[i] * G + g;
     if (fn == RDFGPU_AGG_COUNT || fn == RDFGPU_AGG_COUNT_DISTINCT) { put(o, g, RDFGPU_TV_INTEGER, (long long)w[0], 0); continue; }
+    if (fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX) continue;   // agg_minmax_final_kernel's
     const u32 kinds = (u32)w[0];
     const bool avg = fn == RDFGPU_AGG_AVG;
     if (avg && rows == 0) { put(o, g, RDFGPU_TV_INTEGER, 0, 0); continue; }                   // avg.rs: count 0 => integer 0
@@ -313,6 +456,16 @@ __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
   }
 }
 
+// The MIN / MAX of every group, one lane per group like agg_final_kernel and launched beside it for the nodes that have one (a.minmax):
+// the five candidates and their comparisons stay out of the kernel that every other node runs.
+__global__ __launch_bounds__(kAggBlock) void agg_minmax_final_kernel(const AggArgs a) {
+  const u32 g = blockIdx.x * kAggBlock + threadIdx.x;
+  if (g >= a.n_groups) return;
+  const u64 rows = a.acc[g];
+  for (u32 i = 0; i < a.n_aggs; i++)
+    if (a.fn[i] == RDFGPU_AGG_MIN || a.fn[i] == RDFGPU_AGG_MAX) minmax_final(a, i, g, rows);
+}
+
 // ---- pass 4, aggregate values as columns (RDFGPU_PLAN_AGG_COLUMNS) only ------------------------------------------------------------
 // One lane per group: row g's entry of every aggregate's value column is g + 1, or 0 where the value is the error value (an unbound
 // binding).  A pass of its own, 4 bytes written per group and aggregate: agg_final_kernel stays what it is for the plans without the flag.
@@ -336,11 +489,21 @@ void launch_agg_accum(const AggArgs& a, hipStream_t s) {
     const size_t lds = (size_t)a.n_words * a.n_groups * sizeof(unsigned long long);
     if (lds > kAggLdsBytes) fail(RDFGPU_ERR_INVALID, "aggregate: %zu bytes of LDS partials", lds);
     if (g > 512) g = 512;   // every workgroup zeroes and merges all partials: enough of them to fill the part, not one per tile
+    if (a.minmax) {
+      if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_minmax_lex_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+      else if (a.exprs) hipLaunchKernelGGL(agg_accum_minmax_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+      else hipLaunchKernelGGL(agg_accum_minmax_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
+    } else
     if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_lex_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
     else if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
     else hipLaunchKernelGGL(agg_accum_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
   } else {
     if (g > 16384) g = 16384;
+    if (a.minmax) {
+      if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_minmax_lex_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+      else if (a.exprs) hipLaunchKernelGGL(agg_accum_minmax_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+      else hipLaunchKernelGGL(agg_accum_minmax_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+    } else
     if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_lex_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
     else if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
     else hipLaunchKernelGGL(agg_accum_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
@@ -351,6 +514,16 @@ void launch_agg_accum(const AggArgs& a, hipStream_t s) {
 void launch_agg_final(const AggArgs& a, hipStream_t s) {
   const u64 g = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
   hipLaunchKernelGGL(agg_final_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  if (a.minmax) hipLaunchKernelGGL(agg_minmax_final_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  RDFGPU_HIP(hipGetLastError());
+}
+
+void launch_agg_minmax_refine(const AggArgs& a, hipStream_t s) {
+  u64 g = (a.cap + kAggBlock - 1) / kAggBlock;
+  if (g > 16384) g = 16384;
+  if (a.exprs == 2) hipLaunchKernelGGL((agg_minmax_refine_kernel<true, true>), dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  else if (a.exprs) hipLaunchKernelGGL((agg_minmax_refine_kernel<true, false>), dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+  else hipLaunchKernelGGL((agg_minmax_refine_kernel<false, false>), dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
   RDFGPU_HIP(hipGetLastError());
 }
 

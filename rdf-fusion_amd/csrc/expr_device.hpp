@@ -51,7 +51,8 @@ struct TypedTable {
                                  // parsers are not restated), bit 4 a computed column (RDFGPU_NODE_EXTEND) met a value of a kind its
                                  // 24-byte record cannot carry, bit 5 a SortExec key by term (RDFGPU_NODE_SORT, RDFGPU_SORT_BY_TERM) met a
                                  // kind whose rank is not defined, bit 6 a lexical cast (RDFGPU_EX_CAST_LEX) met a literal the device
-                                 // cannot decide: a float / double at a rounding boundary that Eisel-Lemire declines, or a signed NaN
+                                 // cannot decide: a float / double at a rounding boundary that Eisel-Lemire declines, or a signed NaN,
+                                 // bit 7 a MIN / MAX (RDFGPU_AGG_MIN / _MAX) met a bound value that is not numeric
 };
 
 // Value kinds on the evaluation stack.  VK_VALUE exists at compile only (check_program): COLUMN of an aggregate value column, whose u32 is
@@ -82,6 +83,7 @@ constexpr uint32_t kRtCastFromString = 8u;
 constexpr uint32_t kRtExtendKind = 16u;
 constexpr uint32_t kRtSortTerm = 32u;
 constexpr uint32_t kRtLexParse = 64u;
+constexpr uint32_t kRtMinMaxKind = 128u;
 
 typedef __int128 i128_t;
 typedef unsigned __int128 u128_t;

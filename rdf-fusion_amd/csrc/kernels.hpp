@@ -283,14 +283,15 @@ void launch_semi_join(const SemiJoinArgs& a, int form, bool anti, int filter, hi
 size_t semi_join_lds_bytes(const SemiJoinArgs& a, int form);
 void preload_tu_semi_join();
 
-// ---- AggregateExec(mode=Single) (aggregate.hip): GROUP BY object-id columns with COUNT / COUNT DISTINCT / SUM / AVG ----
+// ---- AggregateExec(mode=Single) (aggregate.hip): GROUP BY object-id columns with COUNT / COUNT DISTINCT / SUM / AVG / MIN / MAX ----
 // Pass 1 (agg_groups_kernel) gives every row a dense group index through one open-addressing table of key tuples in HBM; pass 2
 // (agg_accum_kernel) adds every row into its group's accumulators — per-workgroup LDS partials merged once when the groups fit, else
 // straight into HBM — after summing runs of equal neighbouring groups within the wave; pass 3 (agg_final_kernel) is one lane per group.
 constexpr u32 kAggSumWords = 11;          // accumulator words of a SUM / AVG per group (aggregate.hip)
+constexpr u32 kAggMinMaxWords = 7;        // accumulator words of a MIN / MAX per group (aggregate.hip): flags, five kind keys, the decimal's low word
 constexpr u32 kAggMaxWords = 1 + RDFGPU_MAX_AGGREGATES * kAggSumWords;
 constexpr size_t kAggLdsBytes = 65536;    // LDS partials of one workgroup
-enum AggWordOp : u8 { kAggAdd = 0, kAggOr = 1, kAggAddF64 = 2 };
+enum AggWordOp : u8 { kAggAdd = 0, kAggOr = 1, kAggAddF64 = 2, kAggMax = 3 };
 struct AggArgs {
   u32 n_keys;
   const u32* key[RDFGPU_MAX_KEYS];
@@ -298,7 +299,7 @@ struct AggArgs {
   u32 n_aggs;
   u32 fn[RDFGPU_MAX_AGGREGATES];                 // RDFGPU_AGG_*
   const u32* in[RDFGPU_MAX_AGGREGATES];          // input column (COUNT_STAR and expression inputs: unused)
-  const ExprProgram* prog[RDFGPU_MAX_AGGREGATES];   // SUM / AVG over an expression (RDFGPU_AGG_INPUT_EXPR): its program (device copy), else null
+  const ExprProgram* prog[RDFGPU_MAX_AGGREGATES];   // SUM / AVG / MIN / MAX over an expression (RDFGPU_AGG_INPUT_EXPR): its program (device copy), else null
   const u32* col[kMaxCols];                      // .. the input's columns, which the programs read
   u32 exprs;                                     // 1 = some aggregate has a program: pass 2 runs its VM instantiation; 2 = and one holds RDFGPU_EX_CAST_LEX
   u32 word0[RDFGPU_MAX_AGGREGATES];              // first accumulator word of each aggregate (word 0 = rows of the group)
@@ -315,12 +316,15 @@ struct AggArgs {
   u64* n_groups_dev;
   u32 n_groups;                                  // known on the host before passes 2 and 3
   u32 lds;                                       // pass 2: 1 = LDS partials per workgroup
+  u32 minmax;                                    // 1 = some aggregate is a MIN / MAX: pass 2 runs its MINMAX instantiation, and the refinement follows
+  u64* mm_dec_seen;                              // .. a device word pass 2 sets when a MIN / MAX input held a decimal (else the refinement leaves at once)
   u32* out_key[RDFGPU_MAX_KEYS];
   rdfgpu_agg_value* out[RDFGPU_MAX_AGGREGATES];
   u32* out_val[RDFGPU_MAX_AGGREGATES];           // RDFGPU_PLAN_AGG_COLUMNS: the aggregate's value column (row g: g + 1, or 0 for the error value); else null
 };
 void launch_agg_groups(const AggArgs& a, hipStream_t s);
 void launch_agg_accum(const AggArgs& a, hipStream_t s);
+void launch_agg_minmax_refine(const AggArgs& a, hipStream_t s);   // a.minmax only: settles the low word of the decimal candidates
 void launch_agg_final(const AggArgs& a, hipStream_t s);
 void launch_agg_value_cols(const AggArgs& a, hipStream_t s);   // RDFGPU_PLAN_AGG_COLUMNS: every out_val[i] set
 void preload_tu_aggregate();

@@ -150,7 +150,10 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::band_row_win_keys_kernel", "rdfgpu::band_row_win_rows_kernel", "void rdfgpu::band_pair_bits_kernel",
       "rdfgpu::band_pair_list_count_kernel", "rdfgpu::band_pair_list_write_kernel",
       "rdfgpu::agg_value_cols_kernel", "rdfgpu::extend_kernel",
-      "rdfgpu::sort_keys_kernel", "rdfgpu::sort_tile_kernel", "rdfgpu::sort_merge_kernel", "rdfgpu::sort_gather_kernel"};
+      "rdfgpu::sort_keys_kernel", "rdfgpu::sort_tile_kernel", "rdfgpu::sort_merge_kernel", "rdfgpu::sort_gather_kernel",
+      "void rdfgpu::agg_accum_minmax_kernel<false>", "void rdfgpu::agg_accum_minmax_kernel<true>",
+      "void rdfgpu::agg_accum_minmax_expr_kernel<false>", "void rdfgpu::agg_accum_minmax_expr_kernel<true>",
+      "void rdfgpu::agg_minmax_refine_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -337,6 +340,8 @@ void Plan::execute() {
                                                          "its 24-byte value has no room for the language / datatype (numeric and boolean values are carried)");
     if (rt & kRtLexParse) fail(RDFGPU_ERR_UNSUPPORTED, "a lexical cast (RDFGPU_EX_CAST_LEX, xsd:float / xsd:double of a simple literal) met a literal the device cannot decide: "
                                                        "its value lies at a rounding boundary where Eisel-Lemire declines (the big-decimal path is not restated), or it is a signed NaN");
+    if (rt & kRtMinMaxKind) fail(RDFGPU_ERR_UNSUPPORTED, "MIN / MAX met a bound value that is not numeric (a string, IRI, blank node, boolean, dateTime, date, time or duration): "
+                                                         "the reference's order between those kinds is partial and its 24-byte value has no room for them (numeric values are answered)");
     if (rt & kRtSortTerm) fail(RDFGPU_ERR_UNSUPPORTED, "SortExec: SORT_BY_TERM over a column that is not all strings / IRIs / blank nodes");
     if (rt & 4u) fail(RDFGPU_ERR_UNSUPPORTED, "a string expression met what the device does not restate: UCASE / LCASE of a string with non-ASCII characters (Unicode case tables), "
                                                "a float / double / decimal SUBSTR position, or a comparison with a string that has no bytes on the device");
@@ -623,8 +628,9 @@ DevTable Plan::exec_topk(NodeInfo& nd) {
 
 // AggregateExec(mode=Single) (aggregate.hip): group pass, one read-back of the group count (it sizes the accumulators and is the
 // output's row count), accumulate pass, one lane per group to finish.  Over a zero-key aggregate there is one group and no group pass.
-// Compulsory bytes: per input row 4 per key column, 4 + 16 per SUM / AVG input (id + typed value), 4 per COUNT / COUNT
-// DISTINCT input; per output group 4 per key column + 24 per aggregate.
+// Compulsory bytes: per input row 4 per key column, 4 + 16 per SUM / AVG / MIN / MAX input (id + typed value), 4 per COUNT /
+// COUNT DISTINCT input; per output group 4 per key column + 24 per aggregate.  A MIN / MAX input is read once more by the refinement
+// launch (agg_minmax_refine_kernel), which is counted as if decimals were there: 4 + 16 per row again.
 DevTable Plan::exec_aggregate(NodeInfo& nd) {
   const DevTable in = exec_sub_plan((u32)nd.d.left);
   flush_pending_oj();   // a held-back ordered-join write must have happened before the input is read
@@ -636,7 +642,7 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
   a.n_aggs = nd.n_aggs;
   a.n_words = 1;
   a.word_op[0] = kAggAdd;
-  u64 accum_row_bytes = 0;
+  u64 accum_row_bytes = 0, refine_row_bytes = 0;   // (the refinement reads a MIN / MAX input's id and typed value once more)
   bool distinct = false;
   for (u32 i = 0; i < a.n_aggs; i++) {
     const u32 fn = nd.agg_fn[i];
@@ -648,10 +654,12 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
       for (u32 c = 0; c < in.n_cols; c++) a.col[c] = in.cols[c];
     }
     a.word0[i] = a.n_words;
-    const u32 words = fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? kAggSumWords : 1;
-    for (u32 w = 0; w < words; w++) a.word_op[a.n_words + w] = words == 1 ? kAggAdd : w == 0 ? kAggOr : w >= 9 ? kAggAddF64 : kAggAdd;
+    const bool minmax = fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX;
+    const u32 words = fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? kAggSumWords : minmax ? kAggMinMaxWords : 1;
+    for (u32 w = 0; w < words; w++) a.word_op[a.n_words + w] = words == 1 ? kAggAdd : w == 0 ? kAggOr : minmax ? kAggMax : w >= 9 ? kAggAddF64 : kAggAdd;
     a.n_words += words;
-    accum_row_bytes += fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? 20 : 4;
+    accum_row_bytes += fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG || minmax) ? 20 : 4;
+    if (minmax) { a.minmax = 1; refine_row_bytes += 20; }
     distinct = distinct || fn == RDFGPU_AGG_COUNT_DISTINCT;
   }
   a.tt = typed_table();
@@ -693,7 +701,13 @@ DevTable Plan::exec_aggregate(NodeInfo& nd) {
       }
     }
     a.lds = !opt.on(RDFGPU_OPT_NO_AGG_LDS) && (u64)a.n_words * G * sizeof(unsigned long long) <= kAggLdsBytes;
-    timed(a.exprs ? (a.lds ? KC_AGG_ACCUM_EXPR_LDS : KC_AGG_ACCUM_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
+    const int kc = a.minmax ? (a.exprs ? (a.lds ? KC_AGG_ACCUM_MINMAX_EXPR_LDS : KC_AGG_ACCUM_MINMAX_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_MINMAX_LDS : KC_AGG_ACCUM_MINMAX_HBM)
+                            : a.exprs ? (a.lds ? KC_AGG_ACCUM_EXPR_LDS : KC_AGG_ACCUM_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM;
+    if (a.minmax) a.mm_dec_seen = new_counter();   // (zeroed with the other counters when the execution began)
+    timed(kc, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
+    // MIN / MAX over decimals: the low word of each group's candidate, among the rows whose high word won.  No read-back decides the
+    // launch: the kernel leaves on the device word when the inputs held no decimal.
+    if (a.minmax) timed(KC_AGG_MINMAX_REFINE, 0, cap, in.n_dev, refine_row_bytes, nullptr, 0, 0, [&] { launch_agg_minmax_refine(a, stream); });
   }
   timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
   // the value columns: per group and aggregate the tag read (the value was just written: cache) and 4 bytes written

@@ -167,6 +167,9 @@ enum KernelClass {
   KC_AGG_VALUE_COLS,                              // agg_value_cols_kernel: an AggregateExec's value columns (RDFGPU_PLAN_AGG_COLUMNS)
   KC_EXTEND,                                      // extend_kernel: the computed columns of a ProjectionExec with expressions (RDFGPU_NODE_EXTEND)
   KC_SORT_KEYS, KC_SORT_TILE, KC_SORT_MERGE, KC_SORT_GATHER,   // SortExec (sort.hip, RDFGPU_NODE_SORT): records, tile sort, one launch per merge pass, gather
+  KC_AGG_ACCUM_MINMAX_HBM, KC_AGG_ACCUM_MINMAX_LDS,             // agg_accum_minmax_kernel<LDS>: some aggregate of the node is a MIN / MAX
+  KC_AGG_ACCUM_MINMAX_EXPR_HBM, KC_AGG_ACCUM_MINMAX_EXPR_LDS,   // .. and some SUM / AVG / MIN / MAX reads an expression or a value column
+  KC_AGG_MINMAX_REFINE,                                         // agg_minmax_refine_kernel: the low word of the decimal candidates
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };

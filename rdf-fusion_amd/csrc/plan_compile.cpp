@@ -361,7 +361,11 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
       case RDFGPU_AGG_COUNT: case RDFGPU_AGG_COUNT_DISTINCT:
         if (expr) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: COUNT / COUNT DISTINCT over an expression is not on the device (SUM and AVG are)", i, a);
         [[fallthrough]];
+      case RDFGPU_AGG_MIN: case RDFGPU_AGG_MAX:   // with value columns only (RDFGPU_PLAN_AGG_COLUMNS), like RDFGPU_NODE_EXTEND: an input like SUM's
       case RDFGPU_AGG_SUM: case RDFGPU_AGG_AVG:
+        if ((fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX) && !plan->agg_columns)
+          fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: MIN / MAX / SAMPLE / GROUP_CONCAT are not on the device (MIN / MAX keep the first "
+                                       "value's error state, min.rs:42-53: their result depends on row order)", i, a);   // (the text every plan without the flag has always met)
         if (expr) {   // (expr_off, expr_len) in the pool: a program over the input's columns that leaves a typed value
           const u32 at = col & ~RDFGPU_AGG_INPUT_EXPR;
           if ((u64)at + 2 > d->n_pool) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression input at pool offset %u of %u", i, a, at, d->n_pool);
@@ -383,7 +387,7 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
         } else if (col >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, col, c.width);
         else if (fn == RDFGPU_AGG_COUNT_DISTINCT) refuse_value_column(c.origin[col], i, "COUNT DISTINCT input", col);
         else if (c.origin[col].node >= 0 && fn != RDFGPU_AGG_COUNT) {
-          // SUM / AVG of a value column: the two-node program [COLUMN, value load], so the EXPR form of the accumulate pass runs it.
+          // SUM / AVG / MIN / MAX of a value column: the two-node program [COLUMN, value load], so the EXPR form of the accumulate pass runs it.
           // (COUNT needs nothing: an entry of 0 is "not counted" already.)
           ExprProgram pr{};
           pr.n = 2;
@@ -395,7 +399,8 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
           nd.agg_progs.push_back(pr);
         }
         break;
-      case RDFGPU_AGG_MIN: case RDFGPU_AGG_MAX: case RDFGPU_AGG_SAMPLE: case RDFGPU_AGG_GROUP_CONCAT:
+      case RDFGPU_AGG_SAMPLE: case RDFGPU_AGG_GROUP_CONCAT:
+        if (plan->agg_columns) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: SAMPLE / GROUP_CONCAT are not on the device", i, a);
         fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: MIN / MAX / SAMPLE / GROUP_CONCAT are not on the device (MIN / MAX keep the first "
                                      "value's error state, min.rs:42-53: their result depends on row order)", i, a);
       case RDFGPU_AGG_SUM_DISTINCT: case RDFGPU_AGG_AVG_DISTINCT: case RDFGPU_AGG_COUNT_DISTINCT_STAR:

@@ -555,7 +555,9 @@ class PlanBuilder:
 
     def aggregate(self, left, group_by, aggregates=()):
         """AggregateExec(mode=Single): GROUP BY the id columns `group_by` (0 to 4) with `aggregates` = [(abi.AGG_*, input column), ...]
-        (at most 8; AGG_COUNT_STAR takes no column: None).  The input of AGG_SUM / AGG_AVG may be an `Expr` over the input's columns that
+        (at most 8; AGG_COUNT_STAR takes no column: None).  AGG_MIN / AGG_MAX need a description built with agg_columns=True; their answer
+        is fixed and independent of row order (include/rdfgpu.h: an unbound row makes the group unbound, a value that is not numeric fails
+        the execute).  The input of AGG_SUM / AGG_AVG / AGG_MIN / AGG_MAX may be an `Expr` over the input's columns that
         yields a typed value (`MUL(ENC_TV(col(1)), ENC_TV(col(2)))`): it goes into the pool as abi.AGG_INPUT_EXPR | offset of
         (expr_off, expr_len).  Output: the keys in order, then the aggregates, named like DataFusion's display (`COUNT(y)`,
         `SUM(MUL(ENC_TV(a), ENC_TV(b)))`).  Only the key columns are ids: a node with aggregates must be the plan's root — unless the
