@@ -1,5 +1,5 @@
-// aggregate.hip — AggregateExec(mode=Single) over object-id group columns: COUNT(*), COUNT, COUNT(DISTINCT), SUM, AVG (include/rdfgpu.h,
-// RDFGPU_NODE_AGGREGATE; lib/functions/src/aggregates/sum.rs:34-73, avg.rs:43-134).
+// aggregate.hip — AggregateExec(mode=Single) over object-id group columns: COUNT(*), COUNT, COUNT(DISTINCT), SUM, AVG, MIN, MAX
+// (include/rdfgpu.h, RDFGPU_NODE_AGGREGATE; lib/functions/src/aggregates/sum.rs:34-73, avg.rs:43-134, min.rs / max.rs).
 //
 // Three passes over the input, the group count read back once in between (it sizes the accumulators):
 //   agg_groups_kernel  every row finds its key tuple in one open-addressing table in HBM (slot = row + 1 of the row that claimed it; a
@@ -14,17 +14,13 @@
 // A node with a MIN / MAX (RDFGPU_PLAN_AGG_COLUMNS only) runs the MINMAX instantiation of the accumulate pass (agg_accum_minmax_kernel),
 // then agg_minmax_refine_kernel (the low word of decimal candidates) and, beside agg_final_kernel, agg_minmax_final_kernel.
 //
-// Accumulator words of one group (u64, structure of arrays: word w of group g at acc[w * groups + g]):
-//   word 0                  rows of the group (COUNT(*), AVG's count)
-//   COUNT / COUNT DISTINCT  1 word: rows with a bound id / first insertions of (group, id) into the aggregate's set
-//   SUM / AVG               11 words: kinds seen (bit 0 int/integer, 1 decimal, 2 float, 3 double, 4 not numeric or unbound); the integer
-//                           values as sums of their two 32-bit limbs + the number of negative ones; the decimal values (i128 x 10^18) as
-//                           sums of their four 32-bit limbs + the number of negative ones; the sum of the values cast to f64; the sum of the
-//                           values cast to f32, kept in f64.
-//   MIN / MAX               7 words (kAggMinMaxWords): flags, one key per numeric kind, the decimal's low word ("MIN / MAX" below).
+// Accumulator words of one group (u64, word w of group g at acc[w * groups + g]): word 0 counts the group's rows; COUNT / COUNT DISTINCT have one
+// (rows with a bound id / first insertions of (group, id) into the aggregate's set); SUM / AVG and MIN / MAX index theirs by the names of kernels.hpp.
 // A limb sum of up to 2^32 rows fits a u64, and two's complement makes the exact total sum(limb_i * 2^(32 i)) - negatives * 2^64 (2^128):
 // integer and decimal results are exact and do not depend on row order.  Float and double results are the f64 sums, in the device's
 // order (the header states the bound).
+#include <algorithm>
+
 #include "join_device.hpp"
 
 namespace rdfgpu {
@@ -33,6 +29,8 @@ constexpr int kAggBlock = 256;
 constexpr int kAggItems = 4;                        // rows per lane and tile of the group pass: one reservation per 1024 rows
 constexpr u32 kAggTile = (u32)kAggBlock * kAggItems;
 constexpr u32 kGroupNone = 0xFFFFFFFFu;
+// Workgroups of a launch, at most.  In the LDS form every workgroup zeroes and merges all partials: enough to fill the part, not one per tile.
+constexpr u64 kAggGroupGrid = 16384, kAggAccumLdsGrid = 512, kAggAccumHbmGrid = 16384;
 enum : u32 { kKindInt = 1, kKindDec = 2, kKindFloat = 4, kKindDouble = 8, kKindOther = 16 };
 
 // ---- pass 1 ---------------------------------------------------------------------------------------------------------------------
@@ -102,6 +100,23 @@ __global__ __launch_bounds__(kAggBlock) void agg_groups_kernel(const AggArgs a) 
 // ---- pass 2 ---------------------------------------------------------------------------------------------------------------------
 // A lane's run: the lanes [lane, end) of its wave hold rows of the same group; the head lane (first of the run) issues the atomic.
 struct AggRun { u32 lane, end; bool head; bool merge; };
+// Where the accumulate pass adds: the workgroup's partials in LDS (the LDS form, same layout) or the accumulators in HBM.
+template <bool LDS> __device__ __forceinline__ unsigned long long* agg_acc(const AggArgs& a) {
+  extern __shared__ unsigned long long lacc[];
+  if constexpr (LDS) return lacc; else return a.acc;
+}
+// The group of a row (kGroupNone behind the live rows), and the run of its lane among the wave's groups.
+__device__ __forceinline__ u32 agg_group(const AggArgs& a, u64 row, bool valid) { return !valid ? kGroupNone : a.n_keys ? a.slot_gid[a.row_slot[row]] : 0u; }
+__device__ __forceinline__ AggRun agg_run(u32 g, bool valid, u32 lane) {
+  const u32 prev = __shfl_up(g, 1);
+  const bool head = lane == 0 || prev != g;
+  const unsigned long long heads = __ballot(head);
+  const unsigned long long after = heads & ~((2ull << lane) - 1ull);   // heads of later lanes (lane 63: 2 << 63 wraps to 0, none)
+  return AggRun{lane, after ? (u32)__ffsll((long long)after) - 1u : 64u, head && valid, heads != ~0ull};
+}
+// Where the first word of aggregate `i` lies for group `g`; word `word` (an AggSumWord / AggMinMaxWord) of the aggregate whose first is at `w`.
+__device__ __forceinline__ u64 agg_word0(const AggArgs& a, u32 i, u32 g) { return (u64)a.word0[i] * a.n_groups + g; }
+__device__ __forceinline__ u64 agg_word(const AggArgs& a, u64 w, u32 word) { return w + (u64)word * a.n_groups; }
 
 template <class T, class Op>
 __device__ __forceinline__ T run_reduce(T v, const AggRun& r, Op op) {
@@ -137,32 +152,63 @@ __device__ __forceinline__ void acc_max(unsigned long long* acc, u64 at, unsigne
 }
 
 // ---- MIN / MAX (min.rs / max.rs; the rule is in include/rdfgpu.h) ----------------------------------------------------------------
-// Words of one MIN / MAX (kAggMinMaxWords): word 0 the flags below (kAggOr); words 1 .. 5 one key per kind in the order int, integer,
-// decimal (its high word), float, double; word 6 the decimal's low word, which the refinement settles.  A key is an order-preserving u64
-// of the value, complemented for MIN: the largest key is the candidate for both functions and 0 is the identity of both, so the memset
+// Words of one MIN / MAX (AggMinMaxWord): the flags below (kAggOr), one key per kind, the decimal's low word.  A key is an order-preserving
+// u64 of the value, complemented for MIN: the largest key is the candidate for both functions and 0 is the identity of both, so the memset
 // and the merge that skips zero partials stay what they are.  A kind's `seen` bit tells a legitimate key of 0 from "no value".
 enum : u32 { kMmSeen0 = 1, kMmNanFloat = 32, kMmNanDouble = 64, kMmError = 128, kMmOther = 256 };
-constexpr u32 kMmDecKind = 2, kMmDecHi = 3, kMmDecLo = 6;   // the decimal's kind index, and its two words
 __device__ __forceinline__ u64 mm_key_i64(long long v) { return (u64)v ^ (1ull << 63); }
 __device__ __forceinline__ u64 mm_key_f32(u32 b) { return (b & 0x80000000u) ? (u32)~b : (b | 0x80000000u); }   // IEEE order, -0 below +0
 __device__ __forceinline__ u64 mm_key_f64(u64 b) { return (b >> 63) ? ~b : (b | (1ull << 63)); }
 __device__ __forceinline__ u32 mm_unkey_f32(u64 k) { const u32 b = (u32)k; return (b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b; }
 __device__ __forceinline__ u64 mm_unkey_f64(u64 k) { return (k >> 63) ? (k & ~(1ull << 63)) : ~k; }
 
-// One row's contribution: which flag it sets and, for a numeric value that is not NaN, its kind (0 .. 4) and key (before MIN's complement).
+// One row's contribution: which flag it sets and, for a numeric value that is not NaN, its kind (AggMinMaxKind) and key (before MIN's complement).
 struct MmRow { u32 flags; u32 kind; u64 key; bool has; };
 __device__ __forceinline__ MmRow mm_row(const Val& v) {
   MmRow m{0, 0, 0, false};
   switch (num_kind(v.tag)) {
-    case NK_INT: m.kind = 0; m.key = mm_key_i64(v.lo); m.has = true; break;
-    case NK_INTEGER: m.kind = 1; m.key = mm_key_i64(v.lo); m.has = true; break;
+    case NK_INT: m.kind = kMmInt; m.key = mm_key_i64(v.lo); m.has = true; break;
+    case NK_INTEGER: m.kind = kMmInteger; m.key = mm_key_i64(v.lo); m.has = true; break;
     case NK_DECIMAL: m.kind = kMmDecKind; m.key = mm_key_i64(v.hi); m.has = true; break;
-    case NK_FLOAT: { const u32 b = (u32)v.lo; if ((b & 0x7FFFFFFFu) > 0x7F800000u) m.flags = kMmNanFloat; else { m.kind = 3; m.key = mm_key_f32(b); m.has = true; } break; }
-    case NK_DOUBLE: { const u64 b = (u64)v.lo; if ((b & ~(1ull << 63)) > 0x7FF0000000000000ull) m.flags = kMmNanDouble; else { m.kind = 4; m.key = mm_key_f64(b); m.has = true; } break; }
+    case NK_FLOAT: { const u32 b = (u32)v.lo; if ((b & 0x7FFFFFFFu) > 0x7F800000u) m.flags = kMmNanFloat; else { m.kind = kMmFloat; m.key = mm_key_f32(b); m.has = true; } break; }
+    case NK_DOUBLE: { const u64 b = (u64)v.lo; if ((b & ~(1ull << 63)) > 0x7FF0000000000000ull) m.flags = kMmNanDouble; else { m.kind = kMmDouble; m.key = mm_key_f64(b); m.has = true; } break; }
     default: m.flags = v.tag == RDFGPU_TV_NULL ? kMmError : kMmOther;
   }
   if (m.has) m.flags = kMmSeen0 << m.kind;
   return m;
+}
+// .. into the words of a MIN (`mn`) / MAX whose first word of the row's group is at `w`.  true: the row held a decimal (the refinement has work).
+template <bool LDS> __device__ __forceinline__ bool minmax_accum(const AggArgs& a, u64 w, const Val v, bool valid, bool mn, const AggRun& r) {
+  unsigned long long* acc = agg_acc<LDS>(a);
+  MmRow m = mm_row(v);
+  if (!valid) m = MmRow{0, 0, 0, false};
+  if (mn) m.key = ~m.key;
+  acc_or(acc, agg_word(a, w, kMmFlags), m.flags, r);
+#pragma unroll
+  for (u32 q = 0; q < kMmKinds; q++) acc_max(acc, agg_word(a, w, kMmKey0 + q), m.has && m.kind == q ? m.key : 0ull, r);
+  return m.has && m.kind == kMmDecKind;
+}
+
+// One row's contribution to the words of a SUM / AVG whose first word of the row's group is at `w`.
+template <bool LDS> __device__ __forceinline__ void sum_accum(const AggArgs& a, u64 w, const Val v, bool valid, const AggRun& r) {
+  unsigned long long* acc = agg_acc<LDS>(a);
+  const int k = num_kind(v.tag);
+  u32 kind = k == NK_NONE ? kKindOther : k == NK_DECIMAL ? kKindDec : k == NK_FLOAT ? kKindFloat : k == NK_DOUBLE ? kKindDouble : kKindInt;
+  if (!valid) kind = 0;
+  const bool is_int = kind == kKindInt, is_dec = kind == kKindDec, num = valid && k != NK_NONE;
+  const u64 ix = is_int ? (u64)v.lo : 0ull;
+  const u64 d0 = is_dec ? (u64)v.lo : 0ull, d1 = is_dec ? (u64)v.hi : 0ull;
+  acc_or(acc, agg_word(a, w, kSumKinds), kind, r);
+  acc_add(acc, agg_word(a, w, kSumIntLo), ix & 0xFFFFFFFFull, r);
+  acc_add(acc, agg_word(a, w, kSumIntHi), ix >> 32, r);
+  acc_add(acc, agg_word(a, w, kSumIntNeg), is_int && v.lo < 0, r);
+  acc_add(acc, agg_word(a, w, kSumDec0), d0 & 0xFFFFFFFFull, r);
+  acc_add(acc, agg_word(a, w, kSumDec1), d0 >> 32, r);
+  acc_add(acc, agg_word(a, w, kSumDec2), d1 & 0xFFFFFFFFull, r);
+  acc_add(acc, agg_word(a, w, kSumDec3), d1 >> 32, r);
+  acc_add(acc, agg_word(a, w, kSumDecNeg), is_dec && v.hi < 0, r);
+  acc_add_f64(acc, agg_word(a, w, kSumF64), num ? to_f64(v, k) : 0.0, r);
+  acc_add_f64(acc, agg_word(a, w, kSumF32), num ? (double)to_f32(v, k) : 0.0, r);
 }
 
 // First insertion of (g, id) into the COUNT DISTINCT set.
@@ -190,81 +236,51 @@ __device__ __forceinline__ const u32* agg_col(const AggArgs& a, u32 c) {
   for (u32 q = 1; q < (u32)kMaxCols; q++) p = c == q ? a.col[q] : p;
   return p;
 }
+// The input of aggregate `i` at `row`: its id (0 behind the live rows, and for an expression input, which has no column) ..
+template <bool EXPR> __device__ __forceinline__ u32 agg_input_id(const AggArgs& a, u32 i, u64 row, bool valid) {
+  return valid && (!EXPR || a.in[i]) ? a.in[i][row] : 0u;
+}
+// .. and its value: ENC_TV of that id, one 16-byte gather, or the value of the aggregate's program (uniform).  COUNT / COUNT DISTINCT stop at the id.
+template <bool EXPR, bool LEX> __device__ __forceinline__ Val agg_input(const AggArgs& a, u32 i, u32 id, u64 row, bool valid) {
+  if constexpr (EXPR) return a.prog[i] ? eval_program<LEX>(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
+  else return enc_tv(a.tt, id);
+}
 
-// EXPR: some SUM / AVG reads an expression (RDFGPU_AGG_INPUT_EXPR): that aggregate's value is its program's, evaluated by the VM.  A node
-// whose aggregates are all plain columns runs the instantiation without the VM in it.
-// MINMAX: some aggregate is a MIN / MAX.  The instantiations without it are the code they were before MIN / MAX existed.
+// EXPR: some aggregate reads an expression (RDFGPU_AGG_INPUT_EXPR): its value is its program's, evaluated by the VM.  A node whose aggregates
+// are all plain columns runs the instantiation without the VM in it.  MINMAX: some aggregate is a MIN / MAX; the others leave that code out.
 template <bool LDS, bool EXPR, bool LEX = false, bool MINMAX = false>
 __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
-  extern __shared__ unsigned long long lacc[];
   const u32 tid = threadIdx.x, lane = tid & 63;
   [[maybe_unused]] bool dec_seen = false;
   const u64 n = live_rows(a.n_dev, a.cap);
   const u32 G = a.n_groups;
-  unsigned long long* acc = a.acc;
+  unsigned long long* const acc = agg_acc<LDS>(a);
   if constexpr (LDS) {
-    for (u32 i = tid; i < a.n_words * G; i += kAggBlock) lacc[i] = 0ull;
+    for (u32 i = tid; i < a.n_words * G; i += kAggBlock) acc[i] = 0ull;
     __syncthreads();
-    acc = lacc;
   }
   for (u64 base = (u64)blockIdx.x * kAggBlock; base < n; base += (u64)gridDim.x * kAggBlock) {
     const u64 row = base + tid;
     const bool valid = row < n;
-    const u32 g = !valid ? kGroupNone : a.n_keys ? a.slot_gid[a.row_slot[row]] : 0u;
-    const u32 prev = __shfl_up(g, 1);
-    const bool head = lane == 0 || prev != g;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = heads & ~((2ull << lane) - 1ull);   // heads of later lanes (lane 63: 2 << 63 wraps to 0, none)
-    AggRun r{lane, after ? (u32)__ffsll((long long)after) - 1u : 64u, head && valid, heads != ~0ull};
+    const u32 g = agg_group(a, row, valid);
+    const AggRun r = agg_run(g, valid, lane);
     acc_add(acc, g, 1ull, r);   // word 0: rows of the group
     for (u32 i = 0; i < a.n_aggs; i++) {
       const u32 fn = a.fn[i];
       if (fn == RDFGPU_AGG_COUNT_STAR) continue;
-      const u64 w = (u64)a.word0[i] * G + (valid ? g : 0u);
-      u32 id;
-      if constexpr (EXPR) id = valid && a.in[i] ? a.in[i][row] : 0u;
-      else id = valid ? a.in[i][row] : 0u;
+      const u64 w = agg_word0(a, i, valid ? g : 0u);
+      const u32 id = agg_input_id<EXPR>(a, i, row, valid);
       if (fn == RDFGPU_AGG_COUNT) { acc_add(acc, w, id != 0, r); continue; }
       if (fn == RDFGPU_AGG_COUNT_DISTINCT) { acc_add(acc, w, id != 0 && dset_insert(a.dset[i], a.dset_mask, g, id), r); continue; }
-      // SUM / AVG: ENC_TV of the id, one 16-byte gather — or the value of the aggregate's program (the branch is uniform)
-      Val v;
-      if constexpr (EXPR) v = a.prog[i] ? eval_program<LEX>(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
-      else v = enc_tv(a.tt, id);
-      if constexpr (MINMAX) {
-        if (fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX) {   // (uniform)
-          MmRow m = mm_row(v);
-          if (!valid) m = MmRow{0, 0, 0, false};
-          if (fn == RDFGPU_AGG_MIN) m.key = ~m.key;
-          dec_seen = dec_seen || (m.has && m.kind == kMmDecKind);
-          acc_or(acc, w, m.flags, r);
-#pragma unroll
-          for (u32 q = 0; q < 5; q++) acc_max(acc, w + (u64)(1 + q) * G, m.has && m.kind == q ? m.key : 0ull, r);
-          continue;
-        }
-      }
-      const int k = num_kind(v.tag);
-      u32 kind = k == NK_NONE ? kKindOther : k == NK_DECIMAL ? kKindDec : k == NK_FLOAT ? kKindFloat : k == NK_DOUBLE ? kKindDouble : kKindInt;
-      if (!valid) kind = 0;
-      const bool is_int = kind == kKindInt, is_dec = kind == kKindDec, num = valid && k != NK_NONE;
-      const u64 ix = is_int ? (u64)v.lo : 0ull;
-      const u64 d0 = is_dec ? (u64)v.lo : 0ull, d1 = is_dec ? (u64)v.hi : 0ull;
-      acc_or(acc, w, kind, r);
-      acc_add(acc, w + 1ull * G, ix & 0xFFFFFFFFull, r);
-      acc_add(acc, w + 2ull * G, ix >> 32, r);
-      acc_add(acc, w + 3ull * G, is_int && v.lo < 0, r);
-      acc_add(acc, w + 4ull * G, d0 & 0xFFFFFFFFull, r);
-      acc_add(acc, w + 5ull * G, d0 >> 32, r);
-      acc_add(acc, w + 6ull * G, d1 & 0xFFFFFFFFull, r);
-      acc_add(acc, w + 7ull * G, d1 >> 32, r);
-      acc_add(acc, w + 8ull * G, is_dec && v.hi < 0, r);
-      acc_add_f64(acc, w + 9ull * G, num ? to_f64(v, k) : 0.0, r);
-      acc_add_f64(acc, w + 10ull * G, num ? (double)to_f32(v, k) : 0.0, r);
+      const Val v = agg_input<EXPR, LEX>(a, i, id, row, valid);
+      if (MINMAX && agg_is_minmax(fn)) dec_seen = minmax_accum<LDS>(a, w, v, valid, fn == RDFGPU_AGG_MIN, r) || dec_seen;   // (uniform)
+      else sum_accum<LDS>(a, w, v, valid, r);
     }
   }
   if constexpr (LDS) {   // merge this workgroup's partials once (same layout: the LDS form holds every group)
     __syncthreads();
     for (u32 i = tid; i < a.n_words * G; i += kAggBlock) {
-      const unsigned long long v = lacc[i];
+      const unsigned long long v = acc[i];
       if (v == 0ull) continue;
       const u8 op = a.word_op[i / G];
       if (op == kAggOr) atomicOr(a.acc + i, v);
@@ -295,31 +311,21 @@ __global__ __launch_bounds__(kAggBlock) void agg_minmax_refine_kernel(const AggA
   if (*a.mm_dec_seen == 0) return;
   const u32 tid = threadIdx.x, lane = tid & 63;
   const u64 n = live_rows(a.n_dev, a.cap);
-  const u32 G = a.n_groups;
   for (u64 base = (u64)blockIdx.x * kAggBlock; base < n; base += (u64)gridDim.x * kAggBlock) {
     const u64 row = base + tid;
     const bool valid = row < n;
-    const u32 g = !valid ? kGroupNone : a.n_keys ? a.slot_gid[a.row_slot[row]] : 0u;
-    const u32 prev = __shfl_up(g, 1);
-    const bool head = lane == 0 || prev != g;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = heads & ~((2ull << lane) - 1ull);
-    AggRun r{lane, after ? (u32)__ffsll((long long)after) - 1u : 64u, head && valid, heads != ~0ull};
+    const u32 g = agg_group(a, row, valid);
+    const AggRun r = agg_run(g, valid, lane);
     for (u32 i = 0; i < a.n_aggs; i++) {
       const u32 fn = a.fn[i];
-      if (fn != RDFGPU_AGG_MIN && fn != RDFGPU_AGG_MAX) continue;
-      const u64 w = (u64)a.word0[i] * G + (valid ? g : 0u);
-      u32 id;
-      if constexpr (EXPR) id = valid && a.in[i] ? a.in[i][row] : 0u;
-      else id = valid ? a.in[i][row] : 0u;
-      Val v;
-      if constexpr (EXPR) v = a.prog[i] ? eval_program<LEX>(*a.prog[i], a.tt, [&](u32 c) { return valid ? agg_col(a, c)[row] : 0u; }) : enc_tv(a.tt, id);
-      else v = enc_tv(a.tt, id);
+      if (!agg_is_minmax(fn)) continue;
+      const u64 w = agg_word0(a, i, valid ? g : 0u);
+      const Val v = agg_input<EXPR, LEX>(a, i, agg_input_id<EXPR>(a, i, row, valid), row, valid);
       const bool mn = fn == RDFGPU_AGG_MIN;
       const bool dec = valid && v.tag == RDFGPU_TV_DECIMAL;
       const u64 hi = mn ? ~mm_key_i64(v.hi) : mm_key_i64(v.hi);
-      const bool won = dec && a.acc[w + (u64)kMmDecHi * G] == hi;
-      acc_max(a.acc, w + (u64)kMmDecLo * G, won ? (mn ? ~(u64)v.lo : (u64)v.lo) : 0ull, r);
+      const bool won = dec && a.acc[agg_word(a, w, kMmDecHi)] == hi;
+      acc_max(a.acc, agg_word(a, w, kMmDecLo), won ? (mn ? ~(u64)v.lo : (u64)v.lo) : 0ull, r);
     }
   }
 }
@@ -366,25 +372,25 @@ __device__ __forceinline__ void put(rdfgpu_agg_value* o, u32 g, u8 tag, long lon
 // unbeaten candidate of the lowest kind.  NaN candidates (a kind whose values were all NaN) take part only if there is no other.
 __device__ __noinline__ int mm_cmp(const Val& x, const Val& y) { return tv_partial_cmp(x, y); }
 __device__ __forceinline__ void minmax_final(const AggArgs& a, u32 i, u32 g, u64 rows) {
-  const u32 G = a.n_groups;
   const bool mn = a.fn[i] == RDFGPU_AGG_MIN;
   rdfgpu_agg_value* o = a.out[i];
-  const unsigned long long* w = a.acc + (u64)a.word0[i] * G + g;
-  const u32 flags = (u32)w[0];
+  const unsigned long long* w = a.acc + agg_word0(a, i, g);
+  auto word = [&](u32 k) { return w[agg_word(a, 0, k)]; };
+  const u32 flags = (u32)word(kMmFlags);
   if (flags & kMmOther) { if (a.tt.rt_error) atomicOr(a.tt.rt_error, kRtMinMaxKind); put(o, g, RDFGPU_TV_NULL, 0, 0); return; }   // rule 3: the execute fails
   if (rows == 0 || (flags & kMmError)) { put(o, g, RDFGPU_TV_NULL, 0, 0); return; }                                                // rules 1 and 2
-  const u8 tags[5] = {RDFGPU_TV_INT, RDFGPU_TV_INTEGER, RDFGPU_TV_DECIMAL, RDFGPU_TV_FLOAT, RDFGPU_TV_DOUBLE};
-  Val c[5];
-  u32 have = flags & 31u;
-  for (u32 q = 0; q < 5; q++) {
+  const u8 tags[kMmKinds] = {RDFGPU_TV_INT, RDFGPU_TV_INTEGER, RDFGPU_TV_DECIMAL, RDFGPU_TV_FLOAT, RDFGPU_TV_DOUBLE};
+  Val c[kMmKinds];
+  u32 have = flags & ((kMmSeen0 << kMmKinds) - 1u);
+  for (u32 q = 0; q < kMmKinds; q++) {
     c[q] = val_tv_null();
     if (!(have >> q & 1u)) continue;
-    u64 k = w[(u64)(1 + q) * G];
+    u64 k = word(kMmKey0 + q);
     if (mn) k = ~k;
     c[q].tag = tags[q];
-    if (q == 3) c[q].lo = (int64_t)(u64)mm_unkey_f32(k);
-    else if (q == 4) c[q].lo = (int64_t)mm_unkey_f64(k);
-    else if (q == kMmDecKind) { const u64 lo = w[(u64)kMmDecLo * G]; c[q].hi = (int64_t)(k ^ (1ull << 63)); c[q].lo = (int64_t)(mn ? ~lo : lo); }
+    if (q == kMmFloat) c[q].lo = (int64_t)(u64)mm_unkey_f32(k);
+    else if (q == kMmDouble) c[q].lo = (int64_t)mm_unkey_f64(k);
+    else if (q == kMmDecKind) { const u64 lo = word(kMmDecLo); c[q].hi = (int64_t)(k ^ (1ull << 63)); c[q].lo = (int64_t)(mn ? ~lo : lo); }
     else c[q].lo = (int64_t)(k ^ (1ull << 63));
   }
   if (have == 0) {   // every value a NaN: the lowest kind's
@@ -392,19 +398,18 @@ __device__ __forceinline__ void minmax_final(const AggArgs& a, u32 i, u32 g, u64
     return;
   }
   const int beats = mn ? -1 : 1;
-  for (u32 q = 0; q < 5; q++) {
+  for (u32 q = 0; q < kMmKinds; q++) {
     if (!(have >> q & 1u)) continue;
     bool beaten = false;
-    for (u32 p = 0; p < 5; p++) if (p != q && (have >> p & 1u) && mm_cmp(c[p], c[q]) == beats) beaten = true;
+    for (u32 p = 0; p < kMmKinds; p++) if (p != q && (have >> p & 1u) && mm_cmp(c[p], c[q]) == beats) beaten = true;
     if (!beaten) { put(o, g, c[q].tag, c[q].lo, c[q].hi); return; }
   }
   put(o, g, RDFGPU_TV_NULL, 0, 0);   // (unreachable: the exact extremum's candidate is unbeaten)
 }
 
 __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
-  const u32 G = a.n_groups;
   const u32 g = blockIdx.x * kAggBlock + threadIdx.x;
-  if (g >= G) return;
+  if (g >= a.n_groups) return;
   if (a.n_keys) {
     const u32 rep = a.rep_row[g];
     for (u32 q = 0; q < a.n_keys; q++) a.out_key[q][g] = a.key[q][rep];
@@ -414,15 +419,17 @@ __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
     const u32 fn = a.fn[i];
     rdfgpu_agg_value* o = a.out[i];
     if (fn == RDFGPU_AGG_COUNT_STAR) { put(o, g, RDFGPU_TV_INTEGER, (long long)rows, 0); continue; }
-    const unsigned long long* w = a.acc + (u64)a.word0[i] * G + g;
+    const unsigned long long* w = a.acc + agg_word0(a, i, g);
+    auto word = [&](u32 k) { return w[agg_word(a, 0, k)]; };
     if (fn == RDFGPU_AGG_COUNT || fn == RDFGPU_AGG_COUNT_DISTINCT) { put(o, g, RDFGPU_TV_INTEGER, (long long)w[0], 0); continue; }
-    if (fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX) continue;   // agg_minmax_final_kernel's
-    const u32 kinds = (u32)w[0];
+    if (agg_is_minmax(fn)) continue;   // agg_minmax_final_kernel's
+    // SUM / AVG (sum.rs, avg.rs).  The arithmetic stays in this kernel's loop: as a function beside minmax_final it cost the kernel 5 % at 2^24 groups.
+    const u32 kinds = (u32)word(kSumKinds);
     const bool avg = fn == RDFGPU_AGG_AVG;
     if (avg && rows == 0) { put(o, g, RDFGPU_TV_INTEGER, 0, 0); continue; }                   // avg.rs: count 0 => integer 0
     if (avg && (kinds & kKindOther)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }            // avg.rs:63-78
-    const double f64 = __longlong_as_double((long long)w[9 * (u64)G]);
-    const double f32s = __longlong_as_double((long long)w[10 * (u64)G]);
+    const double f64 = __longlong_as_double((long long)word(kSumF64));
+    const double f32s = __longlong_as_double((long long)word(kSumF32));
     if (kinds & kKindDouble) {
       const double v = avg ? __ddiv_rn(f64, (double)rows) : f64;
       put(o, g, RDFGPU_TV_DOUBLE, __double_as_longlong(v), 0); continue;
@@ -433,19 +440,19 @@ __global__ __launch_bounds__(kAggBlock) void agg_final_kernel(const AggArgs a) {
       put(o, g, RDFGPU_TV_FLOAT, (long long)(u64)__float_as_uint(v), 0); continue;
     }
     // exact integer part I = L0 + L1 * 2^32 - negatives * 2^64
-    Wide I = wide_shifted(w[1 * (u64)G], 0);
-    wide_add(I, wide_shifted(w[2 * (u64)G], 32));
-    wide_add(I, wide_neg(wide_shifted(w[3 * (u64)G], 64)));
+    Wide I = wide_shifted(word(kSumIntLo), 0);
+    wide_add(I, wide_shifted(word(kSumIntHi), 32));
+    wide_add(I, wide_neg(wide_shifted(word(kSumIntNeg), 64)));
     if (!avg && !(kinds & kKindDec)) {   // sum.rs: starts as integer 0, integers only
       if (wide_fits(I, 1)) put(o, g, RDFGPU_TV_INTEGER, (long long)I.w[0], 0); else put(o, g, RDFGPU_TV_NULL, 0, 0);
       continue;
     }
     // decimal: D = sum(limb_i * 2^(32 i)) - negatives * 2^128, plus I * 10^18
-    Wide D = wide_shifted(w[4 * (u64)G], 0);
-    wide_add(D, wide_shifted(w[5 * (u64)G], 32));
-    wide_add(D, wide_shifted(w[6 * (u64)G], 64));
-    wide_add(D, wide_shifted(w[7 * (u64)G], 96));
-    wide_add(D, wide_neg(wide_shifted(w[8 * (u64)G], 128)));
+    Wide D = wide_shifted(word(kSumDec0), 0);
+    wide_add(D, wide_shifted(word(kSumDec1), 32));
+    wide_add(D, wide_shifted(word(kSumDec2), 64));
+    wide_add(D, wide_shifted(word(kSumDec3), 96));
+    wide_add(D, wide_neg(wide_shifted(word(kSumDecNeg), 128)));
     wide_mul(I, 1000000000000000000ull);
     wide_add(D, I);
     if (!wide_fits(D, 2)) { put(o, g, RDFGPU_TV_NULL, 0, 0); continue; }
@@ -463,7 +470,7 @@ __global__ __launch_bounds__(kAggBlock) void agg_minmax_final_kernel(const AggAr
   if (g >= a.n_groups) return;
   const u64 rows = a.acc[g];
   for (u32 i = 0; i < a.n_aggs; i++)
-    if (a.fn[i] == RDFGPU_AGG_MIN || a.fn[i] == RDFGPU_AGG_MAX) minmax_final(a, i, g, rows);
+    if (agg_is_minmax(a.fn[i])) minmax_final(a, i, g, rows);
 }
 
 // ---- pass 4, aggregate values as columns (RDFGPU_PLAN_AGG_COLUMNS) only ------------------------------------------------------------
@@ -476,62 +483,32 @@ __global__ __launch_bounds__(kAggBlock) void agg_value_cols_kernel(const AggArgs
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-void launch_agg_groups(const AggArgs& a, hipStream_t s) {
-  u64 g = (a.cap + kAggTile - 1) / kAggTile;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(agg_groups_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
+using AggKernel = void (*)(const AggArgs);
+// The accumulate kernels by [a.minmax][a.exprs][a.lds], the refinement's by [a.exprs]  (plan.hpp, agg_accum_class: the class reported for the same fields).
+static const AggKernel kAggAccumKernels[2][3][2] = {
+    {{agg_accum_kernel<false>, agg_accum_kernel<true>}, {agg_accum_expr_kernel<false>, agg_accum_expr_kernel<true>}, {agg_accum_lex_kernel<false>, agg_accum_lex_kernel<true>}},
+    {{agg_accum_minmax_kernel<false>, agg_accum_minmax_kernel<true>}, {agg_accum_minmax_expr_kernel<false>, agg_accum_minmax_expr_kernel<true>},
+     {agg_accum_minmax_lex_kernel<false>, agg_accum_minmax_lex_kernel<true>}}};
+static const AggKernel kAggRefineKernels[3] = {agg_minmax_refine_kernel<false, false>, agg_minmax_refine_kernel<true, false>, agg_minmax_refine_kernel<true, true>};
+
+static void agg_launch(AggKernel kernel, u64 grid, size_t lds, const AggArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(grid ? grid : 1)), dim3(kAggBlock), lds, s, a);
   RDFGPU_HIP(hipGetLastError());
 }
-
+void launch_agg_groups(const AggArgs& a, hipStream_t s) { agg_launch(agg_groups_kernel, std::min<u64>((a.cap + kAggTile - 1) / kAggTile, kAggGroupGrid), 0, a, s); }
 void launch_agg_accum(const AggArgs& a, hipStream_t s) {
-  u64 g = (a.cap + kAggBlock - 1) / kAggBlock;
-  if (a.lds) {
-    const size_t lds = (size_t)a.n_words * a.n_groups * sizeof(unsigned long long);
-    if (lds > kAggLdsBytes) fail(RDFGPU_ERR_INVALID, "aggregate: %zu bytes of LDS partials", lds);
-    if (g > 512) g = 512;   // every workgroup zeroes and merges all partials: enough of them to fill the part, not one per tile
-    if (a.minmax) {
-      if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_minmax_lex_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
-      else if (a.exprs) hipLaunchKernelGGL(agg_accum_minmax_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
-      else hipLaunchKernelGGL(agg_accum_minmax_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
-    } else
-    if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_lex_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
-    else if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
-    else hipLaunchKernelGGL(agg_accum_kernel<true>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), lds, s, a);
-  } else {
-    if (g > 16384) g = 16384;
-    if (a.minmax) {
-      if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_minmax_lex_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-      else if (a.exprs) hipLaunchKernelGGL(agg_accum_minmax_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-      else hipLaunchKernelGGL(agg_accum_minmax_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-    } else
-    if (a.exprs == 2) hipLaunchKernelGGL(agg_accum_lex_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-    else if (a.exprs) hipLaunchKernelGGL(agg_accum_expr_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-    else hipLaunchKernelGGL(agg_accum_kernel<false>, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  }
-  RDFGPU_HIP(hipGetLastError());
+  const size_t lds = a.lds ? (size_t)a.n_words * a.n_groups * sizeof(unsigned long long) : 0;
+  if (lds > kAggLdsBytes) fail(RDFGPU_ERR_INVALID, "aggregate: %zu bytes of LDS partials", lds);
+  const u64 grid = std::min<u64>((a.cap + kAggBlock - 1) / kAggBlock, a.lds ? kAggAccumLdsGrid : kAggAccumHbmGrid);
+  agg_launch(kAggAccumKernels[a.minmax ? 1 : 0][std::min(a.exprs, 2u)][a.lds ? 1 : 0], grid, lds, a, s);
 }
-
+void launch_agg_minmax_refine(const AggArgs& a, hipStream_t s) { agg_launch(kAggRefineKernels[std::min(a.exprs, 2u)], std::min<u64>((a.cap + kAggBlock - 1) / kAggBlock, kAggAccumHbmGrid), 0, a, s); }
 void launch_agg_final(const AggArgs& a, hipStream_t s) {
-  const u64 g = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
-  hipLaunchKernelGGL(agg_final_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  if (a.minmax) hipLaunchKernelGGL(agg_minmax_final_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  RDFGPU_HIP(hipGetLastError());
+  const u64 grid = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
+  agg_launch(agg_final_kernel, grid, 0, a, s);
+  if (a.minmax) agg_launch(agg_minmax_final_kernel, grid, 0, a, s);
 }
-
-void launch_agg_minmax_refine(const AggArgs& a, hipStream_t s) {
-  u64 g = (a.cap + kAggBlock - 1) / kAggBlock;
-  if (g > 16384) g = 16384;
-  if (a.exprs == 2) hipLaunchKernelGGL((agg_minmax_refine_kernel<true, true>), dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  else if (a.exprs) hipLaunchKernelGGL((agg_minmax_refine_kernel<true, false>), dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  else hipLaunchKernelGGL((agg_minmax_refine_kernel<false, false>), dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  RDFGPU_HIP(hipGetLastError());
-}
-
-void launch_agg_value_cols(const AggArgs& a, hipStream_t s) {
-  const u64 g = ((u64)a.n_groups + kAggBlock - 1) / kAggBlock;
-  hipLaunchKernelGGL(agg_value_cols_kernel, dim3((unsigned)(g ? g : 1)), dim3(kAggBlock), 0, s, a);
-  RDFGPU_HIP(hipGetLastError());
-}
+void launch_agg_value_cols(const AggArgs& a, hipStream_t s) { agg_launch(agg_value_cols_kernel, ((u64)a.n_groups + kAggBlock - 1) / kAggBlock, 0, a, s); }
 
 // (kernels.hpp, preload_code_objects: the runtime loads a translation unit's code object at the first use of one of its kernels)
 void preload_tu_aggregate() { hipFuncAttributes at; RDFGPU_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void*>(agg_final_kernel))); }

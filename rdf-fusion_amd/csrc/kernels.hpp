@@ -292,6 +292,29 @@ constexpr u32 kAggMinMaxWords = 7;        // accumulator words of a MIN / MAX pe
 constexpr u32 kAggMaxWords = 1 + RDFGPU_MAX_AGGREGATES * kAggSumWords;
 constexpr size_t kAggLdsBytes = 65536;    // LDS partials of one workgroup
 enum AggWordOp : u8 { kAggAdd = 0, kAggOr = 1, kAggAddF64 = 2, kAggMax = 3 };
+// The words of one aggregate, counted from its first (AggArgs::word0); COUNT / COUNT DISTINCT have one, COUNT(*) reads word 0 of the group.
+// This is the one statement of the layout: the host lays the words out by agg_words / agg_word_op, aggregate.hip indexes by the names.
+enum AggSumWord : u32 {      // SUM / AVG
+  kSumKinds,                 // kinds seen (aggregate.hip, kKind*)
+  kSumIntLo, kSumIntHi, kSumIntNeg,                          // the integer values: sums of their two 32-bit limbs, the number of negative ones
+  kSumDec0, kSumDec1, kSumDec2, kSumDec3, kSumDecNeg,        // the decimal values: sums of their four 32-bit limbs, the number of negative ones
+  kSumF64, kSumF32,          // the values cast to f64 / to f32, summed in f64
+  kSumWordsEnd };
+enum AggMinMaxKind : u32 { kMmInt, kMmInteger, kMmDecKind, kMmFloat, kMmDouble, kMmKinds };   // MIN / MAX keeps one key per numeric kind, in this order
+enum AggMinMaxWord : u32 {   // MIN / MAX
+  kMmFlags,                  // which kinds were seen, NaNs, errors (aggregate.hip, kMm*)
+  kMmKey0,                   // .. kMmKey0 + kind: the largest key of that kind; the decimal's is its high word,
+  kMmDecHi = kMmKey0 + kMmDecKind,
+  kMmDecLo = kMmKey0 + kMmKinds,   // and this its low word, which the refinement settles
+  kMmWordsEnd };
+static_assert(kSumWordsEnd == kAggSumWords && kMmWordsEnd == kAggMinMaxWords, "the named words are all the words");
+__host__ __device__ constexpr bool agg_is_sum(u32 fn) { return fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG; }
+__host__ __device__ constexpr bool agg_is_minmax(u32 fn) { return fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX; }
+__host__ __device__ constexpr u32 agg_words(u32 fn) { return fn == RDFGPU_AGG_COUNT_STAR ? 0 : agg_is_sum(fn) ? kAggSumWords : agg_is_minmax(fn) ? kAggMinMaxWords : 1; }
+__host__ __device__ constexpr AggWordOp agg_word_op(u32 fn, u32 w) {   // how word w of an aggregate is merged
+  return agg_is_sum(fn) ? (w == kSumKinds ? kAggOr : w == kSumF64 || w == kSumF32 ? kAggAddF64 : kAggAdd)
+       : agg_is_minmax(fn) ? (w == kMmFlags ? kAggOr : kAggMax) : kAggAdd;
+}
 struct AggArgs {
   u32 n_keys;
   const u32* key[RDFGPU_MAX_KEYS];

@@ -1,6 +1,6 @@
 // plan.cpp — execution (device) of a compiled plan: the driver, timing, scans and the small operators.
 // Compilation: plan_compile.cpp; FilterExec: plan_filter.cpp; the joins: plan_join.cpp; chain fusion and the band join: plan_band.cpp;
-// SortExec: plan_sort.cpp.
+// SortExec: plan_sort.cpp; AggregateExec: plan_aggregate.cpp.
 //
 // What replaces what (reference paths relative to the rdf-fusion tree):
 //   Plan::exec_source       DataSource::open + MemQuadIndexScanIterator::next  pattern_data_source.rs:42-58, scan.rs:104-212
@@ -623,95 +623,6 @@ DevTable Plan::exec_topk(NodeInfo& nd) {
   if ((ctx->counters_host[i0 + 1] >> 32) != 0) fail(RDFGPU_ERR_UNSUPPORTED, "TopK: SORT_BY_TERM over a column that is not all strings / IRIs / blank nodes");
   t.cap = std::min<u64>(out_cap, ctx->counters_host[i0]);
   t.n_dev = n_out;
-  return t;
-}
-
-// AggregateExec(mode=Single) (aggregate.hip): group pass, one read-back of the group count (it sizes the accumulators and is the
-// output's row count), accumulate pass, one lane per group to finish.  Over a zero-key aggregate there is one group and no group pass.
-// Compulsory bytes: per input row 4 per key column, 4 + 16 per SUM / AVG / MIN / MAX input (id + typed value), 4 per COUNT /
-// COUNT DISTINCT input; per output group 4 per key column + 24 per aggregate.  A MIN / MAX input is read once more by the refinement
-// launch (agg_minmax_refine_kernel), which is counted as if decimals were there: 4 + 16 per row again.
-DevTable Plan::exec_aggregate(NodeInfo& nd) {
-  const DevTable in = exec_sub_plan((u32)nd.d.left);
-  flush_pending_oj();   // a held-back ordered-join write must have happened before the input is read
-  if (in.cap >= (1ull << 32)) fail(RDFGPU_ERR_UNSUPPORTED, "AggregateExec over %llu rows (at most 2^32 - 1)", (unsigned long long)in.cap);
-  AggArgs a{};
-  a.n_keys = nd.d.n_keys;
-  for (u32 k = 0; k < a.n_keys; k++) a.key[k] = in.cols[nd.d.left_keys[k]];
-  a.n_dev = in.n_dev; a.cap = in.cap;
-  a.n_aggs = nd.n_aggs;
-  a.n_words = 1;
-  a.word_op[0] = kAggAdd;
-  u64 accum_row_bytes = 0, refine_row_bytes = 0;   // (the refinement reads a MIN / MAX input's id and typed value once more)
-  bool distinct = false;
-  for (u32 i = 0; i < a.n_aggs; i++) {
-    const u32 fn = nd.agg_fn[i];
-    a.fn[i] = fn; a.in[i] = fn == RDFGPU_AGG_COUNT_STAR || nd.agg_prog[i] >= 0 ? nullptr : in.cols[nd.agg_col[i]];
-    if (nd.agg_prog[i] >= 0) {   // SUM / AVG over an expression: the VM form of the accumulate pass, over every input column
-      a.prog[i] = upload_program(nd.agg_progs[nd.agg_prog[i]]);
-      if (a.exprs == 0) a.exprs = 1;
-      if (program_has_lex(nd.agg_progs[nd.agg_prog[i]])) a.exprs = 2;
-      for (u32 c = 0; c < in.n_cols; c++) a.col[c] = in.cols[c];
-    }
-    a.word0[i] = a.n_words;
-    const bool minmax = fn == RDFGPU_AGG_MIN || fn == RDFGPU_AGG_MAX;
-    const u32 words = fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG) ? kAggSumWords : minmax ? kAggMinMaxWords : 1;
-    for (u32 w = 0; w < words; w++) a.word_op[a.n_words + w] = words == 1 ? kAggAdd : w == 0 ? kAggOr : minmax ? kAggMax : w >= 9 ? kAggAddF64 : kAggAdd;
-    a.n_words += words;
-    accum_row_bytes += fn == RDFGPU_AGG_COUNT_STAR ? 0 : (fn == RDFGPU_AGG_SUM || fn == RDFGPU_AGG_AVG || minmax) ? 20 : 4;
-    if (minmax) { a.minmax = 1; refine_row_bytes += 20; }
-    distinct = distinct || fn == RDFGPU_AGG_COUNT_DISTINCT;
-  }
-  a.tt = typed_table();
-  const u64 cap = in.cap;
-  u64 slots = 64;
-  while (slots < 2 * cap && slots < (1ull << 32)) slots <<= 1;
-  u64 G = 1;
-  if (a.n_keys) {
-    G = 0;
-    if (cap) {
-      a.slots = scratch<u32>(slots); a.slot_mask = (u32)(slots - 1);
-      a.row_slot = scratch<u32>(cap); a.slot_gid = scratch<u32>(slots); a.rep_row = scratch<u32>(cap);
-      a.n_groups_dev = new_counter();
-      RDFGPU_HIP(hipMemsetAsync(a.slots, 0, slots * sizeof(u32), stream));
-      timed(KC_AGG_GROUPS, 0, cap, in.n_dev, 4ull * a.n_keys, nullptr, 0, 0, [&] { launch_agg_groups(a, stream); });
-      G = read_back<u64>(a.n_groups_dev);
-    }
-  }
-  a.n_groups = (u32)G;
-  DevTable t;
-  t.n_cols = nd.width; t.cap = G;   // the keys; with aggregate values as columns, one more per aggregate
-  for (u32 k = 0; k < a.n_keys; k++) { a.out_key[k] = scratch<u32>(G); t.cols[k] = a.out_key[k]; }
-  for (u32 i = 0; i < a.n_aggs; i++) {
-    a.out[i] = scratch<rdfgpu_agg_value>(G); nd.values[i] = a.out[i];
-    if (agg_columns) { a.out_val[i] = scratch<u32>(G); t.cols[a.n_keys + i] = a.out_val[i]; }
-  }
-  nd.n_values = G; nd.values_run = run;
-  if (&nd == &nodes[root] && !agg_columns) agg_out.assign(a.out, a.out + a.n_aggs);
-  if (G == 0) return t;
-  a.acc = scratch<unsigned long long>(a.n_words * G);
-  RDFGPU_HIP(hipMemsetAsync(a.acc, 0, a.n_words * G * sizeof(unsigned long long), stream));
-  if (cap) {
-    if (distinct) {
-      a.dset_mask = (u32)(slots - 1);
-      for (u32 i = 0; i < a.n_aggs; i++) {
-        if (a.fn[i] != RDFGPU_AGG_COUNT_DISTINCT) continue;
-        a.dset[i] = scratch<unsigned long long>(slots);
-        RDFGPU_HIP(hipMemsetAsync(a.dset[i], 0, slots * sizeof(unsigned long long), stream));
-      }
-    }
-    a.lds = !opt.on(RDFGPU_OPT_NO_AGG_LDS) && (u64)a.n_words * G * sizeof(unsigned long long) <= kAggLdsBytes;
-    const int kc = a.minmax ? (a.exprs ? (a.lds ? KC_AGG_ACCUM_MINMAX_EXPR_LDS : KC_AGG_ACCUM_MINMAX_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_MINMAX_LDS : KC_AGG_ACCUM_MINMAX_HBM)
-                            : a.exprs ? (a.lds ? KC_AGG_ACCUM_EXPR_LDS : KC_AGG_ACCUM_EXPR_HBM) : a.lds ? KC_AGG_ACCUM_LDS : KC_AGG_ACCUM_HBM;
-    if (a.minmax) a.mm_dec_seen = new_counter();   // (zeroed with the other counters when the execution began)
-    timed(kc, 0, cap, in.n_dev, accum_row_bytes, nullptr, 0, 0, [&] { launch_agg_accum(a, stream); });
-    // MIN / MAX over decimals: the low word of each group's candidate, among the rows whose high word won.  No read-back decides the
-    // launch: the kernel leaves on the device word when the inputs held no decimal.
-    if (a.minmax) timed(KC_AGG_MINMAX_REFINE, 0, cap, in.n_dev, refine_row_bytes, nullptr, 0, 0, [&] { launch_agg_minmax_refine(a, stream); });
-  }
-  timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
-  // the value columns: per group and aggregate the tag read (the value was just written: cache) and 4 bytes written
-  if (agg_columns && a.n_aggs) timed(KC_AGG_VALUE_COLS, 0, 0, nullptr, 0, nullptr, G, 4ull * a.n_aggs, [&] { launch_agg_value_cols(a, stream); });
   return t;
 }
 

@@ -180,6 +180,15 @@ inline int lds_join_class(u32 fs, u32 pfs, int items, int mode, bool chain = fal
 
 inline int semi_join_class(int form, bool anti) { return KC_SEMI_JOIN0 + form * 2 + (anti ? 1 : 0); }
 
+// The class of the accumulate pass that launch_agg_accum (aggregate.hip) launches for these arguments: the one place that maps
+// (minmax, exprs, lds) to a KernelClass.  The LEX kernels (a.exprs == 2: agg_accum_lex_kernel, agg_accum_minmax_lex_kernel) have no
+// class of their own: they are reported under the EXPR classes, as they always were.
+inline int agg_accum_class(const AggArgs& a) {
+  static const int kc[2][2][2] = {{{KC_AGG_ACCUM_HBM, KC_AGG_ACCUM_LDS}, {KC_AGG_ACCUM_EXPR_HBM, KC_AGG_ACCUM_EXPR_LDS}},
+                                  {{KC_AGG_ACCUM_MINMAX_HBM, KC_AGG_ACCUM_MINMAX_LDS}, {KC_AGG_ACCUM_MINMAX_EXPR_HBM, KC_AGG_ACCUM_MINMAX_EXPR_LDS}}};
+  return kc[a.minmax ? 1 : 0][a.exprs ? 1 : 0][a.lds ? 1 : 0];
+}
+
 struct KernelStat { u32 launches = 0; double ms = 0; u64 bytes = 0; u64 rows = 0; };
 
 // One timed launch whose byte count may depend on device-side row counts, resolved after the run.
@@ -193,6 +202,16 @@ struct PendingLaunch {
   const u64* out_dev;   // device count of produced rows (or null)
   u64 out_rows;         // produced rows if known on the host
   u64 bytes_per_out;    // multiplied by the produced rows
+};
+
+// One AggregateExec while it is set up and run (plan_aggregate.cpp).
+struct AggNode {
+  NodeInfo& nd; const DevTable& in;
+  AggArgs a{};
+  u64 slots = 64;             // slots of the group table, and of every COUNT DISTINCT set: a power of two, at least twice the input's capacity
+  u64 G = 1;                  // groups = output rows
+  u64 accum_row_bytes = 0, refine_row_bytes = 0;   // what the accumulate pass / the refinement reads per input row
+  AggNode(NodeInfo& n, const DevTable& t) : nd(n), in(t) {}
 };
 
 struct Plan {
@@ -275,7 +294,8 @@ struct Plan {
   DevTable exec_join(NodeInfo& nd);
   DevTable exec_topk(NodeInfo& nd);
   DevTable exec_semi_join(NodeInfo& nd);
-  DevTable exec_aggregate(NodeInfo& nd);
+  DevTable exec_aggregate(NodeInfo& nd);   // its steps, in order (plan_aggregate.cpp):
+  void agg_bind_inputs(AggNode& n); void agg_group_pass(AggNode& n); DevTable agg_outputs(AggNode& n); void agg_accumulate(AggNode& n); void agg_finish(AggNode& n);
   DevTable exec_extend(NodeInfo& nd);
   DevTable exec_sort(NodeInfo& nd);
   DevTable apply_filter(NodeInfo& nd, const DevTable& in);   // its routes:

@@ -143,9 +143,8 @@ def test_geometry_matches_the_sources():
         assert ac.n_words(aggs) * lo * 8 <= ac.LDS_BYTES < ac.n_words(aggs) * hi * 8
     hip = open(os.path.join(CSRC, "aggregate.hip")).read()
     assert _constant(hip, "kAggBlock") == ac.ACCUM_BLOCK and _constant(hip, "kAggBlock") * _constant(hip, "kAggItems") == ac.GROUP_TILE
-    groups, accum = (hip[hip.index(f"void {f}("):] for f in ("launch_agg_groups", "launch_agg_accum"))
-    assert [int(x) for x in re.findall(r"if \(g > (\d+)\)", groups[:groups.index("void launch_agg_accum(")])] == [ac.GROUP_GRID]
-    assert [int(x) for x in re.findall(r"if \(g > (\d+)\)", accum[:accum.index("void launch_agg_final(")])] == [ac.ACCUM_LDS_GRID, ac.ACCUM_HBM_GRID]
+    assert _constant(hip, "kAggGroupGrid") == ac.GROUP_GRID
+    assert [_constant(hip, "kAggAccumLdsGrid"), _constant(hip, "kAggAccumHbmGrid")] == [ac.ACCUM_LDS_GRID, ac.ACCUM_HBM_GRID]
     # the smallest row counts at which the second trips exist, and partial ones
     assert ac.BIG_ROWS > ac.GROUP_TILE * ac.GROUP_GRID and ac.BIG_ROWS % ac.GROUP_TILE not in (0,) and ac.BIG_ROWS % 64 != 0
     assert ac.BIG_ROWS > ac.ACCUM_BLOCK * ac.ACCUM_HBM_GRID and ac.BIG_ROWS < 2 * ac.GROUP_TILE * ac.GROUP_GRID
