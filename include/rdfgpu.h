@@ -931,6 +931,14 @@ int rdfgpu_band_pair_count_eligible(uint32_t has_list, uint32_t option_set, uint
 int rdfgpu_band_step_form(uint32_t row_static, uint32_t has_verdicts, uint32_t has_list, uint32_t list_option_set, uint32_t counts_option_set,
                           uint32_t n_row_cols, uint64_t n_blocks, uint64_t min_blocks);
 /*
+ * The probe pass of the ordered slice join below such a band join: 0 FULL (the multimap, the stage rows and the packed records, launched where that join runs: every
+ * other route), 1 LEAN (owed by that join and run by the band join as one pass that writes the batch's values by key), 2 FULL_NOW (owed, and the full pass runs in front of
+ * the count pass after all).  held, in_place, row_cache: what the band join's last execution left (the write pass is held back for it; it read the slice's rows in place and
+ * no key had two table rows; the rows' windows were cached on the slice); option_set: RDFGPU_OPT_NO_BAND_ROW_CACHE; row_static: the band join's step took a form that reads
+ * the slice's rows through their cached windows — the ordered join itself asks with 1, and owes its probe unless the answer is FULL.
+ */
+int rdfgpu_oj_probe_form(uint32_t held, uint32_t in_place, uint32_t row_cache, uint32_t option_set, uint32_t row_static);
+/*
  * MemIndexScanPredicate::try_and_with (scan_instructions.rs:170-210).  Predicates are given
  * as (pred, a, b) triples where IN sets are explicit arrays.  Writes the combined predicate;
  * `out_ids` needs room for min(na, nb) ids.  Returns 1 if combinable, 0 if not (EqualTo).

@@ -178,7 +178,7 @@ EXPORTED_SYMBOLS = [
     "rdfgpu_plan_enable_kernel_timing", "rdfgpu_plan_kernel_stats",
     "rdfgpu_plan_pushdown_filters", "rdfgpu_plan_set_dynamic_filters", "rdfgpu_plan_source_predicate",
     "rdfgpu_store_set_option", "rdfgpu_store_get_option", "rdfgpu_plan_set_option", "rdfgpu_option_name",
-    "rdfgpu_scan_score", "rdfgpu_choose_index", "rdfgpu_predicate_and", "rdfgpu_band_row_cache_eligible", "rdfgpu_band_pair_cache_eligible", "rdfgpu_band_pair_list_eligible", "rdfgpu_band_pair_count_eligible", "rdfgpu_band_step_form",
+    "rdfgpu_scan_score", "rdfgpu_choose_index", "rdfgpu_predicate_and", "rdfgpu_band_row_cache_eligible", "rdfgpu_band_pair_cache_eligible", "rdfgpu_band_pair_list_eligible", "rdfgpu_band_pair_count_eligible", "rdfgpu_band_step_form", "rdfgpu_oj_probe_form",
     "rdfgpu_pushdown_to_scan_predicate", "rdfgpu_regex_check",
     "rdfgpu_comm_unique_id", "rdfgpu_comm_create", "rdfgpu_comm_create_host", "rdfgpu_comm_destroy",
     "rdfgpu_exchange_allgatherv", "rdfgpu_exchange_repartition", "rdfgpu_shard_of",

@@ -608,6 +608,11 @@ int rdfgpu_band_step_form(uint32_t row_static, uint32_t has_verdicts, uint32_t h
   s.counts_option_off = counts_option_set == 0; s.n_row_cols = n_row_cols; s.n_blocks = n_blocks; s.min_blocks = min_blocks;
   return (int)band_step_form(s);
 }
+int rdfgpu_oj_probe_form(uint32_t held, uint32_t in_place, uint32_t row_cache, uint32_t option_set, uint32_t row_static) {
+  OjProbeShape s;
+  s.held = held != 0; s.in_place = in_place != 0; s.row_cache = row_cache != 0; s.option_off = option_set == 0; s.row_static = row_static != 0;
+  return (int)oj_probe_form(s);
+}
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;
   if (p->pred == RDFGPU_PRED_IN) { if (p->ids) r.ids.assign(p->ids, p->ids + p->n_ids); else r.ids = {p->from}; }

@@ -181,4 +181,9 @@ BandForm band_step_form(const BandStepShape& s) {
   return band_pair_count_eligible(c) ? BandForm::COUNTS_LIST : BandForm::VERDICTS_LIST;
 }
 
+OjProbeForm oj_probe_form(const OjProbeShape& s) {
+  if (!s.held || !s.in_place || !s.row_cache || !s.option_off) return OjProbeForm::FULL;
+  return s.row_static ? OjProbeForm::LEAN : OjProbeForm::FULL_NOW;
+}
+
 }  // namespace rdfgpu

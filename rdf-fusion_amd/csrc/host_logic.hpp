@@ -97,4 +97,17 @@ struct BandStepShape {
 };
 BandForm band_step_form(const BandStepShape& s);
 
+// The probe pass of the ordered slice join below such a band join (ordered_join.hip): which of its two forms runs, and when.  A step of a row_static form takes from the
+// table only the rows' values by key, and which output column that is the band join alone knows: so when the last execution's flags promise such a step — the write pass
+// held back for the band join (held), that join read the slice's rows in place and no key had two table rows (in_place), the rows' windows were cached on the slice
+// (row_cache), RDFGPU_OPT_NO_BAND_ROW_CACHE off — the ordered join launches nothing and OWES its probe.  It is asked twice with the same four flags: by the ordered join,
+// with row_static = true (anything but FULL: the probe is owed), and where the debt is settled, with what the step turned out to be —
+//   FULL      nothing is owed: the full pass (multimap, stage rows, packed records) ran where the ordered join ran, as on every other route;
+//   LEAN      the band join took a row_static form: it runs the values-by-key pass (OjKeyValues) in the place of its records pass;
+//   FULL_NOW  it did not, or something else takes the table: the full pass runs now, in front of the count pass.
+enum class OjProbeForm : u32 { FULL, LEAN, FULL_NOW };
+constexpr const char* oj_probe_form_name(OjProbeForm f) { return f == OjProbeForm::FULL ? "FULL" : f == OjProbeForm::LEAN ? "LEAN" : "FULL_NOW"; }
+struct OjProbeShape { bool held = false, in_place = false, row_cache = false, option_off = false, row_static = false; };
+OjProbeForm oj_probe_form(const OjProbeShape& s);
+
 }  // namespace rdfgpu

@@ -408,6 +408,7 @@ struct OjBandFuse {
   u8 compact;                        // one 16-byte record per table row and match {lo pair, width pair, id operand, output value 0} instead of {record, aux} (BandArgs::compact)
   uint4* key_rec;                    // in place: the records by KEY (OrderedJoinArgs::key_rec) instead of by table row in brec — a slice row gathers its record in one step
   u32* key_val; u32* row_val;        // in place, the rows' windows cached (BandArgs::row_win): the table rows' output values by KEY (OrderedJoinArgs::key_val); per slice row, its key's value (kNil: the key has no table row)
+  ColRef val_ref; u32* slow_rows;    // OjKeyValues: the ordered join's output column held in word row_slot[0] of its packed record (ptr null: none, the value is 0); BandArgs::slow_rows
 };
 void launch_oj_band_records(const OrderedJoinArgs& a, const BandArgs& b, const OjBandFuse& f, hipStream_t s);
 void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, hipStream_t s);
@@ -418,6 +419,11 @@ struct OjInPlace {};
 void launch_ordered_join_write_band(const OrderedJoinArgs& a, const OjBandFuse& f, OjInPlace, hipStream_t s);
 u64 ordered_join_tiles(u64 n_build);
 void launch_ordered_join_probe(const OrderedJoinArgs& a, hipStream_t s);
+// The probe pass of a step that reads the slice's rows in place through their cached windows (every BandForm but RECORDS): all such a step takes from the
+// table is key_val[key - kmin] = the row's one output value for every table row that has all its stage rows (f.key_val, kNil-filled in front of the launch),
+// a.multi_rows (a key met twice) and f.slow_rows (a value that is kNil).  No multimap, no stage rows, no packed record.  (A tag: an overload of the kernel.)
+struct OjKeyValues {};
+void launch_ordered_join_probe(const OrderedJoinArgs& a, const OjBandFuse& f, OjKeyValues, hipStream_t s);
 void launch_ordered_join_count(const OrderedJoinArgs& a, hipStream_t s);
 void launch_ordered_join_write(const OrderedJoinArgs& a, hipStream_t s);
 

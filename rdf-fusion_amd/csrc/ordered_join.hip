@@ -63,6 +63,43 @@ __global__ __launch_bounds__(256) void oj_probe_kernel(const OrderedJoinArgs a) 
     if (a.multi_rows) atomicAdd(a.multi_rows, 1u);   // costs one atomic here, and nothing for the multi-row counter
   }
 }
+// The probe pass of a step whose band join reads the slice's rows in place through their cached windows (kernels.hpp OjKeyValues): the same rows are
+// linked as above — a key in range and a row in every stage, looked up here and kept in registers — and all that is written per linked row is its one
+// output value at its key (f.key_val, filled with kNil by a memset in front of the launch: a fill in here would race with the exchange).  The value is the
+// word the records pass would have read from the packed record: column f.val_ref at the table row or at its stage's row.  A key met twice shows in the
+// exchange (multi_rows: only zero / non-zero is read), a value equal to kNil is a slow row; either way the plan re-runs exactly.  No LDS, one atomic per row,
+// and three dependent round trips where the full pass has six: {key, every stage's key, a value of the table row} are all issued before the first wait, then
+// every stage's table entry (left to itself the compiler waits for each stage before it loads the next one's key: seven round trips in a row), then a value
+// that sits at a stage's row, then the exchange.
+__global__ __launch_bounds__(256) void oj_probe_kernel(const OrderedJoinArgs a, const OjBandFuse f, OjKeyValues) {
+  const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= live_rows(a.n_probe_dev, a.n_probe_cap)) return;
+  const u32 vsrc = f.val_ref.ptr ? f.val_ref.src : kNil;   // (uniform; kNil: no row column, every linked key holds 0)
+  const u32 key = a.probe_key[r];
+  u32 sk[kMaxChain], row[kMaxChain];
+#pragma unroll
+  for (u32 t = 0; t < (u32)kMaxChain; t++) sk[t] = t < a.n_stages ? a.stage[t].key_col[r] : 0u;
+  u32 v = vsrc == 0u ? f.val_ref.ptr[r] : 0u;
+  asm volatile("" :: "v"(key), "v"(sk[0]), "v"(sk[1]), "v"(sk[2]), "v"(v));
+  static_assert(kMaxChain == 3, "the stages' loads are named one by one");
+  const u32 d = key - a.kmin;
+  bool ok = key != 0 && d < a.kn;                  // null keys never join
+#pragma unroll
+  for (u32 t = 0; t < (u32)kMaxChain; t++) {
+    const u32 sd = sk[t] - a.stage[t].kmin;
+    const bool in = t < a.n_stages && sk[t] != 0 && sd < a.stage[t].kn;
+    row[t] = in ? a.stage[t].direct[sd] : kNil;
+  }
+  asm volatile("" :: "v"(row[0]), "v"(row[1]), "v"(row[2]));
+#pragma unroll
+  for (u32 t = 0; t < (u32)kMaxChain; t++) ok = ok && (t >= a.n_stages || row[t] != kNil);
+  if (!ok) return;
+#pragma unroll
+  for (u32 t = 0; t < (u32)kMaxChain; t++) if (vsrc == t + 2u) v = f.val_ref.ptr[row[t]];   // (uniform; the host checked that stage t exists)
+  if (v == kNil) atomicAdd(f.slow_rows, 1u);       // (the value that says "no table row")
+  const u32 old = atomicExch(&f.key_val[d], v);
+  if (old != kNil) atomicAdd(a.multi_rows, 1u);
+}
 __global__ __launch_bounds__(kOjBlock) void oj_count_kernel(const OrderedJoinArgs a) {
   __shared__ u32 wave_tot[kOjBlock / 64];
   const u64 base = (u64)blockIdx.x * kOjTile;
@@ -276,6 +313,7 @@ __global__ __launch_bounds__(kOjBlock) void oj_write_band_kernel(const OrderedJo
     dk[it] = key != 0 && d < a.kn ? d : kNil;
   }
   if (f.key_val) {   // (uniform)
+    if (blockIdx.x == 0 && threadIdx.x == 0) f.bcount[f.max_blocks] = 0u;   // the scan's closing element; the mask pass of every such form writes all the blocks' own counts
     u32 v[kOjRounds];
 #pragma unroll
     for (int it = 0; it < kOjRounds; it++) v[it] = dk[it] != kNil ? f.key_val[dk[it]] : kNil;
@@ -308,6 +346,10 @@ void launch_ordered_join_probe(const OrderedJoinArgs& a, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(oj_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
 }
+void launch_ordered_join_probe(const OrderedJoinArgs& a, const OjBandFuse& f, OjKeyValues tag, hipStream_t s) {
+  if (!f.key_val || !f.slow_rows || !a.multi_rows) fail(RDFGPU_ERR_INVALID, "ordered join: the values-by-key probe without its table or counters");
+  if (a.n_probe_cap) hipLaunchKernelGGL(oj_probe_kernel, dim3((unsigned)((a.n_probe_cap + 255) / 256)), dim3(256), 0, s, a, f, tag);
+}
 u64 ordered_join_tiles(u64 n_build) { return (n_build + kOjTile - 1) / kOjTile; }
 void launch_ordered_join_count(const OrderedJoinArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(oj_count_kernel, dim3((unsigned)ordered_join_tiles(a.n_build)), dim3(kOjBlock), 0, s, a);
@@ -329,5 +371,5 @@ void launch_ordered_join_write(const OrderedJoinArgs& a, hipStream_t s) {
 }
 
 // (kernels.hpp, preload_code_objects: the runtime loads a translation unit's code object at the first use of one of its kernels)
-void preload_tu_ordered_join() { hipFuncAttributes at; RDFGPU_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void*>(oj_probe_kernel))); }
+void preload_tu_ordered_join() { hipFuncAttributes at; RDFGPU_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void*>(static_cast<void (*)(OrderedJoinArgs)>(oj_probe_kernel)))); }
 }  // namespace rdfgpu

@@ -153,7 +153,8 @@ const char* kernel_class_name(int kc) {
       "rdfgpu::sort_keys_kernel", "rdfgpu::sort_tile_kernel", "rdfgpu::sort_merge_kernel", "rdfgpu::sort_gather_kernel",
       "void rdfgpu::agg_accum_minmax_kernel<false>", "void rdfgpu::agg_accum_minmax_kernel<true>",
       "void rdfgpu::agg_accum_minmax_expr_kernel<false>", "void rdfgpu::agg_accum_minmax_expr_kernel<true>",
-      "void rdfgpu::agg_minmax_refine_kernel"};
+      "void rdfgpu::agg_minmax_refine_kernel",
+      "rdfgpu::oj_probe_kernel(rdfgpu::OrderedJoinArgs, rdfgpu::OjBandFuse, rdfgpu::OjKeyValues)"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;

@@ -79,7 +79,12 @@ struct ChainRequest { NodeInfo* top = nullptr; NodeInfo* base = nullptr; std::ve
 // counted = false: its count pass has not run either (the band join may read the slice's rows in place, OjInPlace); whatever
 // else takes the table runs it first (Plan::count_pending_oj) and registers `check`, the check of the count it writes.
 // rows_seen: that join's last measured output rows (how much of the slice the band join's in-place form would leave idle).
-struct PendingOj { bool active = false; OrderedJoinArgs o{}; const u32* first_col = nullptr; u64 n_build = 0; bool counted = true; SpecCheck check{}; u64 rows_seen = 0; };
+// probe_owed: its probe pass has not run either, and o holds none of head, next, trec and the stage rows (host_logic.hpp, oj_probe_form, asked with `probe`): the band
+// join runs the values-by-key pass in its place (band_row_records), or count_pending_oj the full one.  An owed probe implies !counted.
+struct PendingOj {
+  bool active = false; OrderedJoinArgs o{}; const u32* first_col = nullptr; u64 n_build = 0; bool counted = true; SpecCheck check{}; u64 rows_seen = 0;
+  bool probe_owed = false; OjProbeShape probe{};
+};
 
 struct BoundTable { std::vector<const u32*> cols; u64 n_rows = 0; bool bound = false; };
 
@@ -170,6 +175,7 @@ enum KernelClass {
   KC_AGG_ACCUM_MINMAX_HBM, KC_AGG_ACCUM_MINMAX_LDS,             // agg_accum_minmax_kernel<LDS>: some aggregate of the node is a MIN / MAX
   KC_AGG_ACCUM_MINMAX_EXPR_HBM, KC_AGG_ACCUM_MINMAX_EXPR_LDS,   // .. and some SUM / AVG / MIN / MAX reads an expression or a value column
   KC_AGG_MINMAX_REFINE,                                         // agg_minmax_refine_kernel: the low word of the decimal candidates
+  KC_OJ_PROBE_VALUES,                                           // oj_probe_kernel(.., OjKeyValues): the probe pass of a step that reads the slice's rows through their cached windows
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
@@ -260,6 +266,7 @@ struct Plan {
   void flush_pending_oj();
   void count_pending_oj();
   void count_ordered_join(OrderedJoinArgs& o);
+  void probe_ordered_join(OrderedJoinArgs& o);
   u32 events_used = 0;
   KernelStat kstats[KC__N];
   // Arrow batch stream over a host copy of the result

@@ -241,8 +241,8 @@ void Plan::exec_band_join(LdsJoin& j) {
   hist.in_place = bj.lay.boff != nullptr;   // the layout exists: next time the ordered join below may leave its matches uncounted
   // In place: the ordered join below skipped its count pass, and the slice it streamed IS this join's build side.  Anything else counts the matches now and compacts them (the write-band pass).
   hist.row_cache = bj.rw.row_win != nullptr;   // .. and its probe pass may prepare the values by key instead of the 16-byte records
-  // (the ordered join prepared what the last execution's flags said: values by key when the windows were cached, records by key otherwise — a step whose
-  // cached windows are gone, a non-integer operand having entered the store, counts and compacts once)
+  // (the ordered join prepared what the last execution's flags said: values by key when the windows were cached — it then owes its probe pass, PendingOj::probe_owed —, records by
+  // key otherwise; a step whose cached windows are gone, a non-integer operand having entered the store, counts and compacts once, behind the full probe pass: count_pending_oj)
   BandStepShape step;
   step.row_static = bj.fused && bj.rw.row_win && pending_oj.o.key_val;
   bj.in_place = bj.fused && !pending_oj.counted && bj.fuse.self_index && hist.in_place && (step.row_static || pending_oj.o.key_rec);
@@ -544,7 +544,7 @@ void Plan::band_row_records(BandJoin& bj) {
   // blocks: sum over keys of ceil(E/64) * ceil(R/64) <= cmax * (rows / 64) + sum of ceil(E/64) over the keys
   bj.max_blocks = in_place ? bj.lay.n_blocks : bj.cmax * (np / 64 + 1) + nb / 64 + kn + 1;
   if (bj.max_blocks >= (1ull << 31)) fail(RDFGPU_ERR_UNSUPPORTED, "band join of %llu blocks", (unsigned long long)bj.max_blocks);
-  b.max_blocks = (u32)bj.max_blocks; b.bcount = scratch<u32>(bj.max_blocks + 1); b.bofs = scratch<u32>(bj.max_blocks + 1);   // (bcount is zeroed by the decode pass: a memset is two more launches, ~10 us of launch gap each on this part)
+  b.max_blocks = (u32)bj.max_blocks; b.bcount = scratch<u32>(bj.max_blocks + 1); b.bofs = scratch<u32>(bj.max_blocks + 1);   // (bcount is zeroed by the decode / records pass: a memset is two more launches, ~10 us of launch gap each on this part; a row_static step has neither pass — its mask pass writes every block's count, its in-place pass the scan's closing zero)
   band_form_args(bj);
   // decode, per probe row: key + the window operands + the id operand read, 24 B of record + 8 B of sort pair written
   if (!bj.fused) return timed(KC_BAND_DECODE, 0, np, bj.j.P.n_dev, 4 + 4ull * (b.n_win + b.has_neq) + 9ull * b.n_win + 24 + 8, nullptr, 0, 0, [&] { launch_band_decode(b, stream); });
@@ -555,6 +555,19 @@ void Plan::band_row_records(BandJoin& bj) {
   // per table row: its packed record read + two typed-value gathers + 32 B written; per slice row the count pass's 5 bytes + its key; per match a 32-byte record gathered and stored (in place: per slice row its key read, its key's 16-byte record gathered and stored)
   // (the rows' windows cached: per table row its packed record read and 4 B written by key; per slice row its key read, 4 B gathered, 4 B written)
   const u64 rec_bytes = fuse.compact ? 16 : 32;
+  // An owed probe pass is settled here when the step reads the values by key (host_logic.hpp, oj_probe_form; a step that does not has had count_pending_oj run the full one): the fill of
+  // key_val and the values-by-key pass in the place of the records pass.  Per table row: its key, per stage its key and its direct entry, the value read; 4 B exchanged by key.
+  OjProbeShape owed = pending_oj.probe; owed.row_static = row_static;
+  const OjProbeForm probe = pending_oj.probe_owed ? oj_probe_form(owed) : OjProbeForm::FULL;
+  if (probe == OjProbeForm::FULL_NOW || (probe == OjProbeForm::FULL && row_static)) fail(RDFGPU_ERR_INVALID, "band join: a step of form %s over a probe pass of form %s", band_form_name(bj.form), oj_probe_form_name(probe));
+  if (probe == OjProbeForm::LEAN) {
+    pending_oj.probe_owed = false;
+    fuse.slow_rows = b.slow_rows; fuse.val_ref = ColRef{nullptr, 0u, 0u};
+    for (u32 c = 0; c < o.n_out_cols; c++) if (fuse.row_slot[0] != 0xFFu && o.out_slot[c] == fuse.row_slot[0]) fuse.val_ref = o.out_ref[c];
+    if (fuse.val_ref.src == 1 || (fuse.val_ref.src >= 2 && fuse.val_ref.src - 2 >= o.n_stages)) fail(RDFGPU_ERR_INVALID, "band join: the row's value comes from source %u of the ordered join", fuse.val_ref.src);
+    RDFGPU_HIP(hipMemsetAsync(fuse.key_val, 0xFF, (size_t)o.kn * sizeof(u32), stream));
+    timed(KC_OJ_PROBE_VALUES, 0, o.n_probe_cap, o.n_probe_dev, 4 + 8ull * o.n_stages + (fuse.val_ref.ptr ? 4 : 0) + 4, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, fuse, OjKeyValues{}, stream); });
+  } else
   timed(KC_OJ_BAND_RECORDS, 0, o.n_probe_cap, o.n_probe_dev, row_static ? 16ull * o.n_rec + 4 : 16ull * o.n_rec + 9ull * b.n_win + rec_bytes, nullptr, 0, 0, [&] { launch_oj_band_records(o, b, fuse, stream); });
   if (in_place) timed(KC_OJ_WRITE_BAND_IN_PLACE, 0, nb, nullptr, row_static ? 4 + 4 + 4 : 4 + 2 * rec_bytes, nullptr, 0, 0, [&] { launch_ordered_join_write_band(o, fuse, OjInPlace{}, stream); });
   else timed(KC_OJ_WRITE_BAND, 0, pending_oj.n_build, nullptr, 4 + 1 + 4, a.n_probe_dev, 0, 2 * rec_bytes, [&] { launch_ordered_join_write_band(o, fuse, stream); });

@@ -30,6 +30,14 @@ void Plan::flush_pending_oj() {
   timed(KC_OJ_WRITE, 0, pending_oj.n_build, nullptr, 4, o.n_out_dev, 0, 8ull * o.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
 }
 
+// The full probe pass of an ordered slice join: the multimap of the table's rows by key, every row's stage rows and its packed record (and, on the way, the fill of key_rec / key_val).
+void Plan::probe_ordered_join(OrderedJoinArgs& o) {
+  o.head = scratch<uint2>(o.kn); o.next = scratch<u32>(o.n_probe_cap);
+  RDFGPU_HIP(hipMemsetAsync(o.head, 0xFF, (size_t)o.kn * sizeof(uint2), stream));
+  for (u32 s = 0; s < o.n_stages; s++) o.stage[s].row = scratch<u32>(o.n_probe_cap);
+  o.trec = scratch<uint4>(o.n_probe_cap * o.n_rec);
+  timed(KC_OJ_PROBE, 0, o.n_probe_cap, o.n_probe_dev, 8 + 12ull * o.n_stages, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
+}
 // The count pass of an ordered slice join and the scan of its per-tile counts: where every match goes.
 void Plan::count_ordered_join(OrderedJoinArgs& o) {
   const u64 tiles = ordered_join_tiles(o.n_build);
@@ -42,9 +50,17 @@ void Plan::count_ordered_join(OrderedJoinArgs& o) {
 }
 // The held-back ordered slice join skipped its count pass for an in-place band join that does not take it after all: it runs now,
 // and so does the check of the count its write pass will write.
+// An owed probe pass (PendingOj::probe_owed) is the full one now: the band join did not take a form that reads the values by key, or it is not the band join that
+// takes the table.  From here the step is what it is when the windows were declined after a mutation: it counts and compacts once.
 void Plan::count_pending_oj() {
   if (!pending_oj.active || pending_oj.counted) return;
   pending_oj.counted = true;
+  if (pending_oj.probe_owed) {
+    pending_oj.probe.row_static = false;
+    if (oj_probe_form(pending_oj.probe) != OjProbeForm::FULL_NOW) fail(RDFGPU_ERR_INVALID, "ordered join: an owed probe pass of form %s", oj_probe_form_name(oj_probe_form(pending_oj.probe)));
+    pending_oj.probe_owed = false;
+    probe_ordered_join(pending_oj.o);
+  }
   count_ordered_join(pending_oj.o);
   spec_checks.push_back(pending_oj.check);
 }
@@ -696,10 +712,8 @@ bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap)
   o.build_key = a.build_key[0]; o.n_build = B.cap;
   o.probe_key = a.probe_key[0]; o.n_probe_dev = P.n_dev; o.n_probe_cap = P.cap;
   o.kmin = a.direct_min; o.kn = a.direct_n;
-  o.head = scratch<uint2>(a.direct_n); o.next = scratch<u32>(P.cap);
-  RDFGPU_HIP(hipMemsetAsync(o.head, 0xFF, (size_t)a.direct_n * sizeof(uint2), stream));
   o.n_stages = a.n_chain;
-  for (u32 s = 0; s < a.n_chain; s++) o.stage[s] = OrderedJoinStage{a.chain[s].key.ptr, a.chain[s].direct, a.chain[s].kmin, a.chain[s].kn, scratch<u32>(P.cap)};
+  for (u32 s = 0; s < a.n_chain; s++) o.stage[s] = OrderedJoinStage{a.chain[s].key.ptr, a.chain[s].direct, a.chain[s].kmin, a.chain[s].kn, nullptr};   // (the multimap, the stage rows and the packed records: probe_ordered_join)
   o.n_out_cols = a.n_out_cols;
   u32 n_words = 0;
   for (u32 c = 0; c < a.n_out_cols; c++) {
@@ -710,7 +724,6 @@ bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap)
     if (o.out_ref[c].src == 1 && o.out_ref[c].ptr == B.cols[B.sorted_col] && t.sorted_col < 0) { t.sorted_col = (int)c; t.key_min = B.key_min; t.key_max = B.key_max; }
   }
   o.n_rec = n_words > 4 ? 2u : 1u;
-  o.trec = scratch<uint4>(P.cap * o.n_rec);
   o.out_cap = spec_cap; o.n_out_dev = a.n_out_dev; o.overflow = a.overflow;
   // the consumer is a band join that (last time) found this output sorted by its key and needed nothing else of it: the write
   // pass is held back — that join has it write its row records instead of this table (exec_band_join), anything else flushes it.
@@ -722,13 +735,19 @@ bool Plan::run_ordered_join(LdsJoin& j, const NodeInfo& size_node, u64 spec_cap)
   const bool in_place = held && nodes[consumer].band.in_place && nodes[consumer].band.multi_rows == 0 && !opt.on(RDFGPU_OPT_NO_BAND_COMPACT);
   if (held) o.multi_rows = reinterpret_cast<u32*>(new_counter());
   // (.. and with the rows' windows cached on the slice last time, only the table rows' output values travel by key)
-  if (in_place && nodes[consumer].band.row_cache && !opt.on(RDFGPU_OPT_NO_BAND_ROW_CACHE)) o.key_val = scratch<u32>(a.direct_n);
+  // Such a step takes nothing else from the table, and which column the value is the band join alone knows (take_pending_oj): the probe pass is OWED — nothing is
+  // launched here, the band join runs the values-by-key pass in its place, or count_pending_oj the full one when the step takes another form after all
+  OjProbeShape probe;
+  probe.held = held; probe.in_place = in_place; probe.row_cache = consumer >= 0 && nodes[consumer].band.row_cache; probe.option_off = !opt.on(RDFGPU_OPT_NO_BAND_ROW_CACHE);
+  probe.row_static = true;   // (what the flags promise; the step's own form is known where the debt is settled)
+  const bool owed = oj_probe_form(probe) != OjProbeForm::FULL;
+  if (owed) o.key_val = scratch<u32>(a.direct_n);
   else if (in_place) o.key_rec = scratch<uint4>(a.direct_n);
-  timed(KC_OJ_PROBE, 0, P.cap, P.n_dev, 8 + 12ull * a.n_chain, nullptr, 0, 0, [&] { launch_ordered_join_probe(o, stream); });
+  if (!owed) probe_ordered_join(o);
   if (!in_place) count_ordered_join(o);
   if (held) {
     pending_oj.active = true; pending_oj.o = o; pending_oj.first_col = a.out[0]; pending_oj.n_build = B.cap;
-    pending_oj.counted = !in_place; pending_oj.rows_seen = size_node.last_rows;
+    pending_oj.counted = !in_place; pending_oj.rows_seen = size_node.last_rows; pending_oj.probe_owed = owed; pending_oj.probe = probe;
   } else timed(KC_OJ_WRITE, 0, B.cap, nullptr, 4, a.n_out_dev, 0, 8ull * a.n_out_cols, [&] { launch_ordered_join_write(o, stream); });
   return true;
 }

@@ -129,6 +129,7 @@ def load_library():
     lib.rdfgpu_band_pair_list_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
     lib.rdfgpu_band_pair_count_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
     lib.rdfgpu_band_step_form.argtypes = [C.c_uint32] * 6 + [C.c_uint64] * 2
+    lib.rdfgpu_oj_probe_form.argtypes = [C.c_uint32] * 5
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -207,6 +208,16 @@ def band_step_form(n_blocks, row_static=True, has_verdicts=True, has_list=True, 
     test's verdicts / their list with its per-row counts; `min_blocks`: the BAND_PAIR_COUNT_BLOCKS option, as for band_pair_count_eligible."""
     return BAND_FORMS[_check(load_library().rdfgpu_band_step_form(int(row_static), int(has_verdicts), int(has_list), int(list_option_set), int(counts_option_set),
                                                                    int(n_row_cols), int(n_blocks), int(min_blocks)))]
+
+
+OJ_PROBE_FORMS = ("FULL", "LEAN", "FULL_NOW")   # host_logic.hpp, OjProbeForm
+
+
+def oj_probe_form(held=True, in_place=True, row_cache=True, option_set=False, row_static=True):
+    """The probe pass of the ordered slice join below a band join that reads the slice's rows in place (host_logic.hpp, oj_probe_form), as its name in
+    OJ_PROBE_FORMS.  `held`, `in_place`, `row_cache`: what the band join's last execution left; `option_set`: NO_BAND_ROW_CACHE; `row_static`: the form the
+    band join's step took this time (the ordered join itself asks with True and owes its probe unless the answer is FULL)."""
+    return OJ_PROBE_FORMS[_check(load_library().rdfgpu_oj_probe_form(int(held), int(in_place), int(row_cache), int(option_set), int(row_static)))]
 
 
 def _pred_struct(p, keep):
