@@ -127,7 +127,10 @@ typedef struct rdfgpu_typed_value {
   uint32_t aux;
   uint8_t tag;
   uint8_t flags;
-  uint16_t reserved;
+  int16_t tz_minutes;  /* tags 10 / 11 / 12 with aux bit0 set: the TimezoneOffset in minutes (-840 .. 840); 0 otherwise.  Read by
+                          RDFGPU_EX_YEAR .. RDFGPU_EX_MINUTES only (ordering and equality never look at it: two dateTimes are equal by
+                          value and presence of a timezone, date_time.rs:1605-1613).  The field was `reserved` (0): a host that leaves
+                          it 0 gets the parts of the UTC instant. */
 } rdfgpu_typed_value; /* 16 bytes, one aligned dwordx4 gather per row */
 
 enum {
@@ -356,6 +359,23 @@ enum {
                                  significant digits (w and w + 1 must agree when digits were dropped).  What does not parse => error.  A
                                  literal Eisel-Lemire cannot decide (a half-way neighbourhood) and a signed NaN fail the execute with
                                  RDFGPU_ERR_UNSUPPORTED; never answered differently.  Every other operand: exactly RDFGPU_EX_CAST.        */
+  /* ---- ABI 4 addendum: the parts of an xsd:dateTime (new enum values only) — what the Wind Farm plans group their time series by
+     (bench/tests/plans/snapshots/..Wind Farm - GroupedProduction1..4: `YEAR(tv) as year, MONTH(tv) as month, DAY(tv), HOURS(tv),
+     MUL(9:10, FLOOR(DIV(MINUTES(tv), 10.0)))`).  All six are unary, TV -> TV, and restate scalar/dates_and_times/{year,month,day,hours,
+     minutes,seconds}.rs over Timestamp::{year_month_day, hour, minute, second} (lib/model/src/xsd/date_time.rs:1731-1839) statement by
+     statement (csrc/date_parts.hpp).  Only an RDFGPU_TV_DATE_TIME operand yields a value; every other kind — date, time, null, a number
+     — is the error value (`ThinError::expected()`).  t = value / 10^18 truncated toward zero, plus tz_minutes * 60 (no timezone: 0, i.e.
+     UTC); days = div_euclid(t, 86400) + 366 and the reference's 400 / 100 / 4 / 1-year descent; hour = rem_euclid(t, 86400) / 3600;
+     minute = rem_euclid(t, 3600) / 60.  The offset comes from rdfgpu_typed_value.tz_minutes (ENC_TV) or bits 16..31 of a literal's `u`.
+     Allowed wherever MUL is: FILTER, join filters, SUM / AVG / MIN / MAX inputs, RDFGPU_NODE_EXTEND programs; a predicate with one runs in
+     the generic VM.  TZ / TIMEZONE and the parts of xsd:date / xsd:time are not on the device. */
+  RDFGPU_EX_YEAR = 48,        /* TV(dateTime) -> TV(integer)  year.rs; years before 1 are 0, -1, .. as year_month_day counts them      */
+  RDFGPU_EX_MONTH = 49,       /* TV(dateTime) -> TV(integer)  month.rs: 1..12                                                          */
+  RDFGPU_EX_DAY = 50,         /* TV(dateTime) -> TV(integer)  day.rs: 1..31                                                            */
+  RDFGPU_EX_HOURS = 51,       /* TV(dateTime) -> TV(integer)  hours.rs: 0..23                                                          */
+  RDFGPU_EX_MINUTES = 52,     /* TV(dateTime) -> TV(integer)  minutes.rs: 0..59                                                        */
+  RDFGPU_EX_SECONDS = 53,     /* TV(dateTime) -> TV(decimal)  seconds.rs: rem_euclid(value, 60 * 10^18) on the scaled i128, in [0, 60);
+                                 no offset is applied (offsets are whole minutes)                                                      */
   RDFGPU_EX__COUNT
 };
 
@@ -365,6 +385,8 @@ typedef struct rdfgpu_expr_node {
   uint8_t flags;    /* LIT_TV: rdfgpu_typed_value.flags                                   */
   uint8_t reserved;
   uint32_t u;       /* COLUMN: column index; LIT_ID: id; LIT_TV: aux; LIT_BOOL: 0/1/2     */
+                    /* LIT_TV timestamps: bit 0 = has a timezone, bits 16..31 = the offset in minutes as int16 (rdfgpu_typed_value.tz_minutes;
+                       read by the date parts only, every comparison masks to bit 0) */
   int64_t lo;       /* LIT_TV payload (decimal / dateTime / time / date literals: low 64 bits of the i128) */
   int64_t hi;       /* LIT_TV decimal / timestamp literal: high 64 bits; timestamps: u bit0 = has timezone */
 } rdfgpu_expr_node; /* 24 bytes */
@@ -435,7 +457,24 @@ enum {
                                   node and column): a join key, a group column, a COUNT_DISTINCT input, any TopK key / group / output, a
                                   CLOSURE or UNION input; and so is rdfgpu_plan_decode_terms of a value column.  A value column under
                                   ID_EQ / ID_NEQ / IS_COMPATIBLE / STR is RDFGPU_ERR_INVALID, like every operand of the wrong kind.  A
-                                  predicate that reads a value column runs in the generic VM.                                          */
+                                  predicate that reads a value column runs in the generic VM.
+                                  With RDFGPU_PLAN_VALUE_KEYS as well (opt-in per plan, valid only together with RDFGPU_PLAN_AGG_COLUMNS; without
+                                  it every refusal and every launch above is unchanged) — the tail of the Wind Farm GroupedProduction plans,
+                                  `AggregateExec: gby=[site_label, wtur_label, ENC_PT(year), ENC_PT(month), ENC_PT(day), ENC_PT(hour),
+                                  ENC_PT(minute_10)], aggr=[AVG(val)]` —: n_keys may be up to RDFGPU_MAX_GROUP_KEYS, keys 0..3 in left_keys[], keys
+                                  4..7 in right_keys[] (which an aggregate has no other use for), and any key may be an object-id column or a
+                                  value column (an aggregate's or a computed one).  Group equality: id keys compare as ids.  A value key
+                                  compares by the plain term its value stands for (the reference groups by ENC_PT of the column): the tag;
+                                  `lo`; `hi` for RDFGPU_TV_DECIMAL only (ignored otherwise).  All NaNs of one tag are equal; +0.0 and -0.0
+                                  are different terms; INTEGER 5, INT 5 and DECIMAL 5 are different terms; an entry of 0 and a record with tag
+                                  RDFGPU_TV_NULL are both "unbound", which is one key value like id 0.  Output: the key columns first, in
+                                  order; a value key stays a value column WITH ITS INPUT'S ORIGIN — the entry of the group's representative
+                                  row, which indexes the same value array — so FILTERs, SortExec by value, EXTEND and
+                                  rdfgpu_plan_result_values above the node work unchanged; then the aggregates' value columns, as above.
+                                  The other roles of a value column stay refused, with the texts above: join key, COUNT_DISTINCT input, TopK
+                                  key / group / output, CLOSURE / UNION input.  Joins, TopK and SortExec keep RDFGPU_MAX_KEYS keys.  A node
+                                  with a value key or more than 4 keys runs a group pass of its own (agg_groups_wide_kernel in
+                                  rdfgpu_plan_kernel_stats); a node with at most 4 id keys launches exactly what it launches without the flag.  */
   RDFGPU_NODE_EXTEND = 12,     /* ProjectionExec whose `expr=[..]` holds expressions (SPARQL Extend: BIND, `SELECT (expr AS ?x)`) — what the
                                   BSBM Business Intelligence plans put directly above their aggregates (..Business Intelligence - Q3 / Q4 /
                                   Q8 (Execution Plan).snap: `DIV(xsd:float(monthCount@1), monthBeforeCount@2) as ratio`).  Encoding: left =
@@ -596,6 +635,7 @@ enum { RDFGPU_JOIN_INNER = 0, RDFGPU_JOIN_LEFT = 1,
        RDFGPU_JOIN_LEFT_SEMI = 2, RDFGPU_JOIN_LEFT_ANTI = 3 };
 #define RDFGPU_MAX_KEYS 4u
 #define RDFGPU_MAX_COLUMNS 16u
+#define RDFGPU_MAX_GROUP_KEYS 8u   /* group columns of an RDFGPU_NODE_AGGREGATE in a plan compiled with RDFGPU_PLAN_VALUE_KEYS (else RDFGPU_MAX_KEYS) */
 #define RDFGPU_NO_PROJECTION 0xFFFFFFFFu
 
 typedef struct rdfgpu_plan_node {
@@ -639,6 +679,8 @@ typedef struct rdfgpu_plan_desc {
 } rdfgpu_plan_desc;
 #define RDFGPU_PLAN_ALLOW_OPAQUE 1u
 #define RDFGPU_PLAN_AGG_COLUMNS 2u        /* ABI 4 addendum: aggregate values are columns (RDFGPU_NODE_AGGREGATE) */
+#define RDFGPU_PLAN_VALUE_KEYS 4u         /* ABI 4 addendum: value columns may be group columns, up to RDFGPU_MAX_GROUP_KEYS of them (RDFGPU_NODE_AGGREGATE);
+                                             valid only together with RDFGPU_PLAN_AGG_COLUMNS, alone it is RDFGPU_ERR_INVALID */
 
 /* ------------------------------------------------------------------------------------ */
 /* 4. Plans: compile, execute on device, stream result batches                           */

@@ -31,7 +31,8 @@ NT_IRI, NT_BNODE, NT_SIMPLE, NT_LANG, NT_TYPED = 1, 2, 3, 4, 5   # rdfgpu_ntripl
  EX_EBV, EX_ID_EQ, EX_ID_NEQ, EX_AND, EX_OR, EX_NOT, EX_IS_COMPATIBLE, EX_BOUND, EX_BOOL_AS_TV,
  EX_LIT_BOOL, EX_NEQ, EX_REGEX, EX_CONTAINS, EX_STRSTARTS, EX_STRENDS, EX_LANG_IN, EX_REGEX_VAR,
  EX_STR, EX_LIT_STR, EX_STRLEN, EX_SUBSTR, EX_UCASE, EX_LCASE, EX_STRBEFORE, EX_STRAFTER,
- EX_MUL, EX_DIV, EX_NEG, EX_PLUS, EX_ABS, EX_ROUND, EX_CEIL, EX_FLOOR, EX_CAST, EX_CAST_STRING, EX_CAST_LEX) = range(1, 48)
+ EX_MUL, EX_DIV, EX_NEG, EX_PLUS, EX_ABS, EX_ROUND, EX_CEIL, EX_FLOOR, EX_CAST, EX_CAST_STRING, EX_CAST_LEX,
+ EX_YEAR, EX_MONTH, EX_DAY, EX_HOURS, EX_MINUTES, EX_SECONDS) = range(1, 54)   # EX_YEAR = 48 .. EX_SECONDS = 53: the parts of an xsd:dateTime
 CAST_TARGETS = (TV_BOOLEAN, TV_INT, TV_INTEGER, TV_DECIMAL, TV_FLOAT, TV_DOUBLE)   # EX_CAST's `u`; any other tag is refused at compile
 
 # plan nodes
@@ -52,10 +53,13 @@ SORT_BY_VALUE = 3               # NODE_SORT only: ENC_SORT of the typed value a 
 SORT_DESC = 0x100               # NODE_SORT, or-ed into a key's `how`: descending
 JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
 MAX_KEYS = 4
+MAX_GROUP_KEYS = 8              # group columns of a NODE_AGGREGATE in a plan built with value_keys=True (keys 4.. ride in right_keys[])
 MAX_COLUMNS = 16
 NO_PROJECTION = 0xFFFFFFFF
 PLAN_ALLOW_OPAQUE = 1
 PLAN_AGG_COLUMNS = 2            # rdfgpu_plan_desc.flags: aggregate values are columns that flow into the operators above (RDFGPU_NODE_AGGREGATE)
+
+PLAN_VALUE_KEYS = 4             # rdfgpu_plan_desc.flags, only with PLAN_AGG_COLUMNS: value columns may be group columns, up to MAX_GROUP_KEYS of them
 
 OP_EQ, OP_GT, OP_GTEQ, OP_LT, OP_LTEQ = range(5)
 
@@ -75,7 +79,7 @@ class Config(C.Structure):
 
 class TypedValue(C.Structure):
     _fields_ = [("lo", C.c_int64), ("aux", C.c_uint32), ("tag", C.c_uint8), ("flags", C.c_uint8),
-                ("reserved", C.c_uint16)]
+                ("tz_minutes", C.c_int16)]   # timestamps (tags 10 .. 12) with aux bit 0: the timezone offset in minutes; 0 otherwise
 
 
 class AggValue(C.Structure):

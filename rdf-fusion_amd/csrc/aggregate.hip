@@ -10,6 +10,8 @@
 //                      head lane issues the atomic (Guideline 12).  When every group's words fit in 64 KiB, each workgroup keeps
 //                      partials in LDS and merges them into HBM once; otherwise (or with NO_AGG_LDS) the atomics go to HBM directly.
 //   agg_final_kernel   one lane per group: the key ids from the group's first row, every aggregate's rdfgpu_agg_value.
+// A node with a value column among its group columns, or more than 4 of them (RDFGPU_PLAN_VALUE_KEYS), runs agg_groups_wide_kernel as its
+// group pass (same contract: row_slot, slot_gid, rep_row, the count) and agg_wide_keys_kernel for the key columns 4..; the rest is shared.
 // When aggregate values are columns (RDFGPU_PLAN_AGG_COLUMNS) a fourth, agg_value_cols_kernel, writes each aggregate's value column.
 // A node with a MIN / MAX (RDFGPU_PLAN_AGG_COLUMNS only) runs the MINMAX instantiation of the accumulate pass (agg_accum_minmax_kernel),
 // then agg_minmax_refine_kernel (the low word of decimal candidates) and, beside agg_final_kernel, agg_minmax_final_kernel.
@@ -95,6 +97,113 @@ __global__ __launch_bounds__(kAggBlock) void agg_groups_kernel(const AggArgs a) 
     }
     __syncthreads();   // wave_tot / wg_base are reused by the next tile
   }
+}
+
+// ---- pass 1, the wide form (RDFGPU_PLAN_VALUE_KEYS): value columns among the group columns, or more than RDFGPU_MAX_KEYS of them ----------
+// The same table, claim and compaction as agg_groups_kernel; only what a key IS differs.  An id key is its u32.  A value key is the plain
+// term its value stands for (the reference groups by ENC_PT of the column), in the canonical form of include/rdfgpu.h: the tag, `lo`, and
+// `hi` for a decimal only; every NaN of a tag is one term; +0.0 and -0.0, and INTEGER / INT / DECIMAL of one value, are different terms;
+// entry 0, an entry behind the array and a record with tag RDFGPU_TV_NULL are all "unbound", one key value.  The canonical words are
+// hashed, never the entry: equal values have different entries.  A row's own record is a stream (a computed column's entry is row + 1),
+// the claimant's a gather; two equal entries are the same record and need no read.
+struct WideKey { u32 tag; u64 lo, hi; };
+__device__ __forceinline__ WideKey wide_value_key(const rdfgpu_agg_value* val, u64 val_n, u32 e) {
+  WideKey k{RDFGPU_TV_NULL, 0ull, 0ull};
+  if (e == 0 || (u64)e > val_n) return k;
+  const unsigned long long* p = reinterpret_cast<const unsigned long long*>(val) + 3ull * (e - 1u);
+  const u32 tag = (u32)(p[2] & 0xffull);
+  if (tag == RDFGPU_TV_NULL) return k;
+  k.tag = tag; k.lo = p[0];
+  if (tag == RDFGPU_TV_DECIMAL) k.hi = p[1];
+  else if (tag == RDFGPU_TV_FLOAT && ((u32)k.lo & 0x7FFFFFFFu) > 0x7F800000u) k.lo = 0x7FC00000ull;
+  else if (tag == RDFGPU_TV_DOUBLE && (k.lo & ~(1ull << 63)) > 0x7FF0000000000000ull) k.lo = 0x7FF8000000000000ull;
+  return k;
+}
+__device__ __forceinline__ u32 wide_mix(u32 h, u32 v) { h ^= v; h *= 0x9E3779B1u; h ^= h >> 15; return h; }
+__device__ __forceinline__ u32 wide_hash(const AggWideArgs& w, u64 row) {
+  u32 h = 0x811C9DC5u;
+#pragma unroll
+  for (u32 q = 0; q < RDFGPU_MAX_GROUP_KEYS; q++) {
+    if (q >= w.n_keys) continue;
+    const u32 e = w.key[q][row];
+    if (!(w.value_mask >> q & 1u)) { h = wide_mix(h, e); continue; }
+    const WideKey k = wide_value_key(w.val[q], w.val_n[q], e);
+    h = wide_mix(h, k.tag); h = wide_mix(h, (u32)k.lo); h = wide_mix(h, (u32)(k.lo >> 32)); h = wide_mix(h, (u32)k.hi); h = wide_mix(h, (u32)(k.hi >> 32));
+  }
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+__device__ __forceinline__ bool wide_rows_equal(const AggWideArgs& w, u64 ra, u64 rb) {
+  bool eq = true;
+#pragma unroll
+  for (u32 q = 0; q < RDFGPU_MAX_GROUP_KEYS; q++) {
+    if (q >= w.n_keys || !eq) continue;
+    const u32 ea = w.key[q][ra], eb = w.key[q][rb];
+    if (ea == eb) continue;
+    if (!(w.value_mask >> q & 1u)) { eq = false; continue; }
+    const WideKey x = wide_value_key(w.val[q], w.val_n[q], ea), y = wide_value_key(w.val[q], w.val_n[q], eb);
+    eq = x.tag == y.tag && x.lo == y.lo && x.hi == y.hi;
+  }
+  return eq;
+}
+
+__global__ __launch_bounds__(kAggBlock) void agg_groups_wide_kernel(const AggWideArgs w) {
+  __shared__ u32 wave_tot[kAggBlock / 64];
+  __shared__ u64 wg_base;
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 n = live_rows(w.n_dev, w.cap);
+  const u64 n_tiles = (n + kAggTile - 1) / kAggTile;
+  for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    u64 row[kAggItems]; u32 slot[kAggItems]; bool won[kAggItems];
+#pragma unroll
+    for (int it = 0; it < kAggItems; it++) {
+      row[it] = tile * kAggTile + (u64)it * kAggBlock + tid;
+      won[it] = false; slot[it] = 0;
+      if (row[it] >= n) continue;
+      u32 h = wide_hash(w, row[it]) & w.slot_mask;
+      for (;;) {   // load factor <= 0.5: an empty slot exists
+        u32 cur = w.slots[h];   // slots are written once: a stale read can only be a 0, which the CAS settles
+        if (cur == 0) {
+          cur = atomicCAS(w.slots + h, 0u, (u32)row[it] + 1u);
+          if (cur == 0) { won[it] = true; break; }
+        }
+        if (wide_rows_equal(w, cur - 1, row[it])) break;
+        h = (h + 1) & w.slot_mask;
+      }
+      slot[it] = h;
+      w.row_slot[row[it]] = h;
+    }
+    unsigned long long mask[kAggItems]; u32 off[kAggItems]; u32 wtot = 0;
+#pragma unroll
+    for (int it = 0; it < kAggItems; it++) { mask[it] = __ballot(won[it]); off[it] = wtot; wtot += (u32)__popcll(mask[it]); }
+    if (lane == 0) wave_tot[wave] = wtot;
+    __syncthreads();
+    if (tid == 0) {
+      u32 total = 0;
+      for (int q = 0; q < kAggBlock / 64; q++) { const u32 t = wave_tot[q]; wave_tot[q] = total; total += t; }
+      wg_base = total ? atomicAdd((unsigned long long*)w.n_groups_dev, (unsigned long long)total) : 0ull;
+    }
+    __syncthreads();
+    const u64 base = wg_base + wave_tot[wave];
+#pragma unroll
+    for (int it = 0; it < kAggItems; it++) {
+      if (!won[it]) continue;
+      const u32 gid = (u32)(base + off[it] + lane_prefix(mask[it]));
+      w.slot_gid[slot[it]] = gid;
+      w.rep_row[gid] = (u32)row[it];
+    }
+    __syncthreads();   // wave_tot / wg_base are reused by the next tile
+  }
+}
+
+// The key columns RDFGPU_MAX_KEYS .. of the wide form, one lane per group: the representative row's entries (agg_final_kernel copies the
+// first four as it always did; a value key's entry indexes the same value array as the input's).
+__global__ __launch_bounds__(kAggBlock) void agg_wide_keys_kernel(const AggWideArgs w) {
+  const u32 g = blockIdx.x * kAggBlock + threadIdx.x;
+  if (g >= w.n_groups) return;
+  const u32 rep = w.rep_row[g];
+#pragma unroll
+  for (u32 q = RDFGPU_MAX_KEYS; q < RDFGPU_MAX_GROUP_KEYS; q++) if (q < w.n_keys) w.out_key[q][g] = w.key[q][rep];
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------------------------------------------
@@ -493,6 +602,16 @@ static const AggKernel kAggRefineKernels[3] = {agg_minmax_refine_kernel<false, f
 
 static void agg_launch(AggKernel kernel, u64 grid, size_t lds, const AggArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)(grid ? grid : 1)), dim3(kAggBlock), lds, s, a);
+  RDFGPU_HIP(hipGetLastError());
+}
+void launch_agg_groups_wide(const AggWideArgs& w, hipStream_t s) {
+  const u64 grid = std::min<u64>((w.cap + kAggTile - 1) / kAggTile, kAggGroupGrid);
+  hipLaunchKernelGGL(agg_groups_wide_kernel, dim3((unsigned)(grid ? grid : 1)), dim3(kAggBlock), 0, s, w);
+  RDFGPU_HIP(hipGetLastError());
+}
+void launch_agg_wide_keys(const AggWideArgs& w, hipStream_t s) {
+  const u64 grid = ((u64)w.n_groups + kAggBlock - 1) / kAggBlock;
+  hipLaunchKernelGGL(agg_wide_keys_kernel, dim3((unsigned)(grid ? grid : 1)), dim3(kAggBlock), 0, s, w);
   RDFGPU_HIP(hipGetLastError());
 }
 void launch_agg_groups(const AggArgs& a, hipStream_t s) { agg_launch(agg_groups_kernel, std::min<u64>((a.cap + kAggTile - 1) / kAggTile, kAggGroupGrid), 0, a, s); }

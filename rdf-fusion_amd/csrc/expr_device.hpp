@@ -13,6 +13,8 @@
 //   CAST     scalar/conversion/cast_{boolean,int,integer,decimal,float,double}.rs:48-62 and the From / TryFrom impls they call
 //   CAST_STRING  scalar/conversion/cast_string.rs:51-76 (the lexical form of a term that has one as written: a view, nothing copied)
 //   CAST_LEX     the same casts with the simple-literal arm: the FromStr impls of lib/model/src/xsd, restated in lex_parse.hpp
+//   YEAR .. SECONDS  scalar/dates_and_times/{year,month,day,hours,minutes,seconds}.rs over Timestamp::{year_month_day, hour, minute, second}
+//            (lib/model/src/xsd/date_time.rs:1731-1839), restated in date_parts.hpp
 //   EBV      lib/functions/src/builtin/native/effective_boolean_value.rs:99-119
 //   AND/OR   SQL three-valued logic on native booleans (lib/logical/src/expr_builder_context.rs:393-434)
 #pragma once
@@ -22,6 +24,7 @@
 #include "../../include/rdfgpu.h"
 #include "regex_prog.hpp"
 #include "lex_parse.hpp"
+#include "date_parts.hpp"
 
 namespace rdfgpu {
 
@@ -101,6 +104,10 @@ __device__ __forceinline__ void set_dec(Val& v, i128_t d) { v.lo = (int64_t)(uin
 __device__ __forceinline__ bool tv_is_timestamp(uint8_t tag) { return tag == RDFGPU_TV_DATE_TIME || tag == RDFGPU_TV_TIME || tag == RDFGPU_TV_DATE; }
 
 // ENC_TV: one 16-byte gather (global_load_dwordx4) per row.
+// TZ: a timestamp also takes its timezone offset (rdfgpu_typed_value.tz_minutes, bits 16..31 of the row's fourth dword) into bits 16..31
+// of `aux`, where a timestamp LITERAL carries it (rdfgpu_expr_node.u).  Nothing but the date parts (tv_date_part) reads those bits: the
+// comparisons look at bit 0 only.  Only the VM instantiations that compile the date parts in ask for it (eval_program<true>).
+template <bool TZ = false>
 __device__ __forceinline__ Val enc_tv(const TypedTable& t, uint32_t id) {
   Val v = val_tv_null();
   if (id == 0 || id >= t.n_ids) return v;
@@ -114,6 +121,7 @@ __device__ __forceinline__ Val enc_tv(const TypedTable& t, uint32_t id) {
     if ((uint64_t)v.lo >= t.n_dec) return val_tv_null();
     const int64_t* d = t.dec + 2 * v.lo;
     v.lo = d[0]; v.hi = d[1];
+    if constexpr (TZ) { if (v.tag != RDFGPU_TV_DECIMAL) v.aux |= (uint32_t)raw.w & 0xFFFF0000u; }
   }
   return v;
 }
@@ -485,6 +493,18 @@ __device__ __noinline__ Val tv_cast(Val a, uint32_t target, uint32_t* rt_error) 
   return r;
 }
 
+// YEAR / MONTH / DAY / HOURS / MINUTES / SECONDS, scalar/dates_and_times/*.rs: a dateTime gives an xsd:integer (SECONDS: an xsd:decimal), every
+// other kind — date, time, null, a numeric — the error value (`ThinError::expected()`).  The offset rides in aux bits 16..31 beside bit 0 =
+// "has a timezone" (enc_tv<true>, or the literal's `u`); without a timezone it is 0 (`unwrap_or(TimezoneOffset::UTC)`).
+__device__ __noinline__ Val tv_date_part(Val a, uint32_t op) {
+  Val r = val_tv_null();
+  if (a.tag != RDFGPU_TV_DATE_TIME) return r;
+  if (op == RDFGPU_EX_SECONDS) { r.tag = RDFGPU_TV_DECIMAL; date_seconds(a.lo, a.hi, r.lo, r.hi); return r; }
+  const int tz = (a.aux & 1u) ? (int)(int16_t)(uint16_t)(a.aux >> 16) : 0;
+  r.tag = RDFGPU_TV_INTEGER; r.lo = date_part(a.lo, a.hi, tz, (int)(op - RDFGPU_EX_YEAR));
+  return r;
+}
+
 // EBV, effective_boolean_value.rs:99-119 : 0 / 1 / 2 (error => null)
 __device__ __forceinline__ uint32_t tv_ebv(const Val& v) {
   switch (v.tag) {
@@ -749,14 +769,18 @@ __device__ __forceinline__ Val tv_regex_var(const RegexProg* progs, uint32_t fir
   return val_tv_null();
 }
 
-// A program that holds RDFGPU_EX_CAST_LEX: its host launches the instantiation of its kernel that compiles the case in (LEX = true).
+// A program that holds RDFGPU_EX_CAST_LEX or a date part (RDFGPU_EX_YEAR .. RDFGPU_EX_SECONDS): its host launches the instantiation of its
+// kernel that compiles those cases in (LEX = true).
+inline bool is_date_part_op(uint32_t op) { return op >= RDFGPU_EX_YEAR && op <= RDFGPU_EX_SECONDS; }
 inline bool program_has_lex(const ExprProgram& pr) {
-  for (uint32_t i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_CAST_LEX) return true;
+  for (uint32_t i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op)) return true;
   return false;
 }
 // LEX: whether `case RDFGPU_EX_CAST_LEX` is compiled in.  The case — the byte resolution and the calls around the leaves — costs a hosting
 // kernel one or two registers, which moved kernels that sit on an occupancy step; so every host exists twice, and the instantiation
 // without the case is, register for register, the kernel it was before the op existed.  Plans pick by program_has_lex / NodeInfo::lex.
+// The date parts (YEAR .. SECONDS) live in the same instantiations, for the same reason: their case, and the timezone offset that ENC_TV
+// then has to carry (enc_tv<true>), exist only where LEX is true.
 template <bool LEX = false, class ColFn>
 __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const TypedTable& tt, ColFn col) {
   Val st[kMaxStack];
@@ -769,7 +793,7 @@ __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const Typed
       case RDFGPU_EX_LIT_ID: v = val_id(e.u); break;
       case RDFGPU_EX_LIT_TV: v = val_tv_null(); v.tag = e.tag; v.flags = e.flags; v.aux = e.u; v.lo = e.lo; v.hi = e.hi; break;
       case RDFGPU_EX_LIT_BOOL: v = val_bool(e.u > 2 ? 2 : e.u); break;
-      case RDFGPU_EX_ENC_TV: v = enc_tv(tt, (uint32_t)st[--sp].lo); break;
+      case RDFGPU_EX_ENC_TV: v = enc_tv<LEX>(tt, (uint32_t)st[--sp].lo); break;
       case kExAggValue: v = agg_value_load(e, (uint32_t)st[--sp].lo); break;
       case RDFGPU_EX_GT: case RDFGPU_EX_LT: case RDFGPU_EX_GEQ: case RDFGPU_EX_LEQ: case RDFGPU_EX_EQ: case RDFGPU_EX_NEQ: {
         const Val b = st[--sp]; const Val a = st[--sp];
@@ -788,6 +812,10 @@ __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const Typed
         else v = val_bool(2);     // (not reached: a program with the op runs in a LEX instantiation)
         break;
       case RDFGPU_EX_CAST_STRING: v = tv_cast_string(tt, (uint32_t)st[--sp].lo); break;
+      case RDFGPU_EX_YEAR: case RDFGPU_EX_MONTH: case RDFGPU_EX_DAY: case RDFGPU_EX_HOURS: case RDFGPU_EX_MINUTES: case RDFGPU_EX_SECONDS:
+        if constexpr (LEX) v = tv_date_part(st[--sp], e.op);
+        else v = val_bool(2);     // (not reached: a program with a date part runs in a LEX instantiation)
+        break;
       case RDFGPU_EX_EBV: v = val_bool(tv_ebv(st[--sp])); break;
       case RDFGPU_EX_REGEX: v = tv_regex(prog.regex[e.u], tt, st[--sp], -1, &prog); break;
       case RDFGPU_EX_REGEX_VAR: { const Val pat = st[--sp]; const Val val = st[--sp]; v = tv_regex_var(prog.regex, e.u, (uint32_t)e.lo, tt, val, pat, &prog); break; }

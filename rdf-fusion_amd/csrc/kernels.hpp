@@ -316,7 +316,7 @@ __host__ __device__ constexpr AggWordOp agg_word_op(u32 fn, u32 w) {   // how wo
        : agg_is_minmax(fn) ? (w == kMmFlags ? kAggOr : kAggMax) : kAggAdd;
 }
 struct AggArgs {
-  u32 n_keys;
+  u32 n_keys;                                    // group columns (the wide form, AggWideArgs below: the first RDFGPU_MAX_KEYS of them — what agg_final_kernel copies)
   const u32* key[RDFGPU_MAX_KEYS];
   const u64* n_dev; u64 cap;                     // input rows: the device count when n_dev, else cap
   u32 n_aggs;
@@ -345,6 +345,22 @@ struct AggArgs {
   rdfgpu_agg_value* out[RDFGPU_MAX_AGGREGATES];
   u32* out_val[RDFGPU_MAX_AGGREGATES];           // RDFGPU_PLAN_AGG_COLUMNS: the aggregate's value column (row g: g + 1, or 0 for the error value); else null
 };
+// The group pass of a node that has a value column among its group columns or more than RDFGPU_MAX_KEYS of them (RDFGPU_PLAN_VALUE_KEYS;
+// aggregate.hip, agg_groups_wide_kernel), and the copy of its key columns 4.. to the output.  A struct of its own: AggArgs — what every
+// other launch of the node takes, and what a node with at most 4 id keys has always taken — keeps its size and layout.  The pass leaves
+// row_slot, slot_gid, rep_row and the group count exactly as agg_groups_kernel does; everything behind it is shared.
+struct AggWideArgs {
+  u32 n_keys;                                    // 1 .. RDFGPU_MAX_GROUP_KEYS
+  u32 value_mask;                                // bit q: key q is a value column (compared by the term its value stands for), else an object-id column
+  const u32* key[RDFGPU_MAX_GROUP_KEYS];         // the key columns' entries
+  const rdfgpu_agg_value* val[RDFGPU_MAX_GROUP_KEYS];   // a value key: the array its entries index (entry e: record e - 1)
+  u64 val_n[RDFGPU_MAX_GROUP_KEYS];              // .. and its length: an entry of 0 or beyond it is "unbound"
+  const u64* n_dev; u64 cap;                     // input rows: the device count when n_dev, else cap
+  u32* slots; u32 slot_mask; u32* row_slot; u32* slot_gid; u32* rep_row; u64* n_groups_dev;   // as in AggArgs
+  u32* out_key[RDFGPU_MAX_GROUP_KEYS]; u32 n_groups;   // the key copy: columns RDFGPU_MAX_KEYS .. n_keys - 1 (agg_final_kernel copies the first four)
+};
+void launch_agg_groups_wide(const AggWideArgs& w, hipStream_t s);
+void launch_agg_wide_keys(const AggWideArgs& w, hipStream_t s);
 void launch_agg_groups(const AggArgs& a, hipStream_t s);
 void launch_agg_accum(const AggArgs& a, hipStream_t s);
 void launch_agg_minmax_refine(const AggArgs& a, hipStream_t s);   // a.minmax only: settles the low word of the decimal candidates

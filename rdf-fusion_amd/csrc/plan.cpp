@@ -154,7 +154,8 @@ const char* kernel_class_name(int kc) {
       "void rdfgpu::agg_accum_minmax_kernel<false>", "void rdfgpu::agg_accum_minmax_kernel<true>",
       "void rdfgpu::agg_accum_minmax_expr_kernel<false>", "void rdfgpu::agg_accum_minmax_expr_kernel<true>",
       "void rdfgpu::agg_minmax_refine_kernel",
-      "rdfgpu::oj_probe_kernel(rdfgpu::OrderedJoinArgs, rdfgpu::OjBandFuse, rdfgpu::OjKeyValues)"};
+      "rdfgpu::oj_probe_kernel(rdfgpu::OrderedJoinArgs, rdfgpu::OjBandFuse, rdfgpu::OjKeyValues)",
+      "rdfgpu::agg_groups_wide_kernel", "rdfgpu::agg_wide_keys_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;

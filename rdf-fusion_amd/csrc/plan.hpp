@@ -176,6 +176,7 @@ enum KernelClass {
   KC_AGG_ACCUM_MINMAX_EXPR_HBM, KC_AGG_ACCUM_MINMAX_EXPR_LDS,   // .. and some SUM / AVG / MIN / MAX reads an expression or a value column
   KC_AGG_MINMAX_REFINE,                                         // agg_minmax_refine_kernel: the low word of the decimal candidates
   KC_OJ_PROBE_VALUES,                                           // oj_probe_kernel(.., OjKeyValues): the probe pass of a step that reads the slice's rows through their cached windows
+  KC_AGG_GROUPS_WIDE, KC_AGG_WIDE_KEYS,                         // agg_groups_wide_kernel / agg_wide_keys_kernel: the group pass over value keys or more than 4 keys (RDFGPU_PLAN_VALUE_KEYS), its key copy
   KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
@@ -183,6 +184,9 @@ const char* kernel_class_name(int kc);
 inline int lds_join_class(u32 fs, u32 pfs, int items, int mode, bool chain = false) {
   return KC_LDS_JOIN0 + (int)((((fs * 3 + pfs) * 2 + (items == 4 ? 0 : 1)) * 4 + mode) * 2) + (chain ? 1 : 0);
 }
+
+// Group column k of an AggregateExec: columns 0..3 in left_keys[], 4..7 in right_keys[] (RDFGPU_PLAN_VALUE_KEYS).
+inline u32 agg_key_col(const rdfgpu_plan_node& d, u32 k) { return k < RDFGPU_MAX_KEYS ? d.left_keys[k] : d.right_keys[k - RDFGPU_MAX_KEYS]; }
 
 inline int semi_join_class(int form, bool anti) { return KC_SEMI_JOIN0 + form * 2 + (anti ? 1 : 0); }
 
@@ -214,9 +218,11 @@ struct PendingLaunch {
 struct AggNode {
   NodeInfo& nd; const DevTable& in;
   AggArgs a{};
+  bool wide = false; AggWideArgs w{};   // a value key or more than RDFGPU_MAX_KEYS keys (RDFGPU_PLAN_VALUE_KEYS): the group pass is agg_groups_wide_kernel over `w`
   u64 slots = 64;             // slots of the group table, and of every COUNT DISTINCT set: a power of two, at least twice the input's capacity
   u64 G = 1;                  // groups = output rows
   u64 accum_row_bytes = 0, refine_row_bytes = 0;   // what the accumulate pass / the refinement reads per input row
+  u64 group_row_bytes = 0;                         // .. and the group pass: 4 per key column, 24 more per value key (its record)
   AggNode(NodeInfo& n, const DevTable& t) : nd(n), in(t) {}
 };
 
@@ -233,6 +239,7 @@ struct Plan {
   u32 root = 0;
   u64 run = 0;                    // counts the executions (a value array belongs to the one that wrote it)
   bool agg_columns = false;       // RDFGPU_PLAN_AGG_COLUMNS: aggregate values are u32 columns that flow into the operators above
+  bool value_keys = false;        // RDFGPU_PLAN_VALUE_KEYS: an AggregateExec takes value columns as group columns, and up to RDFGPU_MAX_GROUP_KEYS of them
   ExecContext* ctx = nullptr;     // stream, events, counters (pooled per store)
   hipStream_t stream = nullptr;
   std::vector<BoundTable> tables;

@@ -8,8 +8,27 @@ namespace rdfgpu {
 void Plan::agg_bind_inputs(AggNode& n) {
   AggArgs& a = n.a;
   const NodeInfo& nd = n.nd;
-  a.n_keys = nd.d.n_keys;
-  for (u32 k = 0; k < a.n_keys; k++) a.key[k] = n.in.cols[nd.d.left_keys[k]];
+  // The wide form (RDFGPU_PLAN_VALUE_KEYS): a value column among the group columns, or more than RDFGPU_MAX_KEYS of them.  Every other node is
+  // bound, and launches, exactly as before.  AggArgs then carries the first four keys only (agg_final_kernel's copy); `w` carries them all.
+  const u32 nk = nd.d.n_keys;
+  n.wide = value_keys && nk > RDFGPU_MAX_KEYS;
+  for (u32 k = 0; k < nk && value_keys; k++) n.wide = n.wide || nd.origin[k].node >= 0;
+  a.n_keys = std::min<u32>(nk, RDFGPU_MAX_KEYS);
+  for (u32 k = 0; k < a.n_keys; k++) a.key[k] = n.in.cols[agg_key_col(nd.d, k)];
+  if (n.wide) {
+    AggWideArgs& w = n.w;
+    w.n_keys = nk; w.n_dev = n.in.n_dev; w.cap = n.in.cap;
+    for (u32 k = 0; k < nk; k++) {
+      w.key[k] = n.in.cols[agg_key_col(nd.d, k)];
+      const ValueOrigin& o = nd.origin[k];
+      if (o.node < 0) continue;
+      const NodeInfo& src = nodes[o.node];   // the arrays are scratch of the execution that wrote them (bind_values)
+      if (src.values_run != run) fail(RDFGPU_ERR_INVALID, "a value column of node %d is grouped by before the node ran", o.node);
+      w.value_mask |= 1u << k; w.val[k] = src.values[o.agg]; w.val_n[k] = src.n_values;
+      n.group_row_bytes += 24;
+    }
+  }
+  n.group_row_bytes += 4ull * nk;
   a.n_dev = n.in.n_dev; a.cap = n.in.cap; a.n_aggs = nd.n_aggs;
   for (u32 i = 0; i < a.n_aggs; i++) {
     const u32 fn = nd.agg_fn[i];
@@ -46,6 +65,11 @@ void Plan::agg_group_pass(AggNode& n) {
     a.row_slot = scratch<u32>(a.cap); a.slot_gid = scratch<u32>(n.slots); a.rep_row = scratch<u32>(a.cap);
     a.n_groups_dev = new_counter();
     RDFGPU_HIP(hipMemsetAsync(a.slots, 0, n.slots * sizeof(u32), stream));
+    if (n.wide) {   // per row 4 bytes per key column and the 24-byte record of every value key
+      AggWideArgs& w = n.w;
+      w.slots = a.slots; w.slot_mask = a.slot_mask; w.row_slot = a.row_slot; w.slot_gid = a.slot_gid; w.rep_row = a.rep_row; w.n_groups_dev = a.n_groups_dev;
+      timed(KC_AGG_GROUPS_WIDE, 0, a.cap, a.n_dev, n.group_row_bytes, nullptr, 0, 0, [&] { launch_agg_groups_wide(w, stream); });
+    } else
     timed(KC_AGG_GROUPS, 0, a.cap, a.n_dev, 4ull * a.n_keys, nullptr, 0, 0, [&] { launch_agg_groups(a, stream); });
     n.G = read_back<u64>(a.n_groups_dev);
   }
@@ -56,10 +80,17 @@ void Plan::agg_group_pass(AggNode& n) {
 DevTable Plan::agg_outputs(AggNode& n) {
   AggArgs& a = n.a;
   DevTable t; t.n_cols = n.nd.width; t.cap = n.G;
-  for (u32 k = 0; k < a.n_keys; k++) { a.out_key[k] = scratch<u32>(n.G); t.cols[k] = a.out_key[k]; }
+  const u32 nk = n.nd.d.n_keys;   // (a.n_keys is the first four of them in the wide form)
+  for (u32 k = 0; k < nk; k++) {
+    u32* const c = scratch<u32>(n.G);
+    t.cols[k] = c;
+    if (k < a.n_keys) a.out_key[k] = c;
+    if (n.wide) n.w.out_key[k] = c;
+  }
+  n.w.n_groups = (u32)n.G;
   for (u32 i = 0; i < a.n_aggs; i++) {
     a.out[i] = scratch<rdfgpu_agg_value>(n.G); n.nd.values[i] = a.out[i];
-    if (agg_columns) { a.out_val[i] = scratch<u32>(n.G); t.cols[a.n_keys + i] = a.out_val[i]; }
+    if (agg_columns) { a.out_val[i] = scratch<u32>(n.G); t.cols[nk + i] = a.out_val[i]; }
   }
   n.nd.n_values = n.G; n.nd.values_run = run;
   if (&n.nd == &nodes[root] && !agg_columns) agg_out.assign(a.out, a.out + a.n_aggs);
@@ -87,6 +118,7 @@ void Plan::agg_accumulate(AggNode& n) {
 void Plan::agg_finish(AggNode& n) {
   const AggArgs& a = n.a;
   timed(KC_AGG_FINAL, 0, 0, nullptr, 0, nullptr, n.G, 4ull * a.n_keys + 24ull * a.n_aggs, [&] { launch_agg_final(a, stream); });
+  if (n.wide && n.w.n_keys > RDFGPU_MAX_KEYS) timed(KC_AGG_WIDE_KEYS, 0, 0, nullptr, 0, nullptr, n.G, 4ull * (n.w.n_keys - RDFGPU_MAX_KEYS), [&] { launch_agg_wide_keys(n.w, stream); });
   if (agg_columns && a.n_aggs) timed(KC_AGG_VALUE_COLS, 0, 0, nullptr, 0, nullptr, n.G, 4ull * a.n_aggs, [&] { launch_agg_value_cols(a, stream); });
 }
 

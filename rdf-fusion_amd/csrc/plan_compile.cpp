@@ -54,6 +54,8 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
       case RDFGPU_EX_ADD: case RDFGPU_EX_SUB: case RDFGPU_EX_MUL: case RDFGPU_EX_DIV: pop(VK_TV, "binary typed op"); pop(VK_TV, "binary typed op"); out = VK_TV; break;
       case RDFGPU_EX_NEG: case RDFGPU_EX_PLUS: case RDFGPU_EX_ABS: case RDFGPU_EX_ROUND: case RDFGPU_EX_CEIL: case RDFGPU_EX_FLOOR:
         pop(VK_TV, "unary numeric op"); out = VK_TV; break;
+      case RDFGPU_EX_YEAR: case RDFGPU_EX_MONTH: case RDFGPU_EX_DAY: case RDFGPU_EX_HOURS: case RDFGPU_EX_MINUTES: case RDFGPU_EX_SECONDS:
+        pop(VK_TV, "date part (YEAR .. SECONDS)"); out = VK_TV; break;
       case RDFGPU_EX_CAST:
         if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
           fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
@@ -103,10 +105,10 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
   return st[0];
 }
 
-// A program with a value load or a lexical cast in it runs in the generic VM: the specialised forms gather from the typed-value table by
-// object id and know the ops of their shape only.
+// A program with a value load, a lexical cast or a date part in it runs in the generic VM: the specialised forms gather from the typed-value
+// table by object id and know the ops of their shape only.
 bool needs_generic_vm(const ExprProgram& pr) {
-  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue || pr.nodes[i].op == RDFGPU_EX_CAST_STRING || pr.nodes[i].op == RDFGPU_EX_CAST_LEX) return true;
+  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue || pr.nodes[i].op == RDFGPU_EX_CAST_STRING || pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op)) return true;
   return false;
 }
 
@@ -343,14 +345,19 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   NodeInfo& nd = plan->nodes[i];
   const rdfgpu_plan_node& r = nd.d;
   const NodeInfo& c = child(plan, i, r.left, "input");
-  if (r.n_keys > RDFGPU_MAX_KEYS) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u group columns (at most %u)", i, r.n_keys, RDFGPU_MAX_KEYS);
+  // RDFGPU_PLAN_VALUE_KEYS: up to RDFGPU_MAX_GROUP_KEYS group columns (4.. in right_keys[]), value columns among them; without the flag every
+  // refusal is what it was
+  const u32 max_keys = plan->value_keys ? RDFGPU_MAX_GROUP_KEYS : RDFGPU_MAX_KEYS;
+  if (r.n_keys > max_keys) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u group columns (at most %u)", i, r.n_keys, max_keys);
   if (r.table_cols > RDFGPU_MAX_AGGREGATES) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: AggregateExec with %u aggregates (at most %u)", i, r.table_cols, RDFGPU_MAX_AGGREGATES);
   if (r.n_proj != RDFGPU_NO_PROJECTION) fail(RDFGPU_ERR_INVALID, "node %u: AggregateExec takes no projection", i);
   if (r.n_keys + r.table_cols == 0) fail(RDFGPU_ERR_INVALID, "node %u: AggregateExec without group columns and aggregates", i);
   InputSchema in; in.append(c);
   for (u32 k = 0; k < r.n_keys; k++) {
-    if (r.left_keys[k] >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: group column %u out of range", i, r.left_keys[k]);
-    refuse_value_column(c.origin[r.left_keys[k]], i, "group", r.left_keys[k]);
+    const u32 col = agg_key_col(r, k);
+    if (col >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: group column %u out of range", i, col);
+    if (!plan->value_keys) refuse_value_column(c.origin[col], i, "group", col);
+    else nd.origin[k] = c.origin[col];   // a value key stays a value column with its input's origin: the representative row's entry indexes the same array
   }
   if (r.table_cols && ((u64)r.table_slot + 2ull * r.table_cols > d->n_pool || !d->pool)) fail(RDFGPU_ERR_INVALID, "node %u: aggregate list outside the pool", i);
   for (u32 a = 0; a < r.table_cols; a++) {
@@ -642,6 +649,12 @@ void account_columns_read(Plan* plan) {
 
 }  // namespace
 
+// rdfgpu_plan_desc.flags: RDFGPU_PLAN_VALUE_KEYS groups by value columns, which exist only when aggregate values are columns.
+void check_plan_flags(u32 flags) {
+  if ((flags & RDFGPU_PLAN_VALUE_KEYS) && !(flags & RDFGPU_PLAN_AGG_COLUMNS))
+    fail(RDFGPU_ERR_INVALID, "plan_compile: RDFGPU_PLAN_VALUE_KEYS is valid only together with RDFGPU_PLAN_AGG_COLUMNS (value columns exist only in such a plan)");
+}
+
 Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
   if (!store) fail(RDFGPU_ERR_INVALID, "plan_compile: null store");
   if (!d || !d->nodes || d->n_nodes == 0) fail(RDFGPU_ERR_INVALID, "plan_compile: empty plan");
@@ -651,7 +664,9 @@ Plan* plan_compile(Store* store, const rdfgpu_plan_desc* d) {
   plan->opt = store->opt;
   store->retain();
   plan->root = d->root;
+  check_plan_flags(d->flags);
   plan->agg_columns = (d->flags & RDFGPU_PLAN_AGG_COLUMNS) != 0;
+  plan->value_keys = (d->flags & RDFGPU_PLAN_VALUE_KEYS) != 0;
   plan->nodes.resize(d->n_nodes);
   if (d->n_regexes) compile_string_table(plan.get(), d);   // REGEX patterns are plan constants: compiled here, simulated per row on the device
   check_string_functions(store, d);

@@ -518,7 +518,7 @@ def shard_of(object_id, world):
     return int(load_library().rdfgpu_shard_of(int(object_id), int(world)))
 
 
-TV_DTYPE = np.dtype([("lo", "<i8"), ("aux", "<u4"), ("tag", "u1"), ("flags", "u1"), ("reserved", "<u2")])
+TV_DTYPE = np.dtype([("lo", "<i8"), ("aux", "<u4"), ("tag", "u1"), ("flags", "u1"), ("tz_minutes", "<i2")])
 
 
 class GpuPlan:

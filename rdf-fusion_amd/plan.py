@@ -154,16 +154,22 @@ def decimal(scaled_i128):
     return lit_tv(abi.TV_DECIMAL, to_i64(lo), hi=to_i64(hi))
 
 
-def _timestamp(tag, scaled_i128, has_timezone):
+def _timestamp(tag, scaled_i128, has_timezone, tz_minutes=0):
     v = int(scaled_i128) & ((1 << 128) - 1)
     lo, hi = v & ((1 << 64) - 1), v >> 64
     to_i64 = lambda x: x - (1 << 64) if x >= (1 << 63) else x
-    return lit_tv(tag, to_i64(lo), aux=1 if has_timezone else 0, hi=to_i64(hi))
+    if tz_minutes and not has_timezone:
+        raise ValueError("a timestamp without a timezone has no offset")
+    if not -840 <= int(tz_minutes) <= 840:
+        raise ValueError("a timezone offset lies within -14:00 .. +14:00")
+    # `u`: bit 0 = has a timezone, bits 16..31 = the offset in minutes as int16 (read by the date parts only)
+    return lit_tv(tag, to_i64(lo), aux=(1 if has_timezone else 0) | ((int(tz_minutes) & 0xFFFF) << 16), hi=to_i64(hi))
 
 
-def date_time(scaled_i128, has_timezone):
-    """xsd:dateTime literal: Timestamp value * 10**18 (rdf_fusion_amd.xsd.parse_date_time) + timezone presence."""
-    return _timestamp(abi.TV_DATE_TIME, scaled_i128, has_timezone)
+def date_time(scaled_i128, has_timezone, tz_minutes=0):
+    """xsd:dateTime literal: Timestamp value * 10**18 (rdf_fusion_amd.xsd.parse_date_time) + timezone presence + the offset in minutes
+    (what YEAR .. MINUTES shift the UTC instant by; comparisons never look at it)."""
+    return _timestamp(abi.TV_DATE_TIME, scaled_i128, has_timezone, tz_minutes)
 
 
 def date(scaled_i128, has_timezone):
@@ -196,6 +202,16 @@ def ABS(e): return e._un(abi.EX_ABS)
 def ROUND(e): return e._un(abi.EX_ROUND)
 def CEIL(e): return e._un(abi.EX_CEIL)
 def FLOOR(e): return e._un(abi.EX_FLOOR)
+
+
+# The parts of an xsd:dateTime (include/rdfgpu.h, ABI 4 addendum): scalar/dates_and_times/{year,month,day,hours,minutes,seconds}.rs.  Only a
+# dateTime yields a value (xsd:integer; SECONDS: xsd:decimal), every other kind is the error value.
+def YEAR(e): return e._un(abi.EX_YEAR)
+def MONTH(e): return e._un(abi.EX_MONTH)
+def DAY(e): return e._un(abi.EX_DAY)
+def HOURS(e): return e._un(abi.EX_HOURS)
+def MINUTES(e): return e._un(abi.EX_MINUTES)
+def SECONDS(e): return e._un(abi.EX_SECONDS)
 
 
 def CAST(e, tag):
@@ -424,8 +440,11 @@ class PlanBuilder:
     def _value_columns(self, node, width):
         """Which output columns of `node` carry aggregate values when they are columns: an AggregateExec's aggregates, and whatever a
         projection, filter, sort or join hands on of its inputs' (a semi / anti join: of its left input's)."""
-        if node.kind == abi.NODE_AGGREGATE:
-            return [False] * (width - node.table_cols) + [True] * node.table_cols
+        if node.kind == abi.NODE_AGGREGATE:     # a key that is a value column stays one (build(value_keys=True)); the aggregates always are
+            below = self.values[node.left]
+            n_keys = width - node.table_cols       # (keys beyond the bound have no slot: the library refuses the node)
+            keys = [_agg_key_col(node, k) if k < abi.MAX_GROUP_KEYS else len(below) for k in range(n_keys)]
+            return [bool(c < len(below) and below[c]) for c in keys] + [True] * node.table_cols
         if node.kind in (abi.NODE_DATA_SOURCE, abi.NODE_TABLE) or node.left < 0:
             return [False] * width
         if node.kind == abi.NODE_EXTEND:        # the kept columns as the input has them, then the computed ones
@@ -554,7 +573,8 @@ class PlanBuilder:
         return self._push(n, self._proj(n, None, 3), self.names[left])
 
     def aggregate(self, left, group_by, aggregates=()):
-        """AggregateExec(mode=Single): GROUP BY the id columns `group_by` (0 to 4) with `aggregates` = [(abi.AGG_*, input column), ...]
+        """AggregateExec(mode=Single): GROUP BY the columns `group_by` — 0 to 4 id columns; in a description built with value_keys=True up to
+        8 columns, value columns (aggregates, computed columns) among them, grouped by the term their value stands for — with `aggregates` = [(abi.AGG_*, input column), ...]
         (at most 8; AGG_COUNT_STAR takes no column: None).  AGG_MIN / AGG_MAX need a description built with agg_columns=True; their answer
         is fixed and independent of row order (include/rdfgpu.h: an unbound row makes the group unbound, a value that is not numeric fails
         the execute).  The input of AGG_SUM / AGG_AVG / AGG_MIN / AGG_MAX may be an `Expr` over the input's columns that
@@ -567,9 +587,12 @@ class PlanBuilder:
         names = self.names[left]
         n = abi.PlanNode(kind=abi.NODE_AGGREGATE, left=left, right=-1, n_keys=len(group_by), table_cols=len(aggregates),
                          table_slot=len(self.pool))
-        for k, c in enumerate(group_by[:abi.MAX_KEYS]):
-            n.left_keys[k] = c
-        n.n_keys = len(group_by)           # (more than MAX_KEYS is the library's to refuse)
+        for k, c in enumerate(group_by[:abi.MAX_GROUP_KEYS]):      # keys 0..3 in left_keys[], 4..7 in right_keys[] (an aggregate has no other use for them)
+            if k < abi.MAX_KEYS:
+                n.left_keys[k] = c
+            else:
+                n.right_keys[k - abi.MAX_KEYS] = c
+        n.n_keys = len(group_by)           # (more than the bound is the library's to refuse)
         first = len(self.pool) + 2 * len(aggregates)   # the (expr_off, expr_len) pairs follow the aggregate list
         n_expr = 0
         for fn, c in aggregates:
@@ -618,12 +641,15 @@ class PlanBuilder:
         """BIND(expr AS ?name) / SELECT (expr AS ?name): every column of `child`, then the computed one."""
         return self.extend(child, [expr], keep=None, names=[name])
 
-    def build(self, root, agg_columns=False):
-        """agg_columns=True sets abi.PLAN_AGG_COLUMNS: an AggregateExec with aggregates may sit anywhere, its output is the keys and then
+    def build(self, root, agg_columns=False, value_keys=False):
+        """value_keys=True (only with agg_columns=True) sets abi.PLAN_VALUE_KEYS: an AggregateExec groups by up to 8 columns, value columns
+        among them.  agg_columns=True sets abi.PLAN_AGG_COLUMNS: an AggregateExec with aggregates may sit anywhere, its output is the keys and then
         one value column per aggregate (n_columns counts them), and FilterExec / joins / further aggregates above read the values through
         ENC_TV.  Without it the description is what it always was: aggregates at the root only, values through GpuPlan.aggregate_values."""
+        if value_keys and not agg_columns:
+            raise ValueError("value_keys=True needs agg_columns=True: value columns exist only in such a plan")
         return PlanDescription(self.nodes, self.exprs, self.pool, root, list(self.width), list(self.regexes),
-                               flags=abi.PLAN_AGG_COLUMNS if agg_columns else 0,
+                               flags=(abi.PLAN_AGG_COLUMNS if agg_columns else 0) | (abi.PLAN_VALUE_KEYS if value_keys else 0),
                                value_columns=[c for c, v in enumerate(self.values[root]) if v] if agg_columns else [])
 
     def sparql_having(self, agg, predicate, projection=None):
@@ -707,10 +733,16 @@ _BIN = {abi.EX_GT: "GT", abi.EX_LT: "LT", abi.EX_GEQ: "GEQ", abi.EX_LEQ: "LEQ", 
         abi.EX_IS_COMPATIBLE: "IS_COMPATIBLE", abi.EX_MUL: "MUL", abi.EX_DIV: "DIV"}
 _JOIN_TYPE_NAMES = {abi.JOIN_INNER: "Inner", abi.JOIN_LEFT: "Left", abi.JOIN_LEFT_SEMI: "LeftSemi", abi.JOIN_LEFT_ANTI: "LeftAnti"}
 _UN = {abi.EX_ENC_TV: "ENC_TV", abi.EX_EBV: "EBV", abi.EX_BOUND: "BOUND", abi.EX_BOOL_AS_TV: "BOOLEAN_AS_TERM",
-       abi.EX_NEG: "MINUS", abi.EX_PLUS: "PLUS", abi.EX_ABS: "ABS", abi.EX_ROUND: "ROUND", abi.EX_CEIL: "CEIL", abi.EX_FLOOR: "FLOOR"}
+       abi.EX_NEG: "MINUS", abi.EX_PLUS: "PLUS", abi.EX_ABS: "ABS", abi.EX_ROUND: "ROUND", abi.EX_CEIL: "CEIL", abi.EX_FLOOR: "FLOOR",
+       abi.EX_YEAR: "YEAR", abi.EX_MONTH: "MONTH", abi.EX_DAY: "DAY", abi.EX_HOURS: "HOURS", abi.EX_MINUTES: "MINUTES", abi.EX_SECONDS: "SECONDS"}
 # BuiltinName::CastBoolean .. CastDouble as the reference's plans print them (`xsd:integer(..)`)
 _CAST = {abi.TV_BOOLEAN: "xsd:boolean", abi.TV_INT: "xsd:int", abi.TV_INTEGER: "xsd:integer", abi.TV_DECIMAL: "xsd:decimal",
          abi.TV_FLOAT: "xsd:float", abi.TV_DOUBLE: "xsd:double"}
+
+
+def _agg_key_col(node, k):
+    """group column k of an AggregateExec node: 0..3 in left_keys[], 4..7 in right_keys[]"""
+    return node.left_keys[k] if k < abi.MAX_KEYS else node.right_keys[k - abi.MAX_KEYS]
 
 
 def _agg_label(fn, column, at=None):
@@ -824,7 +856,10 @@ def explain(pb, root, choose_index=None, agg_columns=False):
             return
         if n.kind == abi.NODE_AGGREGATE:
             full = pb.names[n.left]
-            gby = ", ".join(f"{full[n.left_keys[k]]}@{n.left_keys[k]} as {full[n.left_keys[k]]}" for k in range(min(n.n_keys, abi.MAX_KEYS)))
+            # a value key prints as the reference groups by it: the plain term of the value, `ENC_PT(year@7) as year`
+            keys = [_agg_key_col(n, k) for k in range(min(n.n_keys, abi.MAX_GROUP_KEYS))]
+            is_value = lambda c: c < len(pb.values[n.left]) and pb.values[n.left][c]
+            gby = ", ".join((f"ENC_PT({full[c]}@{c}) as {full[c]}" if is_value(c) else f"{full[c]}@{c} as {full[c]}") for c in keys)
             aggs = []
             for a in range(n.table_cols):
                 fn, c = pb.pool[n.table_slot + 2 * a], pb.pool[n.table_slot + 2 * a + 1]
