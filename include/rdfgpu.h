@@ -376,6 +376,32 @@ enum {
   RDFGPU_EX_MINUTES = 52,     /* TV(dateTime) -> TV(integer)  minutes.rs: 0..59                                                        */
   RDFGPU_EX_SECONDS = 53,     /* TV(dateTime) -> TV(decimal)  seconds.rs: rem_euclid(value, 60 * 10^18) on the scaled i128, in [0, 60);
                                  no offset is applied (offsets are whole minutes)                                                      */
+  /* ---- ABI 4 addendum: functional forms (SPARQL 1.1 §17.4.1) and term tests (§17.4.2), new enum values only.  Evaluation is EAGER, as in
+     the reference (dispatch_ternary_typed_value computes all three argument arrays of IF; DataFusion's `coalesce` gets evaluated arrays):
+     every operand is computed for every row and errors are values.  A RUN-TIME REFUSAL of the device is not a value: an operand that
+     raises one (a CAST of a simple literal, a CAST_LEX the device cannot decide, ..) fails the execute with RDFGPU_ERR_UNSUPPORTED even
+     when it sits in the branch IF does not choose or behind the operand COALESCE returns — louder than the reference, never a different
+     answer.  Allowed wherever MUL is: FILTER, the filter of every join kind, SUM / AVG / MIN / MAX inputs, RDFGPU_NODE_EXTEND programs,
+     HAVING over value columns; a predicate with one runs in the generic VM.
+     IN / NOT IN need no op: expression_rewriter.rs:302-322 (rewrite_in) is BOOL_AS_TV(OR(EBV(EQ(lhs, e_1)), EBV(EQ(lhs, e_2)), ..)),
+     BOOL_AS_TV(LIT_BOOL false) for an empty list, and NOT IN is BOOL_AS_TV(NOT(EBV(IN(..)))).  sameTerm over ids stays ID_EQ.
+     LANG(v) = "tag" is an RDFGPU_EX_LANG_IN whose table is 1 exactly for the language ids with that tag (a literal without a language
+     gives "": id 0; IRIs, blank nodes and null the error value, lang.rs:49-55).  LANG and DATATYPE as VALUES are not on the device.
+     The value 54 is not assigned: a description that holds it is refused as an unknown op, as before. */
+  RDFGPU_EX_IF = 55,          /* TV TV TV -> TV  functional_form/sparql_if.rs:38-61: operands test, then, else.  The test must be a typed
+                                 value of tag RDFGPU_TV_BOOLEAN (Boolean::try_from, lib/model/src/xsd/boolean.rs:93-102 — NOT the EBV):
+                                 the null value, a number, a string, an IRI => the error value.  Otherwise the chosen branch comes out
+                                 unchanged, also when the other branch is the error value.  EBV semantics: BOOL_AS_TV(EBV(test)).        */
+  RDFGPU_EX_COALESCE = 56,    /* u x TV -> TV  or  u x ID -> ID   DataFusion's `coalesce` (lib/functions/src/registry.rs:264-270): `u` = the
+                                 number of operands, 1 .. 8, all of one kind (mixed kinds, u = 0 or u > 8: RDFGPU_ERR_INVALID).  TV form: the
+                                 first operand that is not the error value (tag RDFGPU_TV_NULL), else the error value.  ID form: the first
+                                 non-zero object id, else 0.  A value column is read through ENC_TV (unwrapped it is refused: its entries
+                                 are not object ids).                                                                                    */
+  RDFGPU_EX_IS_IRI = 57,      /* TV -> TV(boolean|null)  scalar/terms/is_iri.rs: tag NAMED_NODE; the null value => error (all four)       */
+  RDFGPU_EX_IS_BLANK = 58,    /* TV -> TV(boolean|null)  is_blank.rs: tag BLANK_NODE                                                      */
+  RDFGPU_EX_IS_LITERAL = 59,  /* TV -> TV(boolean|null)  is_literal.rs: every non-null tag but NAMED_NODE / BLANK_NODE; a computed string
+                                 (a view) is a literal                                                                                   */
+  RDFGPU_EX_IS_NUMERIC = 60,  /* TV -> TV(boolean|null)  is_numeric.rs: INT, INTEGER, DECIMAL, FLOAT or DOUBLE                            */
   RDFGPU_EX__COUNT
 };
 
@@ -632,7 +658,22 @@ enum { RDFGPU_JOIN_INNER = 0, RDFGPU_JOIN_LEFT = 1,
           NestedLoopJoinExec without a filter: SEMI keeps every left row when the right input has at least one row, ANTI keeps every
           left row when it has none (the EXISTS lowering for patterns that share no variable).
           Row order unspecified, as for the other joins; duplicate left rows are all kept.                                         */
-       RDFGPU_JOIN_LEFT_SEMI = 2, RDFGPU_JOIN_LEFT_ANTI = 3 };
+       RDFGPU_JOIN_LEFT_SEMI = 2, RDFGPU_JOIN_LEFT_ANTI = 3,
+       /* ABI 4 addendum: JoinType::LeftMark of HashJoinExec and NestedLoopJoinExec — what EXISTS becomes when it is an OPERAND (inside
+          `||`, IF, a BIND: `Expr::Exists`, lib/logical/src/expr_builder_context.rs:197-300, is decorrelated by DataFusion into a
+          LeftMark join wherever it is not a conjunct of its own).  Accepted only in a plan compiled with RDFGPU_PLAN_AGG_COLUMNS
+          (RDFGPU_ERR_UNSUPPORTED at compile without it): the mark is a value column.
+          Rows: every left row exactly once and IN LEFT INPUT ORDER (output row r is left row r).
+          Output schema: [left cols, mark]; the node's projection indexes that, the mark at index n_left_cols (at most 16 columns);
+          the join filter sees [left cols, right cols].
+          The mark is true when at least one right row equals the left row on every key and the filter evaluates to exactly true,
+          else false — never null: keys are NullEqualsNothing, a left row with a null key is false.  NestedLoopJoinExec without a
+          filter: the mark is "the right input has a row".
+          The mark column is a value column whose origin is the join node and whose value array has exactly two records,
+          {RDFGPU_TV_BOOLEAN, 0} and {RDFGPU_TV_BOOLEAN, 1}: a row carries entry 1 (false) or 2 (true), never 0.  Everything a value column
+          can do it can (ENC_TV in expressions above, SUM / COUNT / AVG, RDFGPU_SORT_BY_VALUE, a group column under RDFGPU_PLAN_VALUE_KEYS,
+          rdfgpu_plan_result_values); what a value column is refused for stays refused (join key, COUNT DISTINCT, TopK, UNION, CLOSURE). */
+       RDFGPU_JOIN_LEFT_MARK = 4 };
 #define RDFGPU_MAX_KEYS 4u
 #define RDFGPU_MAX_COLUMNS 16u
 #define RDFGPU_MAX_GROUP_KEYS 8u   /* group columns of an RDFGPU_NODE_AGGREGATE in a plan compiled with RDFGPU_PLAN_VALUE_KEYS (else RDFGPU_MAX_KEYS) */

@@ -33,6 +33,9 @@ NT_IRI, NT_BNODE, NT_SIMPLE, NT_LANG, NT_TYPED = 1, 2, 3, 4, 5   # rdfgpu_ntripl
  EX_STR, EX_LIT_STR, EX_STRLEN, EX_SUBSTR, EX_UCASE, EX_LCASE, EX_STRBEFORE, EX_STRAFTER,
  EX_MUL, EX_DIV, EX_NEG, EX_PLUS, EX_ABS, EX_ROUND, EX_CEIL, EX_FLOOR, EX_CAST, EX_CAST_STRING, EX_CAST_LEX,
  EX_YEAR, EX_MONTH, EX_DAY, EX_HOURS, EX_MINUTES, EX_SECONDS) = range(1, 54)   # EX_YEAR = 48 .. EX_SECONDS = 53: the parts of an xsd:dateTime
+# functional forms and term tests (SPARQL 1.1 §17.4.1 / §17.4.2): EX_COALESCE's `u` = its number of operands (1 .. MAX_STACK)
+EX_IF, EX_COALESCE, EX_IS_IRI, EX_IS_BLANK, EX_IS_LITERAL, EX_IS_NUMERIC = range(55, 61)   # (54 is not assigned)
+MAX_STACK = 8                   # values an expression may hold at once (csrc/expr_device.hpp kMaxStack)
 CAST_TARGETS = (TV_BOOLEAN, TV_INT, TV_INTEGER, TV_DECIMAL, TV_FLOAT, TV_DOUBLE)   # EX_CAST's `u`; any other tag is refused at compile
 
 # plan nodes
@@ -52,6 +55,7 @@ SORT_BY_ID, SORT_BY_TERM, SORT_BY_DOUBLE = 0, 1, 2
 SORT_BY_VALUE = 3               # NODE_SORT only: ENC_SORT of the typed value a value column's entry stands for
 SORT_DESC = 0x100               # NODE_SORT, or-ed into a key's `how`: descending
 JOIN_INNER, JOIN_LEFT, JOIN_LEFT_SEMI, JOIN_LEFT_ANTI = 0, 1, 2, 3
+JOIN_LEFT_MARK = 4              # JoinType::LeftMark: every left row once, in input order, plus the mark (a boolean value column; PLAN_AGG_COLUMNS)
 MAX_KEYS = 4
 MAX_GROUP_KEYS = 8              # group columns of a NODE_AGGREGATE in a plan built with value_keys=True (keys 4.. ride in right_keys[])
 MAX_COLUMNS = 16

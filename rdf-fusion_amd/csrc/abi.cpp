@@ -389,7 +389,7 @@ int rdfgpu_plan_decode_terms(rdfgpu_plan* plan, uint32_t col, uint64_t first_row
     if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
     if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
     if (const ValueOrigin& o = p->nodes[p->root].origin[col]; o.node >= 0)
-      fail(RDFGPU_ERR_UNSUPPORTED, "ENC_PT of result column %u: it is %s value column (%s %u of node %d), its entries are not object ids (rdfgpu_plan_result_values)", col, o.extend ? "a computed" : "an aggregate", o.extend ? "expression" : "aggregate", o.agg, o.node);
+      fail(RDFGPU_ERR_UNSUPPORTED, "ENC_PT of result column %u: it is %s value column (%s %u of node %d), its entries are not object ids (rdfgpu_plan_result_values)", col, o.mark ? "a mark" : o.extend ? "a computed" : "an aggregate", o.mark ? "mark" : o.extend ? "expression" : "aggregate", o.agg, o.node);
     if (first_row > p->result_rows || n_rows > p->result_rows - first_row) fail(RDFGPU_ERR_INVALID, "rows %llu .. + %llu of a %llu-row result", (unsigned long long)first_row, (unsigned long long)n_rows, (unsigned long long)p->result_rows);
     Store* st = p->store;
     st->activate();

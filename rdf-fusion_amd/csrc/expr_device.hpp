@@ -16,6 +16,9 @@
 //   YEAR .. SECONDS  scalar/dates_and_times/{year,month,day,hours,minutes,seconds}.rs over Timestamp::{year_month_day, hour, minute, second}
 //            (lib/model/src/xsd/date_time.rs:1731-1839), restated in date_parts.hpp
 //   EBV      lib/functions/src/builtin/native/effective_boolean_value.rs:99-119
+//   IF       scalar/functional_form/sparql_if.rs:38-61 (Boolean::try_from of the test, lib/model/src/xsd/boolean.rs:93-102: not the EBV)
+//   COALESCE lib/functions/src/registry.rs:264-270 (DataFusion's `coalesce`: the first argument that is not null)
+//   IS_IRI / IS_BLANK / IS_LITERAL / IS_NUMERIC  scalar/terms/is_{iri,blank,literal,numeric}.rs
 //   AND/OR   SQL three-valued logic on native booleans (lib/logical/src/expr_builder_context.rs:393-434)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -769,18 +772,30 @@ __device__ __forceinline__ Val tv_regex_var(const RegexProg* progs, uint32_t fir
   return val_tv_null();
 }
 
-// A program that holds RDFGPU_EX_CAST_LEX or a date part (RDFGPU_EX_YEAR .. RDFGPU_EX_SECONDS): its host launches the instantiation of its
-// kernel that compiles those cases in (LEX = true).
+// IS_IRI / IS_BLANK / IS_LITERAL / IS_NUMERIC, scalar/terms/is_*.rs: the null value is the error value (`ThinError::expected`); a string
+// view is a literal like the string it is a window of (its tag is STRING).
+__device__ __forceinline__ Val tv_term_test(const Val& a, uint32_t op) {
+  if (a.tag == RDFGPU_TV_NULL) return val_tv_null();
+  const bool node = a.tag == RDFGPU_TV_NAMED_NODE || a.tag == RDFGPU_TV_BLANK_NODE;
+  return val_tv_bool(op == RDFGPU_EX_IS_IRI ? a.tag == RDFGPU_TV_NAMED_NODE : op == RDFGPU_EX_IS_BLANK ? a.tag == RDFGPU_TV_BLANK_NODE
+                   : op == RDFGPU_EX_IS_LITERAL ? !node : num_kind(a.tag) != NK_NONE);
+}
+
+// A program that holds RDFGPU_EX_CAST_LEX, a date part (RDFGPU_EX_YEAR .. RDFGPU_EX_SECONDS) or a functional form / term test
+// (RDFGPU_EX_IF .. RDFGPU_EX_IS_NUMERIC): its host launches the instantiation of its kernel that compiles those cases in (LEX = true).
 inline bool is_date_part_op(uint32_t op) { return op >= RDFGPU_EX_YEAR && op <= RDFGPU_EX_SECONDS; }
+inline bool is_form_op(uint32_t op) { return op >= RDFGPU_EX_IF && op <= RDFGPU_EX_IS_NUMERIC; }
 inline bool program_has_lex(const ExprProgram& pr) {
-  for (uint32_t i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op)) return true;
+  for (uint32_t i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op) || is_form_op(pr.nodes[i].op)) return true;
   return false;
 }
 // LEX: whether `case RDFGPU_EX_CAST_LEX` is compiled in.  The case — the byte resolution and the calls around the leaves — costs a hosting
 // kernel one or two registers, which moved kernels that sit on an occupancy step; so every host exists twice, and the instantiation
 // without the case is, register for register, the kernel it was before the op existed.  Plans pick by program_has_lex / NodeInfo::lex.
 // The date parts (YEAR .. SECONDS) live in the same instantiations, for the same reason: their case, and the timezone offset that ENC_TV
-// then has to carry (enc_tv<true>), exist only where LEX is true.
+// then has to carry (enc_tv<true>), exist only where LEX is true.  So do IF, COALESCE and the term tests.  Their operands are all
+// evaluated before the op is reached (the program is postfix): eager, as in the reference, and a run-time refusal an operand raised stays
+// raised whichever operand the op then picks.
 template <bool LEX = false, class ColFn>
 __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const TypedTable& tt, ColFn col) {
   Val st[kMaxStack];
@@ -815,6 +830,23 @@ __device__ __forceinline__ Val eval_program(const ExprProgram& prog, const Typed
       case RDFGPU_EX_YEAR: case RDFGPU_EX_MONTH: case RDFGPU_EX_DAY: case RDFGPU_EX_HOURS: case RDFGPU_EX_MINUTES: case RDFGPU_EX_SECONDS:
         if constexpr (LEX) v = tv_date_part(st[--sp], e.op);
         else v = val_bool(2);     // (not reached: a program with a date part runs in a LEX instantiation)
+        break;
+      case RDFGPU_EX_IF:   // (test, then, else): Boolean::try_from of the test — a boolean typed value, or the error value
+        if constexpr (LEX) { const Val no = st[--sp]; const Val yes = st[--sp]; const Val test = st[--sp];
+          v = test.tag != RDFGPU_TV_BOOLEAN ? val_tv_null() : test.lo != 0 ? yes : no; }
+        else v = val_bool(2);     // (not reached: a program with a functional form or a term test runs in a LEX instantiation)
+        break;
+      case RDFGPU_EX_COALESCE:   // the first of the `u` operands that is not the error value (TV) / not 0 (ID), else the last: the error value / 0
+        if constexpr (LEX) {
+          const int k = e.u < 1u ? 1 : e.u > (uint32_t)sp ? sp : (int)e.u;   // (check_program: 1 <= u <= the stack's depth)
+          sp -= k;
+          v = st[sp];
+          for (int q = 1; q < k; q++) { const bool unset = v.kind == VK_ID ? v.lo == 0 : v.tag == RDFGPU_TV_NULL; if (unset) v = st[sp + q]; }
+        } else v = val_bool(2);
+        break;
+      case RDFGPU_EX_IS_IRI: case RDFGPU_EX_IS_BLANK: case RDFGPU_EX_IS_LITERAL: case RDFGPU_EX_IS_NUMERIC:
+        if constexpr (LEX) v = tv_term_test(st[--sp], e.op);
+        else v = val_bool(2);
         break;
       case RDFGPU_EX_EBV: v = val_bool(tv_ebv(st[--sp])); break;
       case RDFGPU_EX_REGEX: v = tv_regex(prog.regex[e.u], tt, st[--sp], -1, &prog); break;

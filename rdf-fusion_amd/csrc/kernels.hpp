@@ -281,6 +281,9 @@ struct SemiJoinArgs {
 void launch_semi_build(const SemiJoinArgs& a, bool dedupe, hipStream_t s);
 void launch_semi_join(const SemiJoinArgs& a, int form, bool anti, int filter, hipStream_t s);
 size_t semi_join_lds_bytes(const SemiJoinArgs& a, int form);
+// LeftMark joins (RDFGPU_JOIN_LEFT_MARK): the same arguments, tables and filters; `proj` indexes [left cols, mark] (entry n_left_cols =
+// the mark), every left row is stored at its own index with the mark as 1 (false) / 2 (true); n_out_dev is not used.
+void launch_mark_join(const SemiJoinArgs& a, int form, int filter, hipStream_t s);
 void preload_tu_semi_join();
 
 // ---- AggregateExec(mode=Single) (aggregate.hip): GROUP BY object-id columns with COUNT / COUNT DISTINCT / SUM / AVG / MIN / MAX ----

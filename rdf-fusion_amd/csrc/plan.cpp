@@ -117,6 +117,7 @@ Plan::~Plan() {
   if (pool_dev) (void)hipFree(pool_dev);
   if (regex_dev) (void)hipFree(regex_dev);
   if (str_consts_dev) (void)hipFree(str_consts_dev);
+  if (mark_values_dev) (void)hipFree(mark_values_dev);
 
   if (store && ctx) store->release_context(ctx);
   if (store) store->release();
@@ -155,7 +156,8 @@ const char* kernel_class_name(int kc) {
       "void rdfgpu::agg_accum_minmax_expr_kernel<false>", "void rdfgpu::agg_accum_minmax_expr_kernel<true>",
       "void rdfgpu::agg_minmax_refine_kernel",
       "rdfgpu::oj_probe_kernel(rdfgpu::OrderedJoinArgs, rdfgpu::OjBandFuse, rdfgpu::OjKeyValues)",
-      "rdfgpu::agg_groups_wide_kernel", "rdfgpu::agg_wide_keys_kernel"};
+      "rdfgpu::agg_groups_wide_kernel", "rdfgpu::agg_wide_keys_kernel",
+      "void rdfgpu::mark_join_kernel<0", "void rdfgpu::mark_join_kernel<1", "void rdfgpu::mark_nested_kernel"};
   if (kc < KC_LDS_JOIN0) return fixed[kc];
   static std::string names[192];
   static std::once_flag once;
@@ -443,8 +445,9 @@ DevTable Plan::exec_node(u32 idx) {
     case RDFGPU_NODE_FILTER: t = exec_filter(nd); break;
     case RDFGPU_NODE_PROJECTION: t = exec_projection(nd); break;
     case RDFGPU_NODE_HASH_JOIN: case RDFGPU_NODE_CROSS_JOIN: case RDFGPU_NODE_NESTED_LOOP_JOIN:
-      // semi / anti joins leave before anything of exec_join (chain planning, filter fusion, side choice) sees them
-      t = nd.d.join_type == RDFGPU_JOIN_LEFT_SEMI || nd.d.join_type == RDFGPU_JOIN_LEFT_ANTI ? exec_semi_join(nd) : exec_join(nd);
+      // semi / anti / mark joins leave before anything of exec_join (chain planning, filter fusion, side choice) sees them
+      t = nd.d.join_type == RDFGPU_JOIN_LEFT_SEMI || nd.d.join_type == RDFGPU_JOIN_LEFT_ANTI ? exec_semi_join(nd)
+        : nd.d.join_type == RDFGPU_JOIN_LEFT_MARK ? exec_mark_join(nd) : exec_join(nd);
       break;
     case RDFGPU_NODE_TOPK: t = exec_topk(nd); break;
     case RDFGPU_NODE_AGGREGATE: t = exec_aggregate(nd); break;

@@ -41,7 +41,8 @@ struct BandHistory {
 // Where an output column's values come from (RDFGPU_PLAN_AGG_COLUMNS): node < 0 = an object-id column; else the column holds 1-based
 // indexes into value array `agg` of `node` (0 = unbound) — aggregate `agg` of an AggregateExec, or expression `agg` of a ProjectionExec
 // with expressions (RDFGPU_NODE_EXTEND).  Fixed at compile, carried through every operator above.
-struct ValueOrigin { int node = -1; u32 agg = 0; bool extend = false; };   // extend: `node` is an EXTEND (for the refusals' texts)
+// The mark column of a LeftMark join (RDFGPU_JOIN_LEFT_MARK) is value array 0 of the join node: two records, false and true.
+struct ValueOrigin { int node = -1; u32 agg = 0; bool extend = false; bool mark = false; };   // extend / mark: `node` is an EXTEND / a LeftMark join (for the refusals' texts)
 
 struct NodeInfo {
   rdfgpu_plan_node d;
@@ -177,7 +178,8 @@ enum KernelClass {
   KC_AGG_MINMAX_REFINE,                                         // agg_minmax_refine_kernel: the low word of the decimal candidates
   KC_OJ_PROBE_VALUES,                                           // oj_probe_kernel(.., OjKeyValues): the probe pass of a step that reads the slice's rows through their cached windows
   KC_AGG_GROUPS_WIDE, KC_AGG_WIDE_KEYS,                         // agg_groups_wide_kernel / agg_wide_keys_kernel: the group pass over value keys or more than 4 keys (RDFGPU_PLAN_VALUE_KEYS), its key copy
-  KC_LDS_JOIN0,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
+  KC_MARK_JOIN0, KC_MARK_JOIN_END = KC_MARK_JOIN0 + 3,          // 3 names: mark_join_kernel<form 0 / 1>, mark_nested_kernel (mark_join_class): LeftMark joins (RDFGPU_JOIN_LEFT_MARK)
+  KC_LDS_JOIN0 = KC_MARK_JOIN_END,   // 192 names: lds_join_kernel<FS in {0..3}, PFS in {0,1,2}, ITEMS in {4,1}, MODE in {0,1,2,3}, CHAIN>
   KC__N = KC_LDS_JOIN0 + 192
 };
 const char* kernel_class_name(int kc);
@@ -189,6 +191,7 @@ inline int lds_join_class(u32 fs, u32 pfs, int items, int mode, bool chain = fal
 inline u32 agg_key_col(const rdfgpu_plan_node& d, u32 k) { return k < RDFGPU_MAX_KEYS ? d.left_keys[k] : d.right_keys[k - RDFGPU_MAX_KEYS]; }
 
 inline int semi_join_class(int form, bool anti) { return KC_SEMI_JOIN0 + form * 2 + (anti ? 1 : 0); }
+inline int mark_join_class(int form) { return KC_MARK_JOIN0 + form; }
 
 // The class of the accumulate pass that launch_agg_accum (aggregate.hip) launches for these arguments: the one place that maps
 // (minmax, exprs, lds) to a KernelClass.  The LEX kernels (a.exprs == 2: agg_accum_lex_kernel, agg_accum_minmax_lex_kernel) have no
@@ -235,6 +238,7 @@ struct Plan {
   u32* pool_dev = nullptr;        // same, on device
   RegexProg* regex_dev = nullptr; // compiled REGEX patterns of the plan (device)
   unsigned char* str_consts_dev = nullptr;   // bytes of the plan's string constants (RDFGPU_EX_LIT_STR)
+  rdfgpu_agg_value* mark_values_dev = nullptr;   // {boolean false, boolean true}: the value array of every LeftMark join's mark column (allocated by the first one that runs)
   std::vector<std::string> regex_strings; std::vector<rdfgpu_regex> regex_text;   // their texts (pattern, flags per entry)
   u32 root = 0;
   u64 run = 0;                    // counts the executions (a value array belongs to the one that wrote it)
@@ -308,6 +312,7 @@ struct Plan {
   DevTable exec_join(NodeInfo& nd);
   DevTable exec_topk(NodeInfo& nd);
   DevTable exec_semi_join(NodeInfo& nd);
+  DevTable exec_mark_join(NodeInfo& nd);
   DevTable exec_aggregate(NodeInfo& nd);   // its steps, in order (plan_aggregate.cpp):
   void agg_bind_inputs(AggNode& n); void agg_group_pass(AggNode& n); DevTable agg_outputs(AggNode& n); void agg_accumulate(AggNode& n); void agg_finish(AggNode& n);
   DevTable exec_extend(NodeInfo& nd);

@@ -65,6 +65,23 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
         if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
           fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST_LEX to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
         pop_bytes("CAST_LEX"); out = VK_TV; break;
+      // IF / COALESCE hand an operand on: a string literal given by rank among them still has no bytes where the result is read
+      case RDFGPU_EX_IF:
+        out_no_bytes = sp >= 2 && (no_bytes[sp - 1] || no_bytes[sp - 2]);
+        pop(VK_TV, "IF branch"); pop(VK_TV, "IF branch"); pop(VK_TV, "IF test (a typed value: BOOLEAN_AS_TERM(EBV(..)) for the EBV)"); out = VK_TV; break;
+      case RDFGPU_EX_COALESCE: {   // `u` operands of one kind, typed values or object ids
+        if (e.u < 1 || e.u > (u32)kMaxStack) fail(RDFGPU_ERR_INVALID, "expression: COALESCE takes 1 to %d operands, not %u", kMaxStack, e.u);
+        if ((u32)sp < e.u) fail(RDFGPU_ERR_INVALID, "expression: stack underflow at COALESCE");
+        const u32 kind = st[sp - 1] == VK_TV ? VK_TV : VK_ID;
+        for (u32 k = 0; k < e.u; k++) {
+          if (st[sp - 1] == VK_VALUE) pop(VK_ID, "COALESCE");   // (refused with the text of a value column read as an object id)
+          if (st[sp - 1] != kind) fail(RDFGPU_ERR_INVALID, "expression: COALESCE mixes operand kinds (all typed values or all object ids)");
+          out_no_bytes = out_no_bytes || no_bytes[sp - 1];
+          pop(kind, "COALESCE");
+        }
+        out = kind; break; }
+      case RDFGPU_EX_IS_IRI: case RDFGPU_EX_IS_BLANK: case RDFGPU_EX_IS_LITERAL: case RDFGPU_EX_IS_NUMERIC:
+        pop(VK_TV, "term test (isIRI / isBlank / isLiteral / isNumeric)"); out = VK_TV; break;
       case RDFGPU_EX_EBV: pop(VK_TV, "EBV"); out = VK_BOOL; break;
       case RDFGPU_EX_REGEX: case RDFGPU_EX_CONTAINS: case RDFGPU_EX_STRSTARTS: case RDFGPU_EX_STRENDS:
         if (e.u >= n_regexes) fail(RDFGPU_ERR_INVALID, "expression: REGEX pattern %u out of range (%u patterns)", e.u, n_regexes);
@@ -105,10 +122,10 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
   return st[0];
 }
 
-// A program with a value load, a lexical cast or a date part in it runs in the generic VM: the specialised forms gather from the typed-value
-// table by object id and know the ops of their shape only.
+// A program with a value load, a lexical cast, a date part, a functional form (IF / COALESCE) or a term test in it runs in the generic VM:
+// the specialised forms gather from the typed-value table by object id and know the ops of their shape only.
 bool needs_generic_vm(const ExprProgram& pr) {
-  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue || pr.nodes[i].op == RDFGPU_EX_CAST_STRING || pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op)) return true;
+  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue || pr.nodes[i].op == RDFGPU_EX_CAST_STRING || pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op) || is_form_op(pr.nodes[i].op)) return true;
   return false;
 }
 
@@ -195,6 +212,8 @@ void load_projection(NodeInfo& nd, const rdfgpu_plan_desc* d, const InputSchema&
 
 // The operators that compare, sort, chain or decode ids refuse a value column: equal values have different indexes.
 void refuse_value_column(const ValueOrigin& o, u32 node, const char* role, u32 column) {
+  if (o.node >= 0 && o.mark)
+    fail(RDFGPU_ERR_UNSUPPORTED, "node %u: %s column %u is a mark column (of the LeftMark join, node %d): its entries index values (1 = false, 2 = true), they are not object ids", node, role, column, o.node);
   if (o.node >= 0 && o.extend)
     fail(RDFGPU_ERR_UNSUPPORTED, "node %u: %s column %u is a computed value column (expression %u of the ProjectionExec with expressions, node %d): its entries index values, equal values have different indexes", node, role, column, o.agg, o.node);
   if (o.node >= 0)
@@ -295,7 +314,9 @@ void compile_join(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   const NodeInfo& l = child(plan, i, r.left, "left");
   const NodeInfo& rr = child(plan, i, r.right, "right");
   const bool semi = r.join_type == RDFGPU_JOIN_LEFT_SEMI || r.join_type == RDFGPU_JOIN_LEFT_ANTI;
-  if (r.join_type != RDFGPU_JOIN_INNER && r.join_type != RDFGPU_JOIN_LEFT && !semi) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: join type %u", i, r.join_type);
+  const bool mark = r.join_type == RDFGPU_JOIN_LEFT_MARK && r.kind != RDFGPU_NODE_CROSS_JOIN;
+  if (r.join_type != RDFGPU_JOIN_INNER && r.join_type != RDFGPU_JOIN_LEFT && !semi && r.join_type != RDFGPU_JOIN_LEFT_MARK) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: join type %u", i, r.join_type);
+  if (mark && !plan->agg_columns) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: a LeftMark join outputs its mark as a value column, which is not an object id: the plan must be compiled with RDFGPU_PLAN_AGG_COLUMNS", i);
   if (r.kind == RDFGPU_NODE_HASH_JOIN) {
     if (r.n_keys == 0 || r.n_keys > RDFGPU_MAX_KEYS) fail(RDFGPU_ERR_INVALID, "node %u: HashJoinExec needs 1..%u keys", i, RDFGPU_MAX_KEYS);
     for (u32 k = 0; k < r.n_keys; k++) {
@@ -310,7 +331,13 @@ void compile_join(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   both.append(l); both.append(rr); left.append(l);
   load_program(nd, d, both, "join filter", plan->regex_dev, plan->str_consts_dev);
   // a semi / anti join outputs the left columns only: its projection indexes them (the filter still sees both sides)
-  load_projection(nd, d, semi ? left : both, "join");
+  // .. and a mark join the left columns and the mark: a value column whose origin is this node
+  if (mark) {
+    if (left.n >= 2u * kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
+    left.origin[left.n] = ValueOrigin{(int)i, 0, false, true};
+    left.n++;
+  }
+  load_projection(nd, d, semi || mark ? left : both, "join");
   nd.shape = detect_join_filter_shape(nd.prog, plan->opt.on(RDFGPU_OPT_FORCE_GENERIC_VM));
   if (l.width > (u32)kMaxCols || rr.width > (u32)kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
 }

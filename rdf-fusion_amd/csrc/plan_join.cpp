@@ -307,6 +307,87 @@ DevTable Plan::exec_semi_join(NodeInfo& nd) {
   return t;
 }
 
+// HashJoinExec / NestedLoopJoinExec with JoinType::LeftMark (semi_join.hip: mark_join_kernel, mark_nested_kernel).  The output is the left
+// input row for row — same capacity, same count, also when that count is known on the device only — with the mark as one further column:
+// a value column of this node whose array is the plan's two records {false, true}.  Tables and their choice are the semi join's.
+DevTable Plan::exec_mark_join(NodeInfo& nd) {
+  const DevTable L = exec_sub_plan((u32)nd.d.left);
+  const DevTable R = exec_sub_plan((u32)nd.d.right);
+  flush_pending_oj();
+  if (!mark_values_dev) {   // once per plan
+    rdfgpu_agg_value two[2] = {};
+    two[0].tag = two[1].tag = RDFGPU_TV_BOOLEAN; two[1].lo = 1;
+    RDFGPU_HIP(hipMalloc((void**)&mark_values_dev, sizeof two));
+    RDFGPU_HIP(hipMemcpyAsync(mark_values_dev, two, sizeof two, hipMemcpyHostToDevice, stream));
+    RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;   // `two` is a stack variable
+  }
+  nd.values[0] = mark_values_dev; nd.n_values = 2; nd.n_values_dev = nullptr; nd.values_run = run;
+  DevTable t;
+  t.n_cols = nd.n_proj; t.cap = L.cap; t.n_dev = L.n_dev;
+  if (L.cap == 0) return t;
+  const u32 mark_col = L.n_cols;
+  const bool hash = nd.d.kind == RDFGPU_NODE_HASH_JOIN;
+  // the mark is the same for every left row when the right input is empty (false), or for a nested-loop join without a filter over a
+  // right input whose row count the host knows (true): the left columns as they are, the mark filled in, no join kernel
+  const bool right_empty = R.cap == 0;
+  if (right_empty || (!hash && nd.prog.n == 0 && R.n_dev == nullptr)) {
+    for (u32 c = 0; c < nd.n_proj; c++) {
+      if (nd.proj[c] != mark_col) { t.cols[c] = L.cols[nd.proj[c]]; continue; }
+      u32* m = scratch<u32>(L.cap);
+      launch_fill_u32(m, right_empty ? 1u : 2u, L.cap, stream);
+      t.cols[c] = m;
+    }
+    return t;
+  }
+  if (L.cap >= 0xFFFFFFF0ull || R.cap >= 0x7FFFFFFFull) fail(RDFGPU_ERR_UNSUPPORTED, "semi / anti join of %llu x %llu rows", (unsigned long long)L.cap, (unsigned long long)R.cap);
+  SemiJoinArgs a{};
+  for (u32 c = 0; c < L.n_cols; c++) a.cols[c] = L.cols[c];
+  for (u32 c = 0; c < R.n_cols; c++) a.cols[L.n_cols + c] = R.cols[c];
+  a.n_left_cols = L.n_cols; a.n_right_cols = R.n_cols;
+  a.n_out_cols = nd.n_proj;
+  for (u32 c = 0; c < nd.n_proj; c++) { a.proj[c] = nd.proj[c]; a.out[c] = scratch<u32>(L.cap); t.cols[c] = a.out[c]; }
+  a.n_keys = hash ? nd.d.n_keys : 0;
+  for (u32 k = 0; k < a.n_keys; k++) { a.left_key[k] = L.cols[nd.d.left_keys[k]]; a.right_key[k] = R.cols[nd.d.right_keys[k]]; }
+  a.n_left_dev = L.n_dev; a.n_left_cap = L.cap; a.n_right_dev = R.n_dev; a.n_right_cap = R.cap;
+  a.tt = typed_table();
+  int filter = kSemiNoFilter;
+  u32 left_fcols = 0;   // distinct left columns the filter reads (compulsory bytes)
+  if (nd.prog.n) {
+    left_fcols = (u32)__builtin_popcount(columns_read(nd.prog) & ((1u << L.n_cols) - 1u));
+    if (nd.shape == 2) {   // `col <ID_EQ | ID_NEQ> col`
+      filter = kSemiIdPair;
+      a.idp = IdPairFilter{nd.prog.nodes[0].u, nd.prog.nodes[1].u, nd.prog.nodes[2].op == RDFGPU_EX_ID_EQ ? 1u : 0u};
+    } else {
+      filter = nd.lex ? kSemiVmLex : kSemiVm;
+      a.prog = upload_program(nd.prog);
+    }
+  }
+  int form = kSemiNested;
+  u64 build_bytes = 0;
+  if (hash) {   // (the rule of exec_semi_join)
+    const u64 lds_max = std::min<u64>(opt.v[RDFGPU_OPT_LDS_MAX_BUILD], kSemiLdsMaxBuild);
+    form = R.cap <= lds_max && !opt.on(RDFGPU_OPT_NO_SEMI_LDS) ? kSemiLds : kSemiHbm;
+    u64 slots = 64;
+    while (slots < 2 * R.cap) slots <<= 1;
+    a.tbl_mask = (u32)(slots - 1);
+    build_bytes = (4ull * a.n_keys + 8) * R.cap;
+    if (form == kSemiHbm) {
+      a.gslots = scratch<unsigned long long>(slots);
+      RDFGPU_HIP(hipMemsetAsync(a.gslots, 0, slots * sizeof(unsigned long long), stream));
+      timed(KC_SEMI_BUILD, 0, R.cap, R.n_dev, 4ull * a.n_keys + 8, nullptr, 0, 0, [&] { launch_semi_build(a, filter == kSemiNoFilter, stream); });
+      build_bytes = 0;
+    }
+  } else {
+    build_bytes = 4ull * R.n_cols * R.cap;
+  }
+  // compulsory bytes: per left row its keys and filter columns, its projected columns read and every output column written; the build's
+  u32 left_out = 0;
+  for (u32 c = 0; c < nd.n_proj; c++) left_out += nd.proj[c] != mark_col;
+  timed(mark_join_class(form), build_bytes, L.cap, L.n_dev, 4ull * (a.n_keys + left_fcols + left_out + nd.n_proj), nullptr, 0, 0,
+        [&] { launch_mark_join(a, form, filter, stream); });
+  return t;
+}
+
 // Which input the hash join builds on.  A left join must build on the preserved (left) side.  An inner join builds
 // on the smaller input — unless exactly one input is a pure slice of the store (the same rows on every execution
 // until the store changes) and the other one is no larger: the slice's join table (direct-address / CSR / hash) is

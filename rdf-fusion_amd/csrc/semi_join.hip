@@ -185,6 +185,69 @@ __global__ __launch_bounds__(kSemiBlock) void semi_nested_kernel(const SemiJoinA
   }
 }
 
+// ---- JoinType::LeftMark (RDFGPU_JOIN_LEFT_MARK): EXISTS as an operand ----
+// Every left row comes out once, at its own index, with one further column: the mark, 1 + "the row has a partner" (an index into the
+// node's two-record value array: 1 = false, 2 = true).  Same tables, same probe, same filter as the semi join — but nothing is compacted
+// and nothing reserved: a lane settles its row's bit and stores the row.  SemiJoinArgs::proj indexes [left cols, mark]: entry
+// n_left_cols is the mark.
+__device__ __forceinline__ void mark_store(const SemiJoinArgs& a, u64 j, bool bit) {
+  for (u32 c = 0; c < a.n_out_cols; c++) a.out[c][j] = a.proj[c] == a.n_left_cols ? 1u + (u32)bit : a.cols[a.proj[c]][j];
+}
+
+// Hash forms (FORM as for semi_join_kernel).
+template <int FORM, int FK, bool ONE>
+__global__ __launch_bounds__(kSemiBlock) void mark_join_kernel(const SemiJoinArgs a) {
+  extern __shared__ unsigned long long lds_tbl[];
+  const u32 tid = threadIdx.x;
+  const u64 nl = live_rows(a.n_left_dev, a.n_left_cap);
+  const unsigned long long* tbl = a.gslots;
+  if constexpr (FORM == kSemiLds) {
+    const u64 nr = live_rows(a.n_right_dev, a.n_right_cap);
+    for (u32 s = tid; s <= a.tbl_mask; s += kSemiBlock) lds_tbl[s] = 0ull;
+    __syncthreads();
+    for (u64 r = tid; r < nr; r += kSemiBlock) {
+      Keys k;
+      if (load_keys(a.right_key, ONE ? 1u : a.n_keys, r, k)) semi_insert<ONE, FK == kSemiNoFilter>(a, lds_tbl, k, r);
+    }
+    __syncthreads();
+    tbl = lds_tbl;
+  }
+  for (u64 j = (u64)blockIdx.x * kSemiBlock + tid; j < nl; j += (u64)gridDim.x * kSemiBlock) mark_store(a, j, semi_probe<ONE, FK>(a, tbl, j));
+}
+
+// NestedLoopJoinExec.  Without a filter the mark is the same for every row: does the right input have a row?
+template <int FK>
+__global__ __launch_bounds__(kSemiBlock) void mark_nested_kernel(const SemiJoinArgs a) {
+  __shared__ u32 rt[kMaxCols * kNljTile];   // right rows r0 .. r0 + kNljTile, column-major
+  const u32 tid = threadIdx.x;
+  const u64 nl = live_rows(a.n_left_dev, a.n_left_cap), nr = live_rows(a.n_right_dev, a.n_right_cap);
+  const u64 n_tiles = (nl + kSemiBlock - 1) / kSemiBlock;
+  for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const u64 row = tile * kSemiBlock + tid;
+    const bool valid = row < nl;
+    bool matched = false;
+    if constexpr (FK == kSemiNoFilter) {
+      matched = nr > 0;
+    } else {
+      bool decided = !valid;
+      for (u64 r0 = 0; r0 < nr; r0 += kNljTile) {
+        const u32 cnt = (u32)(nr - r0 < kNljTile ? nr - r0 : kNljTile);
+        for (u32 i = tid; i < a.n_right_cols * kNljTile; i += kSemiBlock) {
+          const u32 c = i / kNljTile, t = i % kNljTile;
+          if (t < cnt) rt[i] = a.cols[a.n_left_cols + c][r0 + t];
+        }
+        __syncthreads();
+        for (u32 t = 0; t < cnt; t++) {
+          if (__ballot(!decided) == 0ull) break;   // every lane of the wave knows its answer
+          if (!decided && semi_filter<FK>(a, row, [&](u32 c) { return rt[c * kNljTile + t]; })) decided = matched = true;
+        }
+        if (!__syncthreads_or(!decided)) break;   // (also the barrier before the tile is overwritten)
+      }
+    }
+    if (valid) mark_store(a, row, matched);
+  }
+}
+
 size_t semi_join_lds_bytes(const SemiJoinArgs& a, int form) {
   return form == kSemiLds ? (size_t)(a.tbl_mask + 1) * sizeof(unsigned long long) : 0;
 }
@@ -246,6 +309,46 @@ void launch_semi_join(const SemiJoinArgs& a, int form, bool anti, int filter, hi
   if (form < kSemiLds || form > kSemiNested) fail(RDFGPU_ERR_INVALID, "semi join: table form %d", form);
   if (form == kSemiLds && a.tbl_mask + 1 > 2 * kSemiLdsMaxBuild) fail(RDFGPU_ERR_INVALID, "semi join: LDS set of %u slots", a.tbl_mask + 1);
   if (anti) launch_anti<true>(a, form, filter, s); else launch_anti<false>(a, form, filter, s);
+  RDFGPU_HIP(hipGetLastError());
+}
+
+template <int FORM, int FK, bool ONE>
+static void launch_mark_hash_form(const SemiJoinArgs& a, hipStream_t s) {
+  const size_t lds = semi_join_lds_bytes(a, FORM);
+  if constexpr (FORM == kSemiLds) {   // more than 64 KiB of dynamic LDS has to be allowed per kernel
+    static std::once_flag attr_once;
+    std::call_once(attr_once, [] {
+      RDFGPU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mark_join_kernel<FORM, FK, ONE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(2 * kSemiLdsMaxBuild * sizeof(unsigned long long) + 1024)));
+    });
+  }
+  u64 g = (a.n_left_cap + kSemiTile - 1) / kSemiTile;   // kSemiItems rows per lane, as in the semi join; the LDS form builds the set per workgroup
+  const u64 max_g = FORM == kSemiLds ? 1024 : 16384;
+  if (g > max_g) g = max_g;
+  hipLaunchKernelGGL((mark_join_kernel<FORM, FK, ONE>), dim3((unsigned)(g ? g : 1)), dim3(kSemiBlock), lds, s, a);
+}
+
+template <int FK>
+static void launch_mark_form(const SemiJoinArgs& a, int form, hipStream_t s) {
+  const bool one = a.n_keys == 1;
+  if (form == kSemiLds) { if (one) launch_mark_hash_form<kSemiLds, FK, true>(a, s); else launch_mark_hash_form<kSemiLds, FK, false>(a, s); }
+  else if (form == kSemiHbm) { if (one) launch_mark_hash_form<kSemiHbm, FK, true>(a, s); else launch_mark_hash_form<kSemiHbm, FK, false>(a, s); }
+  else {
+    u64 g = (a.n_left_cap + kSemiBlock - 1) / kSemiBlock;
+    if (g > 16384) g = 16384;
+    hipLaunchKernelGGL((mark_nested_kernel<FK>), dim3((unsigned)(g ? g : 1)), dim3(kSemiBlock), 0, s, a);
+  }
+}
+
+// The HBM set of a mark join is built by launch_semi_build, like a semi join's.
+void launch_mark_join(const SemiJoinArgs& a, int form, int filter, hipStream_t s) {
+  if (form < kSemiLds || form > kSemiNested) fail(RDFGPU_ERR_INVALID, "mark join: table form %d", form);
+  if (form == kSemiLds && a.tbl_mask + 1 > 2 * kSemiLdsMaxBuild) fail(RDFGPU_ERR_INVALID, "mark join: LDS set of %u slots", a.tbl_mask + 1);
+  for (u32 c = 0; c < a.n_out_cols; c++) if (a.proj[c] > a.n_left_cols) fail(RDFGPU_ERR_INVALID, "mark join: output column %u of [%u left columns, mark]", a.proj[c], a.n_left_cols);
+  if (filter == kSemiNoFilter) launch_mark_form<kSemiNoFilter>(a, form, s);
+  else if (filter == kSemiIdPair) launch_mark_form<kSemiIdPair>(a, form, s);
+  else if (filter == kSemiVmLex) launch_mark_form<kSemiVmLex>(a, form, s);
+  else launch_mark_form<kSemiVm>(a, form, s);
   RDFGPU_HIP(hipGetLastError());
 }
 

@@ -333,6 +333,55 @@ def LANGMATCHES_LANG(e, language_range, language_tags):
         raise ValueError("language_tags[0] is the empty tag")
     verdicts = bytes(1 if lang_matches(t, language_range) else 0 for t in language_tags)
     return Expr(e.nodes + [(abi.EX_LANG_IN, 0, 0, (verdicts, b"", abi.EX_LANG_IN), 0, 0)])
+
+
+def LANG_EQUALS(e, tag, language_tags):
+    """LANG(value) = "tag" — scalar/terms/lang.rs:49-55 under `=`: the same op as LANGMATCHES_LANG with a table that is 1 exactly for the
+    language ids whose tag IS `tag` (byte for byte: `=` on simple literals).  A literal without a language has the tag "" (id 0); IRIs,
+    blank nodes and the null value are the error value.  `language_tags` as for LANGMATCHES_LANG."""
+    if not language_tags or language_tags[0] != "":
+        raise ValueError("language_tags[0] is the empty tag")
+    verdicts = bytes(1 if t == tag else 0 for t in language_tags)
+    return Expr(e.nodes + [(abi.EX_LANG_IN, 0, 0, (verdicts, b"", abi.EX_LANG_IN), 0, 0)])
+
+
+# Functional forms and term tests (include/rdfgpu.h, ABI 4 addendum).  Every operand is evaluated for every row, as in the reference.
+def IF(test, a, b):
+    """IF(test, a, b) — scalar/functional_form/sparql_if.rs: `test` is a typed value that must be an xsd:boolean (Boolean::try_from, not the
+    EBV: write BOOLEAN_AS_TERM(EBV(x)) for that); anything else is the error value.  The chosen branch comes out unchanged."""
+    return Expr(test.nodes + a.nodes + b.nodes + [(abi.EX_IF, 0, 0, 0, 0, 0)])
+
+
+def COALESCE(*es):
+    """COALESCE(e1, ..) — DataFusion's `coalesce` (lib/functions/src/registry.rs:264-270): the first operand that is not the error value
+    (typed values) or not 0 (object ids); 1 to abi.MAX_STACK operands, all typed values or all object ids."""
+    if not 1 <= len(es) <= abi.MAX_STACK:
+        raise ValueError(f"COALESCE takes 1 to {abi.MAX_STACK} operands")
+    return Expr([n for e in es for n in e.nodes] + [(abi.EX_COALESCE, 0, 0, len(es), 0, 0)])
+
+
+def IS_IRI(e): return e._un(abi.EX_IS_IRI)
+def IS_BLANK(e): return e._un(abi.EX_IS_BLANK)
+def IS_LITERAL(e): return e._un(abi.EX_IS_LITERAL)
+def IS_NUMERIC(e): return e._un(abi.EX_IS_NUMERIC)
+
+
+def IN(lhs, es):
+    """lhs IN (e1, ..) — expression_rewriter.rs:302-322 (rewrite_in): BOOLEAN_AS_TERM of the OR chain of EBV(EQ(lhs, e_i)), left to right;
+    the empty list is BOOLEAN_AS_TERM(false).  A typed value (boolean, or the error value where no member is equal and one comparison
+    is an error)."""
+    chain = None
+    for e in es:
+        t = EBV(EQ(lhs, e))
+        chain = t if chain is None else OR(chain, t)
+    return BOOLEAN_AS_TERM(lit_bool(False) if chain is None else chain)
+
+
+def NOT_IN(lhs, es):
+    """lhs NOT IN (e1, ..): BOOLEAN_AS_TERM(NOT(EBV(IN(lhs, es))))."""
+    return BOOLEAN_AS_TERM(NOT(EBV(IN(lhs, es))))
+
+
 def ID_EQ(a, b): return a._bin(b, abi.EX_ID_EQ)
 def ID_NEQ(a, b): return a._bin(b, abi.EX_ID_NEQ)
 def AND(a, b): return a._bin(b, abi.EX_AND)
@@ -453,7 +502,9 @@ class PlanBuilder:
             return [full[c] for c in kept] + [True] * node.table_cols
         full = list(self.values[node.left])
         binary = node.kind in (abi.NODE_HASH_JOIN, abi.NODE_CROSS_JOIN, abi.NODE_NESTED_LOOP_JOIN)
-        if binary and node.join_type not in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI):
+        if binary and node.join_type == abi.JOIN_LEFT_MARK and node.kind != abi.NODE_CROSS_JOIN:
+            full += [True]                      # [left cols, mark]: the mark is a value column of the join's own
+        elif binary and node.join_type not in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI):
             full += self.values[node.right]
         if node.n_proj == abi.NO_PROJECTION:
             return full[:width] + [False] * (width - len(full))
@@ -486,9 +537,12 @@ class PlanBuilder:
         return self._push(n, self._proj(n, columns, self.width[child]), self._projected(self.names[child], columns) if names is None else names)
 
     def _join_output(self, left, right, join_type):
-        """Columns a join outputs before its projection: [left, right], or the left ones only for LeftSemi / LeftAnti."""
+        """Columns a join outputs before its projection: [left, right], the left ones only for LeftSemi / LeftAnti, or the left ones and
+        the mark for LeftMark."""
         if join_type in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI):
             return self.width[left], self.names[left]
+        if join_type == abi.JOIN_LEFT_MARK:
+            return self.width[left] + 1, self.names[left] + ["mark"]
         return self.width[left] + self.width[right], self.names[left] + self.names[right]
 
     def hash_join(self, left, right, on, join_type=abi.JOIN_INNER, filter=None, projection=None):
@@ -682,10 +736,10 @@ class PlanBuilder:
         return self.hash_join(left, right, on, join_type=join_type, filter=filter, projection=keep)
 
     # -- EXISTS / NOT EXISTS / MINUS lowering -----------------------------------------------------
-    def _semi_anti(self, left, right, anti, nullable, minus):
+    def _semi_anti(self, left, right, anti, nullable, minus, mark=False):
         ln, rn = self.names[left], self.names[right]
         shared = sorted(v for v in ln if v in rn)
-        jt = abi.JOIN_LEFT_ANTI if anti else abi.JOIN_LEFT_SEMI
+        jt = abi.JOIN_LEFT_MARK if mark else abi.JOIN_LEFT_ANTI if anti else abi.JOIN_LEFT_SEMI
         if not any(v in nullable for v in shared):
             on = [(ln.index(v), rn.index(v)) for v in shared]
             return self.hash_join(left, right, on, join_type=jt)
@@ -715,6 +769,16 @@ class PlanBuilder:
             return self.nested_loop_join(outer, inner, abi.JOIN_LEFT_ANTI if negate else abi.JOIN_LEFT_SEMI)
         return self._semi_anti(outer, inner, negate, set(nullable), minus=False)
 
+    def sparql_exists_value(self, outer, inner, nullable=()):
+        """EXISTS { inner } as an OPERAND (`FILTER(?p > 10 || EXISTS {..})`, `BIND(IF(EXISTS {..}, ..))`): the same correlated subquery,
+        which DataFusion decorrelates into a LeftMark join wherever EXISTS is not a conjunct of its own.  The lowering of sparql_exists —
+        the same keys, the same IS_COMPATIBLE filter for nullable shared variables — with abi.JOIN_LEFT_MARK: `outer`'s columns, every
+        row once and in order, followed by the mark, a boolean value column (`ENC_TV(col(mark))` reads it; NOT EXISTS is
+        `NOT(EBV(ENC_TV(col(mark))))`).  The description must be built with agg_columns=True."""
+        if not any(v in self.names[inner] for v in self.names[outer]):
+            return self.nested_loop_join(outer, inner, abi.JOIN_LEFT_MARK)
+        return self._semi_anti(outer, inner, False, set(nullable), minus=False, mark=True)
+
     def sparql_minus(self, left, right, nullable=()):
         """left MINUS right (lib/logical/src/minus/rewrite.rs:58-130): a LeftAnti join.  No shared variable: `left` unchanged
         (:62-64).  Shared variables all non-nullable: anti join on them.  Otherwise a NestedLoopJoinExec whose filter is the AND
@@ -731,10 +795,13 @@ class PlanBuilder:
 # ----------------------------------------------------------------------------------------------
 _BIN = {abi.EX_GT: "GT", abi.EX_LT: "LT", abi.EX_GEQ: "GEQ", abi.EX_LEQ: "LEQ", abi.EX_EQ: "EQ", abi.EX_ADD: "ADD", abi.EX_SUB: "SUB",
         abi.EX_IS_COMPATIBLE: "IS_COMPATIBLE", abi.EX_MUL: "MUL", abi.EX_DIV: "DIV"}
-_JOIN_TYPE_NAMES = {abi.JOIN_INNER: "Inner", abi.JOIN_LEFT: "Left", abi.JOIN_LEFT_SEMI: "LeftSemi", abi.JOIN_LEFT_ANTI: "LeftAnti"}
+_JOIN_TYPE_NAMES = {abi.JOIN_INNER: "Inner", abi.JOIN_LEFT: "Left", abi.JOIN_LEFT_SEMI: "LeftSemi", abi.JOIN_LEFT_ANTI: "LeftAnti",
+                    abi.JOIN_LEFT_MARK: "LeftMark"}
 _UN = {abi.EX_ENC_TV: "ENC_TV", abi.EX_EBV: "EBV", abi.EX_BOUND: "BOUND", abi.EX_BOOL_AS_TV: "BOOLEAN_AS_TERM",
        abi.EX_NEG: "MINUS", abi.EX_PLUS: "PLUS", abi.EX_ABS: "ABS", abi.EX_ROUND: "ROUND", abi.EX_CEIL: "CEIL", abi.EX_FLOOR: "FLOOR",
-       abi.EX_YEAR: "YEAR", abi.EX_MONTH: "MONTH", abi.EX_DAY: "DAY", abi.EX_HOURS: "HOURS", abi.EX_MINUTES: "MINUTES", abi.EX_SECONDS: "SECONDS"}
+       abi.EX_YEAR: "YEAR", abi.EX_MONTH: "MONTH", abi.EX_DAY: "DAY", abi.EX_HOURS: "HOURS", abi.EX_MINUTES: "MINUTES", abi.EX_SECONDS: "SECONDS",
+       # BuiltinName's spelling (lib/extensions/src/functions/builtin.rs:144-147)
+       abi.EX_IS_IRI: "isIRI", abi.EX_IS_BLANK: "isBLANK", abi.EX_IS_LITERAL: "isLITERAL", abi.EX_IS_NUMERIC: "isNUMERIC"}
 # BuiltinName::CastBoolean .. CastDouble as the reference's plans print them (`xsd:integer(..)`)
 _CAST = {abi.TV_BOOLEAN: "xsd:boolean", abi.TV_INT: "xsd:int", abi.TV_INTEGER: "xsd:integer", abi.TV_DECIMAL: "xsd:decimal",
          abi.TV_FLOAT: "xsd:float", abi.TV_DOUBLE: "xsd:double"}
@@ -784,6 +851,12 @@ def format_expr(nodes, names, at=True):
             st.append(f"{a} {({abi.EX_ID_EQ: '=', abi.EX_ID_NEQ: '!=', abi.EX_AND: 'AND', abi.EX_OR: 'OR'})[op]} {b}")
         elif op == abi.EX_NOT:
             st.append(f"NOT {st.pop()}")
+        elif op == abi.EX_IF:
+            c, b, a = st.pop(), st.pop(), st.pop()
+            st.append(f"IF({a}, {b}, {c})")
+        elif op == abi.EX_COALESCE:
+            args = [st.pop() for _ in range(u)][::-1]
+            st.append(f"COALESCE({', '.join(args)})")
         else:
             st.append(f"op{op}({st.pop()})")
     assert len(st) == 1
@@ -844,7 +917,8 @@ def explain(pb, root, choose_index=None, agg_columns=False):
                 both = ln + rn
                 fake = [abi.ExprNode(e.op, e.tag, e.flags, 0, renum[e.u] if e.op == abi.EX_COLUMN else e.u, e.lo, e.hi) for e in ex]
                 text += ", filter=" + format_expr(fake, [both[c] for c in used])
-            lines.append(f"{pad}{text}{proj(i, ln if n.join_type in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI) else ln + rn)}")
+            out = ln if n.join_type in (abi.JOIN_LEFT_SEMI, abi.JOIN_LEFT_ANTI) else ln + ["mark"] if n.join_type == abi.JOIN_LEFT_MARK else ln + rn
+            lines.append(f"{pad}{text}{proj(i, out)}")
             walk(n.left, depth + 1); walk(n.right, depth + 1)
             return
         if n.kind == abi.NODE_CROSS_JOIN:

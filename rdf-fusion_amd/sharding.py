@@ -173,6 +173,8 @@ def run_stages(stages, execute, repartition):
     for k, (desc, key_col) in enumerate(stages):
         if any(n.kind == abi.NODE_SORT for n in desc._nodes[:desc.desc.n_nodes]):
             raise ValueError(f"stage {k}: a SortExec (abi.NODE_SORT) in the sharded path: a rank sorts its own rows only, and the exchange keeps no order")
+        if any(n.kind in (abi.NODE_HASH_JOIN, abi.NODE_NESTED_LOOP_JOIN) and n.join_type == abi.JOIN_LEFT_MARK for n in desc._nodes[:desc.desc.n_nodes]):
+            raise ValueError(f"stage {k}: a LeftMark join (abi.JOIN_LEFT_MARK) in the sharded path: its mark is a value column, and the exchange carries object ids only")
         table = execute(desc, [] if table is None else [table])
         if key_col is not None:
             table = repartition(table, key_col)
