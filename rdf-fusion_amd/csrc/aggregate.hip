@@ -405,7 +405,7 @@ __device__ __forceinline__ void agg_accum_rows(const AggArgs& a) {
 
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_kernel(const AggArgs a) { agg_accum_rows<LDS, false>(a); }
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_expr_kernel(const AggArgs a) { agg_accum_rows<LDS, true>(a); }
-template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_lex_kernel(const AggArgs a) { agg_accum_rows<LDS, true, true>(a); }   // a.exprs == 2: a program holds RDFGPU_EX_CAST_LEX
+template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_lex_kernel(const AggArgs a) { agg_accum_rows<LDS, true, true>(a); }   // a.exprs == 2: a program holds an op with kOpExtended (expr_ops.hpp)
 
 // .. and with a MIN / MAX among the aggregates (a.minmax): kernels of their own, so that a node without one launches what it always did
 template <bool LDS> __global__ __launch_bounds__(kAggBlock) void agg_accum_minmax_kernel(const AggArgs a) { agg_accum_rows<LDS, false, false, true>(a); }

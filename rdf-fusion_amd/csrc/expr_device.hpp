@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/rdfgpu.h"
+#include "expr_ops.hpp"
 #include "regex_prog.hpp"
 #include "lex_parse.hpp"
 #include "date_parts.hpp"
@@ -64,13 +65,6 @@ struct TypedTable {
 // Value kinds on the evaluation stack.  VK_VALUE exists at compile only (check_program): COLUMN of an aggregate value column, whose u32 is
 // an index into its AggregateExec's value array and not an object id; on the device such a column is a VK_ID like any other.
 enum : uint32_t { VK_ID = 0, VK_TV = 1, VK_BOOL = 2, VK_VALUE = 3 };
-
-// Internal op (never accepted from a description: check_program knows RDFGPU_EX_* only).  plan_compile writes it in place of the ENC_TV of
-// an aggregate value column (RDFGPU_PLAN_AGG_COLUMNS): u = origin node << 8 | aggregate (of an AggregateExec) or expression (of a
-// ProjectionExec with expressions, RDFGPU_NODE_EXTEND); Plan::bind_values fills in, per execution, lo = the device address of that
-// rdfgpu_agg_value array and hi = its length.
-constexpr uint8_t kExAggValue = 250;
-static_assert(kExAggValue >= RDFGPU_EX__COUNT, "the internal op must lie outside the ABI's ops");
 
 struct Val {
   int64_t lo;     // ID: object id; TV: payload; BOOL: 0 false / 1 true / 2 null
@@ -781,17 +775,10 @@ __device__ __forceinline__ Val tv_term_test(const Val& a, uint32_t op) {
                    : op == RDFGPU_EX_IS_LITERAL ? !node : num_kind(a.tag) != NK_NONE);
 }
 
-// A program that holds RDFGPU_EX_CAST_LEX, a date part (RDFGPU_EX_YEAR .. RDFGPU_EX_SECONDS) or a functional form / term test
-// (RDFGPU_EX_IF .. RDFGPU_EX_IS_NUMERIC): its host launches the instantiation of its kernel that compiles those cases in (LEX = true).
-inline bool is_date_part_op(uint32_t op) { return op >= RDFGPU_EX_YEAR && op <= RDFGPU_EX_SECONDS; }
-inline bool is_form_op(uint32_t op) { return op >= RDFGPU_EX_IF && op <= RDFGPU_EX_IS_NUMERIC; }
-inline bool program_has_lex(const ExprProgram& pr) {
-  for (uint32_t i = 0; i < pr.n; i++) if (pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op) || is_form_op(pr.nodes[i].op)) return true;
-  return false;
-}
-// LEX: whether `case RDFGPU_EX_CAST_LEX` is compiled in.  The case — the byte resolution and the calls around the leaves — costs a hosting
-// kernel one or two registers, which moved kernels that sit on an occupancy step; so every host exists twice, and the instantiation
-// without the case is, register for register, the kernel it was before the op existed.  Plans pick by program_has_lex / NodeInfo::lex.
+// LEX: whether the extended cases (the ops with kOpExtended, expr_ops.hpp) are compiled in.  The first of them was `case
+// RDFGPU_EX_CAST_LEX`: the byte resolution and the calls around the leaves cost a hosting kernel one or two registers, which moved kernels
+// that sit on an occupancy step; so every host exists twice, and the instantiation without the cases is, register for register, the kernel
+// it was before the op existed.  Plans pick by program_has_lex / NodeInfo::lex.
 // The date parts (YEAR .. SECONDS) live in the same instantiations, for the same reason: their case, and the timezone offset that ENC_TV
 // then has to carry (enc_tv<true>), exist only where LEX is true.  So do IF, COALESCE and the term tests.  Their operands are all
 // evaluated before the op is reached (the program is postfix): eager, as in the reference, and a run-time refusal an operand raised stays

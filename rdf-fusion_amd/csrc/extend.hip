@@ -67,11 +67,11 @@ __device__ __forceinline__ void extend_rows(const ExtendArgs& a) {
   }
 }
 __global__ __launch_bounds__(kExtendBlock) void extend_kernel(const ExtendArgs a) { extend_rows<false>(a); }
-__global__ __launch_bounds__(kExtendBlock) void extend_lex_kernel(const ExtendArgs a) { extend_rows<true>(a); }   // RDFGPU_EX_CAST_LEX compiled into the VM
+__global__ __launch_bounds__(kExtendBlock) void extend_lex_kernel(const ExtendArgs a) { extend_rows<true>(a); }   // the extended cases (kOpExtended, expr_ops.hpp) compiled into the VM
 
 void launch_extend(const ExtendArgs& a, bool lex, hipStream_t s) {
   const u64 g = (a.cap + kExtendBlock - 1) / kExtendBlock;       // (cap < 2^32 - 1: Plan::exec_extend)
-  if (lex) hipLaunchKernelGGL(extend_lex_kernel, dim3((unsigned)(g ? g : 1)), dim3(kExtendBlock), 0, s, a);   // (a program holds RDFGPU_EX_CAST_LEX)
+  if (lex) hipLaunchKernelGGL(extend_lex_kernel, dim3((unsigned)(g ? g : 1)), dim3(kExtendBlock), 0, s, a);   // (a program holds an op with kOpExtended)
   else hipLaunchKernelGGL(extend_kernel, dim3((unsigned)(g ? g : 1)), dim3(kExtendBlock), 0, s, a);
   RDFGPU_HIP(hipGetLastError());
 }

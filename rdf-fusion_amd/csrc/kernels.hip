@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void filter_kernel(const FilterArgs a) {
   const u64 base = (u64)blockIdx.x * chunk;
   if (base >= nv) return;                           // uniform per workgroup
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr bool VM = SHAPE == 0 || SHAPE == kFilterVmLex;   // (kFilterVmLex: the generic VM with RDFGPU_EX_CAST_LEX compiled in)
+  constexpr bool VM = SHAPE == 0 || SHAPE == kFilterVmLex;   // (kFilterVmLex: the generic VM with the extended cases, kOpExtended, compiled in)
   const u32* pcol = !VM ? a.in[a.prog.nodes[0].u] : nullptr;
   unsigned long long bits = 0;
 #pragma unroll 2
@@ -861,7 +861,7 @@ __device__ __forceinline__ void join_probe_rows(const JoinArgs a) {
   }
 }
 
-// (.._lex_kernel: the same rows with RDFGPU_EX_CAST_LEX compiled into the filter's VM; launched for a program that holds the op)
+// (.._lex_kernel: the same rows with the extended cases, kOpExtended, compiled into the filter's VM; launched for a program that holds such an op)
 template <bool WRITE> __global__ __launch_bounds__(kBlock) void join_probe_kernel(const JoinArgs a) { join_probe_rows<WRITE, false>(a); }
 template <bool WRITE> __global__ __launch_bounds__(kBlock) void join_probe_lex_kernel(const JoinArgs a) { join_probe_rows<WRITE, true>(a); }
 

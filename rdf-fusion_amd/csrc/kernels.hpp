@@ -258,7 +258,7 @@ void preload_tu_join_fs3();
 // kernel), or, for NestedLoopJoinExec, staged tile by tile through LDS.  A left row survives when some right row equals it on every
 // key (NullEqualsNothing) and passes the join filter with exactly `true` (semi), or when none does (anti).
 enum SemiForm { kSemiLds = 0, kSemiHbm = 1, kSemiNested = 2 };
-enum SemiFilter { kSemiNoFilter = 0, kSemiVm = 1, kSemiIdPair = 2, kSemiVmLex = 3 };   // kSemiVmLex: the VM with RDFGPU_EX_CAST_LEX compiled in
+enum SemiFilter { kSemiNoFilter = 0, kSemiVm = 1, kSemiIdPair = 2, kSemiVmLex = 3 };   // kSemiVmLex: the VM with the extended cases (kOpExtended, expr_ops.hpp) compiled in
 constexpr u32 kSemiLdsMaxBuild = kLdsJoinMaxBuild;   // 16384 slots x 8 B = 128 KiB of LDS
 struct SemiJoinArgs {
   const u32* cols[2 * kMaxCols];   // [left cols, right cols]: what the join filter sees
@@ -327,7 +327,7 @@ struct AggArgs {
   const u32* in[RDFGPU_MAX_AGGREGATES];          // input column (COUNT_STAR and expression inputs: unused)
   const ExprProgram* prog[RDFGPU_MAX_AGGREGATES];   // SUM / AVG / MIN / MAX over an expression (RDFGPU_AGG_INPUT_EXPR): its program (device copy), else null
   const u32* col[kMaxCols];                      // .. the input's columns, which the programs read
-  u32 exprs;                                     // 1 = some aggregate has a program: pass 2 runs its VM instantiation; 2 = and one holds RDFGPU_EX_CAST_LEX
+  u32 exprs;                                     // 1 = some aggregate has a program: pass 2 runs its VM instantiation; 2 = and one holds an op with kOpExtended (expr_ops.hpp)
   u32 word0[RDFGPU_MAX_AGGREGATES];              // first accumulator word of each aggregate (word 0 = rows of the group)
   u32 n_words;
   u8 word_op[kAggMaxWords];                      // how each word is merged (AggWordOp)

@@ -51,7 +51,7 @@ struct NodeInfo {
   u32 n_proj = 0; u32 proj[kMaxCols] = {};
   ExprProgram prog{};             // filter / join filter
   int shape = 0;                  // filter kernel specialisation
-  bool lex = false;               // a program of the node holds RDFGPU_EX_CAST_LEX: its host runs the instantiation with the case compiled in
+  bool lex = false;               // a program of the node holds an op with kOpExtended (a lexical cast of a literal, a date part, IF, COALESCE, a term test): its host runs the instantiation with those cases compiled in
   u32 n_enc_tv = 0;               // ENC_TV gathers per row (algorithmic bytes)
   u32 n_cols_read = 0;            // distinct input columns the kernel has to read
   int source = -1;                // index into Plan::sources

@@ -10,17 +10,13 @@ namespace rdfgpu {
 
 namespace {
 
-bool is_cmp(u8 op) {
-  return op == RDFGPU_EX_GT || op == RDFGPU_EX_LT || op == RDFGPU_EX_GEQ || op == RDFGPU_EX_LEQ || op == RDFGPU_EX_EQ || op == RDFGPU_EX_NEQ;
-}
-
 // Type-checks a postfix program against `n_cols` input columns; returns the kind it leaves.  `value_cols`: bit c = input column c is an
 // aggregate value column (RDFGPU_PLAN_AGG_COLUMNS) — COLUMN of it is a VK_VALUE, which only ENC_TV and BOUND take: its u32 is an index, so
 // whatever compares or prints ids (ID_EQ, ID_NEQ, IS_COMPATIBLE, STR) would answer about the index.
 u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 0, u32 value_cols = 0) {
   if (n > (u32)kMaxExpr) fail(RDFGPU_ERR_UNSUPPORTED, "expression has %u nodes (max %d)", n, kMaxExpr);
   u32 st[kMaxStack]; bool no_bytes[kMaxStack]; int sp = 0;
-  bool views = false, rank_only_string = false;   // computed strings (views) / a string literal given by its rank in the dictionary only
+  bool views = false, rank_only_string = false;   // computed strings (an op with kOpView) / a string literal given by its rank in the dictionary only
   bool out_no_bytes = false;                      // the value being pushed is such a literal: it has no lexical form on the device
   auto pop = [&](u32 kind, const char* what) {
     if (sp < 1) fail(RDFGPU_ERR_INVALID, "expression: stack underflow at %s", what);
@@ -41,6 +37,12 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
     const rdfgpu_expr_node& e = p[i];
     u32 out;
     out_no_bytes = false;
+    if (op_is(e.op, kOpSlot) && e.u >= n_regexes) {   // a slot of the plan's string table: the text names what the op keeps there
+      const bool constant = e.op == RDFGPU_EX_LIT_STR, langs = e.op == RDFGPU_EX_LANG_IN;
+      fail(RDFGPU_ERR_INVALID, "expression: %s %u out of range (%u %s)", constant ? "string constant" : langs ? "language table" : "REGEX pattern", e.u, n_regexes,
+           constant ? "entries" : langs ? "tables" : "patterns");
+    }
+    views = views || op_is(e.op, kOpView);
     switch (e.op) {
       case RDFGPU_EX_COLUMN: if (e.u >= n_cols) fail(RDFGPU_ERR_INVALID, "expression: column %u out of range (%u columns)", e.u, n_cols);
         out = e.u < 32 && ((value_cols >> e.u) & 1u) ? VK_VALUE : VK_ID; break;
@@ -56,15 +58,13 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
         pop(VK_TV, "unary numeric op"); out = VK_TV; break;
       case RDFGPU_EX_YEAR: case RDFGPU_EX_MONTH: case RDFGPU_EX_DAY: case RDFGPU_EX_HOURS: case RDFGPU_EX_MINUTES: case RDFGPU_EX_SECONDS:
         pop(VK_TV, "date part (YEAR .. SECONDS)"); out = VK_TV; break;
-      case RDFGPU_EX_CAST:
-        if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
-          fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
-        pop(VK_TV, "CAST"); out = VK_TV; break;
-      case RDFGPU_EX_CAST_STRING: pop(VK_ID, "CAST_STRING (xsd:string)"); out = VK_TV; views = true; break;
-      case RDFGPU_EX_CAST_LEX:
-        if (e.u != RDFGPU_TV_BOOLEAN && e.u != RDFGPU_TV_INT && e.u != RDFGPU_TV_INTEGER && e.u != RDFGPU_TV_DECIMAL && e.u != RDFGPU_TV_FLOAT && e.u != RDFGPU_TV_DOUBLE)
-          fail(RDFGPU_ERR_UNSUPPORTED, "expression: CAST_LEX to tag %u (on the device: boolean, int, integer, decimal, float, double)", e.u);
-        pop_bytes("CAST_LEX"); out = VK_TV; break;
+      case RDFGPU_EX_CAST: case RDFGPU_EX_CAST_LEX: {   // CAST_LEX reads the bytes of a simple literal, CAST none
+        const bool lex = e.op == RDFGPU_EX_CAST_LEX;
+        const char* what = lex ? "CAST_LEX" : "CAST";
+        if (!is_cast_target(e.u)) fail(RDFGPU_ERR_UNSUPPORTED, "expression: %s to tag %u (on the device: boolean, int, integer, decimal, float, double)", what, e.u);
+        if (lex) pop_bytes(what); else pop(VK_TV, what);
+        out = VK_TV; break; }
+      case RDFGPU_EX_CAST_STRING: pop(VK_ID, "CAST_STRING (xsd:string)"); out = VK_TV; break;
       // IF / COALESCE hand an operand on: a string literal given by rank among them still has no bytes where the result is read
       case RDFGPU_EX_IF:
         out_no_bytes = sp >= 2 && (no_bytes[sp - 1] || no_bytes[sp - 2]);
@@ -84,27 +84,22 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
         pop(VK_TV, "term test (isIRI / isBlank / isLiteral / isNumeric)"); out = VK_TV; break;
       case RDFGPU_EX_EBV: pop(VK_TV, "EBV"); out = VK_BOOL; break;
       case RDFGPU_EX_REGEX: case RDFGPU_EX_CONTAINS: case RDFGPU_EX_STRSTARTS: case RDFGPU_EX_STRENDS:
-        if (e.u >= n_regexes) fail(RDFGPU_ERR_INVALID, "expression: REGEX pattern %u out of range (%u patterns)", e.u, n_regexes);
         // (the operand is any string value: ENC_TV of a column, or a view — STR / SUBSTR / UCASE / LCASE / a constant with bytes)
         pop_bytes("REGEX / CONTAINS / STRSTARTS / STRENDS"); out = VK_TV; break;
-      case RDFGPU_EX_STR: pop(VK_ID, "STR"); out = VK_TV; views = true; break;
-      case RDFGPU_EX_LIT_STR:
-        if (e.u >= n_regexes) fail(RDFGPU_ERR_INVALID, "expression: string constant %u out of range (%u entries)", e.u, n_regexes);
-        out = VK_TV; views = true; break;
+      case RDFGPU_EX_STR: pop(VK_ID, "STR"); out = VK_TV; break;
+      case RDFGPU_EX_LIT_STR: out = VK_TV; break;
       case RDFGPU_EX_STRLEN: pop_bytes("STRLEN"); out = VK_TV; break;
       case RDFGPU_EX_SUBSTR:
         if (e.u != 2 && e.u != 3) fail(RDFGPU_ERR_INVALID, "expression: SUBSTR takes 2 or 3 operands, not %u", e.u);
         for (u32 k = 0; k + 1 < e.u; k++) pop(VK_TV, "SUBSTR position / length");
         pop_bytes("SUBSTR");
-        out = VK_TV; views = true; break;
-      case RDFGPU_EX_UCASE: case RDFGPU_EX_LCASE: pop_bytes("UCASE / LCASE"); out = VK_TV; views = true; break;
-      case RDFGPU_EX_STRBEFORE: case RDFGPU_EX_STRAFTER: pop_bytes("STRBEFORE / STRAFTER"); pop_bytes("STRBEFORE / STRAFTER"); out = VK_TV; views = true; break;
+        out = VK_TV; break;
+      case RDFGPU_EX_UCASE: case RDFGPU_EX_LCASE: pop_bytes("UCASE / LCASE"); out = VK_TV; break;
+      case RDFGPU_EX_STRBEFORE: case RDFGPU_EX_STRAFTER: pop_bytes("STRBEFORE / STRAFTER"); pop_bytes("STRBEFORE / STRAFTER"); out = VK_TV; break;
       case RDFGPU_EX_REGEX_VAR:
         if (e.lo < 1 || (u64)e.u + (u64)e.lo > n_regexes) fail(RDFGPU_ERR_INVALID, "expression: REGEX pattern table %u .. +%lld out of range (%u patterns)", e.u, (long long)e.lo, n_regexes);
         pop(VK_TV, "REGEX pattern"); pop_bytes("REGEX"); out = VK_TV; break;
-      case RDFGPU_EX_LANG_IN:
-        if (e.u >= n_regexes) fail(RDFGPU_ERR_INVALID, "expression: language table %u out of range (%u tables)", e.u, n_regexes);
-        pop(VK_TV, "LANGMATCHES(LANG())"); out = VK_TV; break;
+      case RDFGPU_EX_LANG_IN: pop(VK_TV, "LANGMATCHES(LANG())"); out = VK_TV; break;
       case RDFGPU_EX_ID_EQ: case RDFGPU_EX_ID_NEQ: case RDFGPU_EX_IS_COMPATIBLE: pop(VK_ID, "id comparison"); pop(VK_ID, "id comparison"); out = VK_BOOL; break;
       case RDFGPU_EX_AND: case RDFGPU_EX_OR: pop(VK_BOOL, "AND/OR"); pop(VK_BOOL, "AND/OR"); out = VK_BOOL; break;
       case RDFGPU_EX_NOT: pop(VK_BOOL, "NOT"); out = VK_BOOL; break;
@@ -124,10 +119,7 @@ u32 check_program(const rdfgpu_expr_node* p, u32 n, u32 n_cols, u32 n_regexes = 
 
 // A program with a value load, a lexical cast, a date part, a functional form (IF / COALESCE) or a term test in it runs in the generic VM:
 // the specialised forms gather from the typed-value table by object id and know the ops of their shape only.
-bool needs_generic_vm(const ExprProgram& pr) {
-  for (u32 i = 0; i < pr.n; i++) if (pr.nodes[i].op == kExAggValue || pr.nodes[i].op == RDFGPU_EX_CAST_STRING || pr.nodes[i].op == RDFGPU_EX_CAST_LEX || is_date_part_op(pr.nodes[i].op) || is_form_op(pr.nodes[i].op)) return true;
-  return false;
-}
+bool needs_generic_vm(const ExprProgram& pr) { return program_has(pr, kOpGenericVm); }
 
 int detect_shape(const ExprProgram& pr, bool force_vm) {
   if (force_vm || needs_generic_vm(pr)) return 0;
@@ -176,18 +168,24 @@ void rewrite_value_loads(ExprProgram& pr, const InputSchema& in) {
   }
 }
 
-void load_program(NodeInfo& nd, const rdfgpu_plan_desc* d, const InputSchema& in, const char* what, const RegexProg* regex_dev, const unsigned char* str_consts = nullptr) {
-  const u32 n_cols = in.n;
+// `len` checked nodes as a program of the plan: the plan's string table attached, the ENC_TV of a value column made its value load.
+ExprProgram load_value_program(const Plan* plan, const InputSchema& in, const rdfgpu_expr_node* nodes, u32 len) {
+  ExprProgram pr{};
+  pr.n = len;
+  std::memcpy(pr.nodes, nodes, len * sizeof(rdfgpu_expr_node));
+  pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
+  rewrite_value_loads(pr, in);
+  return pr;
+}
+
+// The predicate of a FilterExec or a join (none: an empty program).
+void load_program(NodeInfo& nd, const Plan* plan, const rdfgpu_plan_desc* d, const InputSchema& in, const char* what) {
   const rdfgpu_plan_node& r = nd.d;
   nd.prog.n = 0;
   if (r.expr_len == 0) return;
   if ((u64)r.expr_off + r.expr_len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "%s: expression outside the expression array", what);
-  if (check_program(d->exprs + r.expr_off, r.expr_len, n_cols, d->n_regexes, in.value_cols()) != VK_BOOL) fail(RDFGPU_ERR_INVALID, "%s: predicate does not yield a boolean", what);
-  nd.prog.n = r.expr_len;
-  std::memcpy(nd.prog.nodes, d->exprs + r.expr_off, r.expr_len * sizeof(rdfgpu_expr_node));
-  nd.prog.regex = regex_dev;
-  nd.prog.str_consts = str_consts;
-  rewrite_value_loads(nd.prog, in);
+  if (check_program(d->exprs + r.expr_off, r.expr_len, in.n, d->n_regexes, in.value_cols()) != VK_BOOL) fail(RDFGPU_ERR_INVALID, "%s: predicate does not yield a boolean", what);
+  nd.prog = load_value_program(plan, in, d->exprs + r.expr_off, r.expr_len);
 }
 
 void load_projection(NodeInfo& nd, const rdfgpu_plan_desc* d, const InputSchema& in, const char* what) {
@@ -220,12 +218,8 @@ void refuse_value_column(const ValueOrigin& o, u32 node, const char* role, u32 c
     fail(RDFGPU_ERR_UNSUPPORTED, "node %u: %s column %u is an aggregate value column (aggregate %u of node %d): its entries index values, equal values have different indexes", node, role, column, o.agg, o.node);
 }
 
-// The plan's string table (REGEX patterns, needles, language sets, string constants): compiled by use, kept as texts, uploaded.
-void compile_string_table(Plan* plan, const rdfgpu_plan_desc* d) {
-  Store* store = plan->store;
-  if (!d->regexes) fail(RDFGPU_ERR_INVALID, "plan_compile: %u regexes but no table", d->n_regexes);
-  // how each table entry is used decides how it is compiled: REGEX = a pattern with flags; CONTAINS / STRSTARTS /
-  // STRENDS = a literal needle (like the `q` flag), anchored at the start / end for the latter two
+// The op that uses each entry of the plan's string table (-1: none): the use decides how the entry is compiled.
+std::vector<int> string_table_uses(const rdfgpu_plan_desc* d) {
   std::vector<int> use(d->n_regexes, -1);
   for (u32 i = 0; i < d->n_exprs; i++) {
     const rdfgpu_expr_node& e = d->exprs[i];
@@ -233,11 +227,33 @@ void compile_string_table(Plan* plan, const rdfgpu_plan_desc* d) {
       for (int64_t k = 0; k < e.lo && (u64)e.u + (u64)k < d->n_regexes; k++) use[e.u + k] = RDFGPU_EX_REGEX;
       continue;
     }
-    if (e.op != RDFGPU_EX_REGEX && e.op != RDFGPU_EX_CONTAINS && e.op != RDFGPU_EX_STRSTARTS && e.op != RDFGPU_EX_STRENDS && e.op != RDFGPU_EX_LANG_IN && e.op != RDFGPU_EX_LIT_STR) continue;
+    if (!op_is(e.op, kOpSlot)) continue;
     if (e.u >= d->n_regexes) fail(RDFGPU_ERR_INVALID, "expression: string pattern %u out of range", e.u);
     if (use[e.u] >= 0 && use[e.u] != (int)e.op) fail(RDFGPU_ERR_INVALID, "string pattern %u is used by two different functions", e.u);
     use[e.u] = (int)e.op;
   }
+  return use;
+}
+
+// Entry `r` as a matcher: REGEX (and an unused entry) = a pattern with its flags; CONTAINS / STRSTARTS / STRENDS = a literal needle (like
+// the `q` flag), anchored at the start / end for the latter two.
+void compile_pattern(u32 r, const rdfgpu_regex& rx, int use, RegexProg& prog) {
+  std::string why;
+  const bool literal = use >= 0 && op_is((u32)use, kOpNeedle);
+  const char* flags = literal ? "q" : (rx.flags ? rx.flags : "");
+  const size_t n_flags = literal ? 1 : (rx.flags ? rx.flags_len : 0);
+  if (regex_compile(rx.pattern ? rx.pattern : "", rx.pattern_len, flags, n_flags, prog, why) != REGEX_OK)
+    fail(RDFGPU_ERR_UNSUPPORTED, "string pattern %u: %s", r, why.c_str());
+  prog.pattern_id = rx.pattern_id;
+  if (use == RDFGPU_EX_STRSTARTS) prog.anchor_start = 1;
+  if (use == RDFGPU_EX_STRENDS) prog.anchor_end = 1;
+}
+
+// The plan's string table (REGEX patterns, needles, language sets, string constants): compiled by use, kept as texts, uploaded.
+void compile_string_table(Plan* plan, const rdfgpu_plan_desc* d) {
+  Store* store = plan->store;
+  if (!d->regexes) fail(RDFGPU_ERR_INVALID, "plan_compile: %u regexes but no table", d->n_regexes);
+  const std::vector<int> use = string_table_uses(d);
   std::vector<RegexProg> progs(d->n_regexes);
   std::vector<unsigned char> consts;   // the bytes of the string constants (RDFGPU_EX_LIT_STR), back to back
   for (u32 r = 0; r < d->n_regexes; r++) {
@@ -257,15 +273,7 @@ void compile_string_table(Plan* plan, const rdfgpu_plan_desc* d) {
       continue;
     }
     if (use[r] >= 0 && !store->str_off) fail(RDFGPU_ERR_INVALID, "plan uses string functions but the store has no strings (rdfgpu_store_set_strings)");
-    std::string why;
-    const bool literal = use[r] == RDFGPU_EX_CONTAINS || use[r] == RDFGPU_EX_STRSTARTS || use[r] == RDFGPU_EX_STRENDS;
-    const char* flags = literal ? "q" : (rx.flags ? rx.flags : "");
-    const size_t n_flags = literal ? 1 : (rx.flags ? rx.flags_len : 0);
-    if (regex_compile(rx.pattern ? rx.pattern : "", rx.pattern_len, flags, n_flags, progs[r], why) != REGEX_OK)
-      fail(RDFGPU_ERR_UNSUPPORTED, "string pattern %u: %s", r, why.c_str());
-    progs[r].pattern_id = rx.pattern_id;
-    if (use[r] == RDFGPU_EX_STRSTARTS) progs[r].anchor_start = 1;
-    if (use[r] == RDFGPU_EX_STRENDS) progs[r].anchor_end = 1;
+    compile_pattern(r, rx, use[r], progs[r]);
   }
   for (u32 r = 0; r < d->n_regexes; r++) {   // own copies of the texts: they key the store's per-term verdict tables
     const rdfgpu_regex& rx = d->regexes[r];
@@ -292,9 +300,7 @@ void compile_string_table(Plan* plan, const rdfgpu_plan_desc* d) {
 // String functions that need no table entry still need the store's strings.
 void check_string_functions(const Store* store, const rdfgpu_plan_desc* d) {
   for (u32 i = 0; i < d->n_exprs; i++) {
-    const u8 op = d->exprs[i].op;
-    if ((op == RDFGPU_EX_STR || op == RDFGPU_EX_STRLEN || op == RDFGPU_EX_SUBSTR || op == RDFGPU_EX_UCASE || op == RDFGPU_EX_LCASE || op == RDFGPU_EX_STRBEFORE || op == RDFGPU_EX_STRAFTER ||
-         op == RDFGPU_EX_CAST_STRING || op == RDFGPU_EX_CAST_LEX) && !store->str_off)
+    if (op_is(d->exprs[i].op, kOpStoreStrings) && !store->str_off)
       fail(RDFGPU_ERR_INVALID, "plan uses string functions but the store has no strings (rdfgpu_store_set_strings)");
   }
 }
@@ -329,7 +335,7 @@ void compile_join(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   if (l.width + rr.width > 2u * kMaxCols) fail(RDFGPU_ERR_UNSUPPORTED, "node %u: too many columns", i);
   InputSchema both, left;
   both.append(l); both.append(rr); left.append(l);
-  load_program(nd, d, both, "join filter", plan->regex_dev, plan->str_consts_dev);
+  load_program(nd, plan, d, both, "join filter");
   // a semi / anti join outputs the left columns only: its projection indexes them (the filter still sees both sides)
   // .. and a mark join the left columns and the mark: a value column whose origin is this node
   if (mark) {
@@ -405,32 +411,21 @@ void compile_aggregate(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
           if ((u64)at + 2 > d->n_pool) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression input at pool offset %u of %u", i, a, at, d->n_pool);
           const u32 off = d->pool[at], len = d->pool[at + 1];
           if (len == 0 || (u64)off + len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: expression outside the expression array", i, a);
-          for (u32 q = 0; q < len; q++) {   // the pattern ops get their per-node preparation in FilterExec and the joins only
-            const u8 op = d->exprs[off + q].op;
-            if (op == RDFGPU_EX_REGEX || op == RDFGPU_EX_REGEX_VAR || op == RDFGPU_EX_CONTAINS || op == RDFGPU_EX_STRSTARTS || op == RDFGPU_EX_STRENDS || op == RDFGPU_EX_LANG_IN)
-              fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES in an aggregate's input expression are not on the device", i, a);
-          }
+          if (any_op_is(d->exprs + off, len, kOpPattern))   // the pattern ops get their per-node preparation in FilterExec and the joins only
+            fail(RDFGPU_ERR_UNSUPPORTED, "node %u: aggregate %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES in an aggregate's input expression are not on the device", i, a);
           if (check_program(d->exprs + off, len, c.width, d->n_regexes, in.value_cols()) != VK_TV) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u: the input expression does not yield a typed value", i, a);
-          ExprProgram pr{};
-          pr.n = len;
-          std::memcpy(pr.nodes, d->exprs + off, len * sizeof(rdfgpu_expr_node));
-          pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
-          rewrite_value_loads(pr, in);
           nd.agg_prog[a] = (int)nd.agg_progs.size();
-          nd.agg_progs.push_back(pr);
+          nd.agg_progs.push_back(load_value_program(plan, in, d->exprs + off, len));
         } else if (col >= c.width) fail(RDFGPU_ERR_INVALID, "node %u: aggregate %u reads column %u of %u", i, a, col, c.width);
         else if (fn == RDFGPU_AGG_COUNT_DISTINCT) refuse_value_column(c.origin[col], i, "COUNT DISTINCT input", col);
         else if (c.origin[col].node >= 0 && fn != RDFGPU_AGG_COUNT) {
           // SUM / AVG / MIN / MAX of a value column: the two-node program [COLUMN, value load], so the EXPR form of the accumulate pass runs it.
           // (COUNT needs nothing: an entry of 0 is "not counted" already.)
-          ExprProgram pr{};
-          pr.n = 2;
-          pr.nodes[0].op = RDFGPU_EX_COLUMN; pr.nodes[0].u = col;
-          pr.nodes[1].op = RDFGPU_EX_ENC_TV;
-          pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
-          rewrite_value_loads(pr, in);
+          rdfgpu_expr_node load[2] = {};
+          load[0].op = RDFGPU_EX_COLUMN; load[0].u = col;
+          load[1].op = RDFGPU_EX_ENC_TV;
           nd.agg_prog[a] = (int)nd.agg_progs.size();
-          nd.agg_progs.push_back(pr);
+          nd.agg_progs.push_back(load_value_program(plan, in, load, 2));
         }
         break;
       case RDFGPU_AGG_SAMPLE: case RDFGPU_AGG_GROUP_CONCAT:
@@ -471,22 +466,13 @@ void compile_extend(Plan* plan, const rdfgpu_plan_desc* d, u32 i) {
   for (u32 q = 0; q < k; q++) {
     const u32 off = d->pool[r.table_slot + 2 * q], len = d->pool[r.table_slot + 2 * q + 1];
     if (len == 0 || (u64)off + len > d->n_exprs) fail(RDFGPU_ERR_INVALID, "node %u: expression %u: program outside the expression array", i, q);
-    for (u32 e = 0; e < len; e++) {   // the pattern ops get their per-node preparation in FilterExec and the joins only; a string view has no 24-byte form
-      const u8 op = d->exprs[off + e].op;
-      if (op == RDFGPU_EX_REGEX || op == RDFGPU_EX_REGEX_VAR || op == RDFGPU_EX_CONTAINS || op == RDFGPU_EX_STRSTARTS || op == RDFGPU_EX_STRENDS || op == RDFGPU_EX_LANG_IN ||
-          op == RDFGPU_EX_STR || op == RDFGPU_EX_LIT_STR || op == RDFGPU_EX_STRLEN || op == RDFGPU_EX_SUBSTR || op == RDFGPU_EX_UCASE || op == RDFGPU_EX_LCASE ||
-          op == RDFGPU_EX_STRBEFORE || op == RDFGPU_EX_STRAFTER)
-        fail(RDFGPU_ERR_UNSUPPORTED, "node %u: expression %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES and the string functions in a computed column are not on the device", i, q);
-    }
+    // the pattern ops get their per-node preparation in FilterExec and the joins only; a string view has no 24-byte form
+    if (any_op_is(d->exprs + off, len, kOpPattern | kOpStringFn))
+      fail(RDFGPU_ERR_UNSUPPORTED, "node %u: expression %u: REGEX / CONTAINS / STRSTARTS / STRENDS / LANGMATCHES and the string functions in a computed column are not on the device", i, q);
     const u32 kind = check_program(d->exprs + off, len, c.width, d->n_regexes, in.value_cols());
     if (kind == VK_BOOL) fail(RDFGPU_ERR_INVALID, "node %u: expression %u leaves a boolean verdict, not a typed value: wrap it in BOOLEAN_AS_TERM", i, q);
     if (kind != VK_TV) fail(RDFGPU_ERR_INVALID, "node %u: expression %u leaves an id, not a typed value: a plain column is a projection", i, q);
-    ExprProgram pr{};
-    pr.n = len;
-    std::memcpy(pr.nodes, d->exprs + off, len * sizeof(rdfgpu_expr_node));
-    pr.regex = plan->regex_dev; pr.str_consts = plan->str_consts_dev;
-    rewrite_value_loads(pr, in);
-    nd.agg_progs.push_back(pr);
+    nd.agg_progs.push_back(load_value_program(plan, in, d->exprs + off, len));
   }
   nd.width = nd.n_proj + k;
   for (u32 q = 0; q < k; q++) nd.origin[nd.n_proj + q] = ValueOrigin{(int)i, q, true};
@@ -541,7 +527,7 @@ void compile_nodes(Plan* plan, const rdfgpu_plan_desc* d) {
       }
       case RDFGPU_NODE_FILTER: {
         InputSchema in; in.append(child(plan, i, r.left, "input"));
-        load_program(nd, d, in, "FilterExec", plan->regex_dev, plan->str_consts_dev);
+        load_program(nd, plan, d, in, "FilterExec");
         load_projection(nd, d, in, "FilterExec");
         nd.shape = detect_shape(nd.prog, plan->opt.on(RDFGPU_OPT_FORCE_GENERIC_VM));
         break;

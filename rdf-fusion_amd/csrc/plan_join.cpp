@@ -76,8 +76,8 @@ DevTable Plan::exec_join(NodeInfo& nd) {
   DevTable t;
   t.n_cols = nd.n_proj;
   if (L.cap == 0 || (R.cap == 0 && !left_join)) { t.cap = 0; return t; }
-  // (a filter with RDFGPU_EX_CAST_LEX takes the generic join: the case is compiled into join_probe_lex_kernel / nlj_lex_kernel, not into
-  // the LDS / partitioned join forms, whose instantiations stay what they were)
+  // (a filter with an op of kOpExtended, expr_ops.hpp, takes the generic join: those cases are compiled into join_probe_lex_kernel /
+  // nlj_lex_kernel, not into the LDS / partitioned join forms, whose instantiations stay what they were)
   if (nd.d.kind == RDFGPU_NODE_HASH_JOIN && !opt.on(RDFGPU_OPT_NO_LDS_JOIN) && !nd.lex) {
     const bool build_left = choose_build_left(nd, L, R, left_join, in.lf, in.rf);
     if ((build_left ? L.cap : R.cap) <= kLdsJoinMaxBuild || !opt.on(RDFGPU_OPT_NO_GLOBAL_TABLE_JOIN)) {

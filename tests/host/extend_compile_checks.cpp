@@ -1,89 +1,12 @@
 // extend_compile_checks.cpp — the host-side checks of ProjectionExec with expressions (RDFGPU_NODE_EXTEND; plan_compile.cpp:
-// compile_extend and what it calls) as a stand-alone program, so that they can run under AddressSanitizer / UndefinedBehaviorSanitizer
-// without a device:
-//
-//   make -C rdf-fusion_amd/csrc host-checks-extend SANITIZE=1     (without SANITIZE: a plain build, what tests/test_extend_cpu.py runs)
-//
-// Built like plan_compile_checks.cpp: the unit under test is included as text, what it needs of the store and the device is stubbed out,
-// the plans have bound tables as leaves.  Every case is a plan description and the status its compilation must end in; a refusal's text
-// must hold the key words given.
-#include "../../rdf-fusion_amd/csrc/plan_compile.cpp"
-
-#include <cstdio>
-
-namespace rdfgpu {
-Plan::~Plan() {}
-void Plan::derive_source(SourceInfo&, const ScanInstructions&) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Plan::upload_pool() {}
-ScanInstructions make_gspo(const rdfgpu_scan_instruction*, const u32*, u32) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Store::activate() const {}
-ExecContext* Store::acquire_context(u32) { return nullptr; }
-}  // namespace rdfgpu
-
-using namespace rdfgpu;
+// compile_extend and what it calls).  `make host-checks-extend`: what tests/test_extend_cpu.py runs.
+#include "compile_check_harness.hpp"
 
 namespace {
-typedef std::vector<rdfgpu_expr_node> Program;
-struct Builder {
-  std::vector<rdfgpu_plan_node> nodes; std::vector<rdfgpu_expr_node> exprs; std::vector<u32> pool;
-  u32 push(rdfgpu_plan_node n) { nodes.push_back(n); return (u32)nodes.size() - 1; }
-  static rdfgpu_plan_node blank(u32 kind, int left, int right = -1) {
-    rdfgpu_plan_node n{}; n.kind = kind; n.left = left; n.right = right; n.n_proj = RDFGPU_NO_PROJECTION; return n;
-  }
-  u32 table(u32 slot, u32 cols) { auto n = blank(RDFGPU_NODE_TABLE, -1); n.table_slot = slot; n.table_cols = cols; return push(n); }
-  void project(rdfgpu_plan_node& n, std::vector<u32> p) { n.proj_off = (u32)pool.size(); n.n_proj = (u32)p.size(); pool.insert(pool.end(), p.begin(), p.end()); }
-  u32 aggregate(int in, std::vector<u32> keys, std::vector<std::pair<u32, u32>> aggs) {
-    auto n = blank(RDFGPU_NODE_AGGREGATE, in);
-    n.n_keys = (u32)keys.size();
-    for (size_t k = 0; k < keys.size() && k < RDFGPU_MAX_KEYS; k++) n.left_keys[k] = keys[k];
-    n.table_cols = (u32)aggs.size(); n.table_slot = (u32)pool.size();
-    for (auto& a : aggs) { pool.push_back(a.first); pool.push_back(a.second); }
-    return push(n);
-  }
-  // EXTEND: `keep` (empty: all columns), then one computed column per program
-  u32 extend(int in, std::vector<Program> progs, std::vector<u32> keep = {}) {
-    auto n = blank(RDFGPU_NODE_EXTEND, in);
-    if (!keep.empty()) project(n, keep);
-    std::vector<u32> pairs;
-    for (auto& p : progs) { pairs.push_back((u32)exprs.size()); pairs.push_back((u32)p.size()); exprs.insert(exprs.end(), p.begin(), p.end()); }
-    n.table_cols = (u32)progs.size(); n.table_slot = (u32)pool.size();
-    pool.insert(pool.end(), pairs.begin(), pairs.end());
-    return push(n);
-  }
-  u32 join(u32 kind, int l, int r, std::vector<std::pair<u32, u32>> on, u32 type = RDFGPU_JOIN_INNER) {
-    auto n = blank(kind, l, r); n.join_type = type; n.n_keys = (u32)on.size();
-    for (size_t k = 0; k < on.size(); k++) { n.left_keys[k] = on[k].first; n.right_keys[k] = on[k].second; }
-    return push(n);
-  }
-};
-rdfgpu_expr_node op(u8 o, u32 u = 0, u8 tag = 0, int64_t lo = 0) { rdfgpu_expr_node e{}; e.op = o; e.u = u; e.tag = tag; e.lo = lo; return e; }
-rdfgpu_expr_node column(u32 c) { return op(RDFGPU_EX_COLUMN, c); }
-Program tv(u32 c) { return {column(c), op(RDFGPU_EX_ENC_TV)}; }
-Program ratio(u32 a, u32 b) {   // DIV(xsd:float(ENC_TV(col a)), ENC_TV(col b))
+Prog ratio(u32 a, u32 b) {   // DIV(xsd:float(ENC_TV(col a)), ENC_TV(col b))
   return {column(a), op(RDFGPU_EX_ENC_TV), op(RDFGPU_EX_CAST, RDFGPU_TV_FLOAT), column(b), op(RDFGPU_EX_ENC_TV), op(RDFGPU_EX_DIV)};
 }
 
-int failures = 0;
-void check(const char* name, bool ok) { std::printf("%-52s %s\n", name, ok ? "ok  " : "FAIL"); failures += !ok; }
-// Compiles the nodes of `b` (root = the last node); `want` = the status, `needles` = what a refusal's text must hold.  -> the compiled nodes
-std::vector<NodeInfo> expect(const char* name, Builder& b, u32 flags, int want, std::vector<const char*> needles = {}) {
-  rdfgpu_plan_desc d{};
-  d.nodes = b.nodes.data(); d.n_nodes = (u32)b.nodes.size(); d.root = d.n_nodes - 1;
-  d.exprs = b.exprs.data(); d.n_exprs = (u32)b.exprs.size(); d.pool = b.pool.data(); d.n_pool = (u32)b.pool.size(); d.flags = flags;
-  Plan plan;
-  plan.root = d.root; plan.agg_columns = (flags & RDFGPU_PLAN_AGG_COLUMNS) != 0;
-  plan.nodes.resize(d.n_nodes);
-  int got = RDFGPU_OK; std::string text;
-  try { compile_nodes(&plan, &d); reorder_cross_joins(&plan); count_consumers(&plan); account_columns_read(&plan); }
-  catch (const Error& e) { got = e.status; text = e.what(); }
-  bool ok = got == want;
-  for (const char* n : needles) ok = ok && text.find(n) != std::string::npos;
-  std::printf("%-52s %s  %s\n", name, ok ? "ok  " : "FAIL", text.c_str());
-  if (!ok) failures++;
-  return plan.nodes;
-}
-constexpr u32 F = RDFGPU_PLAN_AGG_COLUMNS;
-constexpr int UNSUP = RDFGPU_ERR_UNSUPPORTED, INVALID = RDFGPU_ERR_INVALID;
 // table(0: k, x, y) -> EXTEND keep all, [MUL(ENC_TV(x), ENC_TV(y))]: columns k, x, y, product; node 1, its computed column is column 3
 u32 ext(Builder& b) {
   return b.extend((int)b.table(0, 3), {{column(1), op(RDFGPU_EX_ENC_TV), column(2), op(RDFGPU_EX_ENC_TV), op(RDFGPU_EX_MUL)}});
@@ -98,7 +21,7 @@ int main() {
     check("  .. width, origins, the program as written", nd.width == 4 && nd.n_proj == 3 && nd.origin[2].node < 0 && nd.origin[3].node == (int)e && nd.origin[3].agg == 0 &&
           nd.agg_progs.size() == 1 && nd.agg_progs[0].n == 5 && nd.agg_progs[0].nodes[1].op == RDFGPU_EX_ENC_TV && nd.n_cols_read == 2 && nd.n_enc_tv == 2); }
   { Builder b; u32 a = b.aggregate((int)b.table(0, 3), {0}, {{RDFGPU_AGG_COUNT, 1}, {RDFGPU_AGG_COUNT, 2}});
-    u32 e = b.extend((int)a, {ratio(1, 2), tv(0)}, {0, 2});   // a program ranges over all input columns, not only the kept ones
+    u32 e = b.extend((int)a, {ratio(1, 2), enc(0)}, {0, 2});   // a program ranges over all input columns, not only the kept ones
     auto nodes = expect("EXTEND over an AGGREGATE (the Q3 ratio)", b, F, RDFGPU_OK);
     const NodeInfo& nd = nodes[e];
     const ExprProgram& p = nd.agg_progs[0];
@@ -115,34 +38,33 @@ int main() {
   { Builder b; u32 e = ext(b); b.aggregate((int)e, {0}, {{RDFGPU_AGG_SUM, 3}, {RDFGPU_AGG_COUNT, 3}, {RDFGPU_AGG_AVG, 3}});
     auto nodes = expect("SUM / COUNT / AVG of a computed column", b, F, RDFGPU_OK);
     check("  .. SUM as [COLUMN, value load]", nodes.back().agg_progs.size() == 2 && nodes.back().agg_progs[0].nodes[1].op == kExAggValue && nodes.back().agg_progs[0].nodes[1].u == ((e << 8) | 0u)); }
-  { Builder b; u32 e = ext(b); u32 t = b.table(1, 2); b.join(RDFGPU_NODE_HASH_JOIN, (int)t, (int)e, {{0, 0}}, RDFGPU_JOIN_LEFT);
+  { Builder b; u32 e = ext(b); u32 t = b.table(1, 2); b.join(RDFGPU_NODE_HASH_JOIN, (int)t, (int)e, RDFGPU_JOIN_LEFT, {{0, 0}});
     auto nodes = expect("a computed column as LEFT join payload", b, F, RDFGPU_OK);
     check("  .. origin carried through the join", nodes.back().width == 6 && nodes.back().origin[5].node == (int)e); }
-  { Builder b; std::vector<Program> eight(8, tv(1)); b.extend((int)b.table(0, 8), eight); expect("8 expressions over 8 columns: 16 outputs", b, F, RDFGPU_OK); }
+  { Builder b; std::vector<Prog> eight(8, enc(1)); b.extend((int)b.table(0, 8), eight); expect("8 expressions over 8 columns: 16 outputs", b, F, RDFGPU_OK); }
   // ---- the refusals of the node itself
   { Builder b; ext(b); expect("no flag", b, 0, UNSUP, {"node 1", "RDFGPU_PLAN_AGG_COLUMNS"}); }
   { Builder b; b.extend((int)b.table(0, 3), {}); expect("k = 0", b, F, UNSUP, {"node 1", "0 expressions"}); }
-  { Builder b; std::vector<Program> nine(9, tv(1)); b.extend((int)b.table(0, 3), nine); expect("k = 9", b, F, UNSUP, {"node 1", "9 expressions"}); }
-  { Builder b; b.extend((int)b.table(0, 16), {tv(1)}); expect("17 output columns", b, F, UNSUP, {"node 1", "17 output columns"}); }
+  { Builder b; std::vector<Prog> nine(9, enc(1)); b.extend((int)b.table(0, 3), nine); expect("k = 9", b, F, UNSUP, {"node 1", "9 expressions"}); }
+  { Builder b; b.extend((int)b.table(0, 16), {enc(1)}); expect("17 output columns", b, F, UNSUP, {"node 1", "17 output columns"}); }
   { Builder b; b.extend((int)b.table(0, 3), {{column(1), op(RDFGPU_EX_ENC_TV), column(2), op(RDFGPU_EX_ENC_TV), op(RDFGPU_EX_GT), op(RDFGPU_EX_EBV)}});
     expect("a program leaving a verdict", b, F, INVALID, {"node 1", "expression 0", "BOOLEAN_AS_TERM"}); }
-  { Builder b; b.extend((int)b.table(0, 3), {tv(1), {column(1)}}); expect("a program leaving an id", b, F, INVALID, {"node 1", "expression 1", "projection"}); }
+  { Builder b; b.extend((int)b.table(0, 3), {enc(1), {column(1)}}); expect("a program leaving an id", b, F, INVALID, {"node 1", "expression 1", "projection"}); }
   { Builder b; b.extend((int)b.table(0, 3), {{column(1), op(RDFGPU_EX_STR), op(RDFGPU_EX_STRLEN)}}); expect("a string op (STR, STRLEN)", b, F, UNSUP, {"node 1", "expression 0", "string"}); }
   { Builder b; b.extend((int)b.table(0, 3), {{column(1), op(RDFGPU_EX_ENC_TV), op(RDFGPU_EX_CONTAINS)}}); expect("a string op (CONTAINS)", b, F, UNSUP, {"node 1", "CONTAINS"}); }
   { Builder b; u32 e = ext(b); b.nodes[e].table_slot = (u32)b.pool.size() - 1; expect("a pool pair out of range", b, F, INVALID, {"node 1", "outside the pool"}); }
   { Builder b; u32 e = ext(b); b.pool[b.nodes[e].table_slot + 1] = 99; expect("a program out of range", b, F, INVALID, {"node 1", "outside the expression array"}); }
-  { Builder b; b.extend((int)b.table(0, 3), {tv(3)}); expect("a program reading a column past the input", b, F, INVALID, {"out of range"}); }
-  { Builder b; b.extend((int)b.table(0, 3), {tv(1)}, {0, 3}); expect("keeping a column past the input", b, F, INVALID, {"out of range"}); }
+  { Builder b; b.extend((int)b.table(0, 3), {enc(3)}); expect("a program reading a column past the input", b, F, INVALID, {"out of range"}); }
+  { Builder b; b.extend((int)b.table(0, 3), {enc(1)}, {0, 3}); expect("keeping a column past the input", b, F, INVALID, {"out of range"}); }
   { Builder b; u32 e = ext(b); b.extend((int)e, {{column(3), op(RDFGPU_EX_LIT_ID, 3), op(RDFGPU_EX_ID_EQ), op(RDFGPU_EX_BOOL_AS_TV)}}); expect("ID_EQ of a computed column", b, F, INVALID, {"value column"}); }
   // ---- a computed column where ids are compared: RDFGPU_ERR_UNSUPPORTED, the text names the node and the expression
-  { Builder b; u32 e = ext(b); u32 t = b.table(1, 2); b.join(RDFGPU_NODE_HASH_JOIN, (int)e, (int)t, {{3, 0}});
+  { Builder b; u32 e = ext(b); u32 t = b.table(1, 2); b.join(RDFGPU_NODE_HASH_JOIN, (int)e, (int)t, RDFGPU_JOIN_INNER, {{3, 0}});
     expect("join key", b, F, UNSUP, {"node 3: left join key column 3", "expression 0", "node 1"}); }
   { Builder b; u32 e = ext(b); b.aggregate((int)e, {0, 3}, {}); expect("group column", b, F, UNSUP, {"node 2: group column 3", "expression 0", "node 1"}); }
   { Builder b; u32 e = ext(b); b.aggregate((int)e, {0}, {{RDFGPU_AGG_COUNT_DISTINCT, 3}}); expect("COUNT_DISTINCT input", b, F, UNSUP, {"node 2: COUNT DISTINCT input column 3", "expression 0"}); }
   { Builder b; u32 e = ext(b); auto n = Builder::blank(RDFGPU_NODE_TOPK, (int)e); n.n_keys = 2; n.left_keys[0] = 0; n.left_keys[1] = 3; n.right_keys[1] = RDFGPU_SORT_BY_DOUBLE; n.table_cols = 5; b.project(n, {0}); b.push(n);
     expect("TopK key", b, F, UNSUP, {"node 2: TopK sort key column 3", "expression 0"}); }
-  { Builder b; u32 e = b.extend((int)b.table(0, 3), {tv(1), tv(2)}, {0, 1, 2}); u32 t = b.table(1, 5); b.push(Builder::blank(RDFGPU_NODE_UNION, (int)t, (int)e));
+  { Builder b; u32 e = b.extend((int)b.table(0, 3), {enc(1), enc(2)}, {0, 1, 2}); u32 t = b.table(1, 5); b.push(Builder::blank(RDFGPU_NODE_UNION, (int)t, (int)e));
     expect("UNION input", b, F, UNSUP, {"node 3: UnionExec right input column 3", "expression 0", "node 1"}); }
-  std::printf("%d failure(s)\n", failures);
-  return failures ? 1 : 0;
+  return finish();
 }

@@ -1,97 +1,10 @@
 // forms_compile_checks.cpp — the host-side checks of the functional forms and term tests (RDFGPU_EX_IF, RDFGPU_EX_COALESCE,
 // RDFGPU_EX_IS_IRI .. RDFGPU_EX_IS_NUMERIC) and of LeftMark joins (RDFGPU_JOIN_LEFT_MARK; plan_compile.cpp: check_program, compile_join,
-// needs_generic_vm) as a stand-alone program, so that they can run under AddressSanitizer / UndefinedBehaviorSanitizer without a device:
-//
-//   make -C rdf-fusion_amd/csrc host-checks-forms SANITIZE=1     (without SANITIZE: a plain build, what tests/test_forms_cpu.py runs)
-//
-// Built like value_keys_compile_checks.cpp: the unit under test is included as text, what it needs of the store and the device is stubbed
-// out, the plans have bound tables as leaves.  Every case is a plan description and the status its compilation must end in; a refusal's
-// text must hold the key words given.
-#include "../../rdf-fusion_amd/csrc/plan_compile.cpp"
-
-#include <cstdio>
-
-namespace rdfgpu {
-Plan::~Plan() {}
-void Plan::derive_source(SourceInfo&, const ScanInstructions&) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Plan::upload_pool() {}
-ScanInstructions make_gspo(const rdfgpu_scan_instruction*, const u32*, u32) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Store::activate() const {}
-ExecContext* Store::acquire_context(u32) { return nullptr; }
-}  // namespace rdfgpu
-
-using namespace rdfgpu;
+// needs_generic_vm).  `make host-checks-forms`: what tests/test_forms_cpu.py runs.
+#include "compile_check_harness.hpp"
 
 namespace {
-typedef std::vector<rdfgpu_expr_node> Prog;
-rdfgpu_expr_node op(u8 o, u32 u = 0) { rdfgpu_expr_node e{}; e.op = o; e.u = u; return e; }
-Prog column(u32 c) { return {op(RDFGPU_EX_COLUMN, c)}; }
-Prog enc(u32 c) { return {op(RDFGPU_EX_COLUMN, c), op(RDFGPU_EX_ENC_TV)}; }
-Prog integer(long long v) { rdfgpu_expr_node e{}; e.op = RDFGPU_EX_LIT_TV; e.tag = RDFGPU_TV_INTEGER; e.lo = v; return {e}; }
-Prog cat(std::initializer_list<Prog> parts, std::initializer_list<rdfgpu_expr_node> tail = {}) {
-  Prog p;
-  for (const Prog& q : parts) p.insert(p.end(), q.begin(), q.end());
-  p.insert(p.end(), tail.begin(), tail.end());
-  return p;
-}
-
-struct Builder {
-  std::vector<rdfgpu_plan_node> nodes; std::vector<rdfgpu_expr_node> exprs; std::vector<u32> pool;
-  u32 push(rdfgpu_plan_node n) { nodes.push_back(n); return (u32)nodes.size() - 1; }
-  static rdfgpu_plan_node blank(u32 kind, int left, int right = -1) {
-    rdfgpu_plan_node n{}; n.kind = kind; n.left = left; n.right = right; n.n_proj = RDFGPU_NO_PROJECTION; return n;
-  }
-  std::pair<u32, u32> program(const Prog& p) { const u32 off = (u32)exprs.size(); exprs.insert(exprs.end(), p.begin(), p.end()); return {off, (u32)p.size()}; }
-  u32 table(u32 slot, u32 cols) { auto n = blank(RDFGPU_NODE_TABLE, -1); n.table_slot = slot; n.table_cols = cols; return push(n); }
-  u32 filter(int in, const Prog& p) { auto pr = program(p); auto n = blank(RDFGPU_NODE_FILTER, in); n.expr_off = pr.first; n.expr_len = pr.second; return push(n); }
-  u32 join(u32 kind, int l, int r, u32 type, std::vector<std::pair<u32, u32>> on, const Prog& flt = {}, std::vector<u32> proj = {}, bool with_proj = false) {
-    auto n = blank(kind, l, r); n.join_type = type; n.n_keys = (u32)on.size();
-    for (size_t k = 0; k < on.size() && k < RDFGPU_MAX_KEYS; k++) { n.left_keys[k] = on[k].first; n.right_keys[k] = on[k].second; }
-    if (!flt.empty()) { auto pr = program(flt); n.expr_off = pr.first; n.expr_len = pr.second; }
-    if (with_proj) { n.proj_off = (u32)pool.size(); n.n_proj = (u32)proj.size(); pool.insert(pool.end(), proj.begin(), proj.end()); }
-    return push(n);
-  }
-  u32 extend(int in, std::vector<Prog> progs) {
-    std::vector<std::pair<u32, u32>> at;
-    for (const Prog& p : progs) at.push_back(program(p));
-    auto n = blank(RDFGPU_NODE_EXTEND, in); n.table_cols = (u32)progs.size(); n.table_slot = (u32)pool.size();
-    for (auto& p : at) { pool.push_back(p.first); pool.push_back(p.second); }
-    return push(n);
-  }
-  u32 aggregate(int in, std::vector<u32> keys, std::vector<std::pair<u32, u32>> aggs) {
-    auto n = blank(RDFGPU_NODE_AGGREGATE, in);
-    n.n_keys = (u32)keys.size();
-    for (size_t k = 0; k < keys.size() && k < RDFGPU_MAX_KEYS; k++) n.left_keys[k] = keys[k];
-    n.table_cols = (u32)aggs.size(); n.table_slot = (u32)pool.size();
-    for (auto& a : aggs) { pool.push_back(a.first); pool.push_back(a.second); }
-    return push(n);
-  }
-  u32 input_expr(const Prog& p) { auto pr = program(p); const u32 at = (u32)pool.size(); pool.push_back(pr.first); pool.push_back(pr.second); return RDFGPU_AGG_INPUT_EXPR | at; }
-};
-
-int failures = 0;
-void check(const char* name, bool ok) { std::printf("%-84s %s\n", name, ok ? "ok  " : "FAIL"); failures += !ok; }
-constexpr u32 F = RDFGPU_PLAN_AGG_COLUMNS;
-constexpr int UNSUP = RDFGPU_ERR_UNSUPPORTED, INVALID = RDFGPU_ERR_INVALID;
-std::vector<NodeInfo> expect(const char* name, Builder& b, u32 flags, int want, std::vector<const char*> needles = {}) {
-  rdfgpu_plan_desc d{};
-  d.nodes = b.nodes.data(); d.n_nodes = (u32)b.nodes.size(); d.root = d.n_nodes - 1;
-  d.exprs = b.exprs.data(); d.n_exprs = (u32)b.exprs.size(); d.pool = b.pool.data(); d.n_pool = (u32)b.pool.size(); d.flags = flags;
-  Plan plan;
-  plan.root = d.root;
-  plan.nodes.resize(d.n_nodes);
-  int got = RDFGPU_OK; std::string text;
-  try {
-    check_plan_flags(flags);
-    plan.agg_columns = (flags & RDFGPU_PLAN_AGG_COLUMNS) != 0; plan.value_keys = (flags & RDFGPU_PLAN_VALUE_KEYS) != 0;
-    compile_nodes(&plan, &d); reorder_cross_joins(&plan); count_consumers(&plan); account_columns_read(&plan);
-  } catch (const Error& e) { got = e.status; text = e.what(); }
-  bool ok = got == want;
-  for (const char* n : needles) ok = ok && text.find(n) != std::string::npos;
-  std::printf("%-84s %s  %s\n", name, ok ? "ok  " : "FAIL", text.c_str());
-  if (!ok) failures++;
-  return plan.nodes;
-}
+Prog integer(long long v) { return {lit(RDFGPU_TV_INTEGER, v)}; }
 
 // the ops, each as a program over columns 0 .. 2 that leaves a typed value
 struct Form { const char* name; Prog tv; };
@@ -100,7 +13,7 @@ std::vector<Form> forms() {
       {"IF", cat({enc(0), enc(1), enc(2)}, {op(RDFGPU_EX_IF)})},
       {"COALESCE x 3", cat({enc(0), enc(1), enc(2)}, {op(RDFGPU_EX_COALESCE, 3)})},
       {"COALESCE x 1", cat({enc(0)}, {op(RDFGPU_EX_COALESCE, 1)})},
-      {"COALESCE of ids", cat({column(0), column(1)}, {op(RDFGPU_EX_COALESCE, 2), op(RDFGPU_EX_ENC_TV)})},
+      {"COALESCE of ids", cat({{column(0)}, {column(1)}}, {op(RDFGPU_EX_COALESCE, 2), op(RDFGPU_EX_ENC_TV)})},
       {"IS_IRI", cat({enc(0)}, {op(RDFGPU_EX_IS_IRI)})},
       {"IS_BLANK", cat({enc(0)}, {op(RDFGPU_EX_IS_BLANK)})},
       {"IS_LITERAL", cat({enc(0)}, {op(RDFGPU_EX_IS_LITERAL)})},
@@ -161,20 +74,20 @@ int main() {
     expect("COALESCE with u = 9", b, 0, INVALID, {"COALESCE takes 1 to 8 operands, not 9"}); }
   { Builder b; b.filter((int)b.table(0, 3), ebv(cat({enc(0), enc(1)}, {op(RDFGPU_EX_COALESCE, 3)})));
     expect("COALESCE with more operands than the stack holds", b, 0, INVALID, {"stack underflow at COALESCE"}); }
-  { Builder b; b.filter((int)b.table(0, 3), ebv(cat({column(0), enc(1)}, {op(RDFGPU_EX_COALESCE, 2)})));
+  { Builder b; b.filter((int)b.table(0, 3), ebv(cat({{column(0)}, enc(1)}, {op(RDFGPU_EX_COALESCE, 2)})));
     expect("COALESCE mixing an id and a typed value", b, 0, INVALID, {"COALESCE mixes operand kinds"}); }
-  { Builder b; b.filter((int)b.table(0, 3), ebv(cat({enc(1), column(0)}, {op(RDFGPU_EX_COALESCE, 2), op(RDFGPU_EX_ENC_TV)})));
+  { Builder b; b.filter((int)b.table(0, 3), ebv(cat({enc(1), {column(0)}}, {op(RDFGPU_EX_COALESCE, 2), op(RDFGPU_EX_ENC_TV)})));
     expect("COALESCE mixing a typed value and an id", b, 0, INVALID, {"COALESCE mixes operand kinds"}); }
   { Builder b; Prog eight; for (u32 k = 0; k < 8; k++) { Prog e = enc(k % 3); eight.insert(eight.end(), e.begin(), e.end()); }
     eight.push_back(op(RDFGPU_EX_COALESCE, 8));
     b.filter((int)b.table(0, 3), ebv(eight)); expect("COALESCE with 8 operands", b, 0, RDFGPU_OK); }
   { Builder b; u32 a = b.aggregate((int)b.table(0, 2), {0}, {{RDFGPU_AGG_COUNT, 1}});
-    b.filter((int)a, ebv(cat({column(1), column(0)}, {op(RDFGPU_EX_COALESCE, 2), op(RDFGPU_EX_ENC_TV)})));
+    b.filter((int)a, ebv(cat({{column(1)}, {column(0)}}, {op(RDFGPU_EX_COALESCE, 2), op(RDFGPU_EX_ENC_TV)})));
     expect("COALESCE with a value column unwrapped", b, F, INVALID, {"COALESCE got an aggregate value column, whose entries are not object ids"}); }
   { Builder b; u32 a = b.aggregate((int)b.table(0, 2), {0}, {{RDFGPU_AGG_COUNT, 1}});
     b.filter((int)a, ebv(cat({enc(1), enc(0)}, {op(RDFGPU_EX_COALESCE, 2)})));
     expect("COALESCE with a value column through ENC_TV", b, F, RDFGPU_OK); }
-  { Builder b; b.filter((int)b.table(0, 3), ebv(cat({column(0)}, {op(RDFGPU_EX_IS_IRI)})));
+  { Builder b; b.filter((int)b.table(0, 3), ebv(cat({{column(0)}}, {op(RDFGPU_EX_IS_IRI)})));
     expect("IS_IRI over an id operand", b, 0, INVALID, {"term test", "wrong kind"}); }
   // ---- LeftMark joins
   for (u32 kind : {(u32)RDFGPU_NODE_HASH_JOIN, (u32)RDFGPU_NODE_NESTED_LOOP_JOIN}) {
@@ -187,10 +100,10 @@ int main() {
       const NodeInfo& nd = nodes[j];
       check("  .. outputs [left cols, mark], the mark a value column of the join", nd.width == 4 && nd.origin[0].node < 0 && nd.origin[2].node < 0 &&
                                                                                 nd.origin[3].node == (int)j && nd.origin[3].agg == 0 && nd.origin[3].mark && !nd.origin[3].extend); }
-    { Builder b; u32 l = b.table(0, 3), r = b.table(1, 2); u32 j = b.join(kind, (int)l, (int)r, RDFGPU_JOIN_LEFT_MARK, on, ebv(cat({enc(4)}, {op(RDFGPU_EX_IS_LITERAL)})), {3, 1}, true);
+    { Builder b; u32 l = b.table(0, 3), r = b.table(1, 2); u32 j = b.join(kind, (int)l, (int)r, RDFGPU_JOIN_LEFT_MARK, on, ebv(cat({enc(4)}, {op(RDFGPU_EX_IS_LITERAL)})), {3, 1});
       auto nodes = expect("  with a filter over [left cols, right cols] and a projection [mark, c1]", b, F, RDFGPU_OK);
       check("  .. the projection indexes [left cols, mark]", nodes[j].width == 2 && nodes[j].origin[0].node == (int)j && nodes[j].origin[0].mark && nodes[j].origin[1].node < 0 && nodes[j].shape == 1); }
-    { Builder b; u32 l = b.table(0, 3), r = b.table(1, 2); b.join(kind, (int)l, (int)r, RDFGPU_JOIN_LEFT_MARK, on, {}, {0, 4}, true);
+    { Builder b; u32 l = b.table(0, 3), r = b.table(1, 2); b.join(kind, (int)l, (int)r, RDFGPU_JOIN_LEFT_MARK, on, {}, {0, 4});
       expect("  a projection index beyond n_left_cols", b, F, INVALID, {"projection column 4 out of range (4 columns)"}); }
   }
   { Builder b; u32 l = b.table(0, 3), r = b.table(1, 2); b.join(RDFGPU_NODE_CROSS_JOIN, (int)l, (int)r, RDFGPU_JOIN_LEFT_MARK, {});
@@ -227,14 +140,13 @@ int main() {
   // ---- a semi join's compile result is what it was
   for (u32 type : {(u32)RDFGPU_JOIN_LEFT_SEMI, (u32)RDFGPU_JOIN_LEFT_ANTI}) {
     Builder b; u32 l = b.table(0, 3), r = b.table(1, 2);
-    u32 j = b.join(RDFGPU_NODE_HASH_JOIN, (int)l, (int)r, type, {{0, 0}, {1, 1}}, {op(RDFGPU_EX_COLUMN, 1), op(RDFGPU_EX_COLUMN, 4), op(RDFGPU_EX_ID_NEQ)}, {2, 0}, true);
+    u32 j = b.join(RDFGPU_NODE_HASH_JOIN, (int)l, (int)r, type, {{0, 0}, {1, 1}}, {op(RDFGPU_EX_COLUMN, 1), op(RDFGPU_EX_COLUMN, 4), op(RDFGPU_EX_ID_NEQ)}, {2, 0});
     auto nodes = expect(type == RDFGPU_JOIN_LEFT_SEMI ? "a semi join" : "an anti join", b, 0, RDFGPU_OK);
     const NodeInfo& nd = nodes[j];
     check("  .. left columns only, the id-pair filter shape, no value column, no new cases", nd.width == 2 && nd.n_proj == 2 && nd.proj[0] == 2 && nd.proj[1] == 0 && nd.shape == 2 &&
                                                                                           !nd.lex && nd.origin[0].node < 0 && nd.origin[1].node < 0 && nd.prog.n == 3);
-    Builder c; u32 l2 = c.table(0, 3), r2 = c.table(1, 2); c.join(RDFGPU_NODE_HASH_JOIN, (int)l2, (int)r2, type, {{0, 0}}, {}, {3}, true);
+    Builder c; u32 l2 = c.table(0, 3), r2 = c.table(1, 2); c.join(RDFGPU_NODE_HASH_JOIN, (int)l2, (int)r2, type, {{0, 0}}, {}, {3});
     expect("  .. its projection still indexes the left columns only", c, 0, INVALID, {"projection column 3 out of range (3 columns)"});
   }
-  std::printf("%d failure(s)\n", failures);
-  return failures ? 1 : 0;
+  return finish();
 }

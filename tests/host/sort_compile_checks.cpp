@@ -1,86 +1,11 @@
-// sort_compile_checks.cpp — the host-side checks of SortExec (RDFGPU_NODE_SORT; plan_compile.cpp: compile_sort and what it calls) as a
-// stand-alone program, so that they can run under AddressSanitizer / UndefinedBehaviorSanitizer without a device:
-//
-//   make -C rdf-fusion_amd/csrc host-checks-sort SANITIZE=1     (without SANITIZE: a plain build, what tests/test_sort_cpu.py runs)
-//
-// Built like extend_compile_checks.cpp: the unit under test is included as text, what it needs of the store and the device is stubbed
-// out, the plans have bound tables as leaves.  Every case is a plan description and the status its compilation must end in; a refusal's
-// text must hold the key words given.
-#include "../../rdf-fusion_amd/csrc/plan_compile.cpp"
-
-#include <cstdio>
-
-namespace rdfgpu {
-Plan::~Plan() {}
-void Plan::derive_source(SourceInfo&, const ScanInstructions&) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Plan::upload_pool() {}
-ScanInstructions make_gspo(const rdfgpu_scan_instruction*, const u32*, u32) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Store::activate() const {}
-ExecContext* Store::acquire_context(u32) { return nullptr; }
-}  // namespace rdfgpu
-
-using namespace rdfgpu;
+// sort_compile_checks.cpp — the host-side checks of SortExec (RDFGPU_NODE_SORT; plan_compile.cpp: compile_sort and what it calls).
+// `make host-checks-sort`: what tests/test_sort_cpu.py runs.
+#include "compile_check_harness.hpp"
 
 namespace {
-struct Key { u32 col, how; bool desc; };
-struct Builder {
-  std::vector<rdfgpu_plan_node> nodes; std::vector<rdfgpu_expr_node> exprs; std::vector<u32> pool;
-  u32 push(rdfgpu_plan_node n) { nodes.push_back(n); return (u32)nodes.size() - 1; }
-  static rdfgpu_plan_node blank(u32 kind, int left, int right = -1) {
-    rdfgpu_plan_node n{}; n.kind = kind; n.left = left; n.right = right; n.n_proj = RDFGPU_NO_PROJECTION; return n;
-  }
-  u32 table(u32 slot, u32 cols) { auto n = blank(RDFGPU_NODE_TABLE, -1); n.table_slot = slot; n.table_cols = cols; return push(n); }
-  void project(rdfgpu_plan_node& n, std::vector<u32> p) { n.proj_off = (u32)pool.size(); n.n_proj = (u32)p.size(); pool.insert(pool.end(), p.begin(), p.end()); }
-  u32 aggregate(int in, std::vector<u32> keys, std::vector<std::pair<u32, u32>> aggs) {
-    auto n = blank(RDFGPU_NODE_AGGREGATE, in);
-    n.n_keys = (u32)keys.size();
-    for (size_t k = 0; k < keys.size() && k < RDFGPU_MAX_KEYS; k++) n.left_keys[k] = keys[k];
-    n.table_cols = (u32)aggs.size(); n.table_slot = (u32)pool.size();
-    for (auto& a : aggs) { pool.push_back(a.first); pool.push_back(a.second); }
-    return push(n);
-  }
-  // EXTEND keeping every column, one computed column: ENC_TV(col c)
-  u32 extend(int in, u32 c) {
-    auto n = blank(RDFGPU_NODE_EXTEND, in);
-    rdfgpu_expr_node a{}, b{}; a.op = RDFGPU_EX_COLUMN; a.u = c; b.op = RDFGPU_EX_ENC_TV;
-    n.table_cols = 1; n.table_slot = (u32)pool.size();
-    pool.push_back((u32)exprs.size()); pool.push_back(2);
-    exprs.push_back(a); exprs.push_back(b);
-    return push(n);
-  }
-  u32 sort(int in, std::vector<Key> keys, u32 fetch = 0, std::vector<u32> proj = {}) {
-    auto n = blank(RDFGPU_NODE_SORT, in);
-    n.n_keys = (u32)keys.size(); n.table_cols = fetch;
-    for (size_t k = 0; k < keys.size() && k < RDFGPU_MAX_KEYS; k++) { n.left_keys[k] = keys[k].col; n.right_keys[k] = keys[k].how | (keys[k].desc ? RDFGPU_SORT_DESC : 0u); }
-    if (!proj.empty()) project(n, proj);
-    return push(n);
-  }
-};
-
-int failures = 0;
-void check(const char* name, bool ok) { std::printf("%-52s %s\n", name, ok ? "ok  " : "FAIL"); failures += !ok; }
-// Compiles the nodes of `b` (root = the last node); `want` = the status, `needles` = what a refusal's text must hold.  -> the compiled nodes
-std::vector<NodeInfo> expect(const char* name, Builder& b, u32 flags, int want, std::vector<const char*> needles = {}) {
-  rdfgpu_plan_desc d{};
-  d.nodes = b.nodes.data(); d.n_nodes = (u32)b.nodes.size(); d.root = d.n_nodes - 1;
-  d.exprs = b.exprs.data(); d.n_exprs = (u32)b.exprs.size(); d.pool = b.pool.data(); d.n_pool = (u32)b.pool.size(); d.flags = flags;
-  Plan plan;
-  plan.root = d.root; plan.agg_columns = (flags & RDFGPU_PLAN_AGG_COLUMNS) != 0;
-  plan.nodes.resize(d.n_nodes);
-  int got = RDFGPU_OK; std::string text;
-  try { compile_nodes(&plan, &d); reorder_cross_joins(&plan); count_consumers(&plan); account_columns_read(&plan); }
-  catch (const Error& e) { got = e.status; text = e.what(); }
-  bool ok = got == want;
-  for (const char* n : needles) ok = ok && text.find(n) != std::string::npos;
-  std::printf("%-52s %s  %s\n", name, ok ? "ok  " : "FAIL", text.c_str());
-  if (!ok) failures++;
-  return plan.nodes;
-}
-constexpr u32 F = RDFGPU_PLAN_AGG_COLUMNS;
-constexpr int UNSUP = RDFGPU_ERR_UNSUPPORTED, INVALID = RDFGPU_ERR_INVALID;
 constexpr u32 ID = RDFGPU_SORT_BY_ID, TERM = RDFGPU_SORT_BY_TERM, DOUBLE = RDFGPU_SORT_BY_DOUBLE, VALUE = RDFGPU_SORT_BY_VALUE;
 // table(0: product, x, y) -> EXTEND [ENC_TV(x)]: columns product, x, y, value; node 1, its computed column is column 3
-u32 ext(Builder& b) { return b.extend((int)b.table(0, 3), 1); }
+u32 ext(Builder& b) { return b.extend((int)b.table(0, 3), {enc(1)}); }
 }  // namespace
 
 int main() {
@@ -99,7 +24,7 @@ int main() {
     auto nodes = expect("the widest record: value + three id forms", b, F, RDFGPU_OK);
     check("  .. 8 words", nodes.back().sort_words == kSortMaxWords); }
   { Builder b; b.sort((int)b.table(0, 3), {{0, ID, false}, {0, ID, true}, {1, TERM, false}, {2, DOUBLE, true}}); expect("four id keys, a column twice", b, 0, RDFGPU_OK); }
-  { Builder b; u32 e = ext(b); u32 s = b.sort((int)e, {{3, VALUE, true}}); u32 x = b.extend((int)s, 0); b.sort((int)x, {{4, VALUE, false}, {0, ID, false}});
+  { Builder b; u32 e = ext(b); u32 s = b.sort((int)e, {{3, VALUE, true}}); u32 x = b.extend((int)s, {enc(0)}); b.sort((int)x, {{4, VALUE, false}, {0, ID, false}});
     auto nodes = expect("SORT under EXTEND under SORT", b, F, RDFGPU_OK);
     check("  .. origins of both nodes above", nodes.back().width == 5 && nodes.back().origin[3].node == (int)e && nodes.back().origin[4].node == (int)x); }
   { Builder b; u32 e = ext(b); u32 s = b.sort((int)e, {{3, VALUE, true}}); auto f = Builder::blank(RDFGPU_NODE_PROJECTION, (int)s); b.project(f, {3, 0}); b.push(f);
@@ -119,12 +44,11 @@ int main() {
   { Builder b; b.sort((int)b.table(0, 3), {{1, VALUE, true}}); expect("BY_VALUE without the flag", b, 0, UNSUP, {"node 1", "RDFGPU_PLAN_AGG_COLUMNS"}); }
   { Builder b; u32 a = b.aggregate((int)b.table(0, 2), {0}, {{RDFGPU_AGG_COUNT, 1}}); b.sort((int)a, {{0, ID, false}});
     expect("over an aggregate's values without the flag", b, 0, UNSUP, {"node 2", "AggregateExec with aggregates"}); }
-  { Builder b; u32 e = ext(b); u32 x = b.extend((int)e, 2); b.sort((int)x, {{3, VALUE, true}, {4, VALUE, false}});
+  { Builder b; u32 e = ext(b); u32 x = b.extend((int)e, {enc(2)}); b.sort((int)x, {{3, VALUE, true}, {4, VALUE, false}});
     expect("two value keys: a record of 9 words", b, F, UNSUP, {"node 3", "9 64-bit words", "at most 8", "64 KB of LDS"}); }
   { Builder b; b.sort((int)b.table(0, 3), {{0, ID, false}}, 0, {0, 3}); expect("projecting a column past the input", b, 0, INVALID, {"SortExec", "out of range"}); }
   // ---- the value column of a SORT is refused where ids are compared, like any other
   { Builder b; u32 e = ext(b); u32 s = b.sort((int)e, {{3, VALUE, true}}); auto n = Builder::blank(RDFGPU_NODE_HASH_JOIN, (int)s, (int)b.table(1, 2)); n.n_keys = 1; n.left_keys[0] = 3; b.push(n);
     expect("a sorted value column as join key", b, F, UNSUP, {"left join key column 3", "computed value column"}); }
-  std::printf("%d failure(s)\n", failures);
-  return failures ? 1 : 0;
+  return finish();
 }

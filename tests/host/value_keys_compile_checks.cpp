@@ -1,95 +1,24 @@
 // value_keys_compile_checks.cpp — the host-side checks of the date parts (RDFGPU_EX_YEAR .. RDFGPU_EX_SECONDS) and of GROUP BY over value
-// columns and up to 8 group columns (RDFGPU_PLAN_VALUE_KEYS; plan_compile.cpp: check_program, compile_aggregate, check_plan_flags) as a
-// stand-alone program, so that they can run under AddressSanitizer / UndefinedBehaviorSanitizer without a device:
-//
-//   make -C rdf-fusion_amd/csrc host-checks-value-keys SANITIZE=1     (without SANITIZE: a plain build, what tests/test_dateparts_cpu.py runs)
-//
-// Built like minmax_compile_checks.cpp: the unit under test is included as text, what it needs of the store and the device is stubbed
-// out, the plans have bound tables as leaves.  Every case is a plan description and the status its compilation must end in; a refusal's
-// text must hold the key words given.
-#include "../../rdf-fusion_amd/csrc/plan_compile.cpp"
-
-#include <cstdio>
-
-namespace rdfgpu {
-Plan::~Plan() {}
-void Plan::derive_source(SourceInfo&, const ScanInstructions&) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Plan::upload_pool() {}
-ScanInstructions make_gspo(const rdfgpu_scan_instruction*, const u32*, u32) { fail(RDFGPU_ERR_INVALID, "no store in this program"); }
-void Store::activate() const {}
-ExecContext* Store::acquire_context(u32) { return nullptr; }
-}  // namespace rdfgpu
-
-using namespace rdfgpu;
+// columns and up to 8 group columns (RDFGPU_PLAN_VALUE_KEYS; plan_compile.cpp: check_program, compile_aggregate, check_plan_flags).
+// `make host-checks-value-keys`: what tests/test_dateparts_cpu.py runs.
+#include "compile_check_harness.hpp"
 
 namespace {
-struct Builder {
-  std::vector<rdfgpu_plan_node> nodes; std::vector<rdfgpu_expr_node> exprs; std::vector<u32> pool;
-  u32 push(rdfgpu_plan_node n) { nodes.push_back(n); return (u32)nodes.size() - 1; }
-  static rdfgpu_plan_node blank(u32 kind, int left, int right = -1) {
-    rdfgpu_plan_node n{}; n.kind = kind; n.left = left; n.right = right; n.n_proj = RDFGPU_NO_PROJECTION; return n;
-  }
-  u32 table(u32 slot, u32 cols) { auto n = blank(RDFGPU_NODE_TABLE, -1); n.table_slot = slot; n.table_cols = cols; return push(n); }
-  u32 aggregate(int in, std::vector<u32> keys, std::vector<std::pair<u32, u32>> aggs) {   // keys 0..3 in left_keys[], 4..7 in right_keys[]
-    auto n = blank(RDFGPU_NODE_AGGREGATE, in);
-    n.n_keys = (u32)keys.size();
-    for (size_t k = 0; k < keys.size() && k < RDFGPU_MAX_GROUP_KEYS; k++) (k < RDFGPU_MAX_KEYS ? n.left_keys[k] : n.right_keys[k - RDFGPU_MAX_KEYS]) = keys[k];
-    n.table_cols = (u32)aggs.size(); n.table_slot = (u32)pool.size();
-    for (auto& a : aggs) { pool.push_back(a.first); pool.push_back(a.second); }
-    return push(n);
-  }
-  // the program `op`(ENC_TV(col c)) (enc = false: `op`(col c), an id operand), followed by `tail` -> (offset, length)
-  std::pair<u32, u32> program(u32 c, bool enc, u8 op, std::vector<u8> tail = {}) {
-    const u32 off = (u32)exprs.size();
-    rdfgpu_expr_node e{}; e.op = RDFGPU_EX_COLUMN; e.u = c; exprs.push_back(e);
-    if (enc) { rdfgpu_expr_node t{}; t.op = RDFGPU_EX_ENC_TV; exprs.push_back(t); }
-    rdfgpu_expr_node o{}; o.op = op; exprs.push_back(o);
-    for (u8 t : tail) { rdfgpu_expr_node x{}; x.op = t; if (t == RDFGPU_EX_LIT_TV) { x.tag = RDFGPU_TV_INTEGER; x.lo = 2024; } exprs.push_back(x); }
-    return {off, (u32)exprs.size() - off};
-  }
-  u32 filter(int in, std::pair<u32, u32> pr) { auto n = blank(RDFGPU_NODE_FILTER, in); n.expr_off = pr.first; n.expr_len = pr.second; return push(n); }
-  u32 extend(int in, std::vector<std::pair<u32, u32>> progs) {
-    auto n = blank(RDFGPU_NODE_EXTEND, in); n.table_cols = (u32)progs.size(); n.table_slot = (u32)pool.size();
-    for (auto& p : progs) { pool.push_back(p.first); pool.push_back(p.second); }
-    return push(n);
-  }
-  u32 input_expr(std::pair<u32, u32> pr) { const u32 at = (u32)pool.size(); pool.push_back(pr.first); pool.push_back(pr.second); return RDFGPU_AGG_INPUT_EXPR | at; }
-  u32 hash_join(int l, int r, u32 lk, u32 rk, std::pair<u32, u32> pr = {0, 0}) {
-    auto n = blank(RDFGPU_NODE_HASH_JOIN, l, r); n.n_keys = 1; n.left_keys[0] = lk; n.right_keys[0] = rk; n.expr_off = pr.first; n.expr_len = pr.second; return push(n);
-  }
-};
-
-int failures = 0;
-void check(const char* name, bool ok) { std::printf("%-72s %s\n", name, ok ? "ok  " : "FAIL"); failures += !ok; }
-constexpr u32 F = RDFGPU_PLAN_AGG_COLUMNS, V = RDFGPU_PLAN_AGG_COLUMNS | RDFGPU_PLAN_VALUE_KEYS;
-constexpr int UNSUP = RDFGPU_ERR_UNSUPPORTED, INVALID = RDFGPU_ERR_INVALID;
-// Compiles the nodes of `b` (root = the last node) as plan_compile does for these flags; `want` = the status, `needles` = what a refusal's text must hold.
-std::vector<NodeInfo> expect(const char* name, Builder& b, u32 flags, int want, std::vector<const char*> needles = {}) {
-  rdfgpu_plan_desc d{};
-  d.nodes = b.nodes.data(); d.n_nodes = (u32)b.nodes.size(); d.root = d.n_nodes - 1;
-  d.exprs = b.exprs.data(); d.n_exprs = (u32)b.exprs.size(); d.pool = b.pool.data(); d.n_pool = (u32)b.pool.size(); d.flags = flags;
-  Plan plan;
-  plan.root = d.root;
-  plan.nodes.resize(d.n_nodes);
-  int got = RDFGPU_OK; std::string text;
-  try {
-    check_plan_flags(flags);
-    plan.agg_columns = (flags & RDFGPU_PLAN_AGG_COLUMNS) != 0; plan.value_keys = (flags & RDFGPU_PLAN_VALUE_KEYS) != 0;
-    compile_nodes(&plan, &d); reorder_cross_joins(&plan); count_consumers(&plan); account_columns_read(&plan);
-  } catch (const Error& e) { got = e.status; text = e.what(); }
-  bool ok = got == want;
-  for (const char* n : needles) ok = ok && text.find(n) != std::string::npos;
-  std::printf("%-72s %s  %s\n", name, ok ? "ok  " : "FAIL", text.c_str());
-  if (!ok) failures++;
-  return plan.nodes;
+constexpr u32 V = RDFGPU_PLAN_AGG_COLUMNS | RDFGPU_PLAN_VALUE_KEYS;
+// the program `o`(ENC_TV(col c)) (of_value = false: `o`(col c), an id operand), followed by `tail`
+Prog part(u32 c, bool of_value, u8 o, std::vector<u8> tail = {}) {
+  Prog p = of_value ? enc(c) : Prog{column(c)};
+  p.push_back(op(o));
+  for (u8 t : tail) p.push_back(t == RDFGPU_EX_LIT_TV ? lit(RDFGPU_TV_INTEGER, 2024) : op(t));
+  return p;
 }
 const u8 PARTS[6] = {RDFGPU_EX_YEAR, RDFGPU_EX_MONTH, RDFGPU_EX_DAY, RDFGPU_EX_HOURS, RDFGPU_EX_MINUTES, RDFGPU_EX_SECONDS};
 const char* const PART_NAMES[6] = {"YEAR", "MONTH", "DAY", "HOURS", "MINUTES", "SECONDS"};
 // the Wind Farm tail: table(site, wtur, val, tv) -> EXTEND(year .. minute of tv) -> AggregateExec by 2 ids + 5 values, AVG(val)
 u32 windfarm(Builder& b) {
   const u32 t = b.table(0, 4);
-  const u32 x = b.extend((int)t, {b.program(3, true, RDFGPU_EX_YEAR), b.program(3, true, RDFGPU_EX_MONTH), b.program(3, true, RDFGPU_EX_DAY),
-                                  b.program(3, true, RDFGPU_EX_HOURS), b.program(3, true, RDFGPU_EX_MINUTES)});
+  const u32 x = b.extend((int)t, {part(3, true, RDFGPU_EX_YEAR), part(3, true, RDFGPU_EX_MONTH), part(3, true, RDFGPU_EX_DAY),
+                                  part(3, true, RDFGPU_EX_HOURS), part(3, true, RDFGPU_EX_MINUTES)});
   return b.aggregate((int)x, {0, 1, 4, 5, 6, 7, 8}, {{RDFGPU_AGG_AVG, 2}});
 }
 }  // namespace
@@ -100,25 +29,25 @@ int main() {
   // ---- the six ops: TV -> TV, wherever MUL is allowed; refused over an id operand
   for (int p = 0; p < 6; p++) {
     char name[96];
-    { Builder b; u32 t = b.table(0, 2); u32 f = b.filter((int)t, b.program(1, true, PARTS[p], {RDFGPU_EX_LIT_TV, RDFGPU_EX_EQ, RDFGPU_EX_EBV}));
+    { Builder b; u32 t = b.table(0, 2); u32 f = b.filter((int)t, part(1, true, PARTS[p], {RDFGPU_EX_LIT_TV, RDFGPU_EX_EQ, RDFGPU_EX_EBV}));
       std::snprintf(name, sizeof name, "FILTER EBV(EQ(%s(ENC_TV(c1)), 2024))", PART_NAMES[p]);
       auto nodes = expect(name, b, 0, RDFGPU_OK);
       check("  .. runs in the generic VM, in the instantiation that compiles the op in", nodes[f].shape == 0 && nodes[f].lex); }
-    { Builder b; b.filter((int)b.table(0, 2), b.program(1, false, PARTS[p], {RDFGPU_EX_LIT_TV, RDFGPU_EX_EQ, RDFGPU_EX_EBV}));
+    { Builder b; b.filter((int)b.table(0, 2), part(1, false, PARTS[p], {RDFGPU_EX_LIT_TV, RDFGPU_EX_EQ, RDFGPU_EX_EBV}));
       std::snprintf(name, sizeof name, "%s over an id operand", PART_NAMES[p]);
       expect(name, b, 0, INVALID, {"date part", "wrong kind"}); }
-    { Builder b; u32 t = b.table(0, 2); u32 x = b.extend((int)t, {b.program(1, true, PARTS[p])});
+    { Builder b; u32 t = b.table(0, 2); u32 x = b.extend((int)t, {part(1, true, PARTS[p])});
       std::snprintf(name, sizeof name, "EXTEND %s(ENC_TV(c1))", PART_NAMES[p]);
       auto nodes = expect(name, b, F, RDFGPU_OK);
       check("  .. a computed column of its own origin", nodes[x].width == 3 && nodes[x].origin[2].node == (int)x && nodes[x].origin[2].extend && nodes[x].lex); }
   }
-  { Builder b; u32 t = b.table(0, 3); u32 e = b.input_expr(b.program(2, true, RDFGPU_EX_HOURS)); u32 a = b.aggregate((int)t, {0}, {{RDFGPU_AGG_AVG, e}, {RDFGPU_AGG_MAX, e}});
+  { Builder b; u32 t = b.table(0, 3); u32 e = b.input_expr(part(2, true, RDFGPU_EX_HOURS)); u32 a = b.aggregate((int)t, {0}, {{RDFGPU_AGG_AVG, e}, {RDFGPU_AGG_MAX, e}});
     auto nodes = expect("AVG and MAX over HOURS(ENC_TV(c2))", b, F, RDFGPU_OK);
     check("  .. the programs are loaded", nodes[a].agg_progs.size() == 2 && nodes[a].agg_progs[0].n == 3 && nodes[a].lex); }
-  { Builder b; u32 l = b.table(0, 2), r = b.table(1, 2); u32 j = b.hash_join((int)l, (int)r, 0, 0, b.program(3, true, RDFGPU_EX_MONTH, {RDFGPU_EX_LIT_TV, RDFGPU_EX_GT, RDFGPU_EX_EBV}));
+  { Builder b; u32 l = b.table(0, 2), r = b.table(1, 2); u32 j = b.join(RDFGPU_NODE_HASH_JOIN, (int)l, (int)r, RDFGPU_JOIN_INNER, {{0, 0}}, part(3, true, RDFGPU_EX_MONTH, {RDFGPU_EX_LIT_TV, RDFGPU_EX_GT, RDFGPU_EX_EBV}));
     auto nodes = expect("a join filter with MONTH", b, 0, RDFGPU_OK);
     check("  .. takes the generic join filter", nodes[j].shape == 1 && nodes[j].lex); }
-  { Builder b; b.filter((int)b.table(0, 2), b.program(1, true, 54, {RDFGPU_EX_EBV})); expect("op 54 is still unknown", b, 0, INVALID, {"unknown op 54"}); }
+  { Builder b; b.filter((int)b.table(0, 2), part(1, true, 54, {RDFGPU_EX_EBV})); expect("op 54 is still unknown", b, 0, INVALID, {"unknown op 54"}); }
   // ---- RDFGPU_PLAN_VALUE_KEYS: 5..8 keys, value keys, the origins of the output
   { Builder b; u32 a = windfarm(b);
     auto nodes = expect("the Wind Farm list: 2 id + 5 value keys, AVG", b, V, RDFGPU_OK);
@@ -146,13 +75,13 @@ int main() {
   { Builder b; u32 c = b.aggregate((int)b.table(0, 2), {0}, {{RDFGPU_AGG_COUNT, 1}}); b.aggregate((int)c, {1}, {});
     expect("an aggregate's value column as group column, no flag", b, F, UNSUP,
            {"node 2: group column 1 is an aggregate value column (aggregate 0 of node 1): its entries index values, equal values have different indexes"}); }
-  { Builder b; u32 x = b.extend((int)b.table(0, 4), {b.program(3, true, RDFGPU_EX_YEAR)}); b.aggregate((int)x, {0, 4}, {});
+  { Builder b; u32 x = b.extend((int)b.table(0, 4), {part(3, true, RDFGPU_EX_YEAR)}); b.aggregate((int)x, {0, 4}, {});
     expect("a computed column as group column, no flag", b, F, UNSUP,
            {"node 2: group column 4 is a computed value column (expression 0 of the ProjectionExec with expressions, node 1): its entries index values, equal values have different indexes"}); }
   // ---- with the flag: the other roles of a value column stay refused, with their texts
-  { Builder b; u32 a = windfarm(b); u32 t = b.table(1, 2); b.hash_join((int)a, (int)t, 2, 0);
+  { Builder b; u32 a = windfarm(b); u32 t = b.table(1, 2); b.join(RDFGPU_NODE_HASH_JOIN, (int)a, (int)t, RDFGPU_JOIN_INNER, {{2, 0}});
     expect("a value key's column as join key", b, V, UNSUP, {"node 4: left join key column 2 is a computed value column (expression 0 of the ProjectionExec with expressions, node 1)"}); }
-  { Builder b; u32 a = windfarm(b); u32 t = b.table(1, 2); b.hash_join((int)a, (int)t, 7, 0);
+  { Builder b; u32 a = windfarm(b); u32 t = b.table(1, 2); b.join(RDFGPU_NODE_HASH_JOIN, (int)a, (int)t, RDFGPU_JOIN_INNER, {{7, 0}});
     expect("the AVG's column as join key", b, V, UNSUP, {"node 4: left join key column 7 is an aggregate value column (aggregate 0 of node 2)"}); }
   { Builder b; u32 c = b.aggregate((int)b.table(0, 2), {0}, {{RDFGPU_AGG_COUNT, 1}}); b.aggregate((int)c, {0}, {{RDFGPU_AGG_COUNT_DISTINCT, 1}});
     expect("a value column under COUNT DISTINCT", b, V, UNSUP, {"node 2: COUNT DISTINCT input column 1"}); }
@@ -162,6 +91,5 @@ int main() {
     expect("value keys under a UNION", b, V, UNSUP, {"UnionExec left input column 2"}); }
   { Builder b; u32 t = b.table(0, 2); auto n = Builder::blank(RDFGPU_NODE_SORT, (int)t); n.n_keys = 5; b.push(n);
     expect("SortExec keeps its 4 keys", b, V, UNSUP, {"SortExec with 5 sort keys (1 to 4)"}); }
-  std::printf("%d failure(s)\n", failures);
-  return failures ? 1 : 0;
+  return finish();
 }
