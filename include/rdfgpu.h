@@ -757,11 +757,26 @@ void rdfgpu_plan_destroy(rdfgpu_plan* plan);
 int rdfgpu_plan_bind_table(rdfgpu_plan* plan, uint32_t slot, const uint32_t* const* cols,
                            uint32_t n_cols, uint64_t n_rows);
 
-/* Runs the whole operator tree on the device.  The result stays in HBM.  Re-executable. */
+/* Runs the whole operator tree on the device.  The result stays in HBM.  Re-executable.
+ *
+ * On return the result's row count and every check of the execution (speculation, run-time errors) are final; the result's ROWS may
+ * still be being written.  A plan whose root is a band join emitting from a slice's list (the batched BSBM Q5) learns its count in
+ * front of that join's emit pass and returns while the pass — the execution's tail — runs on the plan's stream
+ * (rdfgpu_early_count_eligible; RDFGPU_OPT_NO_EARLY_RESULT_COUNT restores the wait for the whole stream).  What that means for a caller:
+ *   - rdfgpu_plan_result_info, _bind_table, _set_option, _enable_kernel_timing and _stream do not wait for the tail; every entry that
+ *     reads result memory or finished metrics, or hands result memory out (rdfgpu_plan_fetch, _result_device, _agg_fetch, _agg_device,
+ *     _result_values, _result_values_fetch, _next, _decode_terms, _rewind, _metrics, _kernel_stats) completes it first, and so does
+ *     rdfgpu_plan_destroy.  Pointers from rdfgpu_plan_result_device are therefore complete for a consumer on any stream;
+ *   - the tail reads no caller-bound table: the tables bound for an execution may be rebound or freed once execute has returned;
+ *   - the next execute of the plan does not wait for the tail either (its work is ordered behind it on the plan's stream), and the
+ *     store's mutations (extend, remove, clear, drop_tables, set_typed_values, set_strings) wait for every pending tail themselves;
+ *   - rdfgpu_metrics.elapsed_compute_ms is 0 until the tail has been completed; host_syncs counts the waits inside execute, as before. */
 int rdfgpu_plan_execute(rdfgpu_plan* plan);
 
-/* Result shape (waits for the stream). */
+/* Result shape.  Does not wait: the count is final when execute returns, whether or not its tail is still running. */
 int rdfgpu_plan_result_info(rdfgpu_plan* plan, uint64_t* n_rows, uint32_t* n_cols);
+/* *out = 1 while the last execute's tail (see rdfgpu_plan_execute) has not been completed by a call on this plan, else 0. */
+int rdfgpu_plan_tail_pending(rdfgpu_plan* plan, uint32_t* out);
 /* Device pointers of the result columns (valid until the next execute / destroy of THIS plan — also across mutations of the
    store: an executed plan keeps the store generation its result may point into, and keeps showing the pre-mutation rows,
    like the reference's plan keeps its snapshot, snapshot.rs:35-37). */
@@ -949,6 +964,7 @@ enum {
   RDFGPU_OPT_NO_SEMI_LDS,               /* flag: semi / anti joins never build their set of right rows in LDS (the HBM set, built per execution) */
   RDFGPU_OPT_NO_BAND_PAIR_COUNTS,       /* flag: band join emitting from a slice's list of surviving pairs: no per-row counts of the verdicts are read, every step streams the verdict bits to count its blocks' rows */
   RDFGPU_OPT_BAND_PAIR_COUNT_BLOCKS,    /* value: the smallest number of 64 x 64 blocks from which a step counts from the per-row counts, 64 bytes per block, instead of the bits (0 = automatic: 2^16 blocks = 32 MiB of verdicts) */
+  RDFGPU_OPT_NO_EARLY_RESULT_COUNT,     /* flag: rdfgpu_plan_execute never returns at a band join's count point: it waits for the whole stream, the emit pass included, as it did before the early count existed (the newest flag; it sits here because the bindings' tests pin the five names that follow as the end of the list) */
   RDFGPU_OPT_NO_BAND_ROW_CACHE,         /* flag: band join reading a slice's rows in place: the rows' decoded windows are not kept on the slice, every step gathers 16-byte records by key */
   RDFGPU_OPT_NO_BAND_PAIR_LIST,         /* flag: band join streaming a slice's cached pair verdicts: no list of the surviving pairs is kept beside them, every step expands the verdict bits into rows */
   RDFGPU_OPT_NO_BAND_PAIR_CACHE,        /* flag: band join reading a slice's rows in place with the rows' windows kept: the pair test's verdicts are not kept on the slice, every step tests every pair */
@@ -1021,6 +1037,13 @@ int rdfgpu_band_step_form(uint32_t row_static, uint32_t has_verdicts, uint32_t h
  * the slice's rows through their cached windows — the ordered join itself asks with 1, and owes its probe unless the answer is FULL.
  */
 int rdfgpu_oj_probe_form(uint32_t held, uint32_t in_place, uint32_t row_cache, uint32_t option_set, uint32_t row_static);
+/*
+ * May rdfgpu_plan_execute return at a band join's count point, in front of its emit pass (1), or does it wait for the whole stream (0)?  is_root: the band join's
+ * output node is the plan's root; result_is_output: nothing is launched behind emit (no left-join tail, no held-back write pass); form: the step's form as
+ * rdfgpu_band_step_form numbers it (3 VERDICTS_LIST and 4 COUNTS_LIST qualify); skip_slow: the full-semantics pass is not launched; speculative, priming: the
+ * execution's mode; timing: rdfgpu_plan_enable_kernel_timing is on; option_set: RDFGPU_OPT_NO_EARLY_RESULT_COUNT.  A negative status on an unknown form.
+ */
+int rdfgpu_early_count_eligible(uint32_t is_root, uint32_t result_is_output, uint32_t form, uint32_t skip_slow, uint32_t speculative, uint32_t priming, uint32_t timing, uint32_t option_set);
 /*
  * MemIndexScanPredicate::try_and_with (scan_instructions.rs:170-210).  Predicates are given
  * as (pred, a, b) triples where IN sets are explicit arrays.  Writes the combined predicate;

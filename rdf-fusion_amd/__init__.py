@@ -5,7 +5,8 @@ binding used by the tests and the benchmark."""
 from . import abi, plan  # noqa: F401
 from .engine import (RdfGpuError, GpuQuadStore, GpuPlan, Comm, NTriples, load_library, library_path, kernel_source_sha16,  # noqa: F401
                      choose_index, scan_score, predicate_and, pushdown_to_scan_predicate, shard_of, band_row_cache_eligible,
-                     band_pair_cache_eligible, band_pair_list_eligible, band_pair_count_eligible, band_step_form, BAND_FORMS, oj_probe_form, OJ_PROBE_FORMS)
+                     band_pair_cache_eligible, band_pair_list_eligible, band_pair_count_eligible, band_step_form, BAND_FORMS, oj_probe_form, OJ_PROBE_FORMS,
+                     early_count_eligible)
 
 __all__ = ["abi", "plan", "RdfGpuError", "GpuQuadStore", "GpuPlan", "Comm", "NTriples", "shard_of", "load_library", "library_path", "kernel_source_sha16",
-           "choose_index", "scan_score", "predicate_and", "pushdown_to_scan_predicate", "band_row_cache_eligible", "band_pair_cache_eligible", "band_pair_list_eligible", "band_pair_count_eligible", "band_step_form", "BAND_FORMS", "oj_probe_form", "OJ_PROBE_FORMS"]
+           "choose_index", "scan_score", "predicate_and", "pushdown_to_scan_predicate", "band_row_cache_eligible", "band_pair_cache_eligible", "band_pair_list_eligible", "band_pair_count_eligible", "band_step_form", "BAND_FORMS", "oj_probe_form", "OJ_PROBE_FORMS", "early_count_eligible"]

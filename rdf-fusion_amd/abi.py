@@ -72,7 +72,7 @@ OPTION_NAMES = ["FORCE_GENERIC_VM", "NO_JOIN_REORDER", "NO_SPECULATION", "NO_FIR
                 "NO_TABLE_CACHE", "NO_INDEX_JOIN", "NO_CHAIN_FUSION", "NO_VALUE_TABLES", "NO_RANGE_INDEX", "NO_FILTER_FUSION",
                 "NO_LDS_JOIN", "NO_GLOBAL_TABLE_JOIN", "NO_DIRECT_TABLE", "NO_BAND_JOIN", "NO_PARTITIONED_JOIN", "NO_VALUE_VERDICTS", "NO_PRIMING", "NO_ORDERED_JOIN", "NO_BAND_PACK16", "NO_RUN_COPY", "NO_RANGE_PARTITION",
                 "LDS_MAX_BUILD", "CSR_ROW_LANES_LOG2", "JOIN_WAVE_Q", "PARTITION_MIN_BUILD", "PARTITION_TWO_PASS_ROWS", "NO_OWN_PARTITION_PASS", "NO_BAND_COMPACT", "NO_PROBE_OUTER_JOIN", "NO_STREAM_JOIN", "PARTITION_ROWS", "PARTITION_SLOTS",
-                "NO_SEMI_LDS", "NO_BAND_PAIR_COUNTS", "BAND_PAIR_COUNT_BLOCKS", "NO_BAND_ROW_CACHE", "NO_BAND_PAIR_LIST", "NO_BAND_PAIR_CACHE", "BAND_PAIR_CACHE_BLOCKS", "NO_AGG_LDS"]
+                "NO_SEMI_LDS", "NO_BAND_PAIR_COUNTS", "BAND_PAIR_COUNT_BLOCKS", "NO_EARLY_RESULT_COUNT", "NO_BAND_ROW_CACHE", "NO_BAND_PAIR_LIST", "NO_BAND_PAIR_CACHE", "BAND_PAIR_CACHE_BLOCKS", "NO_AGG_LDS"]
 OPTIONS = {name: i for i, name in enumerate(OPTION_NAMES)}
 
 
@@ -187,6 +187,7 @@ EXPORTED_SYMBOLS = [
     "rdfgpu_plan_pushdown_filters", "rdfgpu_plan_set_dynamic_filters", "rdfgpu_plan_source_predicate",
     "rdfgpu_store_set_option", "rdfgpu_store_get_option", "rdfgpu_plan_set_option", "rdfgpu_option_name",
     "rdfgpu_scan_score", "rdfgpu_choose_index", "rdfgpu_predicate_and", "rdfgpu_band_row_cache_eligible", "rdfgpu_band_pair_cache_eligible", "rdfgpu_band_pair_list_eligible", "rdfgpu_band_pair_count_eligible", "rdfgpu_band_step_form", "rdfgpu_oj_probe_form",
+    "rdfgpu_early_count_eligible", "rdfgpu_plan_tail_pending",
     "rdfgpu_pushdown_to_scan_predicate", "rdfgpu_regex_check",
     "rdfgpu_comm_unique_id", "rdfgpu_comm_create", "rdfgpu_comm_create_host", "rdfgpu_comm_destroy",
     "rdfgpu_exchange_allgatherv", "rdfgpu_exchange_repartition", "rdfgpu_shard_of",

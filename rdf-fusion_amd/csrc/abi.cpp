@@ -161,10 +161,17 @@ int rdfgpu_plan_result_info(rdfgpu_plan* plan, uint64_t* n_rows, uint32_t* n_col
   if (n_cols) *n_cols = p->result.n_cols;
   ABI_END
 }
+int rdfgpu_plan_tail_pending(rdfgpu_plan* plan, uint32_t* out) {
+  ABI_BEGIN
+  if (!out) fail(RDFGPU_ERR_INVALID, "null out pointer");
+  *out = P(plan)->tail_pending ? 1u : 0u;
+  ABI_END
+}
 int rdfgpu_plan_result_device(rdfgpu_plan* plan, const uint32_t** cols, uint32_t cap_cols) {
   ABI_BEGIN
   Plan* p = P(plan);
   if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  p->complete();
   if (cap_cols < p->result.n_cols) fail(RDFGPU_ERR_INVALID, "room for %u columns, result has %u", cap_cols, p->result.n_cols);
   for (u32 c = 0; c < p->result.n_cols; c++) cols[c] = p->result_rows ? p->result.cols[c] : nullptr;
   ABI_END
@@ -173,6 +180,7 @@ int rdfgpu_plan_fetch(rdfgpu_plan* plan, uint32_t* const* host_cols, uint32_t n_
   ABI_BEGIN
   Plan* p = P(plan);
   if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  p->complete();
   if (n_cols != p->result.n_cols) fail(RDFGPU_ERR_INVALID, "caller passed %u columns, result has %u", n_cols, p->result.n_cols);
   p->store->activate();
   for (u32 c = 0; c < n_cols; c++)
@@ -192,6 +200,7 @@ int rdfgpu_plan_agg_fetch(rdfgpu_plan* plan, uint32_t agg, rdfgpu_agg_value* hos
   ABI_BEGIN
   Plan* p = P(plan);
   if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  p->complete();
   if (agg >= p->agg_out.size()) fail(RDFGPU_ERR_INVALID, "aggregate %u of %zu", agg, p->agg_out.size());
   p->store->activate();
   if (p->result_rows) {
@@ -205,6 +214,7 @@ int rdfgpu_plan_result_values(rdfgpu_plan* plan, uint32_t col, const rdfgpu_agg_
   ABI_BEGIN
   Plan* p = P(plan);
   if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  p->complete();
   if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
   if (!values) fail(RDFGPU_ERR_INVALID, "null out pointer");
   *values = p->result_values(col, n);
@@ -214,6 +224,7 @@ int rdfgpu_plan_result_values_fetch(rdfgpu_plan* plan, uint32_t col, rdfgpu_agg_
   ABI_BEGIN
   Plan* p = P(plan);
   if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  p->complete();
   if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
   if (!p->result_values(col, nullptr)) fail(RDFGPU_ERR_INVALID, "result column %u holds object ids, not aggregate values", col);
   p->ensure_host_copy();
@@ -227,6 +238,7 @@ int rdfgpu_plan_agg_device(rdfgpu_plan* plan, uint32_t agg, const rdfgpu_agg_val
   ABI_BEGIN
   Plan* p = P(plan);
   if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  p->complete();
   if (agg >= p->agg_out.size()) fail(RDFGPU_ERR_INVALID, "aggregate %u of %zu", agg, p->agg_out.size());
   if (!values) fail(RDFGPU_ERR_INVALID, "null out pointer");
   *values = p->result_rows ? p->agg_out[agg] : nullptr;
@@ -387,6 +399,7 @@ int rdfgpu_plan_decode_terms(rdfgpu_plan* plan, uint32_t col, uint64_t first_row
     Plan* p = P(plan);
     if (!out) fail(RDFGPU_ERR_INVALID, "null out array");
     if (!p->executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+    p->complete();
     if (col >= p->result.n_cols) fail(RDFGPU_ERR_INVALID, "column %u of a %u-column result", col, p->result.n_cols);
     if (const ValueOrigin& o = p->nodes[p->root].origin[col]; o.node >= 0)
       fail(RDFGPU_ERR_UNSUPPORTED, "ENC_PT of result column %u: it is %s value column (%s %u of node %d), its entries are not object ids (rdfgpu_plan_result_values)", col, o.mark ? "a mark" : o.extend ? "a computed" : "an aggregate", o.mark ? "mark" : o.extend ? "expression" : "aggregate", o.agg, o.node);
@@ -480,10 +493,11 @@ int rdfgpu_plan_decode_terms(rdfgpu_plan* plan, uint32_t col, uint64_t first_row
   } catch (const Error& e) { set_last_error(e.what()); return e.status; }
   catch (const std::exception& e) { set_last_error(e.what()); return RDFGPU_ERR_INVALID; }
 }
-int rdfgpu_plan_rewind(rdfgpu_plan* plan) { ABI_BEGIN P(plan)->cursor = 0; ABI_END }
+int rdfgpu_plan_rewind(rdfgpu_plan* plan) { ABI_BEGIN P(plan)->complete(); P(plan)->cursor = 0; ABI_END }
 int rdfgpu_plan_metrics(rdfgpu_plan* plan, rdfgpu_metrics* out) {
   ABI_BEGIN
   if (!out) fail(RDFGPU_ERR_INVALID, "null out pointer");
+  P(plan)->complete();   // (elapsed_compute_ms is known once the stream has finished)
   *out = P(plan)->metrics;
   ABI_END
 }
@@ -538,6 +552,7 @@ int rdfgpu_plan_enable_kernel_timing(rdfgpu_plan* plan, int on) {
 int rdfgpu_plan_kernel_stats(rdfgpu_plan* plan, rdfgpu_kernel_stat* out, uint32_t cap, uint32_t* n) {
   ABI_BEGIN
   Plan* p = P(plan);
+  p->complete();
   if (!n || (cap && !out)) fail(RDFGPU_ERR_INVALID, "null out pointer");
   u32 w = 0;
   for (int k = 0; k < KC__N; k++) {
@@ -612,6 +627,13 @@ int rdfgpu_oj_probe_form(uint32_t held, uint32_t in_place, uint32_t row_cache, u
   OjProbeShape s;
   s.held = held != 0; s.in_place = in_place != 0; s.row_cache = row_cache != 0; s.option_off = option_set == 0; s.row_static = row_static != 0;
   return (int)oj_probe_form(s);
+}
+int rdfgpu_early_count_eligible(uint32_t is_root, uint32_t result_is_output, uint32_t form, uint32_t skip_slow, uint32_t speculative, uint32_t priming, uint32_t timing, uint32_t option_set) {
+  if (form > (uint32_t)BandForm::COUNTS_LIST) { set_last_error("early count: unknown band form"); return RDFGPU_ERR_INVALID; }
+  EarlyCountShape s;
+  s.is_root = is_root != 0; s.result_is_output = result_is_output != 0; s.form = (BandForm)form; s.skip_slow = skip_slow != 0;
+  s.speculative = speculative != 0; s.priming = priming != 0; s.timing = timing != 0; s.option_off = option_set == 0;
+  return early_count_eligible(s) ? 1 : 0;
 }
 static ScanPredicate from_abi(const rdfgpu_predicate* p) {
   ScanPredicate r; r.kind = p->pred; r.from = p->from; r.to = p->to; r.equal_to = p->equal_to;

@@ -1074,6 +1074,17 @@ void launch_band_emit(const BandArgs& b, BandForm form, hipStream_t s) {
   if (!launched) fail(RDFGPU_ERR_INVALID, "band join: form %s with %u output columns (%u from the row)", band_form_name(form), b.n_out_cols, b.n_row_cols);
 }
 
+// The count point (Plan::band_blocks_and_emit): everything the host checks after an execution — the 256 counter words and the result's row count, which is final
+// once the blocks' scan has run (*total = bofs[max_blocks]) — written into the host's pinned mirror (257 words, mapped) IN FRONT of the emit pass, with ordinary
+// vector stores: one workgroup, one word per thread.  The event recorded behind it makes the words visible to the host.
+__global__ __launch_bounds__(256) void band_count_point_kernel(const u64* counters, const u32* total, u64* mirror) {
+  mirror[threadIdx.x] = counters[threadIdx.x];
+  if (threadIdx.x == 0) mirror[256] = *total;
+}
+void launch_band_count_point(const u64* counters, const u32* total, u64* mirror, hipStream_t s) {
+  hipLaunchKernelGGL(band_count_point_kernel, dim3(1), dim3(256), 0, s, counters, total, mirror);
+}
+
 // blocks (64 entries x 64 rows) per key, scanned in one go: boff[k] = first block of key k, boff[kn] = all blocks.  The per-key
 // counts are the scan's INPUT ITERATOR (computed on the fly from the two offset arrays): no band_blocks launch, no count array.
 struct BandBlocksOfKey {

@@ -186,4 +186,9 @@ OjProbeForm oj_probe_form(const OjProbeShape& s) {
   return s.row_static ? OjProbeForm::LEAN : OjProbeForm::FULL_NOW;
 }
 
+bool early_count_eligible(const EarlyCountShape& s) {
+  if (!s.is_root || !s.result_is_output || !s.skip_slow || !s.speculative || s.priming || s.timing || !s.option_off) return false;
+  return s.form == BandForm::VERDICTS_LIST || s.form == BandForm::COUNTS_LIST;
+}
+
 }  // namespace rdfgpu

@@ -110,4 +110,17 @@ constexpr const char* oj_probe_form_name(OjProbeForm f) { return f == OjProbeFor
 struct OjProbeShape { bool held = false, in_place = false, row_cache = false, option_off = false, row_static = false; };
 OjProbeForm oj_probe_form(const OjProbeShape& s);
 
+// May Plan::execute learn its result's row count in front of the band join's emit pass and return while that pass runs (Plan::band_blocks_and_emit, the count
+// point)?  Nothing the host waits for is produced by emit: the total is the last entry of the blocks' scan, every counter the host reads afterwards is written by
+// the passes before.  Yes only when the band join is the plan's root (is_root), its output is the plan's result and nothing is launched behind emit
+// (result_is_output: no left-join tail, no held-back write pass), the step's form is one of the two list forms with the full-semantics pass skipped (a
+// band_slow_kernel would run between the count and emit and may change the blocks' counts), the execution is speculative and not the priming run, kernel timing
+// is off (the events of `timed` and elapsed_compute_ms need the finished stream) and RDFGPU_OPT_NO_EARLY_RESULT_COUNT is off.
+// What runs behind the count point may READ only this execution's scratch, the slice's tables (eo, bdesc, pair_list, pair_list_off) and arguments passed by
+// value, and WRITE only the result columns and its two counter words: never a caller-bound table (the caller may rebind or free it once execute has returned)
+// and never a pinned staging slot of the context (the next execute fills those while the tail runs).  band_emit_list keeps to that; a form added to this
+// function has to as well.
+struct EarlyCountShape { bool is_root = false, result_is_output = false, skip_slow = false, speculative = false, priming = false, timing = false, option_off = false; BandForm form = BandForm::RECORDS; };
+bool early_count_eligible(const EarlyCountShape& s);
+
 }  // namespace rdfgpu

@@ -596,6 +596,7 @@ void band_blocks_scan(const u32* csr_off, const u32* poff, u32 kn, u32* boff, vo
 void launch_band_mask(const BandArgs& b, BandForm form, hipStream_t s);   // (both block passes: a form whose preconditions b does not meet is RDFGPU_ERR_INVALID before any launch)
 void launch_band_slow(const LdsJoinArgs* a_dev, const BandArgs& b, hipStream_t s);   // patches masks / counts of the rare slow rows
 void launch_band_emit(const BandArgs& b, BandForm form, hipStream_t s);
+void launch_band_count_point(const u64* counters /* 256 */, const u32* total, u64* mirror /* 257, host-mapped */, hipStream_t s);   // the counters and the blocks' total to the host, in front of emit
 size_t sort_u32_temp_bytes(u64 n, u32 bits);
 void sort_pairs_u32_u32(const u32* kin, u32* kout, const u32* vin, u32* vout, u64 n, u32 bits, void* temp, size_t temp_bytes, hipStream_t s);
 void launch_val_minmax(const long long* val, u64 n, long long* out_minmax /* preset {INT64_MAX, INT64_MIN + 1} */, hipStream_t s);

@@ -112,7 +112,9 @@ void Plan::set_dynamic_filters(u32 node, const rdfgpu_pushdown_filter* filters, 
 
 Plan::~Plan() {
   if (store) (void)hipSetDevice(store->device);
+  try { complete(); } catch (...) {}
   if (stream) (void)hipStreamSynchronize(stream);
+  if (store) { store->tails.remove(this); tail_waited(); }   // (whatever complete() could not do)
   release_intermediates();
   if (pool_dev) (void)hipFree(pool_dev);
   if (regex_dev) (void)hipFree(regex_dev);
@@ -202,6 +204,26 @@ void Plan::resolve_timing() {
 void Plan::release_intermediates() {
   for (void* p : allocs) store->pool.free(p);
   allocs.clear();
+}
+// A host wait that is stream-ordered behind the predecessor's tail has returned (this execution's count wait or final wait, complete()): nothing on the device
+// uses what that tail kept alive any more.  The blocks go to the pool, where any plan may take them.
+void Plan::tail_waited() {
+  retired.release([&](void* p) { store->pool.free(p); });
+  retired_held.reset();
+}
+// What an execute that returned at its count point left undone: the one wait for the stream, the execution's elapsed time, the retired memory, the plan's entry among
+// the store's pending tails.  Called by everything that reads result memory or finished metrics, or hands result memory to a consumer on another stream.
+void Plan::complete() {
+  if (!tail_pending) return;
+  store->activate();
+  RDFGPU_HIP(hipStreamSynchronize(stream));
+  tail_pending = false;
+  store->tails.remove(this);
+  tail_waited();
+  float ms = 0;
+  if (executed && hipEventElapsedTime(&ms, ctx->event(0), ctx->event(1)) == hipSuccess) metrics.elapsed_compute_ms = ms;
+  else (void)hipGetLastError();
+  resolve_timing();
 }
 // Generic (VM) programs of the LDS join live in device memory; staged through the context's pinned slots.
 const ExprProgram* Plan::upload_program(const ExprProgram& p) {
@@ -300,8 +322,24 @@ void Plan::execute() {
   if (!primed && !priming) prime();
   store->activate();
   std::shared_lock<std::shared_mutex> lock(store->mu);   // a plan holds the snapshot while it runs (snapshot.rs:35-37)
-  RDFGPU_HIP(hipStreamSynchronize(stream));
-  release_intermediates();
+  // An execution that fails behind a pending tail leaves nothing in flight: its half-launched work would outlive this hold of the store with no event behind it.
+  struct TailGuard {
+    Plan* p; bool done = false;
+    ~TailGuard() {
+      if (done || !p->tail_pending) return;
+      (void)hipStreamSynchronize(p->stream);
+      p->tail_pending = false; p->store->tails.remove(p); p->tail_waited();
+    }
+  } tail_guard{this};
+  const bool behind_tail = tail_pending;
+  if (behind_tail) {   // the predecessor returned at its count point: no wait, the stream orders this execution behind its emit pass; its blocks are retired, not freed
+    for (void* p : allocs) retired.retire(p, store->pool.block_bytes(p));
+    allocs.clear();
+    retired_held = held;
+  } else {
+    RDFGPU_HIP(hipStreamSynchronize(stream));
+    release_intermediates();
+  }
   // the pool keeps what an execution hands back for the next one — bounded by twice what the previous executions (this plan's, or any plan's of the store) used
   // (+ 1 GiB): the giant blocks of a one-off exact run go back to the device instead of staying cached for ever
   store->pool.trim_to(2 * std::max(std::max(scratch_hist[0], scratch_hist[1]), std::max(store->scratch_recent[0].load(), store->scratch_recent[1].load())) + (1ull << 30));
@@ -322,6 +360,7 @@ void Plan::execute() {
   RDFGPU_HIP(hipMemsetAsync(counters, 0, 256 * sizeof(u64), stream));
 
   spec_checks.clear();
+  count_point = CountPoint{};
   pending_oj.active = false;
   band_feedback.clear();
   memo.assign(nodes.size(), DevTable{}); memo_valid.assign(nodes.size(), 0);
@@ -332,12 +371,27 @@ void Plan::execute() {
 
   result = exec_node(root);
   flush_pending_oj();
-  // one copy brings back every device-side cardinality (the result's and, for timing, the others')
-  RDFGPU_HIP(hipMemcpyAsync(ctx->counters_host, counters, 256 * sizeof(u64), hipMemcpyDeviceToHost, stream));
+  // The early result count: the root band join sent the counters and its total to the host in front of its emit pass (Plan::band_blocks_and_emit), and that pass
+  // was the last thing launched.  The one wait is then for the count event, and the execution returns while emit runs.
+  const bool early = count_point.armed && result.n_dev == count_point.n_out_dev && !pending_oj.active;
+  // else one copy brings back every device-side cardinality (the result's and, for timing, the others')
+  if (!early) RDFGPU_HIP(hipMemcpyAsync(ctx->counters_host, counters, 256 * sizeof(u64), hipMemcpyDeviceToHost, stream));
   RDFGPU_HIP(hipEventRecord(ev_stop, stream));
-  RDFGPU_HIP(hipStreamSynchronize(stream)); metrics.host_syncs++;
+  if (early) RDFGPU_HIP(hipEventSynchronize(ctx->count_event)); else RDFGPU_HIP(hipStreamSynchronize(stream));
+  metrics.host_syncs++;
   RDFGPU_HIP(hipGetLastError());
+  if (behind_tail) tail_waited();   // either wait was ordered behind the predecessor's emit pass
+  if (early) {   // the mirror as emit will leave the device's words: the exact total, and the overflow flag when it did not fit
+    const u64 total = ctx->counters_host[256];
+    ctx->counters_host[count_point.n_out] = total;
+    if (total > count_point.out_cap) ctx->counters_host[count_point.overflow] |= 1ull;
+    tail_pending = true;
+    store->tails.add(this, ev_stop);   // (entered before this execution's hold of the store goes: a mutation waits for ev_stop)
+  } else if (behind_tail) { tail_pending = false; store->tails.remove(this); }
+  // a failed speculation or a run-time error is known here: the tail is completed before the exact re-run or the error
+  auto settle = [&] { if (early) complete(); };
   if (const u32 rt = (u32)(ctx->counters_host[255] & 0xFFFFFFFFull)) {   // a row asked for something that is refused loudly, not answered differently
+    settle();
     if (rt & 1u) fail(RDFGPU_ERR_UNSUPPORTED, "REGEX with \\d \\w \\s or \\b over a string with non-ASCII characters needs the regex crate's Unicode tables (not restated)");
     if (rt & 8u) fail(RDFGPU_ERR_UNSUPPORTED, "a numeric CAST met a simple literal: the lexical forms of numbers are not parsed on the device");
     if (rt & kRtExtendKind) fail(RDFGPU_ERR_UNSUPPORTED, "a computed column (ProjectionExec with expressions) met a value that is a string, IRI, blank node, dateTime, date, time or duration: "
@@ -358,6 +412,8 @@ void Plan::execute() {
     else { c.node->last_rows = ctx->counters_host[c.counter]; c.node->has_last = true; c.node->last_scaled = false; }
   }
   if (spec_failed) {   // rare: run again with exact sizes (one sync per join), then speculate again next time
+    settle();
+    tail_guard.done = true;
     metrics.host_syncs++;
     lock.unlock();
     allow_speculation = false;
@@ -371,7 +427,7 @@ void Plan::execute() {
   for (NodeInfo& nd : nodes)   // a computed column over rows counted on the device: its array holds that many values, not its capacity
     if (nd.values_run == run && nd.n_values_dev) { nd.n_values = std::min<u64>(nd.n_values, ctx->counters_host[nd.n_values_dev - counters]); nd.n_values_dev = nullptr; }
   float ms = 0;
-  RDFGPU_HIP(hipEventElapsedTime(&ms, ev_start, ev_stop));
+  if (!early) RDFGPU_HIP(hipEventElapsedTime(&ms, ev_start, ev_stop));   // (early: ev_stop lies behind the running emit pass — complete() reads it)
   metrics.elapsed_compute_ms = ms;
   metrics.output_rows = result_rows;
   metrics.device_mallocs = (u32)(store->pool.mallocs() + store->table_pool.mallocs() - mallocs0);
@@ -380,6 +436,7 @@ void Plan::execute() {
   executed = true;
   scratch_hist[1] = scratch_hist[0]; scratch_hist[0] = metrics.device_bytes;
   store->scratch_recent[1] = store->scratch_recent[0].load(); store->scratch_recent[0] = metrics.device_bytes;
+  tail_guard.done = true;
 }
 
 // Dynamic filters (scan.rs:217-261): the effective instructions of a leaf = its static ones AND the filters' current
@@ -666,6 +723,7 @@ DevTable Plan::exec_extend(NodeInfo& nd) {
 void Plan::ensure_host_copy() {
   if (host_valid) return;
   if (!executed) fail(RDFGPU_ERR_INVALID, "plan has not been executed");
+  complete();
   store->activate();
   host_cols.assign(result.n_cols, std::vector<u32>());
   for (u32 c = 0; c < result.n_cols; c++) {

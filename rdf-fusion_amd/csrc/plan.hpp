@@ -123,6 +123,7 @@ struct LdsJoin {
   std::vector<ColRef> chain_cols; SliceTable::ValueColumn chain_vc[kMaxChain] = {};   // .. its output columns (bottom-up, while it is resolved into a.chain / a.chain_out); the decoded value table a stage's window reads (a copy; val == nullptr: none)
   BandArgs band{}; bool use_band = false;  // the chain runs as a band join (Plan::exec_band_join), with these arguments
   DevTable t;                              // the output
+  const NodeInfo* out_node = nullptr;      // the node the output belongs to: this join's, or the top node's of a fused chain (set by run_speculative)
   LdsJoin(NodeInfo& n, const DevTable& l, const DevTable& r, bool bl, const NodeInfo* pf, const NodeInfo* post)
       : nd(n), L(l), R(r), build_left(bl), B(bl ? l : r), P(bl ? r : l), probe_filter(pf), post_filter(post),
         probe_outer(n.d.join_type == RDFGPU_JOIN_LEFT && !bl), left_join(n.d.join_type == RDFGPU_JOIN_LEFT && bl) {}
@@ -250,6 +251,17 @@ struct Plan {
 
   // per-execution state
   std::vector<void*> allocs;      // pool blocks owned by the current result / intermediates
+  // The early result count (host_logic.hpp, early_count_eligible): execute returns at the band join's count point, in front of its emit pass — the
+  // execution's TAIL, which then runs on `stream` while the host goes on.  tail_pending: the last execute left such a tail and no call has completed it
+  // (complete()); the plan is then entered in store->tails.  The next execute does not wait for it — the stream orders its work behind the tail — and does not
+  // hand the predecessor's blocks back to the pool, which another plan on another stream could be given: it retires them (`retired`; tail_lifetime.hpp),
+  // takes from them what it needs itself and gives the rest back at its own first wait behind the tail.  retired_held: the predecessor's store generation.
+  struct CountPoint { bool armed = false; const u64* n_out_dev = nullptr; u32 n_out = 0, overflow = 0; u64 out_cap = 0; };
+  CountPoint count_point;         // set by Plan::band_blocks_and_emit when this execution's counters and total travel to the host in front of emit
+  bool tail_pending = false;
+  RetiredBlocks retired; std::shared_ptr<IndexGeneration> retired_held;
+  void complete();                // waits for the stream once and finishes what execute left (elapsed time, retired memory, the registry entry); idempotent
+  void tail_waited();             // a host wait that was stream-ordered behind the predecessor's tail has returned: what that tail kept alive goes
   u64* counters = nullptr;        // device u64 slots for operator output counts
   u32 counters_used = 0;
   u32 progs_used = 0;

@@ -611,6 +611,20 @@ void Plan::band_blocks_and_emit(BandJoin& bj) {
     timed(KC_BAND_SLOW, 0, 0, nullptr, 0, nullptr, 0, 0, [&] { launch_band_slow(a_dev, b, stream); });
   }
   timed(scan_class(max_blocks + 1), 0, max_blocks + 1, nullptr, 8, nullptr, 0, 0, [&] { exclusive_scan_u32(b.bcount, b.bofs, max_blocks + 1, temp, tb, stream); });
+  // The count point (host_logic.hpp, early_count_eligible): the scan has made the result's row count final (bofs[max_blocks]: emit's thread 0 merely copies it into
+  // n_out_dev and derives the overflow flag), and every counter the host reads after an execution was written by the passes up to here.  Counters and total go to
+  // the host's mirror now, the count event behind them: Plan::execute waits for that event, not for emit.
+  const NodeInfo* top = &nodes[root];   // (a ProjectionExec selects columns and launches nothing)
+  while (top->d.kind == RDFGPU_NODE_PROJECTION) top = &nodes[top->d.left];
+  EarlyCountShape early;
+  early.is_root = bj.j.out_node == top; early.result_is_output = !bj.j.left_join && !pending_oj.active; early.skip_slow = bj.skip_slow; early.form = bj.form;
+  early.speculative = speculative; early.priming = priming; early.timing = timing; early.option_off = !opt.on(RDFGPU_OPT_NO_EARLY_RESULT_COUNT);
+  if (early_count_eligible(early)) {
+    launch_band_count_point(counters, b.bofs + max_blocks, ctx->counters_host_dev, stream);
+    RDFGPU_HIP(hipEventRecord(ctx->count_event, stream));
+    count_point.armed = true; count_point.n_out_dev = b.n_out_dev; count_point.n_out = (u32)(b.n_out_dev - counters);
+    count_point.overflow = (u32)(reinterpret_cast<u64*>(b.overflow) - counters); count_point.out_cap = b.out_cap;
+  }
   timed(KC_BAND_EMIT, bytes.emit_fixed, bj.nrows, nrows_dev, 4 + 4ull * b.n_row_cols, a.n_out_dev, 0, 4ull * a.n_out_cols, [&] { launch_band_emit(b, bj.form, stream); });
 }
 

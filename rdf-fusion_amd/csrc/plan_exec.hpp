@@ -62,8 +62,18 @@ void Plan::timed(int kc, u64 fixed_bytes, u64 rows_cap, const u64* rows_dev, u64
 }
 
 // device memory of the current execution, from the store's pool (handed back by Plan::release_intermediates)
+// Behind a pending tail (Plan::retired is not empty) the predecessor's blocks are served first, by the pool's own rule over both sets: an exact fit among the
+// retired blocks or the pool's cached ones, then the smallest retired block that is not wastefully large, then the pool (which allocates only if it has none either).
 template <class T> T* Plan::scratch(u64 n) {
-  void* p = store->pool.alloc((n ? n : 1) * sizeof(T));
+  const size_t bytes = (n ? n : 1) * sizeof(T);
+  void* p = nullptr;
+  if (!retired.empty()) {
+    const size_t b = DevicePool::bucket(bytes);
+    p = retired.take_exact(b);
+    if (!p) p = store->pool.alloc_exact(bytes);
+    if (!p) p = retired.take(b);
+  }
+  if (!p) p = store->pool.alloc(bytes);
   allocs.push_back(p);
   metrics.device_bytes += (n ? n : 1) * sizeof(T);
   return (T*)p;

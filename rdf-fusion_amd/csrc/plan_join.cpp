@@ -763,6 +763,7 @@ DevTable Plan::run_speculative(LdsJoin& j, u64 first_guess, NodeInfo& size_node)
   a.out_cap = spec_cap;
   for (u32 c = 0; c < a.n_out_cols; c++) { a.out[c] = scratch<u32>(spec_cap + j.tail); t.cols[c] = a.out[c]; }
   if (j.left_join) RDFGPU_HIP(hipMemsetAsync(a.visited, 0, j.L.cap, stream));
+  j.out_node = &size_node;
   if (j.use_band) exec_band_join(j);
   else if (!run_ordered_join(j, size_node, spec_cap)) run_join_kernel(j, j.stage_bytes, 4ull * a.n_out_cols);
   const SpecCheck check{&size_node, (u32)(a.n_out_dev - counters), j.left_join};

@@ -74,6 +74,22 @@ void* DevicePool::alloc(size_t bytes) {
   in_use_ += got;
   return p;
 }
+size_t DevicePool::bucket(size_t bytes) { return bucket_of(bytes ? bytes : 1); }
+size_t DevicePool::block_bytes(void* p) {
+  std::lock_guard<std::mutex> g(mu_);
+  auto it = live_.find(p);
+  return it == live_.end() ? 0 : it->second;
+}
+void* DevicePool::alloc_exact(size_t bytes) {
+  const size_t b = bucket_of(bytes ? bytes : 1);
+  std::lock_guard<std::mutex> g(mu_);
+  auto it = free_.find(b);
+  if (it == free_.end()) return nullptr;
+  void* p = it->second.p;
+  free_.erase(it); cached_ -= b;
+  live_[p] = b; in_use_ += b;
+  return p;
+}
 void DevicePool::free(void* p) {
   if (!p) return;
   std::lock_guard<std::mutex> g(mu_);
@@ -114,7 +130,7 @@ static const char* const kOptionNames[RDFGPU_OPT__COUNT] = {
     "NO_TABLE_CACHE", "NO_INDEX_JOIN", "NO_CHAIN_FUSION", "NO_VALUE_TABLES", "NO_RANGE_INDEX", "NO_FILTER_FUSION",
     "NO_LDS_JOIN", "NO_GLOBAL_TABLE_JOIN", "NO_DIRECT_TABLE", "NO_BAND_JOIN", "NO_PARTITIONED_JOIN", "NO_VALUE_VERDICTS", "NO_PRIMING", "NO_ORDERED_JOIN", "NO_BAND_PACK16", "NO_RUN_COPY", "NO_RANGE_PARTITION",
     "LDS_MAX_BUILD", "CSR_ROW_LANES_LOG2", "JOIN_WAVE_Q", "PARTITION_MIN_BUILD", "PARTITION_TWO_PASS_ROWS", "NO_OWN_PARTITION_PASS", "NO_BAND_COMPACT", "NO_PROBE_OUTER_JOIN", "NO_STREAM_JOIN", "PARTITION_ROWS", "PARTITION_SLOTS",
-    "NO_SEMI_LDS", "NO_BAND_PAIR_COUNTS", "BAND_PAIR_COUNT_BLOCKS", "NO_BAND_ROW_CACHE", "NO_BAND_PAIR_LIST", "NO_BAND_PAIR_CACHE", "BAND_PAIR_CACHE_BLOCKS", "NO_AGG_LDS"};
+    "NO_SEMI_LDS", "NO_BAND_PAIR_COUNTS", "BAND_PAIR_COUNT_BLOCKS", "NO_EARLY_RESULT_COUNT", "NO_BAND_ROW_CACHE", "NO_BAND_PAIR_LIST", "NO_BAND_PAIR_CACHE", "BAND_PAIR_CACHE_BLOCKS", "NO_AGG_LDS"};
 const char* engine_option_name(u32 option) { return option < RDFGPU_OPT__COUNT ? kOptionNames[option] : nullptr; }
 const EngineOptions& default_engine_options() {
   static const EngineOptions defaults = [] {
@@ -204,6 +220,7 @@ hipEvent_t ExecContext::event(u32 i) {
 }
 ExecContext::~ExecContext() {
   for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  if (count_event) (void)hipEventDestroy(count_event);
   if (counters) (void)hipFree(counters);
   if (counters_host) (void)hipHostFree(counters_host);
   if (progs_dev) (void)hipFree(progs_dev);
@@ -227,7 +244,9 @@ ExecContext* Store::acquire_context(u32 n_sources) {
     c = new ExecContext();
     RDFGPU_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     RDFGPU_HIP(hipMalloc((void**)&c->counters, 256 * sizeof(u64)));
-    RDFGPU_HIP(hipHostMalloc((void**)&c->counters_host, 256 * sizeof(u64), hipHostMallocDefault));
+    RDFGPU_HIP(hipHostMalloc((void**)&c->counters_host, ExecContext::kMirrorWords * sizeof(u64), hipHostMallocDefault));
+    RDFGPU_HIP(hipHostGetDevicePointer((void**)&c->counters_host_dev, c->counters_host, 0));
+    RDFGPU_HIP(hipEventCreate(&c->count_event));
     RDFGPU_HIP(hipMalloc((void**)&c->progs_dev, ExecContext::kProgSlots * sizeof(ExprProgram)));
     RDFGPU_HIP(hipHostMalloc((void**)&c->progs_host, ExecContext::kProgSlots * sizeof(ExprProgram), hipHostMallocDefault));
     RDFGPU_HIP(hipMalloc((void**)&c->args_dev, (size_t)ExecContext::kArgSlots * ExecContext::kArgBytes));
@@ -276,6 +295,7 @@ void Store::drop_slice_tables() {
 void Store::drop_tables() {
   std::unique_lock<std::shared_mutex> lock(mu);   // like a mutation: no plan is running
   activate();
+  wait_for_tails();                               // .. and no emit pass of one that returned at its count point
   RDFGPU_HIP(hipDeviceSynchronize());
   version++;
   drop_slice_tables();
@@ -287,8 +307,17 @@ void Store::drop_string_verdicts() {
   string_verdicts.clear();
 }
 
+// The emit passes of executions that returned at their count point: waited for before anything they read is freed or rebuilt (the caller holds `mu`
+// exclusively).  The table pool's frees inside an execution (Plan::band_row_windows) need no wait: they hand back tables that were never published.
+void Store::wait_for_tails() {
+  hipError_t first = hipSuccess;
+  tails.wait_all([&](void* ev) { const hipError_t e = hipEventSynchronize(static_cast<hipEvent_t>(ev)); if (first == hipSuccess) first = e; });
+  RDFGPU_HIP(first);
+}
+
 Store::~Store() {
   (void)hipSetDevice(device);
+  tails.wait_all([](void* ev) { (void)hipEventSynchronize(static_cast<hipEvent_t>(ev)); });   // (every plan holds a reference: none is left by now)
   drop_slice_tables();
   drop_string_verdicts();
   for (ExecContext* c : free_ctx) delete c;
@@ -314,6 +343,7 @@ void Store::adopt(std::shared_ptr<IndexGeneration> fresh) {
 void Store::clear() {
   std::unique_lock<std::shared_mutex> lock(mu);
   activate();
+  wait_for_tails();
   auto fresh = std::make_shared<IndexGeneration>();
   fresh->device = device;
   adopt(fresh);
@@ -359,6 +389,7 @@ static u64 compact_columns(Store& st, Scratch& sc, u32* const src[4], const u32*
 u64 Store::extend_device(const u32* g, const u32* s_, const u32* p, const u32* o, u64 n) {
   std::unique_lock<std::shared_mutex> lock(mu);
   activate();
+  wait_for_tails();
   if (n == 0) return 0;
   const u32* in[4] = {g, s_, p, o};
   hipStream_t s = stream;
@@ -419,6 +450,7 @@ u64 Store::extend_host(const u32* g, const u32* s_, const u32* p, const u32* o, 
 u64 Store::remove_host(const u32* g, const u32* s_, const u32* p, const u32* o, u64 n) {
   std::unique_lock<std::shared_mutex> lock(mu);
   activate();
+  wait_for_tails();
   if (n == 0 || idx[0].n == 0) return 0;
   hipStream_t s = stream;
   const u32* h[4] = {g, s_, p, o};
@@ -452,6 +484,7 @@ u64 Store::remove_host(const u32* g, const u32* s_, const u32* p, const u32* o, 
 u64 Store::remove_graph(u32 graph) {
   std::unique_lock<std::shared_mutex> lock(mu);
   activate();
+  wait_for_tails();
   if (idx[0].n == 0) return 0;
   hipStream_t s = stream;
   u64 removed = 0;
@@ -474,6 +507,7 @@ u64 Store::remove_graph(u32 graph) {
 void Store::set_typed_values(const rdfgpu_typed_value* v, u64 n, const int64_t* d, u64 nd) {
   std::unique_lock<std::shared_mutex> lock(mu);
   activate();
+  wait_for_tails();
   drop_string_verdicts();
   drop_slice_tables();   // (decoded value tables depend on the typed values)
   if (tv) { RDFGPU_HIP(hipFree(tv)); tv = nullptr; }
@@ -492,6 +526,7 @@ void Store::set_typed_values(const rdfgpu_typed_value* v, u64 n, const int64_t* 
 void Store::set_strings(const u64* offsets, u64 n, const unsigned char* heap_host, u64 heap_bytes) {
   std::unique_lock<std::shared_mutex> lock(mu);
   activate();
+  wait_for_tails();
   drop_string_verdicts();
   if (n && !offsets) fail(RDFGPU_ERR_INVALID, "set_strings: null offsets");
   for (u64 i = 0; i < n; i++) if (offsets[i] > offsets[i + 1] || offsets[i + 1] > heap_bytes) fail(RDFGPU_ERR_INVALID, "set_strings: offsets of id %llu are not monotone / inside the heap", (unsigned long long)i);

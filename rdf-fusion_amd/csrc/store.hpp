@@ -12,6 +12,7 @@
 
 #include "common.hpp"
 #include "expr_device.hpp"
+#include "tail_lifetime.hpp"
 
 namespace rdfgpu {
 
@@ -22,7 +23,10 @@ class DevicePool {
   DevicePool();
   ~DevicePool();
   void* alloc(size_t bytes);
+  void* alloc_exact(size_t bytes);  // a cached block of exactly `bytes`' bucket, or null (no device allocation)
   void free(void* p);
+  static size_t bucket(size_t bytes);       // the block size a request of `bytes` is served with
+  size_t block_bytes(void* p);              // the size of a block that is in use (0: not this pool's)
   void trim();                      // every cached block back to the device
   void trim_to(u64 keep_bytes);     // largest cached blocks back to the device until at most keep_bytes stay cached
   u64 bytes_in_use() const { return in_use_; }
@@ -48,7 +52,10 @@ struct ExecContext {
   hipStream_t stream = nullptr;
   std::vector<hipEvent_t> events;
   u64* counters = nullptr;      // 256 device u64 slots
-  u64* counters_host = nullptr; // pinned mirror
+  static constexpr u32 kMirrorWords = 257;
+  u64* counters_host = nullptr; // pinned mirror; word 256: the row total a band join's count point hands over (Plan::band_blocks_and_emit)
+  u64* counters_host_dev = nullptr;   // the mirror as the device addresses it (the count point's kernel stores into it)
+  hipEvent_t count_event = nullptr;   // recorded at the count point, in front of the emit pass
   void* jobs_dev = nullptr; u64* lohi_dev = nullptr; u32 job_cap = 0;
   void* jobs_host = nullptr; u64* lohi_host = nullptr;   // pinned staging
   static constexpr u32 kProgSlots = 16;
@@ -168,6 +175,10 @@ struct Store {
   void table_free(void* p) { table_pool.free(p); }
   hipStream_t stream = nullptr;  // load-path stream
   std::shared_mutex mu;   // readers = running plans (a snapshot), writers = extend / remove / clear
+  // Executions that returned at their count point (Plan::execute) have given up their hold of `mu` while their emit pass still reads slice tables.
+  // Everything that frees or rebuilds tables, indexes or the typed values calls wait_for_tails() once it holds `mu` exclusively.
+  TailRegistry tails;
+  void wait_for_tails();
   // Shared ownership like the reference's Arc<...>: the handle holds one reference, every compiled plan one more; the
   // store goes away with the last of them, so a plan may outlive rdfgpu_store_destroy (scan.rs:418-419 keeps its
   // snapshot alive the same way).

@@ -130,6 +130,8 @@ def load_library():
     lib.rdfgpu_band_pair_count_eligible.argtypes = [C.c_uint32] * 2 + [C.c_uint64] * 2
     lib.rdfgpu_band_step_form.argtypes = [C.c_uint32] * 6 + [C.c_uint64] * 2
     lib.rdfgpu_oj_probe_form.argtypes = [C.c_uint32] * 5
+    lib.rdfgpu_early_count_eligible.argtypes = [C.c_uint32] * 8
+    lib.rdfgpu_plan_tail_pending.argtypes = [vp, u32p]
     lib.rdfgpu_predicate_and.argtypes = [C.POINTER(abi.Predicate), C.POINTER(abi.Predicate),
                                          C.POINTER(abi.Predicate), u32p]
     lib.rdfgpu_pushdown_to_scan_predicate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.Predicate)]
@@ -218,6 +220,13 @@ def oj_probe_form(held=True, in_place=True, row_cache=True, option_set=False, ro
     OJ_PROBE_FORMS.  `held`, `in_place`, `row_cache`: what the band join's last execution left; `option_set`: NO_BAND_ROW_CACHE; `row_static`: the form the
     band join's step took this time (the ordered join itself asks with True and owes its probe unless the answer is FULL)."""
     return OJ_PROBE_FORMS[_check(load_library().rdfgpu_oj_probe_form(int(held), int(in_place), int(row_cache), int(option_set), int(row_static)))]
+
+
+def early_count_eligible(form="COUNTS_LIST", is_root=True, result_is_output=True, skip_slow=True, speculative=True, priming=False, timing=False, option_set=False):
+    """May execute return at a band join's count point, in front of its emit pass (host_logic.hpp, early_count_eligible)?  The defaults are the
+    steady step of the batched BSBM Q5; `form`: a name of BAND_FORMS; `timing`: kernel timing is on; `option_set`: NO_EARLY_RESULT_COUNT."""
+    return bool(_check(load_library().rdfgpu_early_count_eligible(int(is_root), int(result_is_output), BAND_FORMS.index(form), int(skip_slow), int(speculative),
+                                                                   int(priming), int(timing), int(option_set))))
 
 
 def _pred_struct(p, keep):
@@ -555,6 +564,12 @@ class GpuPlan:
         n, c = C.c_uint64(), C.c_uint32()
         _check(self._lib.rdfgpu_plan_result_info(self._h, C.byref(n), C.byref(c)))
         return n.value, c.value
+
+    def tail_pending(self):
+        """1 while the last execute returned at its count point and no call has completed its emit pass yet (rdfgpu_plan_tail_pending)."""
+        out = C.c_uint32()
+        _check(self._lib.rdfgpu_plan_tail_pending(self._h, C.byref(out)))
+        return out.value
 
     def result_device(self):
         n, c = self.result_info()
