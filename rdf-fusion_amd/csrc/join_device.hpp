@@ -295,6 +295,7 @@ __device__ __forceinline__ bool lprobe_filter(const LdsJoinArgs& a, u64 j) {
 
 // Static-indexed key handling (runtime n_keys <= 4 without private-memory arrays).
 struct Keys { u32 k[RDFGPU_MAX_KEYS]; };
+// (tests/join_cases.py restates this for one key, to place keys whose chain wraps past the last slot: change both together)
 __device__ __forceinline__ u32 hash_keys4(const Keys& key, u32 n) {   // 32-bit multiply/xorshift mix: 64-bit multiplies are 4 quarter-rate ops each
   u32 h = 0x9E3779B9u;
 #pragma unroll
